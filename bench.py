@@ -18,7 +18,10 @@ here). N > 1 GPUs: one process per GPU, independent generations per rank (no dat
 value = total generations of all ranks / max-over-ranks wall time. `python bench.py --gpus N` starts the N ranks itself
 (re-exec under torch.distributed.run); under an external launcher (WORLD_SIZE set) it joins that job.
 
-Usage: python bench.py --gpus N --steps K --warmup W [--config C]   (prints ONE JSON line on rank 0)
+Usage: python bench.py --gpus N --steps K --warmup W [--config C] [--full] [--dump-outputs DIR]   (prints ONE JSON line on rank 0)
+A plain run only sets up, warms up, times the K steps and prints the line; `--full` adds the instrumented roofline pass, the
+second-dtype pass, config 2's plain-flow companion and the CPU baseline to the same line. `--dump-outputs DIR` writes the outputs
+of the last timed step (dump_outputs).
 """
 import argparse
 import json
@@ -207,16 +210,17 @@ def requests_for(vit, inp, dev, vit_comm=None):
                  ids_cmp_mask=mask, patch_positions=ppos) for g in range(G)]
 
 
-def front_half(vit, agent, tok, inp, n_text, dev=None, vit_comm=None):
+def front_half(vit, agent, tok, inp, n_text, dev=None, vit_comm=None, return_ids=False):
     """Paths A + B for BATCH requests: GPU preprocessing, ViT on all crops at once, then the BATCH greedy decodes in lock
-    step. Returns the image-generation features [BATCH, 64, 4096]."""
+    step. Returns the image-generation features [BATCH, 64, 4096] (return_ids: and the generated ids [BATCH, new tokens])."""
     dev = dev or agent.llm.device
     reqs = requests_for(vit, inp, dev, vit_comm=vit_comm)
     outs = agent.generate_batch(tok, reqs, max_new_tokens=n_text + 66 + 1, eos_token_id=None,
                                 force_image_at=n_text)                          # path B, G sequences in lock step
     for out in outs:
         assert out["has_img_output"] and out["img_gen_feat"].shape == (1, 64, 4096), "transcript did not yield an image"
-    return torch.cat([o["img_gen_feat"] for o in outs], dim=0)
+    feats = torch.cat([o["img_gen_feat"] for o in outs], dim=0)
+    return (feats, torch.stack([o["generate_ids"] for o in outs])) if return_ids else feats
 
 
 def back_half(adapter, feats, steps_unet, seed, **kw):
@@ -232,6 +236,8 @@ def back_half(adapter, feats, steps_unet, seed, **kw):
 # workloads (one per BASELINE config)
 # ---------------------------------------------------------------------------------------------------------------------
 class Workload:
+    """step(seed) runs one timed step and returns what a caller of that path receives: {name: tensor}."""
+
     def __init__(self, a, dev, dtype):
         self.a, self.dev, self.dtype, self.tok = a, dev, dtype, BenchTokenizer()
         self.setup()
@@ -250,8 +256,8 @@ class Headline(Workload):
         assert len(self.inp[1]) == 165
 
     def step(self, seed):
-        feats = front_half(self.vit, self.agent, self.tok, self.inp, self.a.text_tokens, self.dev)
-        return back_half(self.adapter, feats, self.a.unet_steps, seed)
+        feats, ids = front_half(self.vit, self.agent, self.tok, self.inp, self.a.text_tokens, self.dev, return_ids=True)
+        return {"generate_ids": ids, "image": back_half(self.adapter, feats, self.a.unet_steps, seed)}
 
     def flops(self):
         return 2 * FLOP_VIT_CROP + (165 + 128) * FLOP_LLM_TOKEN + 2 * self.a.unet_steps * FLOP_UNET_SAMPLE \
@@ -278,7 +284,7 @@ class DetokOneStep(Workload):                                                   
         out = self.adapter.generate(image_tensor=x, num_inference_steps=1, seed=[seed * BATCH + g for g in range(BATCH)],
                                     output_type="latent")
         assert out.shape == (BATCH, 4, 128, 128)
-        return out
+        return {"latents": out}
 
     def flops(self):
         return 2 * FLOP_VIT_CROP + 2 * FLOP_UNET_SAMPLE
@@ -293,7 +299,7 @@ class Comprehension(Workload):                                                  
         reqs = requests_for(self.vit, self.inp, self.dev)
         outs = self.agent.generate_batch(self.tok, reqs, max_new_tokens=128, eos_token_id=None)
         assert all(len(o["generate_ids"]) == 128 for o in outs)
-        return outs
+        return {"generate_ids": torch.stack([o["generate_ids"] for o in outs])}
 
     def flops(self):
         return 2 * FLOP_VIT_CROP + (165 + 128) * FLOP_LLM_TOKEN
@@ -309,7 +315,8 @@ class TextToImage(Workload):                                                    
         reqs = [dict(input_ids=[self.ids]) for _ in range(BATCH)]
         outs = self.agent.generate_batch(self.tok, reqs, max_new_tokens=8 + 66 + 1, eos_token_id=None, force_image_at=8)
         feats = torch.cat([o["img_gen_feat"] for o in outs], dim=0)
-        return back_half(self.adapter, feats, self.a.unet_steps, seed)
+        return {"generate_ids": torch.stack([o["generate_ids"] for o in outs]),
+                "image": back_half(self.adapter, feats, self.a.unet_steps, seed)}
 
     def flops(self):
         return (64 + 75) * FLOP_LLM_TOKEN + 2 * self.a.unet_steps * FLOP_UNET_SAMPLE + (FLOP_VAE_DECODE if USE_VAE else 0.0)
@@ -322,8 +329,9 @@ class Edit(Workload):                                                           
         self.src = torch.randn(1, 4, 128, 128, generator=torch.Generator().manual_seed(7))   # VAE-encoded source stand-in
 
     def step(self, seed):
-        feats = front_half(self.vit, self.agent, self.tok, self.inp, 8, self.dev)
-        return back_half(self.adapter, feats, self.a.unet_steps, seed, image_latents=self.src.repeat(BATCH, 1, 1, 1))
+        feats, ids = front_half(self.vit, self.agent, self.tok, self.inp, 8, self.dev, return_ids=True)
+        return {"generate_ids": ids,
+                "image": back_half(self.adapter, feats, self.a.unet_steps, seed, image_latents=self.src.repeat(BATCH, 1, 1, 1))}
 
     def flops(self):
         return 2 * FLOP_VIT_CROP + (181 + 75) * FLOP_LLM_TOKEN + 3 * self.a.unet_steps * FLOP_UNET_SAMPLE \
@@ -344,7 +352,7 @@ class MultiTurn(Workload):                                                      
         reqs = requests_for(self.vit, self.inp, self.dev)                       # ViT B = 20 per request
         self.agent._conv = {}                                                   # every step is a NEW conversation
         ids = list(self.inp[1])
-        pre = []
+        pre, res = [], {}
         for turn in range(3):
             last = turn == 2
             for r in reqs:
@@ -354,11 +362,13 @@ class MultiTurn(Workload):                                                      
             outs = self.agent.generate_batch(self.tok, reqs, max_new_tokens=(8 + 67) if last else 64, eos_token_id=None,
                                              force_image_at=8 if last else None, reuse_cache=bool(self.a.kv_reuse))
             pre.append(self.agent.last_prefill_tokens[0])
+            res["generate_ids_turn%d" % turn] = torch.stack([o["generate_ids"] for o in outs])
             if not last:
                 ids = ids + outs[0]["generate_ids"].tolist() + self.turn_text[turn]   # every request shares the transcript
         self.prefilled = pre
         feats = torch.cat([o["img_gen_feat"] for o in outs], dim=0)
-        return back_half(self.adapter, feats, self.a.unet_steps, seed)
+        res["image"] = back_half(self.adapter, feats, self.a.unet_steps, seed)
+        return res
 
     def flops(self):
         T0 = len(self.inp[1])
@@ -380,6 +390,7 @@ class StubWorkload(Workload):
 
     def step(self, seed):
         time.sleep(0.01)
+        return {"seed": torch.tensor([seed])}
 
     def flops(self):
         return 0.0
@@ -402,18 +413,19 @@ class Pipeline:
     def submit(self, seed):
         w = self.w
         with torch.cuda.stream(self.s_front):
-            feats = front_half(w.vit, w.agent, w.tok, w.inp, w.a.text_tokens, w.dev)
+            feats, ids = front_half(w.vit, w.agent, w.tok, w.inp, w.a.text_tokens, w.dev, return_ids=True)
             ev = torch.cuda.Event()
             ev.record(self.s_front)
         with torch.cuda.stream(self.s_back):
             self.s_back.wait_event(ev)
             lat = back_half(w.adapter, feats, w.a.unet_steps, seed)
-        self.keep.append((feats, lat))          # keep tensors alive until both streams are drained
+        self.keep.append((feats, ids, lat))     # keep tensors alive until both streams are drained
 
     def drain(self):
+        """What each submitted request returned, as Headline.step returns it."""
         self.s_front.synchronize()
         self.s_back.synchronize()
-        out = [l for _, l in self.keep]
+        out = [{"generate_ids": ids, "image": lat} for _, ids, lat in self.keep]
         self.keep = []
         return out
 
@@ -805,6 +817,42 @@ def cpu_baseline(config=0, full_config1=False):
                       % (cores, t_vit[0], t_vit[1], t_pre, t_dec, t_u, t_total)}
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 22      # outputs with more elements are written as this many elements at fixed, seeded positions
+
+
+def dump_outputs(outputs, out_dir):
+    """--dump-outputs: every output of the last timed step as out_dir/<name>.npy in float32 (exact for the uint8 images, 16-bit
+    tensors and token ids). An output of more than DUMP_SAMPLE elements is written as a 1-D sample at positions drawn from a
+    fixed seed, so that two runs with the same arguments can be compared element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in sorted(outputs.items()):
+        x = t.detach()
+        if x.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, x.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            x = x.reshape(-1)[idx.to(x.device)]
+        arr = x.float().cpu().numpy()
+        total += arr.nbytes
+        assert total <= DUMP_MAX_BYTES, f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB"
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
+def extra_measurements(a, gpu, world, rank):
+    """Which measurements beyond the headline figure this run takes after its timed steps. A plain run takes none. --full takes
+    every one its --no-* switches leave on. Naming a second dtype (--also-dtype bf16 / fp16) or --cpu-baseline full asks for that
+    pass alone, with or without --full."""
+    one = gpu and world == 1
+    other = a.also_dtype
+    if other == "auto":
+        other = {"fp16": "bf16", "bf16": "fp16"}[a.dtype] if (a.full and one and a.config == 0) else "none"
+    return {"roofline": a.full and gpu and rank == 0 and not a.no_roofline,
+            "second_dtype": other if (one and other not in ("none", a.dtype)) else None,
+            "companion": a.full and one and a.config == 2 and not a.no_companion,
+            "cpu_baseline": (a.full or a.cpu_baseline == "full") and one and not a.no_cpu_baseline}
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -822,7 +870,8 @@ def parse_args(argv=None):
                          "full-size parity is asserted at north_star's 1e-3 (bf16: 1.2e-2, DESIGN.md §7)")
     ap.add_argument("--also-dtype", default="auto", choices=["auto", "none", "bf16", "fp16"],
                     help="after the timed run, time a short pass (1 warm-up + 2 steps) in a second dtype and report it as "
-                         "value_<dtype> in the same JSON line. auto: the other 16-bit type for config 0 on one GPU, else none")
+                         "value_<dtype> in the same JSON line. auto: with --full, the other 16-bit type for config 0 on one GPU, "
+                         "else none; bf16 / fp16: that pass, with or without --full")
     ap.add_argument("--unet-steps", type=int, default=50)
     ap.add_argument("--text-tokens", type=int, default=61)
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of HIP-graph replay (profiling aid)")
@@ -840,11 +889,17 @@ def parse_args(argv=None):
                          "bf16 planes, fp32 accumulation; fast: single 16-bit operands; auto: what the reference would do for --dtype")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline", default="sample", choices=["sample", "full"],
-                    help="sample (default): bounded pieces, 1 warm-up + median of 3, extrapolated to a config-0 generation; full (with "
-                         "--config 1): BASELINE config 1 end to end on the host, un-extrapolated (minutes)")
+                    help="sample (default, with --full): bounded pieces, 1 warm-up + median of 3, extrapolated to a config-0 generation; "
+                         "full (with --config 1; runs with or without --full): BASELINE config 1 end to end on the host, un-extrapolated (minutes)")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--profile-markers", action="store_true",
                     help="bracket the timed region with sx_profile_marker dispatches (tools/kstats_step.py: per-kernel table of the step only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed run, also take the measurements beyond the headline figure: the instrumented roofline pass, "
+                         "the second-dtype pass (--also-dtype), config 2's plain-flow companion and the CPU baseline (each still "
+                         "subject to its own --no-* switch; extra_measurements). Off: set up, warm up, time --steps steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32; large outputs as a fixed, seeded sample)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo: CPU launch-path test only (with --stub)")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)
     return ap.parse_args(argv)
@@ -890,13 +945,16 @@ def main(argv=None):
         pipe = Pipeline(w) if (a.overlap and a.config == 0 and gpu) else None
 
         def run(seed_list):
+            out = None
             if pipe is None:
                 for sd_ in seed_list:
-                    w.step(sd_)
+                    out = w.step(sd_)
             else:
                 for sd_ in seed_list:
                     pipe.submit(sd_)
-                pipe.drain()
+                done = pipe.drain()
+                out = done[-1] if done else None
+            return out
         run([100 + i for i in range(a.warmup)])
         sync()
         du.barrier(ctx)
@@ -906,7 +964,7 @@ def main(argv=None):
             _sxlib.load().sx_profile_marker(1, torch.cuda.current_stream().cuda_stream)
             sync()
         t0 = time.perf_counter()
-        run(seeds)
+        last = run(seeds)
         sync()
         if a.profile_markers and gpu:
             _sxlib.load().sx_profile_marker(2, torch.cuda.current_stream().cuda_stream)
@@ -918,24 +976,26 @@ def main(argv=None):
         # per-rank line on stderr (the driver's log shows every rank's own clock next to the max that the JSON line uses)
         print(f"[bench rank {rank}/{world}] device {seen[rank].get('device')} {seen[rank].get('device_id')}: {a.steps} steps x {a.batch} "
               f"generations in {dt_local:.3f} s (max over ranks {dt:.3f} s)", file=sys.stderr, flush=True)
+        if a.dump_outputs and rank == 0 and last is not None:
+            dump_outputs(last, a.dump_outputs)
+        last = None
         # what actually ran (the model's own flag, not the command line): ADVICE r5
         _llm = getattr(getattr(w, "agent", None), "llm", None)
         llm_mode = None if _llm is None else (
             ("precise (fp32-grade activations: two 16-bit operand planes, fp32 q / k / RoPE / attention; KV cache: k fp32, v %s; 40-layer "
              "logits asserted at 1e-3)" % ("16-bit (mixed cache)" if getattr(_llm, "kv_v16", False) else "fp32"))
             if _llm.precise else "plain 16-bit (one rounding per MFMA operand, 16-bit KV cache; 40-layer logits asserted at 3e-3)")
+        extra = extra_measurements(a, gpu, world, rank)
         roof = phases = None
-        if rank == 0 and gpu and not a.no_roofline:
+        if extra["roofline"]:
             try:
                 roof, phases = measure_roofline(w)
             except Exception as ex:      # the timed result above stands on its own: report the failure instead of losing the line
                 roof, phases = {"error": repr(ex)}, None
         # second dtype, short pass (same workload, same kernels, other operand type) → value_<dtype> in the same line
-        other = a.also_dtype
-        if other == "auto":
-            other = ({"fp16": "bf16", "bf16": "fp16"}[a.dtype]) if (a.config == 0 and world == 1 and gpu) else "none"
+        other = extra["second_dtype"]
         second = None
-        if other not in ("none", a.dtype) and gpu and world == 1:
+        if other is not None:
             try:
                 import gc
                 desc0, flops0 = w.describe(), w.flops()
@@ -959,7 +1019,7 @@ def main(argv=None):
         # BASELINE config 2 companion: the same workload at 32 lock-step sequences = the plain 16-bit LLM flow (outside north_star's
         # 1e-3: 2.3e-3 at 40 layers, asserted at 3e-3 by tests/test_fulldepth_gpu.py::test_llama_13b_40_layers_plain16_flow)
         plain32 = None
-        if a.config == 2 and gpu and world == 1 and not a.no_companion:
+        if extra["companion"]:
             try:
                 import gc
                 desc2, flops2 = w.describe(), w.flops()
@@ -1025,11 +1085,11 @@ def main(argv=None):
         if roof is not None:
             rec["roofline"] = roof
             rec["roofline_phases"] = phases
-        if gpu and not a.no_cpu_baseline and world == 1:
+        if extra["cpu_baseline"]:
             try:
                 rec["cpu_baseline"] = cpu_baseline(a.config, full_config1=(a.cpu_baseline == "full" and a.config == 1))
                 # the un-extrapolated CPU figure (BASELINE config 1 end to end on the host cores) is measured once per
-                # round by `bench.py --config 1 --cpu-baseline full` (≈ 1-2 min of CPU) and quoted here from its committed line
+                # round by `bench.py --full --config 1 --cpu-baseline full` (≈ 1-2 min of CPU) and quoted here from its committed line
                 f1 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "r6_bench_config1_cpu_full.json")
                 if not os.path.exists(f1):
                     f1 = f1.replace("r6_", "r5_")

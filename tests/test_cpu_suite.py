@@ -435,6 +435,52 @@ def test_bench_gpus8_launch_path_and_ranks_seen():
     assert out.stderr.count("[bench rank ") == 8
 
 
+def test_bench_plain_run_steps_and_dump_outputs(tmp_path):
+    """A plain run times exactly --steps steps (the stub step sleeps 10 ms), and --dump-outputs writes what the last timed step
+    returned (the stub returns its seed; timed seeds are 0 .. steps - 1) as float32."""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                          "--backend", "gloo", "--stub", "--dump-outputs", str(tmp_path / "out")],
+                         capture_output=True, text=True, timeout=300, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert rec["steps"] == 5 and rec["warmup"] == 2 and rec["ms_per_step"] >= 10.0
+    seed = np.load(tmp_path / "out" / "seed.npy")
+    assert seed.dtype == np.float32 and seed.tolist() == [4.0]
+
+
+def test_bench_extra_measurements_need_full():
+    """On one GPU, a plain run takes none of the measurements beyond the headline figure; --full takes those its --no-* switches
+    leave on; an explicitly named second dtype or --cpu-baseline full takes that pass alone."""
+    import bench
+    x = lambda *argv, gpu=True, world=1, rank=0: bench.extra_measurements(bench.parse_args(list(argv)), gpu, world, rank)
+    off = {"roofline": False, "second_dtype": None, "companion": False, "cpu_baseline": False}
+    assert x() == off and x("--config", "2") == off and x("--config", "1") == off
+    assert x("--full") == {"roofline": True, "second_dtype": "bf16", "companion": False, "cpu_baseline": True}
+    assert x("--full", "--dtype", "bf16")["second_dtype"] == "fp16"
+    assert x("--full", "--config", "2") == {"roofline": True, "second_dtype": None, "companion": True, "cpu_baseline": True}
+    assert x("--full", "--no-roofline", "--no-cpu-baseline", "--also-dtype", "none", "--config", "2", "--no-companion") == off
+    assert x("--also-dtype", "bf16") == dict(off, second_dtype="bf16")
+    assert x("--config", "1", "--cpu-baseline", "full") == dict(off, cpu_baseline=True)
+    assert x("--full", gpu=False) == off                                     # the stub: nothing beyond the timed steps
+    assert x("--full", world=2) == dict(off, roofline=True) and x("--full", world=2, rank=1) == off
+
+
+def test_bench_dump_outputs_samples_large_outputs(tmp_path):
+    """Outputs above DUMP_SAMPLE elements are written as a sample at seeded positions: the same values on every run, exact in float32."""
+    import bench
+    pos = torch.arange(5 * (bench.DUMP_SAMPLE // 5 + 2000), dtype=torch.float32).view(-1, 5)   # each value names its position (exact in float32)
+    n = pos.numel()
+    ids = torch.randint(3, 32000, (4, 128), generator=torch.Generator().manual_seed(1))
+    for d in ("a", "b"):
+        bench.dump_outputs({"image": pos, "generate_ids": ids}, str(tmp_path / d))
+    a, b = np.load(tmp_path / "a" / "image.npy"), np.load(tmp_path / "b" / "image.npy")
+    assert a.shape == (bench.DUMP_SAMPLE,) and a.dtype == np.float32 and np.array_equal(a, b)
+    assert a.min() >= 0 and a.max() < n and (np.diff(a) >= 0).all() and len(np.unique(a)) > bench.DUMP_SAMPLE // 2
+    assert np.array_equal(np.load(tmp_path / "a" / "generate_ids.npy"), ids.numpy().astype(np.float32))
+
+
 def test_ranks_seen_flags_shared_devices(monkeypatch):
     """world = 1 returns early; the duplicate-device / missing-rank logic is exercised with a mocked all_gather_object:
     two ranks reporting one device id are flagged (fatal only with strict_devices), a group that returns a wrong rank set raises."""

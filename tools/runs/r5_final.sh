@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 cd $R
-timeout 700 python bench.py --steps 5 --warmup 2 > $O/r5_bench_line.json 2> $O/r5_bench_line.err; echo "bench rc=$?"; head -c 300 $O/r5_bench_line.json; echo
+timeout 700 python bench.py --full --steps 5 --warmup 2 > $O/r5_bench_line.json 2> $O/r5_bench_line.err; echo "bench rc=$?"; head -c 300 $O/r5_bench_line.json; echo
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/r5_ks
 timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r5_ks -- python $R/bench.py --steps 1 --warmup 0 --no-graph --chains 1 --also-dtype none --no-cpu-baseline --no-roofline --profile-markers > $O/r5_bench_under_rocprof.log 2>&1; echo "kstats rc=$?"

@@ -7,7 +7,7 @@ O=$R/gpurun_out
 cd $R
 timeout 500 bash tools/pmc_unet.sh fp16 > $O/r5_pmc_unet.out 2>&1; head -c 500 $O/r5_unet_pmc_traffic.json; echo
 [ -s $O/r5_unet_pmc_traffic.json ] && cp $O/r5_unet_pmc_traffic.json profiles/r5_unet_pmc_traffic.json       # bench.py reads profiles/ (same box, same sources)
-timeout 600 python bench.py --steps 5 --warmup 2 > $O/r5_bench_line.json 2> $O/r5_bench_line.err; echo "bench rc=$?"; head -c 500 $O/r5_bench_line.json; echo
+timeout 600 python bench.py --full --steps 5 --warmup 2 > $O/r5_bench_line.json 2> $O/r5_bench_line.err; echo "bench rc=$?"; head -c 500 $O/r5_bench_line.json; echo
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/r5_ks
 timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r5_ks -- python $R/bench.py --steps 1 --warmup 0 --no-graph --chains 1 --also-dtype none --no-cpu-baseline --no-roofline --profile-markers > $O/r5_bench_under_rocprof.log 2>&1; echo "kstats rc=$?"

@@ -10,7 +10,7 @@ for c in 1 2 2b 3 4 5; do
   extra="--no-cpu-baseline"
   cc=$c
   [ $c = 2b ] && { cc=2; extra="$extra --dtype bf16"; }
-  timeout 900 python bench.py --config $cc --steps 3 --warmup 1 --also-dtype none $extra >> $O/r6_bench_configs.jsonl 2>> $O/r6_bench_configs.err
+  timeout 900 python bench.py --full --config $cc --steps 3 --warmup 1 --also-dtype none $extra >> $O/r6_bench_configs.jsonl 2>> $O/r6_bench_configs.err
 done
 python - <<PY
 import json

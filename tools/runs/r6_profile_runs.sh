@@ -7,9 +7,9 @@ O=$R/gpurun_out
 cd $R
 timeout 500 bash tools/pmc_unet.sh fp16 r6 > $O/r6_pmc_unet.out 2>&1; head -c 400 $O/r6_unet_pmc_traffic.json; echo
 [ -s $O/r6_unet_pmc_traffic.json ] && cp $O/r6_unet_pmc_traffic.json profiles/r6_unet_pmc_traffic.json       # bench.py reads profiles/ (same box, same sources)
-timeout 400 python bench.py --config 1 --cpu-baseline full --steps 3 --warmup 1 --also-dtype none --no-roofline > $O/r6_bench_config1_cpu_full.json 2> $O/r6_bench_config1_cpu_full.err; echo "config1 cpu rc=$?"
+timeout 400 python bench.py --full --config 1 --cpu-baseline full --steps 3 --warmup 1 --also-dtype none --no-roofline > $O/r6_bench_config1_cpu_full.json 2> $O/r6_bench_config1_cpu_full.err; echo "config1 cpu rc=$?"
 [ -s $O/r6_bench_config1_cpu_full.json ] && cp $O/r6_bench_config1_cpu_full.json profiles/r6_bench_config1_cpu_full.json
-timeout 900 python bench.py --steps 5 --warmup 2 > $O/r6_bench_line.json 2> $O/r6_bench_line.err; echo "bench rc=$?"; head -c 300 $O/r6_bench_line.json; echo
+timeout 900 python bench.py --full --steps 5 --warmup 2 > $O/r6_bench_line.json 2> $O/r6_bench_line.err; echo "bench rc=$?"; head -c 300 $O/r6_bench_line.json; echo
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/r6_ks
 timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/r6_ks -- python $R/bench.py --steps 1 --warmup 0 --no-graph --chains 1 --also-dtype none --no-cpu-baseline --no-roofline --profile-markers > $O/r6_bench_under_rocprof.log 2>&1; echo "kstats rc=$?"

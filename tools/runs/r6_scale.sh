@@ -30,7 +30,7 @@ rocm-smi --showtopo >> "$O/devices.txt" 2>&1 || true
 for n in 1 2 4 8; do
   [ "$n" -le "$NG" ] || continue
   echo "== bench.py --gpus $n"
-  timeout 1500 python bench.py --gpus $n --steps 5 --warmup 2 $([ $n -gt 1 ] && echo --no-roofline --no-cpu-baseline --also-dtype none) \
+  timeout 1500 python bench.py --full --gpus $n --steps 5 --warmup 2 $([ $n -gt 1 ] && echo --no-roofline --no-cpu-baseline --also-dtype none) \
       > "$O/scale_N$n.json" 2> "$O/scale_N$n.err" || echo "   bench --gpus $n failed (rc $?): see $O/scale_N$n.err"
   python - "$O/scale_N$n.json" <<'PY' || true
 import json, sys
