@@ -955,6 +955,22 @@ def test_gemm_tile_picker_host_logic():
         assert 0 <= lib.sx_gemm_pick_tile(M, N, K, 0, 0) <= 8
 
 
+def test_gemm_matrix_covers_every_kernel():
+    """tests/test_gemm_matrix_gpu.py's case table mirrors the GEMM dispatch: PP_SPECS lists every ping-pong kernel that launch_t
+    instantiates (schedule variant 0) exactly once, the lock-step tiles are SX_GEMM_DISPATCH's configs 0-6 with the same shapes, and
+    each dtype has cases on all of them — a specialization added later without a case fails here."""
+    from tests import test_gemm_matrix_gpu as gm
+    ls, pp = gm.source_kernels()
+    assert sorted(ls) == list(gm.LOCKSTEP_TILES) and all(ls[t] == gm.TILES[t][:2] for t in ls), ls
+    assert len(pp) == len(set(pp)) == 21, pp
+    keys = [k for k, _ in gm.PP_SPECS]
+    assert len(keys) == len(set(keys)) and set(keys) == set(pp), (set(pp) ^ set(keys))
+    for dt in gm.DTYPES:
+        have = {gm.kernel_of(c) for c in gm.CASES if c["dt"] == dt}
+        assert {("ls", t) for t in gm.LOCKSTEP_TILES} <= have and set(pp) <= have, dt
+        assert all(gm.kernel_of(c)[0] == "ls" or gm.kernel_of(c) in set(pp) for c in gm.CASES if c["dt"] == dt)
+
+
 def test_layernorm_fold_host_algebra_and_tile_gate():
     """ops.fold_layernorm: rstd (x W'^T - mu colsum) + bias' == LayerNorm(x) W^T + bias (fp32 weights: exact algebra up to rounding);
     GLU-packed rows fold row by row. ops.ln_fold_ok / sx_gemm_ln: the fold exists only where every neighbour GEMM runs on a

@@ -625,6 +625,8 @@ def test_gemm_fused_groupnorm_statistics(dev, dtype):
     gs = ops.GnStats(arena[0], G, H * H)
     out = ops.conv3x3(x, w, bias=torch.zeros(Co, device=dev), bias2d=b2, out_dtype=torch.float32, gn=gs)
     assert gs.ready
+    # the stored output itself: the convolution plus the per-sample time add
+    assert relerr(out, _conv_ref(x, w, None, 1, False) + b2[:, None, :]) < TOL[torch.float32]
     o64 = out.double().view(B, H * H, G, Co // G)
     ref = torch.stack([o64.sum(dim=(1, 3)), (o64 * o64).sum(dim=(1, 3))], dim=-1)
     assert torch.allclose(gs.buf, ref, rtol=2e-6, atol=1e-3), (gs.buf - ref).abs().max()
