@@ -118,11 +118,8 @@ typedef struct sx_gemm_ln_args {
 int sx_gemm_ln(const sx_gemm_args* args, const sx_gemm_ln_args* ln, void* stream);
 /* tuning/test hook: force tile config 0..8 (lock-step 128x128, 128x80, 64x128, 64x64, 256x256, 256x320, 256x160; ping-pong
  * 256x256, 256x320 — the two-wave-group schedule of csrc/gemm_pp.hip); -1 = automatic (cost model); 100/101 = 2-D XCD
- * partition off/on; 200/201 = ping-pong tiles excluded from / offered to the cost model; 300+g = g tile-rows per in-XCD
- * traversal group (300 = default); 400+v = ping-pong schedule variant v (A/B builds of the bf16 256x256 linear kernel);
- * 9 = the persistent strip kernel of csrc/gemm_strip.hip for sx_gemm_ln producers (fails if the launch does not fit it);
- * 500/501 = strip kernel excluded from / offered to the automatic choice; 600 + mask = epilogue A/B switches (bit 0: the GLU
- * epilogue keeps its 8-byte stores) */
+ * partition off/on; 300+g (g = 0..64) = g tile-rows per in-XCD traversal group (300 = default). Any other value fails
+ * (SX_ERR_INVALID) and changes nothing. */
 int sx_gemm_force_tile(int cfg);
 /* tuning hook: `buf` = device buffer of 4 x uint64 per workgroup; following sx_gemm launches store s_memtime stamps
  * {start, first k-tile landed, main loop done, end} per workgroup (tools/gemm_phase_probe.py). NULL switches it off. */
@@ -255,8 +252,6 @@ typedef struct sx_attn_args {
   int32_t dtype;
 } sx_attn_args;
 int sx_attention(const sx_attn_args* args, void* stream);
-/* tuning hook (tools/lab/attn_lab): A/B builds of the flash kernel; 0 = shipped */
-int sx_attention_variant(int v);
 
 /* Small generic attention (any D <= 256, VALU, one wave per query row). Used where FLOPs are negligible:
  * Resampler MHA with head_dim 160 (agent_seed_x_i.yaml:2-7), AttentionPool2d (resampler.py:89-116),

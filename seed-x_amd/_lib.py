@@ -101,7 +101,6 @@ SIGNATURES = {
     "sx_groupnorm_sp": [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32,
                         c_i32, c_vp],
     "sx_attention": [C.POINTER(AttnArgs), c_vp],
-    "sx_attention_variant": [c_i32],
     "sx_norm_tune": [c_i32, c_i32],
     "sx_gemv_tune": [c_i32, c_i32],
     "sx_comm_alloc": [C.POINTER(c_vp), C.c_uint64],

@@ -12,8 +12,10 @@ BASE="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result"
 FAST="-ffast-math -fno-finite-math-only"
 if [ "$FORCE" = 1 ]; then rm -f "$HERE"/.obj/*.o; fi
 pids=()
-for f in gemm gemm_pp gemm_strip norm attn elementwise decode preproc comm precise; do
+objs=()
+for f in gemm gemm_pp norm attn elementwise decode preproc comm precise; do
   src="$HERE/$f.hip"; obj="$HERE/.obj/$f.o"
+  objs+=("$obj")
   if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/sx_common.h" -nt "$obj" ] || [ "$HERE/gemm_common.h" -nt "$obj" ] || [ "$HERE/../../include/seedx_hip.h" -nt "$obj" ]; then
     extra="$FAST"
     if [ "$f" = "preproc" ] || [ "$f" = "precise" ]; then extra=""; fi   # integer / IEEE-exact float work, hi + lo operand splits: no fast-math
@@ -25,5 +27,6 @@ for f in gemm gemm_pp gemm_strip norm attn elementwise decode preproc comm preci
   fi
 done
 for p in "${pids[@]}"; do wait $p; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/libseedx_hip.so" "$HERE"/.obj/*.o
+# link exactly the TUs listed above: an object left in .obj/ by an earlier build (a removed TU) must not come back
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/libseedx_hip.so" "${objs[@]}"
 echo "built $OUT/libseedx_hip.so"

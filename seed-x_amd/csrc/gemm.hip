@@ -375,7 +375,7 @@ static const TileCfg kTiles[kNumTiles] = {
     {256, 320, false, 256, 13.32f, 0.01928f, 15.12f, 0.02173f}};
 
 inline int pick_tile(int M, int N, int K, bool glu, bool conv, int force, unsigned allow = 0x7f) {
-  if (force >= 0 && force < kNumTiles && (!glu || kTiles[force].glu_ok)) return force;   // (force 9 = strip kernel: decided by the caller)
+  if (force >= 0 && force < kNumTiles && (!glu || kTiles[force].glu_ok)) return force;
   int best = 2;
   float best_t = 1e30f;
   for (int c = 0; c < kNumTiles; ++c) {
@@ -394,11 +394,6 @@ inline int pick_tile(int M, int N, int K, bool glu, bool conv, int force, unsign
 using namespace sxk_gemm;
 
 static int g_force_tile = -1;
-// The strip kernel is NOT part of the automatic choice: it is correct (bit-identical C / x16, reproducible row sums) and slower than the
-// 256x320 ping-pong producer on every production shape (profiles/r6_ab_experiments.md §1: its 128x256 sub-tiles need twice the operand
-// bytes per flop and the CU's LDS-DMA path bounds it). sx_gemm_force_tile(9) / (501) select it for the lab and the tests.
-static int g_use_strip = 0;
-namespace sxk_gemm { int g_use_pp = 1; }  // 0 = lock-step kernels only (A/B hook, sx_gemm_force_tile(200))
 extern "C" int sx_gemm_pick_tile(int M, int N, int K, int glu, int conv) {  // host-only: which tile config sx_gemm would use
   return sxk_gemm::pick_tile(M, N, K, glu != 0, conv != 0, -1, 0x1ff);
 }
@@ -408,13 +403,11 @@ extern "C" int sx_gemm_debug_stamps(void* buf) {   // tuning hook: device buffer
   return SX_OK;
 }
 
-extern "C" int sx_gemm_force_tile(int cfg) {  // tuning / test hook: -1 = automatic; 100/101 = 2-D XCD partition off/on
+extern "C" int sx_gemm_force_tile(int cfg) {  // tuning / test hook (include/seedx_hip.h)
   if (cfg == 100 || cfg == 101) { sxk_gemm::g_xcd_2d = cfg - 100; return SX_OK; }
   if (cfg >= 300 && cfg <= 364) { sxk_gemm::g_gm = cfg - 300; return SX_OK; }
-  if (cfg >= 400 && cfg <= 409) { sxk_gemm::g_pp_variant = cfg - 400; return SX_OK; }
-  if (cfg == 200 || cfg == 201) { sxk_gemm::g_use_pp = cfg - 200; return SX_OK; }
-  if (cfg == 500 || cfg == 501) { g_use_strip = cfg - 500; return SX_OK; }
-  if (cfg >= 600 && cfg <= 663) { sxk_gemm::g_tune = cfg - 600; return SX_OK; }
+  SX_CHECK(cfg >= -1 && cfg < kNumTiles, "sx_gemm_force_tile: %d is not -1, a tile config 0..%d, 100/101 or 300..364", cfg,
+           kNumTiles - 1);
   g_force_tile = cfg;
   return SX_OK;
 }
@@ -494,9 +487,6 @@ static int gemm_impl(const sx_gemm_args* a, double* gn_stats, int gn_groups, int
   p.w_bytes = (unsigned)w_bytes;
   hipStream_t st = (hipStream_t)stream;
   p.res_init = (p.residual && p.act == SX_ACT_NONE && !p.glu) ? 1 : 0;
-  // tile configs 0..6: lock-step kernels (this file); 7 / 8: ping-pong 256x256 / 256x320 (gemm_pp.hip). The cost model
-  // ranks the lock-step menu; where it picks a 256-row 8-wave tile, the ping-pong kernel of the same shape runs instead
-  // when its epilogue combination exists (forced 4 / 5 keep the lock-step kernels for A/B runs).
   // tile configs 0..6: lock-step kernels (this file); 7 / 8: ping-pong 256x256 / 256x320 (gemm_pp.hip), offered to the cost
   // model when their epilogue combination is instantiated
   if (ln) {
@@ -515,15 +505,10 @@ static int gemm_impl(const sx_gemm_args* a, double* gn_stats, int gn_groups, int
   }
   unsigned allow = 0x7f;
   if (ln) allow = 0;            // ping-pong tiles or nothing
-  if (g_use_pp || g_force_tile == 7) allow |= pp_supported(p, a->dtype, 256, a->a_mode) ? 0x80u : 0u;
-  if (g_use_pp || g_force_tile == 8) allow |= pp_supported(p, a->dtype, 320, a->a_mode) ? 0x100u : 0u;
+  allow |= pp_supported(p, a->dtype, 256, a->a_mode) ? 0x80u : 0u;
+  allow |= pp_supported(p, a->dtype, 320, a->a_mode) ? 0x100u : 0u;
   SX_CHECK(!(g_force_tile == 7 || g_force_tile == 8) || ((allow >> g_force_tile) & 1u),
            "sx_gemm: forced ping-pong tile has no kernel for this epilogue");
-  // LayerNorm producers (fp32 residual in, fp32 + 16-bit out, row sums): the persistent strip kernel when the launch has at least
-  // 3/4 of a strip per CU (fewer strips leave CUs idle that the one-tile-per-workgroup kernels would use) — forced tile 9 = always
-  if (p.ln_out && (g_force_tile == 9 || (g_use_strip && g_force_tile < 0 && a->M / 128 >= 192)) && strip_supported(p, a->a_mode))
-    return launch_strip(p, a->dtype, st);
-  SX_CHECK(g_force_tile != 9, "sx_gemm: forced strip kernel does not support this launch");
   if (ln) {
     // the fold exists on the tiles the cost model gives this shape without it, or not at all (no silent change of tile)
     const int plain = pick_tile(a->M, a->N, Kk, a->glu != 0, false, g_force_tile, 0x1ff);

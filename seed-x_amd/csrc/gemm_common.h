@@ -17,8 +17,6 @@ struct GemmP {
   int tiles_m, tiles_n, xm, xn;   // tile grid and its XCD partition (xm x xn == 8, or 0 = linear remap)
   int gm;                         // tile-rows per group of the in-XCD traversal
   int res_init;                   // residual is the accumulators' initial value (act == none, no GLU): no epilogue loads
-  int n_tiles;                    // persistent kernels: logical grid size (blocks loop bid += gridDim.x)
-  int tune;                       // A/B switches (sx_gemm_force_tile 600 + mask): bit 0 = GLU epilogue keeps its 8-byte stores
   unsigned a_bytes, w_bytes;
   unsigned long long* dbg;        // tuning hook: per-block s_memtime stamps [block][4] = start, first tile landed, main loop done, end
   // fused GroupNorm statistics of the stored fp32 output (sx_gemm_gn; ping-pong tiles only): stats[sample][group][2] += (sum, sum of
@@ -93,7 +91,6 @@ inline int plan_grid(GemmP& p, int BM, int BN, int xcd_2d, int gm_force) {
     if (p.xm) grid = 8 * ((p.tiles_m + p.xm - 1) / p.xm) * ((p.tiles_n + p.xn - 1) / p.xn);
     p.gm = gm_force > 0 ? gm_force : 8;   // tools/bench_gm.py: 8 is best or within 1 % on every multi-round shape
   }
-  p.n_tiles = grid;
   return grid;
 }
 
@@ -102,15 +99,8 @@ inline int plan_grid(GemmP& p, int BM, int BN, int xcd_2d, int gm_force) {
 int launch_pp(const GemmP& p, int dtype, int bn, int a_mode, hipStream_t st);
 bool pp_supported(const GemmP& p, int dtype, int bn, int a_mode);
 
-// persistent strip kernel of the fp32-residual LayerNorm producers (gemm_strip.hip): whole 128-row strips per workgroup, two
-// accumulator sets, residual loads / output stores under the main loop. strip_supported: the launch fits its contract.
-int launch_strip(const GemmP& p, int dtype, hipStream_t st);
-bool strip_supported(const GemmP& p, int a_mode);
-
 extern unsigned long long* g_dbg;
 extern int g_gm;
 extern int g_xcd_2d;
-extern int g_pp_variant;   // tuning hook (sx_gemm_force_tile 4xx)
-extern int g_tune;         // tuning hook (sx_gemm_force_tile 600 + mask) → GemmP::tune
 
 }  // namespace sxk_gemm

@@ -44,7 +44,7 @@ namespace sxk_gemm {
 
 // LN: 0 = none; 1 = LayerNorm-fold consumer (per-row scale / shift ahead of bias and activation); 2 = producer (fp32 output + its
 // 16-bit copy + per-row sums) — see GemmP::ln_*
-template <typename TT, int BN, int AMODE, bool OUT32, int ACT, bool GLU, int VAR, int LN = 0>
+template <typename TT, int BN, int AMODE, bool OUT32, int ACT, bool GLU, int LN = 0>
 __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef typename TT::vec8 vec8;
@@ -232,17 +232,17 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
   wait_vmcnt<WAITN>();   // X(0), Y(0) landed (this wave's share)
   PP_SYNC();
   if (p.dbg) t_first = __builtin_amdgcn_s_memtime();
-  if (g == 1 && VAR != 3) PP_SYNC();   // group 1 runs one barrier interval behind group 0 (VAR 3: lock-step, A/B only)
+  if (g == 1) PP_SYNC();   // group 1 runs one barrier interval behind group 0
 
   vec8 af[FH], wf0[FN], wf1[FN];
 
   auto mma = [&](const vec8* wf, int h) {
-    if (VAR != 1) __builtin_amdgcn_s_setprio(1);
+    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int i = 0; i < FN; ++i)
 #pragma unroll
       for (int j = 0; j < FH; ++j) acc[i][h * FH + j] = TT::mfma16(wf[i], af[j], acc[i][h * FH + j]);
-    if (VAR != 1) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
   };
   auto lgkm0 = [&]() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };
 
@@ -256,7 +256,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
 #pragma unroll
     for (int i = 0; i < FN; ++i) wf0[i] = *(const vec8*)(sbuf + w_frag + i * 2048 + frag_sw[0]);
     dma_a(2, BUF ^ 1, u + 1, kz);
-    if (VAR != 2) lgkm0();
+    lgkm0();
     PP_SYNC();
     mma(wf0, 0);
     PP_SYNC();
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
     dma_a(3, BUF ^ 1, u + 1, kz);
     tap_next(kz);
     wait_vmcnt<WAITN>();
-    if (VAR != 2) lgkm0();
+    lgkm0();
     PP_SYNC();
     mma(wf1, 0);
     PP_SYNC();
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
 #pragma unroll
     for (int j = 0; j < FH; ++j) af[j] = *(const vec8*)(sbuf + a_frag + 8192 + j * 2048 + frag_sw[0]);
     issue_x(BUF, u + 2, kx);
-    if (VAR != 2) lgkm0();
+    lgkm0();
     PP_SYNC();
     mma(wf0, 1);
     PP_SYNC();
@@ -286,7 +286,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
     issue_y(BUF, u + 2);
     tap_next(kx);
     wait_vmcnt<WAITN>();
-    if (VAR != 2) lgkm0();
+    lgkm0();
     PP_SYNC();
     mma(wf1, 1);
     PP_SYNC();
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
     ktile(std::integral_constant<int, 0>{}, kt);
     if (kt + 1 < nkt) ktile(std::integral_constant<int, 1>{}, kt + 1);
   }
-  if (g == 0 && VAR != 3) PP_SYNC();   // pairs with group 1's last barrier
+  if (g == 0) PP_SYNC();   // pairs with group 1's last barrier
   wait_vmcnt<0>();         // the zero-fill DMAs of the k-tiles past the end must not outlive the block's LDS allocation
 
   if (p.dbg) t_main = __builtin_amdgcn_s_memtime();
@@ -335,7 +335,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
     pair_ok[i] = (2 * i + 1 < FN) && (n0 + wc * TN + i * 32 + 32 <= lim);  // wave-uniform: the whole 32-col pair is stored
   }
   // GLU outputs of this wave: columns [(n0 + wc TN) / 2, + 32) of the [M][N / 2] output — wide stores when all 32 exist and are aligned
-  const bool glu_wide = GLU && !OUT32 && !(p.tune & 1) && (p.ldc & 7) == 0 && (((size_t)p.C) & 15) == 0 &&
+  const bool glu_wide = GLU && !OUT32 && (p.ldc & 7) == 0 && (((size_t)p.C) & 15) == 0 &&
                         ((n0 + wc * TN) >> 1) + 32 <= (p.n_valid < (p.N >> 1) ? p.n_valid : (p.N >> 1));
   auto act1 = [&](f32x4_t x) -> f32x4_t {
     if (ACT == SX_ACT_GELU) {
@@ -571,17 +571,13 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
 #endif
 }
 
-int g_pp_variant = 0;
-int g_tune = 0;
-
-template <typename TT, int BN, int AMODE, bool OUT32, int ACT, bool GLU, int VAR, int LN = 0>
+template <typename TT, int BN, int AMODE, bool OUT32, int ACT, bool GLU, int LN = 0>
 static int launch_one(const GemmP& p0, hipStream_t st) {
   GemmP p = p0;
   p.dbg = g_dbg;
-  p.tune = g_tune;
   const int grid = plan_grid(p, 256, BN, g_xcd_2d, g_gm);
   constexpr size_t lds = 2 * (size_t)(256 + BN) * 128 + (LN == 1 ? 2048 : 0);      // + the consumer's (rstd, -rstd mu) table
-  auto k = gemm_pp_kernel<TT, BN, AMODE, OUT32, ACT, GLU, VAR, LN>;
+  auto k = gemm_pp_kernel<TT, BN, AMODE, OUT32, ACT, GLU, LN>;
   static hipError_t attr[16];
   static bool done[16];
   int dev = 0;
@@ -629,21 +625,18 @@ bool pp_supported(const GemmP& p, int dtype, int bn, int a_mode) {
 template <typename TT>
 static int launch_t(const GemmP& p, int dtype, int bn, int a_mode, hipStream_t st) {
   const int e = epi_code(p, dtype);
-#define PP_CASE(BNV, AM, O32, ACTV, GLUV) return launch_one<TT, BNV, AM, O32, ACTV, GLUV, 0>(p, st)
+#define PP_CASE(BNV, AM, O32, ACTV, GLUV) return launch_one<TT, BNV, AM, O32, ACTV, GLUV>(p, st)
   if (p.ln_in) {
-    if (e == 2) return launch_one<TT, 256, SX_A_LINEAR, false, SX_ACT_GELU, true, 0, 1>(p, st);
-    if (bn == 256) return launch_one<TT, 256, SX_A_LINEAR, false, SX_ACT_NONE, false, 0, 1>(p, st);
-    return launch_one<TT, 320, SX_A_LINEAR, false, SX_ACT_NONE, false, 0, 1>(p, st);
+    if (e == 2) return launch_one<TT, 256, SX_A_LINEAR, false, SX_ACT_GELU, true, 1>(p, st);
+    if (bn == 256) return launch_one<TT, 256, SX_A_LINEAR, false, SX_ACT_NONE, false, 1>(p, st);
+    return launch_one<TT, 320, SX_A_LINEAR, false, SX_ACT_NONE, false, 1>(p, st);
   }
   if (p.ln_out) {
-    if (bn == 256) return launch_one<TT, 256, SX_A_LINEAR, true, SX_ACT_NONE, false, 0, 2>(p, st);
-    return launch_one<TT, 320, SX_A_LINEAR, true, SX_ACT_NONE, false, 0, 2>(p, st);
+    if (bn == 256) return launch_one<TT, 256, SX_A_LINEAR, true, SX_ACT_NONE, false, 2>(p, st);
+    return launch_one<TT, 320, SX_A_LINEAR, true, SX_ACT_NONE, false, 2>(p, st);
   }
   if (a_mode == SX_A_LINEAR) {
     if (bn == 256) {
-      if (std::is_same<TT, BF16>::value && e == 0 && g_pp_variant == 1) return launch_one<BF16, 256, SX_A_LINEAR, false, SX_ACT_NONE, false, 1>(p, st);
-      if (std::is_same<TT, BF16>::value && e == 0 && g_pp_variant == 2) return launch_one<BF16, 256, SX_A_LINEAR, false, SX_ACT_NONE, false, 2>(p, st);
-      if (std::is_same<TT, BF16>::value && e == 0 && g_pp_variant == 3) return launch_one<BF16, 256, SX_A_LINEAR, false, SX_ACT_NONE, false, 3>(p, st);
       switch (e) {
         case 0: PP_CASE(256, SX_A_LINEAR, false, SX_ACT_NONE, false);
         case 1: PP_CASE(256, SX_A_LINEAR, false, SX_ACT_GELU, false);

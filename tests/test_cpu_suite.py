@@ -955,9 +955,29 @@ def test_gemm_tile_picker_host_logic():
         assert 0 <= lib.sx_gemm_pick_tile(M, N, K, 0, 0) <= 8
 
 
-def test_gemm_matrix_covers_every_kernel():
+def test_gemm_force_tile_accepts_only_its_four_forms():
+    """sx_gemm_force_tile (host state, no launch): -1, a tile config 0..8, 100/101 (2-D XCD partition off/on) and 300..364 (in-XCD
+    traversal group height) are accepted; any other code fails with a message and changes nothing."""
+    from seedx_amd import _lib
+    lib = _lib.load()
+    shapes = [(32768, 3840, 1280, 0, 0), (32768, 10240, 1280, 1, 0), (2048, 1280, 1280, 0, 0), (262144, 320, 2880, 0, 1)]
+    before = [lib.sx_gemm_pick_tile(*s) for s in shapes]
+    try:
+        for cfg in [-1, *range(9), 100, 101, *range(300, 365)]:
+            assert lib.sx_gemm_force_tile(cfg) == 0, cfg
+        assert lib.sx_gemm_force_tile(-1) == 0
+        for cfg in (9, 200, 400, 501, 600, -2, 10, 102, 365):
+            assert lib.sx_gemm_force_tile(cfg) == 1, cfg            # SX_ERR_INVALID
+            assert "sx_gemm_force_tile" in lib.sx_last_error().decode(), cfg
+            assert [lib.sx_gemm_pick_tile(*s) for s in shapes] == before, cfg
+    finally:
+        for cfg in (-1, 101, 300):                                # the defaults
+            lib.sx_gemm_force_tile(cfg)
+
+
+def test_gemm_matrix_covers_every_launched_kernel():
     """tests/test_gemm_matrix_gpu.py's case table mirrors the GEMM dispatch: PP_SPECS lists every ping-pong kernel that launch_t
-    instantiates (schedule variant 0) exactly once, the lock-step tiles are SX_GEMM_DISPATCH's configs 0-6 with the same shapes, and
+    instantiates exactly once, the lock-step tiles are SX_GEMM_DISPATCH's configs 0-6 with the same shapes, and
     each dtype has cases on all of them — a specialization added later without a case fails here."""
     from tests import test_gemm_matrix_gpu as gm
     ls, pp = gm.source_kernels()
@@ -1043,41 +1063,6 @@ def test_from_pretrained_with_peft_adapter_directory(tmp_path):
     assert torch.equal(m._sd[p + "post_attention_layernorm.weight"], base[p + "post_attention_layernorm.weight"])
     plain = LlamaForCausalLM.from_pretrained(str(bdir))
     assert torch.equal(plain._sd[p + "mlp.up_proj.weight"], base[p + "mlp.up_proj.weight"])
-
-
-def test_attn64_accumulators_are_private(tmp_path):
-    """`attn64_kernel` (csrc/attn.hip; lab-only experiment of round 6) keeps its O^T accumulators in a[0:95] behind the compiler's back:
-    every asm statement that touches them names the registers literally and clobbers all 96. That is only sound while the compiler
-    itself never allocates one of them — checked here on the ISA it generates (cross-compiles without a GPU)."""
-    hipcc = "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "seed-x_amd", "csrc", "attn.hip")
-    out = tmp_path / "attn.s"
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffast-math", "-fno-finite-math-only", "-mllvm",
-                    "-amdgpu-mfma-vgpr-form=1", "-S", "--cuda-device-only", src, "-o", str(out)], check=True, capture_output=True)
-    lines = out.read_text().splitlines()
-    kernels, cur, in_asm, bad = 0, None, False, []
-    for ln in lines:
-        m = re.match(r"^(_ZN8sxk_attn13attn64_kernel\w+):", ln)
-        if m:
-            cur, kernels = m.group(1), kernels + 1
-            continue
-        if cur is None:
-            continue
-        if "s_endpgm" in ln:
-            cur = None
-            continue
-        if "ASMSTART" in ln:
-            in_asm = True
-        elif "ASMEND" in ln:
-            in_asm = False
-        elif not in_asm:
-            for r in re.finditer(r"\ba(\d+)\b|\ba\[(\d+):\d+\]", ln.split(";")[0]):
-                if int(r.group(1) or r.group(2)) < 96:
-                    bad.append((cur, ln.strip()))
-    assert kernels >= 2, "attn64_kernel instantiations not found in the ISA"
-    assert not bad, f"compiler-generated use of a private accumulator register: {bad[:3]}"
 
 
 def test_llm_mode_selection_and_memory_footprint(monkeypatch):

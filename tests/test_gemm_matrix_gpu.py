@@ -14,7 +14,7 @@ Production shapes (the config-0 UNet step at 32 CFG rows, the ViT-G at 20 / 32 c
 row within 2 of a 256-row tile boundary or of a sample boundary, plus 4096 random rows.
 
 Every test that forces a tile, the XCD partition or gm restores the defaults (-1, 101, 300) in `finally`: that state is process-global.
-tests/test_cpu_suite.py::test_gemm_matrix_covers_every_kernel checks (without a GPU) that PP_SPECS / LOCKSTEP_TILES list every
+tests/test_cpu_suite.py::test_gemm_matrix_covers_every_launched_kernel checks (without a GPU) that PP_SPECS / LOCKSTEP_TILES list every
 specialization that the sources instantiate.
 """
 import ctypes as C
@@ -77,8 +77,8 @@ def kernel_of(c):
 
 
 def source_kernels():
-    """Every lock-step config of SX_GEMM_DISPATCH and every ping-pong instantiation of launch_t (schedule variant 0), parsed from
-    the sources: the table below must list each of them."""
+    """Every lock-step config of SX_GEMM_DISPATCH and every ping-pong instantiation of launch_t, parsed from the sources: the table
+    below must list each of them."""
     src = open(os.path.join(CSRC, "gemm.hip")).read()
     ls = {}
     for i, m in enumerate(re.finditer(r"(?:case (\d)|default): return launch_cfg<TT, (\d+), (\d+), \d, \d, \d>", src)):
@@ -86,10 +86,9 @@ def source_kernels():
     src = open(os.path.join(CSRC, "gemm_pp.hip")).read()
     body = src[src.index("static int launch_t("):src.index("int launch_pp(")]
     pp = []
-    for m in re.finditer(r"launch_one<TT, (\d+), (\w+), (true|false), (\w+), (true|false), (\d)(?:, (\d))?>", body):
-        bn, am, o32, act, glu, var, ln = m.groups()
-        if var == "0":
-            pp.append(("pp", int(bn), am, o32 == "true", act, glu == "true", int(ln or 0)))
+    for m in re.finditer(r"launch_one<TT, (\d+), (\w+), (true|false), (\w+), (true|false)(?:, (\d))?>", body):
+        bn, am, o32, act, glu, ln = m.groups()
+        pp.append(("pp", int(bn), am, o32 == "true", act, glu == "true", int(ln or 0)))
     for m in re.finditer(r"PP_CASE\((\d+), (\w+), (true|false), (\w+), (true|false)\)", body):
         bn, am, o32, act, glu = m.groups()
         pp.append(("pp", int(bn), am, o32 == "true", act, glu == "true", 0))
