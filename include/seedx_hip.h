@@ -335,6 +335,33 @@ int sx_greedy_next_b(float* logits, int ld_logits, int vocab, const int32_t* img
 int sx_scatter_rows_step(const float* src, const int32_t* step_dev, float* dst, int G, int dim, int seq_rows, void* stream);
 /* p[0..n) += delta */
 int sx_add_i32_n(int32_t* p, int delta, int n, void* stream);
+/* In-flight batching: next token + stop rule + slot advance of the lock-step decode step in ONE launch. It replaces four nodes of
+ * the captured token step (sx_greedy_next_b and three sx_add_i32_n) and moves the stop decision of the greedy loop that the
+ * reference drives from seed_x.py:184-189 onto the device; the logits rule is the processor's (generation.py:19-31), the same
+ * device function as sx_greedy_next_b. Per slot g (all arrays int32 [G] in device memory):
+ *   live[g] == 0 (parked): nothing is read from the logits row and nothing at all is written.
+ *   live[g] != 0: id = rule + first-maximal-index arg-max on logits[g]; if n_new[g] == force_at[g] the id is replaced by force_id
+ *     AFTER the arg-max (synthetic weights only; force_at -1 = never). id goes to out_ids[g][step[g]] (if 0 <= step[g] < ld_out)
+ *     and to cur[g]; n_new, step, pos and ctx advance by one. Stop rule: id == eos_id (eos_id -1 = none) or n_new >= max_new[g]
+ *     → live = 0 and the slot is parked: step = -1, pos = -1, ctx = 0. Those are the idle values every kernel of the token step
+ *     honours (no cache, log or id store; the attention kernels read at most key row 0 of the slot's own cache and stay finite).
+ *   status[g] = { id, live, n_new, n_new at the finish or -1 }: what the host reads once per token step. */
+typedef struct sx_slot_step_args {
+  float* logits;                /* [G][ld_logits] fp32; the rule zeroes the image-token columns of LIVE rows in place              */
+  const int32_t* img_ids_dev;   /* [n_img]: <img>, <img_0> ... <img_{n-1}>, </img>                                                 */
+  int32_t* cur;                 /* in: the token just fed, out: the next token                                                     */
+  int32_t* live;
+  int32_t* n_new;               /* tokens generated so far                                                                         */
+  const int32_t* max_new;       /* token budget per slot                                                                           */
+  const int32_t* force_at;
+  int32_t* pos;                 /* the three counters the other kernels of the step consume                                        */
+  int32_t* ctx;
+  int32_t* step;
+  int32_t* out_ids;             /* [G][ld_out] or NULL                                                                             */
+  int32_t* status;              /* [G][4]                                                                                          */
+  int32_t ld_logits, vocab, n_img, ld_out, force_id, eos_id, G, reserved;
+} sx_slot_step_args;
+int sx_greedy_next_slots(const sx_slot_step_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Elementwise / layout helpers

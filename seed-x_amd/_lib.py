@@ -62,6 +62,13 @@ class AttnDecodeArgs(C.Structure):
                 ("cache_seq_stride", c_i64), ("scale", c_f32), ("reserved", c_i32)]
 
 
+class SlotStepArgs(C.Structure):
+    _fields_ = [("logits", c_vp), ("img_ids_dev", c_vp), ("cur", c_vp), ("live", c_vp), ("n_new", c_vp), ("max_new", c_vp),
+                ("force_at", c_vp), ("pos", c_vp), ("ctx", c_vp), ("step", c_vp), ("out_ids", c_vp), ("status", c_vp),
+                ("ld_logits", c_i32), ("vocab", c_i32), ("n_img", c_i32), ("ld_out", c_i32), ("force_id", c_i32),
+                ("eos_id", c_i32), ("G", c_i32), ("reserved", c_i32)]
+
+
 class AttnArgs(C.Structure):
     _fields_ = [("Q", c_vp), ("K", c_vp), ("V", c_vp), ("O", c_vp),
                 ("B", c_i32), ("H", c_i32), ("Sq", c_i32), ("Skv", c_i32), ("D", c_i32), ("reserved", c_i32),
@@ -117,6 +124,7 @@ SIGNATURES = {
     "sx_attn_decode_fused": [C.POINTER(AttnDecodeArgs), c_vp],
     "sx_attn_decode_b": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i64, c_i32, c_f32, c_i32, c_i64, c_vp],
     "sx_greedy_next_b": [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp],
+    "sx_greedy_next_slots": [C.POINTER(SlotStepArgs), c_vp],
     "sx_scatter_rows_step": [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp],
     "sx_add_i32_n": [c_vp, c_i32, c_i32, c_vp],
     "sx_embedding": [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp],

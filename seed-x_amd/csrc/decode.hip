@@ -65,8 +65,19 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvP p) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float x0 = TT::to_f32(xv[e] & 0xffff), x1 = TT::to_f32(xv[e] >> 16);
-        acc0[m] += TT::to_f32(a[e] & 0xffff) * x0 + TT::to_f32(a[e] >> 16) * x1;
-        acc1[m] += TT::to_f32(b[e] & 0xffff) * x0 + TT::to_f32(b[e] >> 16) * x1;
+        if constexpr (MR > 1) {
+          // Several activation rows: every row runs the SAME chain of fused multiply-adds, in element order. This file is built with
+          // -ffast-math, and the free-form expression below was scheduled row by row (a mix of mul + add, fma and packed forms that
+          // differed between the unrolled rows): the same sequence then gave other bits in slot 3 than in slot 0. Rows of a lock-step
+          // batch are independent requests (in-flight batching moves a request between slots), so a row's result must not depend on
+          // its index.
+#pragma clang fp reassociate(off) contract(off)
+          acc0[m] = __builtin_fmaf(TT::to_f32(a[e] >> 16), x1, __builtin_fmaf(TT::to_f32(a[e] & 0xffff), x0, acc0[m]));
+          acc1[m] = __builtin_fmaf(TT::to_f32(b[e] >> 16), x1, __builtin_fmaf(TT::to_f32(b[e] & 0xffff), x0, acc1[m]));
+        } else {
+          acc0[m] += TT::to_f32(a[e] & 0xffff) * x0 + TT::to_f32(a[e] >> 16) * x1;
+          acc1[m] += TT::to_f32(b[e] & 0xffff) * x0 + TT::to_f32(b[e] >> 16) * x1;
+        }
       }
     }
   }
@@ -857,19 +868,12 @@ __global__ void scatter_rows_step_kernel(const float* src, const int* step, floa
 }
 
 // ---- greedy next token with the AutoImageTokenGenerationProcessor rule (generation.py:19-31) ------------------------
-__global__ __launch_bounds__(1024) void greedy_next_kernel(float* logits, int vocab, const int* img_ids, int n_img,
-                                                           const int* prev_id, int* next_id, int* out_ids,
-                                                           const int* step_dev, int ld_logits, int ld_out) {
-  // one block per sequence
-  logits += (size_t)blockIdx.x * ld_logits;
-  prev_id += blockIdx.x;
-  next_id += blockIdx.x;
-  if (out_ids) out_ids += (size_t)blockIdx.x * ld_out;
-  if (step_dev) step_dev += blockIdx.x;
+// One workgroup of 1024 threads per logits row; every thread returns the row's next id. Shared by greedy_next_kernel and
+// greedy_next_slots_kernel: the rule and the first-maximal-index arg-max exist once.
+__device__ __forceinline__ int greedy_next_id(float* logits, int vocab, const int* img_ids, int n_img, int prev) {
   __shared__ float smax[16];
   __shared__ int sidx[16];
   __shared__ int forced;
-  const int prev = *prev_id;
   if (threadIdx.x == 0) forced = -1;
   __syncthreads();
   // prev in img_ids[:-1] → force the next id of the chain (scores[next] = max + 10 in the reference)
@@ -902,6 +906,19 @@ __global__ __launch_bounds__(1024) void greedy_next_kernel(float* logits, int vo
       if (smax[w] > best || (smax[w] == best && sidx[w] < bi)) { best = smax[w]; bi = sidx[w]; }
     result = bi;
   }
+  return result;
+}
+
+__global__ __launch_bounds__(1024) void greedy_next_kernel(float* logits, int vocab, const int* img_ids, int n_img,
+                                                           const int* prev_id, int* next_id, int* out_ids,
+                                                           const int* step_dev, int ld_logits, int ld_out) {
+  // one block per sequence
+  logits += (size_t)blockIdx.x * ld_logits;
+  prev_id += blockIdx.x;
+  next_id += blockIdx.x;
+  if (out_ids) out_ids += (size_t)blockIdx.x * ld_out;
+  if (step_dev) step_dev += blockIdx.x;
+  const int result = greedy_next_id(logits, vocab, img_ids, n_img, *prev_id);
   if (threadIdx.x == 0) {
     *next_id = result;
     if (out_ids) {
@@ -909,6 +926,65 @@ __global__ __launch_bounds__(1024) void greedy_next_kernel(float* logits, int vo
       if (st >= 0 && (ld_out <= 0 || st < ld_out)) out_ids[st] = result;   // ld_out doubles as the row capacity
     }
   }
+}
+
+// ---- in-flight batching: next token + stop rule + slot advance, one launch (sx_greedy_next_slots) --------------------------------
+// Slot g of the lock-step decode step is either LIVE (a request occupies it) or PARKED (free: the host has not refilled it yet).
+// A parked slot keeps stepping through the GEMVs with the others (the weights stream once for all rows anyway) but must leave no
+// trace: its counters hold the idle values
+//     step = -1  → scatter_rows_step_kernel and the out_ids guard drop the row,
+//     pos  = -1  → the RoPE / append kernels and both fused attention kernels write nothing (pos_ok is false),
+//     ctx  =  0  → ctx == pos + 1 as always: the plain attention sees no key (its combine yields 0, not 0 / 0); the fp32 attention
+//                  clamps pos to 0 and reads key row 0 of the slot's own cache, which a request wrote or the allocation zeroed,
+// and this kernel returns for it before it touches anything, the in-place zeroing of its logits row included.
+// A live slot takes the next id by the shared rule, stores it, advances its four counters and tests the stop rule (EOS or budget) on
+// the device; a slot that stops parks itself here, so the very next replay of the captured step already treats it as idle.
+struct SlotStepP {
+  float* logits;
+  const int* img_ids;
+  int* cur;
+  int* live;
+  int* n_new;
+  const int* max_new;
+  const int* force_at;
+  int* pos;
+  int* ctx;
+  int* step;
+  int* out_ids;
+  int* status;
+  int ld_logits, vocab, n_img, ld_out, force_id, eos_id;
+};
+
+__global__ __launch_bounds__(1024) void greedy_next_slots_kernel(const SlotStepP p) {
+  const int g = blockIdx.x;
+  if (p.live[g] == 0) return;                       // parked (uniform over the workgroup: no barrier is skipped by a part of it)
+  // every thread reads cur[g] before the first barrier of greedy_next_id; thread 0 stores to it after the last one
+  int result = greedy_next_id(p.logits + (size_t)g * p.ld_logits, p.vocab, p.img_ids, p.n_img, p.cur[g]);
+  if (threadIdx.x != 0) return;
+  int n = p.n_new[g];
+  const int fa = p.force_at[g];
+  if (fa >= 0 && n == fa) result = p.force_id;      // synthetic weights only: replaced AFTER the full arg-max (no work skipped)
+  const int st = p.step[g];
+  if (p.out_ids && st >= 0 && st < p.ld_out) p.out_ids[(size_t)g * p.ld_out + st] = result;   // ld_out is the row capacity
+  p.cur[g] = result;
+  n += 1;
+  p.n_new[g] = n;
+  const bool stop = (p.eos_id >= 0 && result == p.eos_id) || n >= p.max_new[g];
+  if (stop) {
+    p.live[g] = 0;
+    p.step[g] = -1;
+    p.pos[g] = -1;
+    p.ctx[g] = 0;
+  } else {
+    p.step[g] = st + 1;
+    p.pos[g] += 1;
+    p.ctx[g] += 1;
+  }
+  int* s = p.status + 4 * g;
+  s[0] = result;
+  s[1] = stop ? 0 : 1;
+  s[2] = n;
+  s[3] = stop ? n : -1;
 }
 
 inline dim3 gs_grid(int64_t n) {
@@ -1160,6 +1236,23 @@ extern "C" int sx_greedy_next(float* logits, int vocab, const int32_t* img_ids_d
                               const int32_t* prev_id_dev, int32_t* next_id_dev, int32_t* out_ids,
                               const int32_t* step_dev, void* stream) {
   return sx_greedy_next_b(logits, 0, vocab, img_ids_dev, n_img, prev_id_dev, next_id_dev, out_ids, 0, step_dev, 1, stream);
+}
+
+extern "C" int sx_greedy_next_slots(const sx_slot_step_args* a, void* stream) {
+  SX_CHECK(a && a->logits && a->img_ids_dev && a->cur && a->live && a->n_new && a->max_new && a->force_at && a->pos && a->ctx &&
+           a->step && a->status, "sx_greedy_next_slots: null pointer");
+  SX_CHECK(a->n_img >= 2 && a->n_img <= 1024 && a->G >= 1, "sx_greedy_next_slots: n_img=%d G=%d", a->n_img, a->G);
+  SX_CHECK(a->vocab >= 1 && a->ld_logits >= a->vocab, "sx_greedy_next_slots: vocab=%d ld_logits=%d", a->vocab, a->ld_logits);
+  SX_CHECK(!a->out_ids || a->ld_out >= 1, "sx_greedy_next_slots: out_ids needs ld_out >= 1 (the row capacity)");
+  SlotStepP p;
+  p.logits = a->logits; p.img_ids = a->img_ids_dev; p.cur = a->cur; p.live = a->live; p.n_new = a->n_new;
+  p.max_new = a->max_new; p.force_at = a->force_at; p.pos = a->pos; p.ctx = a->ctx; p.step = a->step;
+  p.out_ids = a->out_ids; p.status = a->status;
+  p.ld_logits = a->ld_logits; p.vocab = a->vocab; p.n_img = a->n_img; p.ld_out = a->ld_out;
+  p.force_id = a->force_id; p.eos_id = a->eos_id;
+  hipLaunchKernelGGL(greedy_next_slots_kernel, dim3(a->G), dim3(1024), 0, ST, p);
+  SX_HIP_LAUNCH_CHECK();
+  return SX_OK;
 }
 
 extern "C" int sx_scatter_rows_step(const float* src, const int32_t* step_dev, float* dst, int G, int dim, int seq_rows,

@@ -123,6 +123,29 @@ class CausalLMOutputWithPast(dict):
         return tuple(v for v in self.values() if v is not None)
 
 
+class SlotState:
+    """Device-side bookkeeping of the in-flight decode step (``decode_step(..., slots=...)``, sx_greedy_next_slots), one int32 entry
+    per slot of the lock-step batch: ``live`` (a request occupies the slot), ``n_new`` (tokens generated so far), ``max_new`` (its
+    budget), ``force_at`` (synthetic weights: index of the generated token replaced by ``force_id``, -1 = none) and ``status``
+    [G, 4] = (next id, live, n_new, n_new at the finish or -1), the one tensor the host reads per token step. ``eos_id`` -1 = no
+    EOS stop. A slot that is not live is PARKED: its counters in the module hold the idle values pos = -1, ctx = 0, step = -1, under
+    which no kernel of the token step writes to its KV cache, id log or hidden-state log. ``logits`` is the [G, Vpad] tensor of
+    the most recent step (the captured graph's own buffer under replay)."""
+    IDLE = {"pos": -1, "ctx": 0, "step": -1}
+
+    def __init__(self, G, device, force_id=-1, eos_id=-1):
+        z = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=device)
+        self.G = G
+        self.live, self.n_new, self.max_new, self.status = z(G), z(G), z(G), z(G, 4)
+        self.force_at = torch.full((G,), -1, dtype=torch.int32, device=device)
+        self.force_id, self.eos_id = int(force_id), int(eos_id)
+        self.logits = None
+
+    def key(self):
+        return tuple(t.data_ptr() for t in (self.live, self.n_new, self.max_new, self.force_at, self.status)) \
+            + (self.force_id, self.eos_id)
+
+
 class LlamaForCausalLM:
     def __init__(self, config, max_cache_len=None, max_batch=1, comm=None, precise=None, kv_v16=None):
         self.config = config if not isinstance(config, dict) else LlamaConfigLite(**config)
@@ -173,6 +196,7 @@ class LlamaForCausalLM:
         self.device, self.dtype = None, torch.float16
         self._sd, self._P = None, None
         self._graph = None
+        self._slot_graph = None         # the captured in-flight token step (decode_step(..., slots=...)): one per engine lifetime
         self.kv_epoch = 0               # bumped whenever the KV cache is reset or written outside generate_batch
 
     def memory_footprint(self):
@@ -373,6 +397,7 @@ class LlamaForCausalLM:
         self._P = P
         self._sd = None
         self._graph = None
+        self._slot_graph = None
         return P
 
     # ---- core passes ---------------------------------------------------------------------------------------------------
@@ -462,9 +487,10 @@ class LlamaForCausalLM:
                 ops.add_i32(P["ctx"][g:g + 1], Ts[i])
         return x
 
-    def _layers_single(self, x):
+    def _layers_single(self, x, slots=None):
         """One token of EVERY sequence (x: fp32 [G, H]) at the device-resident positions: weight-streaming GEMVs with
-        M = G rows + split-KV decode attention per sequence. No host reads → graph-capturable."""
+        M = G rows + split-KV decode attention per sequence. No host reads → graph-capturable. ``slots`` (in-flight batching): the
+        positions are advanced per LIVE slot by sx_greedy_next_slots at the end of the step instead of unconditionally here."""
         P, dt, H, nh, hd, G = self._P, self.dtype, self.H_l, self.nh_l, self.hd, self.G
         comm, lead = self.comm, self.comm.rank == 0
         eps = self.config.rms_norm_eps
@@ -474,7 +500,7 @@ class LlamaForCausalLM:
         # 16 rows that all sit on the same L2 channel — and the down projection may split K over workgroups (workspace)
         tl, ws = P["decode_tiled"] and G >= 5, P["gemv_ws"]
         if self.precise:
-            return self._layers_single_precise(x)
+            return self._layers_single_precise(x, slots)
         # folded RMSNorm: the residual GEMVs (o, down) also emit the new residual stream as 16-bit operand tiles (x16) and its rows'
         # sums of squares (ssq); the projection behind the norm reads x16 with gamma-folded weights and scales by rstd — no norm launch
         fold = tl and P["rms_fold"]
@@ -511,11 +537,12 @@ class LlamaForCausalLM:
             g = ops.gemv(h, lw["wgu"], act="silu", glu=True, w_tiles=lw["wgu_t"], y_tiled=tl)
             x = comm.all_reduce(ops.gemv(g, lw["wd"], residual=x if lead else None, out_dtype=torch.float32,
                                          w_tiles=lw["wd_t"], workspace=ws, w_tiles20=lw["wd_t20"] if tl else None))
-        ops.add_i32(P["pos"], 1)
-        ops.add_i32(P["ctx"], 1)
+        if slots is None:
+            ops.add_i32(P["pos"], 1)
+            ops.add_i32(P["ctx"], 1)
         return x
 
-    def _layers_single_precise(self, x):
+    def _layers_single_precise(self, x, slots=None):
         """_layers_single with fp32-grade activations: the x operand of every skinny GEMM is a two-block Tiled16 (hi plane, lo plane;
         sx_gemv x_planes = 2 — each weight fragment feeds two MFMAs, the weights stream once), its outputs are fp32; RoPE, the KV
         cache and attention are fp32 (sx_rope_kv_append_f32, sx_attention_f32 at T = 1). Shapes outside the skinny GEMM's MFMA path
@@ -565,8 +592,9 @@ class LlamaForCausalLM:
             else:
                 g = ops.split16(lin(h, lw, "wgu", act="silu", glu=True), dt)
             x = comm.all_reduce(lin(g, lw, "wd", residual=x if lead else None))
-        ops.add_i32(P["pos"], 1)
-        ops.add_i32(P["ctx"], 1)
+        if slots is None:
+            ops.add_i32(P["pos"], 1)
+            ops.add_i32(P["ctx"], 1)
         return x
 
     def _final_norm(self, x):
@@ -683,14 +711,44 @@ class LlamaForCausalLM:
 
     __call__ = forward
 
+    # ---- in-flight batching: slot states ---------------------------------------------------------------------------------
+    def slot_state(self, force_id=-1, eos_id=-1):
+        """A fresh SlotState with EVERY slot parked (the module's pos / ctx / step take the idle values; ``reset()`` undoes that)."""
+        if self.tp > 1:
+            raise NotImplementedError("in-flight batching (slot states) is single-rank: tensor-parallel ranks are not supported")
+        self._pack()
+        st = SlotState(self.G, self.device, force_id, eos_id)
+        self.park_slots(range(self.G), st)
+        return st
+
+    def _slot_write(self, t, slots, values):
+        """t[slots[i]] = values[i] (or one value for all) for a device int32 [G] tensor: one small host → device copy."""
+        slots = list(slots)
+        if not slots:
+            return
+        vals = [int(values)] * len(slots) if not isinstance(values, (list, tuple)) else [int(v) for v in values]
+        idx = torch.tensor(slots, dtype=torch.int64, device=self.device)
+        t.index_copy_(0, idx, torch.tensor(vals, dtype=torch.int32, device=self.device))
+
+    def park_slots(self, slots, state):
+        """Host-side parking (a slot the device did not park itself: never used, or finished at admission / in an image chunk)."""
+        P = self._pack()
+        slots = list(slots)
+        self.kv_epoch += 1
+        self._slot_write(state.live, slots, 0)
+        for k, v in SlotState.IDLE.items():
+            self._slot_write(P[k], slots, v)
+
     # ---- device-resident greedy decode step (all sequences in lock step) -----------------------------------------------
-    def _decode_step_body(self, img_ids_dev, out_ids, hid_buf):
+    def _decode_step_body(self, img_ids_dev, out_ids, hid_buf, slots=None):
         """cur[G] → embedding → 40 layers → final norm → lm_head → logits rule + argmax → cur[G]. Records the post-norm
         hidden state of each INPUT token at hid_buf[g, step[g]] (what seed_x.py:196 collects) and the new id at
-        out_ids[g, step[g]]; then step += 1. Everything stays on the device."""
+        out_ids[g, step[g]]; then step += 1. Everything stays on the device. ``slots`` (a SlotState): the tail is ONE
+        sx_greedy_next_slots launch — next id, stop rule and the advance of pos / ctx / step for the live slots only; parked
+        slots ride along through the GEMVs and write nothing."""
         P = self._P
         x = ops.embedding(P["cur"], P["embed"])                                        # [G, H] fp32
-        x = self._layers_single(x)
+        x = self._layers_single(x, slots)
         if self.precise:
             hp, hn = ops.rmsnorm_planes(x, P["norm"], self.config.rms_norm_eps, self.dtype, tiled=P["precise_tiled"], want_f32=True)
             ops.scatter_rows_step(hn, P["step"], hid_buf)
@@ -705,33 +763,52 @@ class LlamaForCausalLM:
                               w_tiles=P["lm_head_t"])                                  # [G, Vpad / tp]
         if self.tp > 1:
             logits = self.comm.all_gather(logits).permute(1, 0, 2).reshape(self.G, self.Vpad).contiguous()
+        if slots is not None:
+            ops.greedy_next_slots(logits, self.V, img_ids_dev, P["cur"], slots.live, slots.n_new, slots.max_new, slots.force_at,
+                                  P["pos"], P["ctx"], P["step"], out_ids, slots.status, slots.force_id, slots.eos_id)
+            slots.logits = logits
+            return
         ops.greedy_next_b(logits, self.V, img_ids_dev, P["cur"], out_ids, P["step"])
         ops.add_i32(P["step"], 1)
 
-    def decode_step(self, img_ids_dev, out_ids, hid_buf, use_graph=True):
-        """out_ids: int32 [G, rows]; hid_buf: fp32 [G, rows, H]."""
+    def decode_step(self, img_ids_dev, out_ids, hid_buf, use_graph=True, slots=None):
+        """out_ids: int32 [G, rows]; hid_buf: fp32 [G, rows, H]. ``slots``: a SlotState → the in-flight step (its captured graph is
+        kept apart from the lock-step one, so one graph serves an engine's lifetime whatever else runs in between)."""
         self._pack()
         assert out_ids.shape[0] == self.G and hid_buf.shape[0] == self.G and hid_buf.shape[1] == out_ids.shape[1]
+        if slots is not None:
+            if self.tp > 1:
+                raise NotImplementedError("in-flight batching (slot states) is single-rank: tensor-parallel ranks are not supported")
+            assert out_ids.is_contiguous() and slots.G == self.G
         if not use_graph or not self.comm.graph_safe:
-            self._decode_step_body(img_ids_dev, out_ids, hid_buf)
+            self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots)
             return
-        key = (img_ids_dev.data_ptr(), out_ids.data_ptr(), hid_buf.data_ptr(), tuple(out_ids.shape))
-        if self._graph is None or self._graph[0] != key:
-            # warm-up on a side stream (allocator / lazy module load), then capture one token step
+        attr = "_graph" if slots is None else "_slot_graph"
+        key = (img_ids_dev.data_ptr(), out_ids.data_ptr(), hid_buf.data_ptr(), tuple(out_ids.shape)) \
+            + (slots.key() if slots is not None else ())
+        held = getattr(self, attr)
+        if held is None or held[0] != key:
+            # warm-up on a side stream (allocator / lazy module load), then capture one token step. The warm-up really runs a
+            # step: everything it advances is put back (in slot mode it may even finish a slot: live / n_new / status too)
             P = self._P
-            snap = {k: P[k].clone() for k in ("pos", "ctx", "step", "cur")}
+            snap = {k: (P[k], P[k].clone()) for k in ("pos", "ctx", "step", "cur")}
+            if slots is not None:
+                snap.update({k: (getattr(slots, k), getattr(slots, k).clone()) for k in ("live", "n_new", "status")})
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
-                self._decode_step_body(img_ids_dev, out_ids, hid_buf)
+                self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots)
             torch.cuda.current_stream().wait_stream(s)
             torch.cuda.synchronize()
-            for k, v in snap.items():
-                P[k].copy_(v)
+            for t, v in snap.values():
+                t.copy_(v)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self._decode_step_body(img_ids_dev, out_ids, hid_buf)
-            for k, v in snap.items():
-                P[k].copy_(v)
-            self._graph = (key, g)
-        self._graph[1].replay()
+                self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots)
+            for t, v in snap.values():
+                t.copy_(v)
+            held = (key, g) + ((slots.logits,) if slots is not None else ())
+            setattr(self, attr, held)
+        if slots is not None:
+            slots.logits = held[2]
+        held[1].replay()

@@ -791,6 +791,30 @@ def greedy_next_b(logits, vocab, img_ids_dev, cur_dev, out_ids, step_dev):
                                _stream()), "sx_greedy_next_b")
 
 
+def greedy_next_slots(logits, vocab, img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, out_ids, status,
+                      force_id=-1, eos_id=-1):
+    """In-flight batching tail of the token step (sx_greedy_next_slots): logits fp32 [G, ld]; every other tensor int32 [G] on the
+    device, out_ids [G, rows] or None, status [G, 4]. Live slots take their next id, advance n_new / step / pos / ctx and park
+    themselves when the id is ``eos_id`` or their budget is reached; parked slots are not touched."""
+    lib = _lib.load()
+    G = logits.shape[0]
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1
+    for t in (img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, status) + ((out_ids,) if out_ids is not None else ()):
+        assert t.dtype == torch.int32 and t.is_contiguous(), "greedy_next_slots: contiguous int32 tensors"
+    for t in (cur, live, n_new, max_new, force_at, pos, ctx, step):
+        assert t.numel() == G
+    assert status.numel() == 4 * G and (out_ids is None or out_ids.shape[0] == G)
+    a = _lib.SlotStepArgs(
+        logits=logits.data_ptr(), img_ids_dev=img_ids_dev.data_ptr(), cur=cur.data_ptr(), live=live.data_ptr(),
+        n_new=n_new.data_ptr(), max_new=max_new.data_ptr(), force_at=force_at.data_ptr(), pos=pos.data_ptr(), ctx=ctx.data_ptr(),
+        step=step.data_ptr(), out_ids=out_ids.data_ptr() if out_ids is not None else None, status=status.data_ptr(),
+        ld_logits=logits.stride(0), vocab=int(vocab), n_img=img_ids_dev.numel(), ld_out=out_ids.shape[1] if out_ids is not None else 0,
+        force_id=int(force_id), eos_id=int(eos_id), G=G, reserved=0)
+    for t in (logits, img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, status):
+        _p(t)                                   # (GPU tensors only: no CPU fallback)
+    check(lib.sx_greedy_next_slots(C.byref(a), _stream()), "sx_greedy_next_slots")
+
+
 def scatter_rows_step(src, step_dev, dst):
     """dst [G, rows, dim] fp32; dst[g, step[g]] = src[g]."""
     lib = _lib.load()

@@ -7,10 +7,13 @@ read-back per token for the EOS / ``<img>`` test (the reference performs ≥45 d
 When ``<img>`` is emitted the 64 forced ``<img_i>`` tokens are run as ONE 65-token causal chunk on the MFMA path
 (identical math, 64× the arithmetic intensity).
 ``generate_batch`` runs G independent requests in lock step (one weight stream from HBM per token step for all G).
+``generate_inflight`` serves a queue of any length on those G slots: the stop rule runs on the device, a finished slot idles
+inside the captured step and is refilled from the queue before the next one (inflight.py holds the schedule).
 """
 import torch
 
 from . import ops
+from .inflight import SlotScheduler
 
 BOI_TOKEN = '<img>'
 EOI_TOKEN = '</img>'
@@ -32,6 +35,8 @@ class ContinuousLVLM:
         self._conv = {}                  # sequence → (token ids, row fingerprints, LLM cache epoch) held by its KV cache
         self._sig_w = {}
         self.last_prefill_tokens = []
+        self.last_inflight_stats = None
+        self._inflight = None            # buffers + slot state of generate_inflight, kept so that ONE captured step serves every call
 
     @classmethod
     def from_pretrained(cls, llm, input_resampler, output_resampler, pretrained_model_path=None, **kwargs):
@@ -259,6 +264,168 @@ class ContinuousLVLM:
             results.append({'text': text, 'has_img_output': len(eoi_indices) > 0, 'img_gen_feat': img_gen_feat,
                             'num_gen_imgs': len(eoi_indices), 'generate_ids': generate_ids,
                             'last_hidden_states': last_hidden})
+        return results
+
+    def _result(self, tokenizer, generate_ids, last_hidden, boi_id, eoi_id, num_img_gen_tokens):
+        """The reference-style result dict of one finished request (seed_x.py:196-234), as generate_batch builds it."""
+        eoi_indices = torch.where(generate_ids == eoi_id)[0].tolist()                        # :199
+        text_mask = torch.ones_like(generate_ids, dtype=torch.bool)
+        img_gen_feat = None
+        if eoi_indices:
+            feats = []
+            for e in eoi_indices:
+                feats.append(last_hidden[e - num_img_gen_tokens:e])                          # :204
+                text_mask[e - num_img_gen_tokens:e] = False
+            img_gen_feat = self.output_resampler(torch.stack(feats))                         # :209-210
+            img_gen_feat = ops.cast(img_gen_feat.contiguous(), self.dtype)
+        text_mask[generate_ids == boi_id] = False
+        text = tokenizer.decode(generate_ids[text_mask], skip_special_tokens=False)          # :214-216
+        return {'text': text, 'has_img_output': len(eoi_indices) > 0, 'img_gen_feat': img_gen_feat,
+                'num_gen_imgs': len(eoi_indices), 'generate_ids': generate_ids, 'last_hidden_states': last_hidden}
+
+    @torch.no_grad()
+    def generate_inflight(self, tokenizer, requests, num_img_gen_tokens=64, max_new_tokens=120, eos_token_id="auto",
+                          max_admit=None, on_result=None):
+        """In-flight (continuous) batching: any number of requests >= 1 on the llm.G slots of the lock-step decode step. The request
+        dicts are generate_batch's; each may carry its own ``max_new_tokens`` and ``force_image_at``. The stop rule (EOS or budget)
+        runs on the device at the end of the captured token step (sx_greedy_next_slots): a finished slot parks itself, writes
+        nothing while it idles, and is refilled from the queue head before the next step — at most ``max_admit`` requests per
+        admission pass (None: every free slot), each round of a pass ONE batched prefill. The host reads one [G, 4] status tensor
+        per step. Returns one reference-style result dict per request, in request order; ``on_result(index, result)`` is called as
+        each request finishes; ``last_inflight_stats`` holds the step counts (inflight.simulate predicts them from the lengths).
+        Forced image blocks stay host-driven chunks as in generate_batch (the other slots wait). Cross-turn cache reuse is not
+        offered here: the call clears those records. Slots are reused without zeroing: keys at or above ``pos`` are never visible."""
+        llm = self.llm
+        if llm.comm.world > 1:
+            raise NotImplementedError("generate_inflight is single-rank: tensor-parallel ranks are not supported")
+        requests = list(requests)
+        N = len(requests)
+        assert N >= 1, "generate_inflight needs at least one request"
+        dev, H, G = llm.device, llm.H, llm.G
+        P = llm._pack()
+        img_ids = tokenizer.encode(''.join([BOI_TOKEN] + [IMG_TOKEN.format(i) for i in range(num_img_gen_tokens)]
+                                           + [EOI_TOKEN]), add_special_tokens=False)        # generation.py:15-17
+        boi_id, eoi_id = img_ids[0], img_ids[-1]
+        if eos_token_id == "auto":
+            eos_token_id = getattr(tokenizer, "eos_token_id", None)
+        eos = -1 if eos_token_id is None else int(eos_token_id)
+        nchunk = num_img_gen_tokens + 1
+        budget = [int(req.get("max_new_tokens") or max_new_tokens) for req in requests]
+        force_at = [-1 if req.get("force_image_at") is None else int(req["force_image_at"]) for req in requests]
+        assert all(b >= 1 for b in budget)
+        rows = max(budget) + 8
+        keep = self._inflight
+        if keep is None or keep["key"] != (tuple(img_ids), eos, G, id(P)) or keep["out_ids"].shape[1] < rows:
+            keep = self._inflight = dict(
+                key=(tuple(img_ids), eos, G, id(P)),
+                img_ids_dev=torch.tensor(img_ids, dtype=torch.int32, device=dev),
+                out_ids=torch.full((G, rows), -1, dtype=torch.int32, device=dev),
+                hid=torch.zeros((G, rows, H), dtype=torch.float32, device=dev),              # row k = state at input new[k-1]
+                state=None)
+        llm.reset()                                      # bumps kv_epoch: the cross-turn records no longer describe the cache
+        self._conv = {}
+        if keep["state"] is None:
+            keep["state"] = llm.slot_state(force_id=boi_id, eos_id=eos)
+        st, img_ids_dev, out_ids, hid = keep["state"], keep["img_ids_dev"], keep["out_ids"], keep["hid"]
+        llm.park_slots(range(G), st)
+        sched = SlotScheduler(G, N, max_admit)
+        results = [None] * N
+        n_new, cur = [0] * G, [0] * G                    # host mirrors of the live slots' state
+        stats = dict(decode_steps=0, live_slot_steps=0, parked_slot_steps=0, admissions=0, prefill_passes=0, prefill_tokens=0)
+        self.last_prefill_tokens = []
+
+        def harvest(g, n):
+            r = sched.finish(g)
+            generate_ids = out_ids[g, :n].cpu().long()
+            last_hidden = hid[g, 1:n].clone()                                                # the slot's rows are reused
+            results[r] = self._result(tokenizer, generate_ids, last_hidden, boi_id, eoi_id, num_img_gen_tokens)
+            if on_result is not None:
+                on_result(r, results[r])
+
+        def stopped(g):
+            return n_new[g] >= budget[sched.slot_req[g]] or (eos >= 0 and cur[g] == eos)
+
+        def admit_round(adm):
+            # ONE batched prefill over the admitted slots; token 1 of each comes from it (host-side stop test: not in the graph)
+            slots = [g for g, _ in adm]
+            xs, last_ids = [], []
+            for g, r in adm:
+                ids, x = self._prompt_embeds(tokenizer, requests[r])
+                assert len(ids) + budget[r] <= llm.Tmax, "KV cache too small for prompt + max_new_tokens"
+                xs.append(x)
+                last_ids.append(ids[-1])
+            llm._slot_write(P["pos"], slots, 0)
+            llm._slot_write(P["ctx"], slots, 1)
+            logits, _ = llm.forward_embeds_batch(xs, slots)
+            first = torch.tensor(last_ids, dtype=torch.int32, device=dev)
+            ops.greedy_next_b(logits.contiguous(), llm.V, img_ids_dev, first, None, None)
+            first = first.tolist()
+            llm.comm.check()
+            stats["admissions"] += len(adm)
+            stats["prefill_passes"] += 1
+            stats["prefill_tokens"] += sum(int(x.shape[0]) for x in xs)
+            self.last_prefill_tokens += [int(x.shape[0]) for x in xs]
+            for i, (g, r) in enumerate(adm):
+                cur[g] = boi_id if force_at[r] == 0 else first[i]      # (synthetic weights: the pinned transcript, see generate_batch)
+                n_new[g] = 1
+            out_ids[torch.tensor(slots, device=dev), 0] = torch.tensor([cur[g] for g in slots], dtype=torch.int32, device=dev)
+            llm._slot_write(P["cur"], slots, [cur[g] for g in slots])
+            llm._slot_write(P["step"], slots, 1)
+            llm._slot_write(st.n_new, slots, 1)
+            llm._slot_write(st.max_new, slots, [budget[r] for _, r in adm])
+            llm._slot_write(st.force_at, slots, [force_at[r] for _, r in adm])
+            llm._slot_write(st.live, slots, 1)
+            fin = [g for g in slots if stopped(g)]
+            if fin:
+                llm.park_slots(fin, st)
+                for g in fin:
+                    harvest(g, n_new[g])
+
+        while not sched.done:
+            sched.new_pass()
+            while True:
+                adm = sched.admit()
+                if not adm:
+                    break
+                admit_round(adm)
+            live = sched.live_slots()
+            hit = [g for g in live if self.chunk_forced_image_tokens and cur[g] == boi_id
+                   and n_new[g] + nchunk <= budget[sched.slot_req[g]]]
+            if hit:
+                # inputs [<img>, <img_0> … <img_63>] as one causal chunk per slot, all such slots in ONE pass; the outputs are
+                # forced (generation.py:23-26). The other slots wait, as in generate_batch.
+                chunk = torch.tensor([boi_id] + img_ids[1:-1], dtype=torch.int32, device=dev)
+                xe = ops.embedding(chunk, P["embed"])
+                _, hns = llm.forward_embeds_batch([xe] * len(hit), hit, need_logits=False)
+                forced = torch.tensor(img_ids[1:], dtype=torch.int32, device=dev)
+                for g, hn in zip(hit, hns):
+                    hid[g, n_new[g]:n_new[g] + nchunk] = hn                                  # plumbing copy
+                    out_ids[g, n_new[g]:n_new[g] + nchunk] = forced
+                    n_new[g] += nchunk
+                    cur[g] = eoi_id
+                llm._slot_write(st.n_new, hit, [n_new[g] for g in hit])
+                llm._slot_write(P["step"], hit, [n_new[g] for g in hit])
+                llm._slot_write(P["cur"], hit, eoi_id)
+                fin = [g for g in hit if stopped(g)]
+                if fin:
+                    llm.park_slots(fin, st)
+                    for g in fin:
+                        harvest(g, n_new[g])
+                live = sched.live_slots()
+            if not live:
+                continue
+            llm.decode_step(img_ids_dev, out_ids, hid, use_graph=self.use_graph, slots=st)   # one token for every live slot
+            status = st.status.tolist()                                                      # the only read-back per step
+            llm.comm.check()
+            stats["decode_steps"] += 1
+            stats["live_slot_steps"] += len(live)
+            stats["parked_slot_steps"] += G - len(live)
+            for g in live:
+                cur[g], alive, n_new[g], fin_n = status[g]
+                if not alive:
+                    harvest(g, fin_n)
+        llm.reset()                                      # pos / ctx / step leave their idle values
+        self.last_inflight_stats = stats
         return results
 
     @torch.no_grad()
