@@ -362,6 +362,37 @@ typedef struct sx_slot_step_args {
   int32_t ld_logits, vocab, n_img, ld_out, force_id, eos_id, G, reserved;
 } sx_slot_step_args;
 int sx_greedy_next_slots(const sx_slot_step_args* args, void* stream);
+/* Seeded sampling of the next token on the device: what generate() does with do_sample=True (the reference passes do_sample=False at
+ * seed_x.py:175-189, one word away), i.e. transformers' sample(): the processor rule first (generation.py:19-31, exactly as
+ * sx_greedy_next applies it, the in-place zeroing of the image columns being the only edit of the row), then temperature → top-k →
+ * top-p and one draw. Per row g, with x the fp32 logits row:
+ *   do_sample[g] == 0, or the previous id inside the image chain: sx_greedy_next_b's id (arg-max / next chain id); nothing is drawn.
+ *   else t = x / T; top-k (0 < top_k < vocab, else off) keeps t >= the k-th largest value, ties kept; w = exp(t − max t) over the
+ *     survivors, W_k their sum; top-p keeps a token iff the mass of the strictly larger survivors is below top_p · W_k (the
+ *     TopPLogitsWarper of transformers 4.30.2 without its sort: the maximum is always kept, equal values are kept or dropped together);
+ *     u = (Philox4x32-10(counter (n, 0, 0, 0), key (seed lo, seed hi))[0] >> 8) · 2^-24; the id is the smallest kept index whose
+ *     inclusive prefix mass exceeds u · W. n is token_index[g] (sx_sample_next_b) or step[g] (sx_sample_next_slots): the 0-based index
+ *     of the generated token within its request.
+ * A token whose fp32 weight underflows to 0 (x more than about 87 T below the maximum, or -inf) has mass 0: it is never drawn, not kept
+ * and not counted in n_kept, also with top_p = 1. The masses are summed as 2^40-scaled integers, so the id depends on the row's values, the parameters, the seed and n only — not on
+ * the slot, the neighbours, the launch or graph replay. One workgroup per row, the row is read once; vocab <= 32768. Every pointer is
+ * device memory with one entry per row, read at launch (a captured graph serves any mix of greedy and sampled rows). */
+typedef struct sx_sample_args {
+  const int32_t* do_sample;     /* 0: greedy row                                                                                   */
+  const float* temperature;     /* T > 0                                                                                           */
+  const int32_t* top_k;         /* 0 = off                                                                                         */
+  const float* top_p;           /* 0 < top_p <= 1                                                                                  */
+  const uint32_t* seed;         /* [G][2]: low word, high word of the 64-bit seed                                                  */
+  const int32_t* token_index;   /* sx_sample_next_b only (sx_sample_next_slots uses step); may be NULL there                       */
+  int32_t* n_kept;              /* optional out: size of the kept set; -1 for greedy rows and rows inside the image chain          */
+  float* p_chosen;              /* optional out: probability of the drawn id within the kept set; 1.0 for those rows               */
+} sx_sample_args;
+/* sx_greedy_next_b's arguments and outputs, with the id by the rule above. */
+int sx_sample_next_b(float* logits, int ld_logits, int vocab, const int32_t* img_ids_dev, int n_img,
+                     const int32_t* prev_id_dev, int32_t* next_id_dev, int32_t* out_ids, int ld_out,
+                     const int32_t* step_dev, int G, const sx_sample_args* sample, void* stream);
+/* sx_greedy_next_slots (parking, force_at after the draw, stop rule, counters, status — all unchanged) with the id by the rule above. */
+int sx_sample_next_slots(const sx_slot_step_args* args, const sx_sample_args* sample, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Elementwise / layout helpers

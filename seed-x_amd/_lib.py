@@ -69,6 +69,11 @@ class SlotStepArgs(C.Structure):
                 ("eos_id", c_i32), ("G", c_i32), ("reserved", c_i32)]
 
 
+class SampleArgs(C.Structure):
+    _fields_ = [("do_sample", c_vp), ("temperature", c_vp), ("top_k", c_vp), ("top_p", c_vp), ("seed", c_vp),
+                ("token_index", c_vp), ("n_kept", c_vp), ("p_chosen", c_vp)]
+
+
 class AttnArgs(C.Structure):
     _fields_ = [("Q", c_vp), ("K", c_vp), ("V", c_vp), ("O", c_vp),
                 ("B", c_i32), ("H", c_i32), ("Sq", c_i32), ("Skv", c_i32), ("D", c_i32), ("reserved", c_i32),
@@ -125,6 +130,8 @@ SIGNATURES = {
     "sx_attn_decode_b": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i64, c_i32, c_f32, c_i32, c_i64, c_vp],
     "sx_greedy_next_b": [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp],
     "sx_greedy_next_slots": [C.POINTER(SlotStepArgs), c_vp],
+    "sx_sample_next_b": [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, C.POINTER(SampleArgs), c_vp],
+    "sx_sample_next_slots": [C.POINTER(SlotStepArgs), C.POINTER(SampleArgs), c_vp],
     "sx_scatter_rows_step": [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp],
     "sx_add_i32_n": [c_vp, c_i32, c_i32, c_vp],
     "sx_embedding": [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp],

@@ -987,6 +987,288 @@ __global__ __launch_bounds__(1024) void greedy_next_slots_kernel(const SlotStepP
   s[3] = stop ? n : -1;
 }
 
+// ---- seeded sampling: temperature → top-k → top-p → draw, one workgroup per row (sx_sample_next_b / sx_sample_next_slots) -------------
+// transformers' sample() order (processors, then TemperatureLogitsWarper → TopKLogitsWarper → TopPLogitsWarper) in one launch, without a
+// sort and without a workspace. The row is read from memory ONCE into registers in a blocked layout (thread t holds the columns
+// [32 t, 32 t + 32): the index-ordered prefix sum of the draw is then one scan over the threads), as
+//   key_i = order-preserving 32-bit image of x_i (ordering by x is the ordering by t = x / T since T > 0; padding columns get key 0),
+//   w_i   = exp((x_i − max x) / T) in fp32 (= exp(t_i − max t); the rounding error of the exponent is relative to the distance from
+//           the maximum, so the tokens that carry mass are the accurate ones),
+//   q_i   = w_i · 2^40 as an integer (at least 1 where w_i > 0). Where the fp32 weight itself underflows to 0 (x_i more than about
+//           87 T .. 103 T below the maximum: a probability below 2^-126; -inf columns likewise) the mass is 0: such a token is never
+//           drawn, and it is neither kept nor counted in n_kept — with top_p = 1 too, where the written rule would keep every finite
+//           token. The fp64 statement drops it the same way once (larger mass) / W_k rounds to 1.
+// Every sum that decides something is a sum of the q_i in 64-bit integers, hence exact and independent of order, slot, launch and
+// replay: the id is a function of the row's values, the four parameters, the seed and the token index alone. Both thresholds come from
+// one radix select over the key (12 + 10 + 10 bits, an LDS histogram of integer masses per pass): it returns the smallest key v with
+// (mass of the keys above v) < target — with unit masses and target k that is the k-th largest value (ties at it are kept), with the
+// masses q and target ⌈top_p · W_k⌉ it is the nucleus threshold τ (kept iff the mass of the strictly larger survivors is below top_p;
+// equal values are kept or dropped together). The draw takes u = (Philox4x32-10((n, 0, 0, 0), seed)[0] >> 8) · 2^-24 and returns the
+// smallest index of the kept set whose inclusive prefix mass exceeds u · W, again in integers.
+typedef unsigned long long smp_u64;
+constexpr int SMP_NPT = 32;            // columns per thread: rows of up to 32768 columns stay in registers
+constexpr int SMP_MAX_VOCAB = SMP_NPT * 1024;
+
+struct SampleP {
+  const int* do_sample;
+  const float* temperature;
+  const int* top_k;
+  const float* top_p;
+  const unsigned* seed;
+  const int* token_index;
+  int* n_kept;
+  float* p_chosen;
+};
+
+__device__ __forceinline__ unsigned philox4x32_10_first(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+    const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return c0;
+}
+
+__device__ __forceinline__ unsigned smp_key(float x) {
+  unsigned u = __float_as_uint(x);
+  if (u == 0x80000000u) u = 0u;                            // −0 → +0 on the bits (x + 0.0f is folded away under fast-math): equal values, equal keys
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float smp_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+__device__ __forceinline__ smp_u64 smp_q(float w) {
+  const smp_u64 q = (smp_u64)(w * 1099511627776.0f);       // 2^40: exact scaling, truncation below 2^-40
+  return (w > 0.f && q == 0) ? 1 : q;
+}
+
+// exclusive prefix of v over the threads of the workgroup in thread order, and the total; wsum: 16 LDS entries
+__device__ __forceinline__ smp_u64 smp_block_scan(smp_u64 v, smp_u64* wsum, smp_u64& total) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  smp_u64 inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const smp_u64 n = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += n;
+  }
+  __syncthreads();                                         // the readers of an earlier call are through
+  if (lane == 63) wsum[wv] = inc;
+  __syncthreads();
+  smp_u64 base = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < 16; ++w) {
+    const smp_u64 s = wsum[w];
+    if (w < wv) base += s;
+    tot += s;
+  }
+  total = tot;
+  return base + inc - v;
+}
+
+// Radix select (see above) over the elements with key >= lo_key (lo_key >= 1 leaves the padding out). MASS: the masses are q(w), else 1.
+// Needs 1 <= target <= total mass of those elements; returns a key that one of them has.
+template <bool MASS>
+__device__ __forceinline__ unsigned smp_select(const unsigned (&key)[SMP_NPT], const float (&w)[SMP_NPT], unsigned lo_key, smp_u64 target,
+                                               smp_u64* hist, smp_u64* wsum, smp_u64* sel) {
+  unsigned prefix = 0, himask = 0;
+  smp_u64 acc = 0;                                         // mass of the keys above the current bucket
+#pragma unroll
+  for (int pass = 0; pass < 3; ++pass) {
+    const int shift = pass == 0 ? 20 : pass == 1 ? 10 : 0;
+    const int nb = pass == 0 ? 4096 : 1024, per = nb / 1024;
+    for (int b = threadIdx.x; b < nb; b += 1024) hist[b] = 0;
+    if (threadIdx.x == 0) { sel[0] = 0; sel[1] = acc; }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < SMP_NPT; ++j)
+      if (key[j] >= lo_key && (key[j] & himask) == prefix)
+        atomicAdd(&hist[(key[j] >> shift) & (nb - 1)], MASS ? smp_q(w[j]) : (smp_u64)1);    // integer: any arrival order, same sum
+    __syncthreads();
+    // thread t owns the bins nb − 1 − (t·per + j), highest first: the scan over the threads yields the mass above them
+    smp_u64 h[4], mine = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      h[j] = j < per ? hist[nb - 1 - ((int)threadIdx.x * per + j)] : 0;
+      mine += h[j];
+    }
+    smp_u64 tot;
+    smp_u64 above = acc + smp_block_scan(mine, wsum, tot);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (j < per && above < target && above + h[j] >= target) {        // exactly one bin of one thread
+        sel[0] = (smp_u64)(nb - 1 - ((int)threadIdx.x * per + j));
+        sel[1] = above;
+      }
+      above += h[j];
+    }
+    __syncthreads();
+    prefix |= (unsigned)sel[0] << shift;
+    acc = sel[1];
+    himask |= (unsigned)(nb - 1) << shift;
+    __syncthreads();                                       // sel and hist are rewritten by the next pass
+  }
+  return prefix;
+}
+
+// The next id of row g by the rule above; every thread returns it. n: 0-based index of the generated token within its request.
+// Greedy rows (do_sample = 0) and rows inside the forced image chain take greedy_next_id's path and value.
+// NOTE: this function is inlined into sample_next_kernel and into sample_next_slots_kernel, and the translation unit is built with
+// -ffast-math: that a request draws the same ids in the lock-step and in the in-flight step rests on the compiler lowering the weight
+// arithmetic (subtract, divide, exp) alike in both copies. Everything after the weights is integer and cannot differ. The two forms are
+// held bit-equal by tests/test_sampling_gpu.py (test_slots_form_samples_with_step_as_the_token_index, test_neighbours_do_not_matter);
+// if they ever part, give the weight its own __noinline__ function.
+__device__ __forceinline__ int sample_next_id(float* logits, int vocab, const int* img_ids, int n_img, int prev, const SampleP& s,
+                                              int g, int n) {
+  __shared__ smp_u64 hist[4096];
+  __shared__ smp_u64 wsum[16];
+  __shared__ smp_u64 sel[2];
+  __shared__ unsigned wmax[16];
+  __shared__ int forced, chosen;
+  __shared__ float chosen_p;
+  if (s.do_sample[g] == 0) {
+    if (threadIdx.x == 0) {
+      if (s.n_kept) s.n_kept[g] = -1;
+      if (s.p_chosen) s.p_chosen[g] = 1.0f;
+    }
+    return greedy_next_id(logits, vocab, img_ids, n_img, prev);
+  }
+  if (threadIdx.x == 0) forced = -1;
+  __syncthreads();
+  if ((int)threadIdx.x < n_img - 1 && img_ids[threadIdx.x] == prev) atomicMax(&forced, (int)threadIdx.x);
+  __syncthreads();
+  if (forced >= 0) {                                       // inside the chain: the next chain id, nothing is drawn (probability 1)
+    if (threadIdx.x == 0) {
+      if (s.n_kept) s.n_kept[g] = -1;
+      if (s.p_chosen) s.p_chosen[g] = 1.0f;
+    }
+    return img_ids[forced + 1];
+  }
+  if ((int)threadIdx.x < n_img - 1) logits[img_ids[1 + threadIdx.x]] = 0.0f;    // the only edit of the row, as in greedy_next_id
+  __syncthreads();
+  // ---- the row, once ----
+  unsigned key[SMP_NPT];
+  float w[SMP_NPT];
+  const int i0 = (int)threadIdx.x * SMP_NPT;
+  const bool vec = (((uintptr_t)logits) & 15) == 0;
+#pragma unroll
+  for (int j = 0; j < SMP_NPT; j += 4) {
+    const int i = i0 + j;
+    if (vec && i + 4 <= vocab) {
+      const float4 v = *reinterpret_cast<const float4*>(logits + i);
+      key[j] = smp_key(v.x); key[j + 1] = smp_key(v.y); key[j + 2] = smp_key(v.z); key[j + 3] = smp_key(v.w);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) key[j + e] = i + e < vocab ? smp_key(logits[i + e]) : 0u;
+    }
+  }
+  unsigned km = 0;
+#pragma unroll
+  for (int j = 0; j < SMP_NPT; ++j) km = max(km, key[j]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) km = max(km, (unsigned)__shfl_xor((int)km, o, 64));
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = km;
+  __syncthreads();
+  km = wmax[0];
+#pragma unroll
+  for (int v = 1; v < 16; ++v) km = max(km, wmax[v]);
+  const float xmax = smp_unkey(km);
+  const float T = s.temperature[g];
+#pragma unroll
+  for (int j = 0; j < SMP_NPT; ++j) w[j] = key[j] ? expf((smp_unkey(key[j]) - xmax) / T) : 0.f;
+  // ---- top-k: the k-th largest value ----
+  const int k = s.top_k[g];
+  unsigned kth = 1;
+  if (k > 0 && k < vocab) kth = smp_select<false>(key, w, 1u, (smp_u64)k, hist, wsum, sel);
+  // ---- top-p over the survivors ----
+  smp_u64 part = 0, Wk;
+#pragma unroll
+  for (int j = 0; j < SMP_NPT; ++j)
+    if (key[j] >= kth) part += smp_q(w[j]);
+  smp_block_scan(part, wsum, Wk);
+  smp_u64 target = (smp_u64)ceil((double)s.top_p[g] * (double)Wk);
+  target = target < 1 ? 1 : target > Wk ? Wk : target;
+  const unsigned tau = smp_select<true>(key, w, kth, target, hist, wsum, sel);
+  // ---- draw: smallest kept index whose inclusive prefix mass exceeds u · W ----
+  part = 0;
+  smp_u64 cnt = 0, W, nk;
+#pragma unroll
+  for (int j = 0; j < SMP_NPT; ++j)
+    if (key[j] >= tau) { part += smp_q(w[j]); cnt += 1; }
+  const smp_u64 base = smp_block_scan(part, wsum, W);
+  smp_block_scan(cnt, wsum, nk);
+  const smp_u64 m = philox4x32_10_first((unsigned)n, 0u, 0u, 0u, s.seed[2 * g], s.seed[2 * g + 1]) >> 8;
+  const smp_u64 thr = m * (W >> 24) + ((m * (W & 0xffffffull)) >> 24);      // ⌊m · W / 2^24⌋; prefix > u · W ⇔ prefix > thr
+  if (threadIdx.x == 0) { chosen = 0; chosen_p = 0.f; }
+  __syncthreads();
+  if (base <= thr && thr < base + part) {                  // exactly one thread: thr < W
+    smp_u64 run = base;
+    int id = -1;
+    smp_u64 qid = 0;
+#pragma unroll
+    for (int j = 0; j < SMP_NPT; ++j)
+      if (key[j] >= tau) {
+        const smp_u64 q = smp_q(w[j]);
+        run += q;
+        if (id < 0 && run > thr) { id = i0 + j; qid = q; }
+      }
+    chosen = id;
+    chosen_p = (float)((double)qid / (double)W);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (s.n_kept) s.n_kept[g] = (int)nk;
+    if (s.p_chosen) s.p_chosen[g] = chosen_p;
+  }
+  return chosen;
+}
+
+__global__ __launch_bounds__(1024) void sample_next_kernel(float* logits, int vocab, const int* img_ids, int n_img, const int* prev_id,
+                                                           int* next_id, int* out_ids, const int* step_dev, int ld_logits, int ld_out,
+                                                           const SampleP s) {
+  const int g = blockIdx.x;
+  const int result = sample_next_id(logits + (size_t)g * ld_logits, vocab, img_ids, n_img, prev_id[g], s, g, s.token_index[g]);
+  if (threadIdx.x == 0) {
+    next_id[g] = result;
+    if (out_ids) {
+      const int st = step_dev[g];
+      if (st >= 0 && (ld_out <= 0 || st < ld_out)) out_ids[(size_t)g * ld_out + st] = result;   // ld_out doubles as the row capacity
+    }
+  }
+}
+
+// greedy_next_slots_kernel with the sampled id: parking, stop rule, counters and status are the same; the token index is step[g]
+__global__ __launch_bounds__(1024) void sample_next_slots_kernel(const SlotStepP p, const SampleP s) {
+  const int g = blockIdx.x;
+  if (p.live[g] == 0) return;                       // parked (uniform over the workgroup: no barrier is skipped by a part of it)
+  // every thread reads cur[g] and step[g] before the first barrier of sample_next_id; thread 0 stores to them after the last one
+  int result = sample_next_id(p.logits + (size_t)g * p.ld_logits, p.vocab, p.img_ids, p.n_img, p.cur[g], s, g, p.step[g]);
+  if (threadIdx.x != 0) return;
+  int n = p.n_new[g];
+  const int fa = p.force_at[g];
+  if (fa >= 0 && n == fa) result = p.force_id;      // synthetic weights only: replaced AFTER the draw (no work skipped)
+  const int st = p.step[g];
+  if (p.out_ids && st >= 0 && st < p.ld_out) p.out_ids[(size_t)g * p.ld_out + st] = result;   // ld_out is the row capacity
+  p.cur[g] = result;
+  n += 1;
+  p.n_new[g] = n;
+  const bool stop = (p.eos_id >= 0 && result == p.eos_id) || n >= p.max_new[g];
+  if (stop) {
+    p.live[g] = 0;
+    p.step[g] = -1;
+    p.pos[g] = -1;
+    p.ctx[g] = 0;
+  } else {
+    p.step[g] = st + 1;
+    p.pos[g] += 1;
+    p.ctx[g] += 1;
+  }
+  int* q = p.status + 4 * g;
+  q[0] = result;
+  q[1] = stop ? 0 : 1;
+  q[2] = n;
+  q[3] = stop ? n : -1;
+}
+
 inline dim3 gs_grid(int64_t n) {
   int64_t b = (n + 255) / 256;
   if (b > 4096) b = 4096;
@@ -1251,6 +1533,49 @@ extern "C" int sx_greedy_next_slots(const sx_slot_step_args* a, void* stream) {
   p.ld_logits = a->ld_logits; p.vocab = a->vocab; p.n_img = a->n_img; p.ld_out = a->ld_out;
   p.force_id = a->force_id; p.eos_id = a->eos_id;
   hipLaunchKernelGGL(greedy_next_slots_kernel, dim3(a->G), dim3(1024), 0, ST, p);
+  SX_HIP_LAUNCH_CHECK();
+  return SX_OK;
+}
+
+static int sample_params(const sx_sample_args* s, int vocab, const char* who, SampleP* out) {
+  SX_CHECK(s && s->do_sample && s->temperature && s->top_k && s->top_p && s->seed, "%s: null pointer in sx_sample_args", who);
+  SX_CHECK(vocab >= 1 && vocab <= SMP_MAX_VOCAB, "%s: vocab=%d (a sampled row holds at most %d columns)", who, vocab, SMP_MAX_VOCAB);
+  out->do_sample = s->do_sample; out->temperature = s->temperature; out->top_k = s->top_k; out->top_p = s->top_p;
+  out->seed = s->seed; out->token_index = s->token_index; out->n_kept = s->n_kept; out->p_chosen = s->p_chosen;
+  return SX_OK;
+}
+
+extern "C" int sx_sample_next_b(float* logits, int ld_logits, int vocab, const int32_t* img_ids_dev, int n_img,
+                                const int32_t* prev_id_dev, int32_t* next_id_dev, int32_t* out_ids, int ld_out,
+                                const int32_t* step_dev, int G, const sx_sample_args* sample, void* stream) {
+  SX_CHECK(logits && img_ids_dev && prev_id_dev && next_id_dev, "sx_sample_next_b: null pointer");
+  SX_CHECK(n_img >= 2 && n_img <= 1024 && G >= 1, "sx_sample_next_b: n_img=%d G=%d", n_img, G);
+  SX_CHECK(!out_ids || step_dev, "sx_sample_next_b: out_ids needs step_dev");
+  SX_CHECK(G == 1 || ld_logits >= vocab, "sx_sample_next_b: vocab=%d ld_logits=%d", vocab, ld_logits);
+  SampleP s;
+  if (int rc = sample_params(sample, vocab, "sx_sample_next_b", &s)) return rc;
+  SX_CHECK(s.token_index, "sx_sample_next_b: token_index is required");
+  hipLaunchKernelGGL(sample_next_kernel, dim3(G), dim3(1024), 0, ST, logits, vocab, img_ids_dev, n_img, prev_id_dev, next_id_dev,
+                     out_ids, step_dev, ld_logits, ld_out, s);
+  SX_HIP_LAUNCH_CHECK();
+  return SX_OK;
+}
+
+extern "C" int sx_sample_next_slots(const sx_slot_step_args* a, const sx_sample_args* sample, void* stream) {
+  SX_CHECK(a && a->logits && a->img_ids_dev && a->cur && a->live && a->n_new && a->max_new && a->force_at && a->pos && a->ctx &&
+           a->step && a->status, "sx_sample_next_slots: null pointer");
+  SX_CHECK(a->n_img >= 2 && a->n_img <= 1024 && a->G >= 1, "sx_sample_next_slots: n_img=%d G=%d", a->n_img, a->G);
+  SX_CHECK(a->vocab >= 1 && a->ld_logits >= a->vocab, "sx_sample_next_slots: vocab=%d ld_logits=%d", a->vocab, a->ld_logits);
+  SX_CHECK(!a->out_ids || a->ld_out >= 1, "sx_sample_next_slots: out_ids needs ld_out >= 1 (the row capacity)");
+  SampleP s;
+  if (int rc = sample_params(sample, a->vocab, "sx_sample_next_slots", &s)) return rc;
+  SlotStepP p;
+  p.logits = a->logits; p.img_ids = a->img_ids_dev; p.cur = a->cur; p.live = a->live; p.n_new = a->n_new;
+  p.max_new = a->max_new; p.force_at = a->force_at; p.pos = a->pos; p.ctx = a->ctx; p.step = a->step;
+  p.out_ids = a->out_ids; p.status = a->status;
+  p.ld_logits = a->ld_logits; p.vocab = a->vocab; p.n_img = a->n_img; p.ld_out = a->ld_out;
+  p.force_id = a->force_id; p.eos_id = a->eos_id;
+  hipLaunchKernelGGL(sample_next_slots_kernel, dim3(a->G), dim3(1024), 0, ST, p, s);
   SX_HIP_LAUNCH_CHECK();
   return SX_OK;
 }

@@ -133,17 +133,63 @@ class SlotState:
     the most recent step (the captured graph's own buffer under replay)."""
     IDLE = {"pos": -1, "ctx": 0, "step": -1}
 
-    def __init__(self, G, device, force_id=-1, eos_id=-1):
+    def __init__(self, G, device, force_id=-1, eos_id=-1, sampling=False):
         z = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=device)
         self.G = G
         self.live, self.n_new, self.max_new, self.status = z(G), z(G), z(G), z(G, 4)
         self.force_at = torch.full((G,), -1, dtype=torch.int32, device=device)
         self.force_id, self.eos_id = int(force_id), int(eos_id)
         self.logits = None
+        self.sampling = SampleState(G, device) if sampling else None     # None: the greedy step (sx_greedy_next_slots)
 
     def key(self):
         return tuple(t.data_ptr() for t in (self.live, self.n_new, self.max_new, self.force_at, self.status)) \
-            + (self.force_id, self.eos_id)
+            + (self.force_id, self.eos_id) + (self.sampling.key() if self.sampling is not None else ())
+
+
+class SampleState:
+    """Per-row sampling parameters of the token step on the device (sx_sample_args; seedx_amd.sampling states the rule): ``do_sample`` /
+    ``top_k`` int32 [G], ``temperature`` / ``top_p`` fp32 [G], ``seed`` int32 [G, 2] (low word, high word). The kernels read them at
+    launch, so a captured step serves any mix of greedy and sampled rows and a row's parameters change without a new capture. A fresh
+    state is all greedy. ``n_kept`` / ``p_chosen``: what the most recent launch reported per row (-1 / 1.0 where nothing was drawn)."""
+
+    def __init__(self, G, device):
+        self.G, self.device = int(G), device
+        self.do_sample = torch.zeros(G, dtype=torch.int32, device=device)
+        self.temperature = torch.ones(G, dtype=torch.float32, device=device)
+        self.top_k = torch.zeros(G, dtype=torch.int32, device=device)
+        self.top_p = torch.ones(G, dtype=torch.float32, device=device)
+        self.seed = torch.zeros((G, 2), dtype=torch.int32, device=device)
+        self.n_kept = torch.full((G,), -1, dtype=torch.int32, device=device)
+        self.p_chosen = torch.ones(G, dtype=torch.float32, device=device)
+
+    def key(self):
+        return tuple(t.data_ptr() for t in (self.do_sample, self.temperature, self.top_k, self.top_p, self.seed, self.n_kept,
+                                            self.p_chosen))
+
+    def set_rows(self, rows, params):
+        """rows[i] takes params[i] (a sampling.SamplingParams, or None = greedy): five small host → device copies."""
+        rows = list(rows)
+        if not rows:
+            return
+        on = [p is not None and p.do_sample for p in params]
+        idx = torch.tensor(rows, dtype=torch.int64, device=self.device)
+        i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=self.device)
+        f32 = lambda v: torch.tensor(v, dtype=torch.float32, device=self.device)
+        s32 = lambda w: w - (1 << 32) if w >= 1 << 31 else w          # the 32-bit pattern as an int32
+        self.do_sample.index_copy_(0, idx, i32([int(o) for o in on]))
+        self.temperature.index_copy_(0, idx, f32([p.temperature if o else 1.0 for p, o in zip(params, on)]))
+        self.top_k.index_copy_(0, idx, i32([p.top_k if o else 0 for p, o in zip(params, on)]))
+        self.top_p.index_copy_(0, idx, f32([p.top_p if o else 1.0 for p, o in zip(params, on)]))
+        self.seed.index_copy_(0, idx, i32([[s32(p.seed & 0xffffffff), s32(p.seed >> 32)] if o else [0, 0] for p, o in zip(params, on)]))
+
+    def gather(self, rows):
+        """A state of len(rows) rows holding copies of the given rows' parameters (the first token of admitted requests)."""
+        out = SampleState(len(rows), self.device)
+        idx = torch.tensor(list(rows), dtype=torch.int64, device=self.device)
+        for k in ("do_sample", "temperature", "top_k", "top_p", "seed"):
+            getattr(out, k).copy_(getattr(self, k).index_select(0, idx))
+        return out
 
 
 class LlamaForCausalLM:
@@ -197,6 +243,9 @@ class LlamaForCausalLM:
         self._sd, self._P = None, None
         self._graph = None
         self._slot_graph = None         # the captured in-flight token step (decode_step(..., slots=...)): one per engine lifetime
+        self._sample_graph = None       # the sampled forms of the two (a greedy step and a sampled step never share a graph)
+        self._slot_sample_graph = None
+        self._sample_state = None
         self.kv_epoch = 0               # bumped whenever the KV cache is reset or written outside generate_batch
 
     def memory_footprint(self):
@@ -398,6 +447,8 @@ class LlamaForCausalLM:
         self._sd = None
         self._graph = None
         self._slot_graph = None
+        self._sample_graph = None
+        self._slot_sample_graph = None
         return P
 
     # ---- core passes ---------------------------------------------------------------------------------------------------
@@ -712,12 +763,14 @@ class LlamaForCausalLM:
     __call__ = forward
 
     # ---- in-flight batching: slot states ---------------------------------------------------------------------------------
-    def slot_state(self, force_id=-1, eos_id=-1):
-        """A fresh SlotState with EVERY slot parked (the module's pos / ctx / step take the idle values; ``reset()`` undoes that)."""
+    def slot_state(self, force_id=-1, eos_id=-1, sampling=False):
+        """A fresh SlotState with EVERY slot parked (the module's pos / ctx / step take the idle values; ``reset()`` undoes that).
+        ``sampling``: the state carries a SampleState (``.sampling``, all rows greedy until set) and its token step ends in
+        sx_sample_next_slots instead of sx_greedy_next_slots."""
         if self.tp > 1:
             raise NotImplementedError("in-flight batching (slot states) is single-rank: tensor-parallel ranks are not supported")
         self._pack()
-        st = SlotState(self.G, self.device, force_id, eos_id)
+        st = SlotState(self.G, self.device, force_id, eos_id, sampling)
         self.park_slots(range(self.G), st)
         return st
 
@@ -740,7 +793,15 @@ class LlamaForCausalLM:
             self._slot_write(P[k], slots, v)
 
     # ---- device-resident greedy decode step (all sequences in lock step) -----------------------------------------------
-    def _decode_step_body(self, img_ids_dev, out_ids, hid_buf, slots=None):
+    def sample_state(self):
+        """The module's SampleState for the lock-step step (``decode_step(..., sampling=...)``), made once: its pointers are part of
+        the captured graph's key."""
+        self._pack()
+        if self._sample_state is None:
+            self._sample_state = SampleState(self.G, self.device)
+        return self._sample_state
+
+    def _decode_step_body(self, img_ids_dev, out_ids, hid_buf, slots=None, sampling=None):
         """cur[G] → embedding → 40 layers → final norm → lm_head → logits rule + argmax → cur[G]. Records the post-norm
         hidden state of each INPUT token at hid_buf[g, step[g]] (what seed_x.py:196 collects) and the new id at
         out_ids[g, step[g]]; then step += 1. Everything stays on the device. ``slots`` (a SlotState): the tail is ONE
@@ -764,28 +825,46 @@ class LlamaForCausalLM:
         if self.tp > 1:
             logits = self.comm.all_gather(logits).permute(1, 0, 2).reshape(self.G, self.Vpad).contiguous()
         if slots is not None:
-            ops.greedy_next_slots(logits, self.V, img_ids_dev, P["cur"], slots.live, slots.n_new, slots.max_new, slots.force_at,
-                                  P["pos"], P["ctx"], P["step"], out_ids, slots.status, slots.force_id, slots.eos_id)
+            if slots.sampling is not None:      # the sampled step: same tail, the id by the seeded rule (token index = step[g])
+                ss = slots.sampling
+                ops.sample_next_slots(logits, self.V, img_ids_dev, P["cur"], slots.live, slots.n_new, slots.max_new, slots.force_at,
+                                      P["pos"], P["ctx"], P["step"], out_ids, slots.status, ss, slots.force_id, slots.eos_id,
+                                      n_kept=ss.n_kept, p_chosen=ss.p_chosen)
+            else:
+                ops.greedy_next_slots(logits, self.V, img_ids_dev, P["cur"], slots.live, slots.n_new, slots.max_new, slots.force_at,
+                                      P["pos"], P["ctx"], P["step"], out_ids, slots.status, slots.force_id, slots.eos_id)
             slots.logits = logits
             return
-        ops.greedy_next_b(logits, self.V, img_ids_dev, P["cur"], out_ids, P["step"])
+        if sampling is not None:                # every rank draws from the same gathered logits with the same seed and index
+            ops.sample_next_b(logits, self.V, img_ids_dev, P["cur"], out_ids, P["step"], sampling, n_kept=sampling.n_kept,
+                              p_chosen=sampling.p_chosen)
+        else:
+            ops.greedy_next_b(logits, self.V, img_ids_dev, P["cur"], out_ids, P["step"])
         ops.add_i32(P["step"], 1)
 
-    def decode_step(self, img_ids_dev, out_ids, hid_buf, use_graph=True, slots=None):
+    def decode_step(self, img_ids_dev, out_ids, hid_buf, use_graph=True, slots=None, sampling=None):
         """out_ids: int32 [G, rows]; hid_buf: fp32 [G, rows, H]. ``slots``: a SlotState → the in-flight step (its captured graph is
-        kept apart from the lock-step one, so one graph serves an engine's lifetime whatever else runs in between)."""
+        kept apart from the lock-step one, so one graph serves an engine's lifetime whatever else runs in between). ``sampling``: a
+        SampleState → the lock-step step ends in sx_sample_next_b (token index = step[g]); a slot state brings its own
+        (``slots.sampling``). The state's pointers are part of the graph key: a sampled step and a greedy step never share a graph,
+        and the parameters are read from device memory at replay."""
         self._pack()
         assert out_ids.shape[0] == self.G and hid_buf.shape[0] == self.G and hid_buf.shape[1] == out_ids.shape[1]
         if slots is not None:
             if self.tp > 1:
                 raise NotImplementedError("in-flight batching (slot states) is single-rank: tensor-parallel ranks are not supported")
             assert out_ids.is_contiguous() and slots.G == self.G
+            assert sampling is None, "a slot state carries its own sampling state (slot_state(sampling=True))"
+        assert sampling is None or sampling.G == self.G
         if not use_graph or not self.comm.graph_safe:
-            self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots)
+            self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling)
             return
-        attr = "_graph" if slots is None else "_slot_graph"
+        if slots is None:
+            attr = "_graph" if sampling is None else "_sample_graph"
+        else:
+            attr = "_slot_graph" if slots.sampling is None else "_slot_sample_graph"
         key = (img_ids_dev.data_ptr(), out_ids.data_ptr(), hid_buf.data_ptr(), tuple(out_ids.shape)) \
-            + (slots.key() if slots is not None else ())
+            + (slots.key() if slots is not None else ()) + (("sample",) + sampling.key() if sampling is not None else ())
         held = getattr(self, attr)
         if held is None or held[0] != key:
             # warm-up on a side stream (allocator / lazy module load), then capture one token step. The warm-up really runs a
@@ -797,14 +876,14 @@ class LlamaForCausalLM:
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
-                self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots)
+                self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling)
             torch.cuda.current_stream().wait_stream(s)
             torch.cuda.synchronize()
             for t, v in snap.values():
                 t.copy_(v)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots)
+                self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling)
             for t, v in snap.values():
                 t.copy_(v)
             held = (key, g) + ((slots.logits,) if slots is not None else ())

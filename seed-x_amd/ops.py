@@ -815,6 +815,58 @@ def greedy_next_slots(logits, vocab, img_ids_dev, cur, live, n_new, max_new, for
     check(lib.sx_greedy_next_slots(C.byref(a), _stream()), "sx_greedy_next_slots")
 
 
+def _sample_args(sample, G, token_index=None, n_kept=None, p_chosen=None):
+    """sx_sample_args from a sampling state (llama.SampleState or anything with its five [G] device tensors; seed is [G, 2])."""
+    i32, f32 = torch.int32, torch.float32
+    for t, dt, n in ((sample.do_sample, i32, G), (sample.temperature, f32, G), (sample.top_k, i32, G), (sample.top_p, f32, G),
+                     (sample.seed, i32, 2 * G), (token_index, i32, G), (n_kept, i32, G), (p_chosen, f32, G)):
+        if t is not None:
+            assert t.dtype == dt and t.is_contiguous() and t.numel() == n, "sampling: contiguous [G] tensors (seed int32 [G, 2])"
+    d = lambda t: None if t is None else _p(t).value      # (GPU tensors only: no CPU fallback)
+    return _lib.SampleArgs(do_sample=d(sample.do_sample), temperature=d(sample.temperature), top_k=d(sample.top_k),
+                           top_p=d(sample.top_p), seed=d(sample.seed), token_index=d(token_index), n_kept=d(n_kept),
+                           p_chosen=d(p_chosen))
+
+
+def sample_next_b(logits, vocab, img_ids_dev, cur_dev, out_ids, step_dev, sample, token_index=None, n_kept=None, p_chosen=None):
+    """greedy_next_b with the seeded sampling rule (sx_sample_next_b; seedx_amd.sampling states the rule): ``sample`` holds the per-row
+    parameters on the device (do_sample / top_k int32 [G], temperature / top_p fp32 [G], seed int32 [G, 2] = low, high word);
+    ``token_index`` int32 [G] is the index of the generated token within its request (default: ``step_dev``). Rows with do_sample = 0
+    take the greedy id. Optional outputs n_kept int32 [G], p_chosen fp32 [G]."""
+    lib = _lib.load()
+    G = logits.shape[0]
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1
+    token_index = step_dev if token_index is None else token_index
+    assert token_index is not None, "sample_next_b: token_index (or step_dev) is required"
+    a = _sample_args(sample, G, token_index, n_kept, p_chosen)
+    check(lib.sx_sample_next_b(_p(logits), logits.stride(0), vocab, _p(img_ids_dev), img_ids_dev.numel(), _p(cur_dev),
+                               _p(cur_dev), _p(out_ids), out_ids.stride(0) if out_ids is not None else 0, _p(step_dev), G,
+                               C.byref(a), _stream()), "sx_sample_next_b")
+
+
+def sample_next_slots(logits, vocab, img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, out_ids, status, sample,
+                      force_id=-1, eos_id=-1, n_kept=None, p_chosen=None):
+    """greedy_next_slots with the seeded sampling rule (sx_sample_next_slots): the token index of slot g is ``step[g]``."""
+    lib = _lib.load()
+    G = logits.shape[0]
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1
+    for t in (img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, status) + ((out_ids,) if out_ids is not None else ()):
+        assert t.dtype == torch.int32 and t.is_contiguous(), "sample_next_slots: contiguous int32 tensors"
+    for t in (cur, live, n_new, max_new, force_at, pos, ctx, step):
+        assert t.numel() == G
+    assert status.numel() == 4 * G and (out_ids is None or out_ids.shape[0] == G)
+    a = _lib.SlotStepArgs(
+        logits=logits.data_ptr(), img_ids_dev=img_ids_dev.data_ptr(), cur=cur.data_ptr(), live=live.data_ptr(),
+        n_new=n_new.data_ptr(), max_new=max_new.data_ptr(), force_at=force_at.data_ptr(), pos=pos.data_ptr(), ctx=ctx.data_ptr(),
+        step=step.data_ptr(), out_ids=out_ids.data_ptr() if out_ids is not None else None, status=status.data_ptr(),
+        ld_logits=logits.stride(0), vocab=int(vocab), n_img=img_ids_dev.numel(), ld_out=out_ids.shape[1] if out_ids is not None else 0,
+        force_id=int(force_id), eos_id=int(eos_id), G=G, reserved=0)
+    for t in (logits, img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, status):
+        _p(t)                                   # (GPU tensors only: no CPU fallback)
+    s = _sample_args(sample, G, None, n_kept, p_chosen)
+    check(lib.sx_sample_next_slots(C.byref(a), C.byref(s), _stream()), "sx_sample_next_slots")
+
+
 def scatter_rows_step(src, step_dev, dst):
     """dst [G, rows, dim] fp32; dst[g, step[g]] = src[g]."""
     lib = _lib.load()

@@ -14,6 +14,7 @@ import torch
 
 from . import ops
 from .inflight import SlotScheduler
+from .sampling import SamplingParams
 
 BOI_TOKEN = '<img>'
 EOI_TOKEN = '</img>'
@@ -152,10 +153,15 @@ class ContinuousLVLM:
                        force_image_at=None, reuse_cache=False):
         """G = len(requests) = llm.G independent requests decoded in lock step. Each request is a dict with the
         ``generate`` keyword arguments (input_ids | prompt, image_embeds, embeds_cmp_mask, ids_cmp_mask,
-        patch_positions). Returns one reference-style result dict per request.
+        patch_positions). Returns one reference-style result dict per request. A request may also carry ``do_sample``, ``temperature``,
+        ``top_k``, ``top_p`` and ``seed`` (sampling.SamplingParams): its tokens — the prefill's first one included, token index 0 —
+        are then drawn on the device by the seeded rule of seedx_amd.sampling (sx_sample_next_b) and its result carries ``'seed'``;
+        without a sampling request the call runs the greedy path unchanged. Tensor-parallel ranks (each its own process) must be
+        given the same explicit ``seed``: ``seed=None`` is refused there (ValueError), since each rank would draw its own.
         ``reuse_cache``: keep each sequence's KV cache across calls and prefill only the part of the new prompt that is not
         already in it (multi-turn conversations; results are identical to a full re-prefill)."""
         llm = self.llm
+        params = [SamplingParams.from_request(req, world=llm.comm.world) for req in requests]     # refuses seed=None on tp > 1 ranks
         dev, H, G = llm.device, llm.H, len(requests)
         P = llm._pack()
         assert G == llm.G, f"the LLM was built for max_batch={llm.G} lock-step sequences, got {G} requests"
@@ -172,6 +178,10 @@ class ContinuousLVLM:
 
         # ---- prefill every request (ONE batched pass: M = sum of the prompt lengths), first token --------------------
         prompts = [self._prompt_embeds(tokenizer, req) for req in requests]
+        ss = None
+        if any(p is not None for p in params):          # per-row parameters on the device; greedy rows keep the arg-max
+            ss = llm.sample_state()
+            ss.set_rows(range(G), params)
         starts = self._reuse_prefix(prompts) if reuse_cache else [0] * G
         if not reuse_cache:
             llm.reset()
@@ -188,7 +198,10 @@ class ContinuousLVLM:
         logits = logits.contiguous()
         self.last_prefill_tokens = [int(x.shape[0]) for x in xs]
         P["cur"].copy_(torch.tensor(last_ids, dtype=torch.int32))
-        ops.greedy_next_b(logits, llm.V, img_ids_dev, P["cur"], out_ids, P["step"])
+        if ss is not None:
+            ops.sample_next_b(logits, llm.V, img_ids_dev, P["cur"], out_ids, P["step"], ss)      # token index 0
+        else:
+            ops.greedy_next_b(logits, llm.V, img_ids_dev, P["cur"], out_ids, P["step"])
         ops.add_i32(P["step"], 1)
         n_new = [1] * G
         cur = P["cur"].tolist()
@@ -231,7 +244,7 @@ class ContinuousLVLM:
                         done[g], final_n[g] = True, n_new[g]
             if all(done):
                 break
-            llm.decode_step(img_ids_dev, out_ids, hid, use_graph=self.use_graph)            # one token for every sequence
+            llm.decode_step(img_ids_dev, out_ids, hid, use_graph=self.use_graph, sampling=ss)   # one token for every sequence
             cur = P["cur"].tolist()                                                          # the only read-back per step
             llm.comm.check()                              # (tensor-parallel only: + 4 bytes) a timed-out collective must not pass
             for g in range(G):
@@ -264,6 +277,8 @@ class ContinuousLVLM:
             results.append({'text': text, 'has_img_output': len(eoi_indices) > 0, 'img_gen_feat': img_gen_feat,
                             'num_gen_imgs': len(eoi_indices), 'generate_ids': generate_ids,
                             'last_hidden_states': last_hidden})
+            if params[g] is not None:
+                results[-1]['seed'] = params[g].seed
         return results
 
     def _result(self, tokenizer, generate_ids, last_hidden, boi_id, eoi_id, num_img_gen_tokens):
@@ -293,6 +308,10 @@ class ContinuousLVLM:
         admission pass (None: every free slot), each round of a pass ONE batched prefill. The host reads one [G, 4] status tensor
         per step. Returns one reference-style result dict per request, in request order; ``on_result(index, result)`` is called as
         each request finishes; ``last_inflight_stats`` holds the step counts (inflight.simulate predicts them from the lengths).
+        Requests may carry ``do_sample``, ``temperature``, ``top_k``, ``top_p`` and ``seed`` as in generate_batch: a queue with at least
+        one such request runs the sampled token step (sx_sample_next_slots: same stop rule, the parameters are read per slot from
+        device memory, greedy requests keep the arg-max); a queue without one runs the greedy step as before. A request's ids depend
+        on its own logits, parameters, seed and token indices only — never on its slot or its neighbours.
         Forced image blocks stay host-driven chunks as in generate_batch (the other slots wait). Cross-turn cache reuse is not
         offered here: the call clears those records. Slots are reused without zeroing: keys at or above ``pos`` are never visible."""
         llm = self.llm
@@ -312,6 +331,8 @@ class ContinuousLVLM:
         nchunk = num_img_gen_tokens + 1
         budget = [int(req.get("max_new_tokens") or max_new_tokens) for req in requests]
         force_at = [-1 if req.get("force_image_at") is None else int(req["force_image_at"]) for req in requests]
+        params = [SamplingParams.from_request(req) for req in requests]
+        sampled = any(p is not None for p in params)
         assert all(b >= 1 for b in budget)
         rows = max(budget) + 8
         keep = self._inflight
@@ -321,12 +342,13 @@ class ContinuousLVLM:
                 img_ids_dev=torch.tensor(img_ids, dtype=torch.int32, device=dev),
                 out_ids=torch.full((G, rows), -1, dtype=torch.int32, device=dev),
                 hid=torch.zeros((G, rows, H), dtype=torch.float32, device=dev),              # row k = state at input new[k-1]
-                state=None)
+                state=None, state_sampled=None)
         llm.reset()                                      # bumps kv_epoch: the cross-turn records no longer describe the cache
         self._conv = {}
-        if keep["state"] is None:
-            keep["state"] = llm.slot_state(force_id=boi_id, eos_id=eos)
-        st, img_ids_dev, out_ids, hid = keep["state"], keep["img_ids_dev"], keep["out_ids"], keep["hid"]
+        which = "state_sampled" if sampled else "state"        # two slot states, two captured steps: neither disturbs the other
+        if keep[which] is None:
+            keep[which] = llm.slot_state(force_id=boi_id, eos_id=eos, sampling=sampled)
+        st, img_ids_dev, out_ids, hid = keep[which], keep["img_ids_dev"], keep["out_ids"], keep["hid"]
         llm.park_slots(range(G), st)
         sched = SlotScheduler(G, N, max_admit)
         results = [None] * N
@@ -339,6 +361,8 @@ class ContinuousLVLM:
             generate_ids = out_ids[g, :n].cpu().long()
             last_hidden = hid[g, 1:n].clone()                                                # the slot's rows are reused
             results[r] = self._result(tokenizer, generate_ids, last_hidden, boi_id, eoi_id, num_img_gen_tokens)
+            if params[r] is not None:
+                results[r]['seed'] = params[r].seed
             if on_result is not None:
                 on_result(r, results[r])
 
@@ -358,7 +382,12 @@ class ContinuousLVLM:
             llm._slot_write(P["ctx"], slots, 1)
             logits, _ = llm.forward_embeds_batch(xs, slots)
             first = torch.tensor(last_ids, dtype=torch.int32, device=dev)
-            ops.greedy_next_b(logits.contiguous(), llm.V, img_ids_dev, first, None, None)
+            if sampled:                                  # the slots take their requests' parameters; token index 0 is drawn here
+                st.sampling.set_rows(slots, [params[r] for _, r in adm])
+                ops.sample_next_b(logits.contiguous(), llm.V, img_ids_dev, first, None, None, st.sampling.gather(slots),
+                                  token_index=torch.zeros(len(slots), dtype=torch.int32, device=dev))
+            else:
+                ops.greedy_next_b(logits.contiguous(), llm.V, img_ids_dev, first, None, None)
             first = first.tolist()
             llm.comm.check()
             stats["admissions"] += len(adm)
@@ -432,13 +461,19 @@ class ContinuousLVLM:
     def generate(self, tokenizer, prompt=None, input_ids=None, image_embeds=None, embeds_cmp_mask=None,
                  ids_cmp_mask=None, logits_processor=None, num_img_gen_tokens=64, temperature=0.7, num_beams=1,
                  max_new_tokens=120, top_p=0.5, dtype=torch.float16, device='cuda', patch_positions=None,
-                 eos_token_id="auto", force_image_at=None, reuse_cache=False):
-        """Reference signature (seed_x.py:130-145). Greedy (do_sample=False, num_beams=1 — temperature/top_p are inert in
-        the reference too, :175-189). ``eos_token_id``: "auto" → tokenizer.eos_token_id; None disables the EOS stop."""
+                 eos_token_id="auto", force_image_at=None, reuse_cache=False, do_sample=False, top_k=50, seed=None):
+        """Reference signature (seed_x.py:130-145). Greedy by default (do_sample=False, num_beams=1 — temperature/top_p are inert
+        in the reference too, :175-189). ``do_sample=True`` makes ``temperature`` / ``top_p`` live (defaults: the reference's 0.7 /
+        0.5) together with ``top_k`` (50, transformers' generation default) and ``seed`` (None: 64 bits from os.urandom): the seeded
+        device-side rule of seedx_amd.sampling; the result then carries ``'seed'``. ``eos_token_id``: "auto" →
+        tokenizer.eos_token_id; None disables the EOS stop. On tensor-parallel ranks ``do_sample=True`` needs an explicit ``seed``, the
+        same on every rank (ValueError otherwise)."""
         assert logits_processor is None, "the AutoImageTokenGenerationProcessor rule is fused on the device"
         assert num_beams == 1
         assert self.llm.G == 1, "this LLM was built for lock-step batches: use generate_batch()"
         req = dict(prompt=prompt, input_ids=input_ids, image_embeds=image_embeds, embeds_cmp_mask=embeds_cmp_mask,
                    ids_cmp_mask=ids_cmp_mask, patch_positions=patch_positions)
+        if do_sample:
+            req.update(do_sample=True, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
         return self.generate_batch(tokenizer, [req], num_img_gen_tokens, max_new_tokens, eos_token_id, force_image_at,
                                    reuse_cache)[0]
