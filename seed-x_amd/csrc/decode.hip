@@ -868,67 +868,58 @@ __global__ void scatter_rows_step_kernel(const float* src, const int* step, floa
 }
 
 // ---- greedy next token with the AutoImageTokenGenerationProcessor rule (generation.py:19-31) ------------------------
-// One workgroup of 1024 threads per logits row; every thread returns the row's next id. Shared by greedy_next_kernel and
-// greedy_next_slots_kernel: the rule and the first-maximal-index arg-max exist once.
-__device__ __forceinline__ int greedy_next_id(float* logits, int vocab, const int* img_ids, int n_img, int prev) {
-  __shared__ float smax[16];
-  __shared__ int sidx[16];
+// One workgroup of 1024 threads per logits row; the rule and the first-maximal-index arg-max exist once, for every form of
+// next_token_kernel below.
+// The rule's prologue: prev in img_ids[:-1] → its index there, so that the caller forces the next id of the chain (scores[next] =
+// max + 10 in the reference); else -1, with the image columns of the row zeroed in place (the only edit of the row) and visible to
+// every thread. Every thread returns the same value.
+__device__ __forceinline__ int image_chain_index(float* logits, const int* img_ids, int n_img, int prev) {
   __shared__ int forced;
   if (threadIdx.x == 0) forced = -1;
   __syncthreads();
-  // prev in img_ids[:-1] → force the next id of the chain (scores[next] = max + 10 in the reference)
+  // list.index() returns the FIRST match; ids are unique so max == first
   if ((int)threadIdx.x < n_img - 1 && img_ids[threadIdx.x] == prev) atomicMax(&forced, (int)threadIdx.x);
   __syncthreads();
-  int result;
-  if (forced >= 0) {
-    // list.index() returns the FIRST match; ids are unique so max == first
-    result = img_ids[forced + 1];
-  } else {
-    if ((int)threadIdx.x < n_img - 1) logits[img_ids[1 + threadIdx.x]] = 0.0f;
-    __syncthreads();
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = threadIdx.x; i < vocab; i += 1024) {
-      const float v = logits[i];
-      if (v > best || (v == best && i < bi)) { best = v; bi = i; }
-    }
+  if (forced >= 0) return forced;
+  if ((int)threadIdx.x < n_img - 1) logits[img_ids[1 + threadIdx.x]] = 0.0f;
+  __syncthreads();
+  return -1;
+}
+
+// first maximal index of the row; every thread returns it
+__device__ __forceinline__ int row_argmax(const float* logits, int vocab) {
+  __shared__ float smax[16];
+  __shared__ int sidx[16];
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int i = threadIdx.x; i < vocab; i += 1024) {
+    const float v = logits[i];
+    if (v > best || (v == best && i < bi)) { best = v; bi = i; }
+  }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(best, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
-    if ((threadIdx.x & 63) == 0) { smax[threadIdx.x >> 6] = best; sidx[threadIdx.x >> 6] = bi; }
-    __syncthreads();
-    best = smax[0];
-    bi = sidx[0];
-    for (int w = 1; w < 16; ++w)
-      if (smax[w] > best || (smax[w] == best && sidx[w] < bi)) { best = smax[w]; bi = sidx[w]; }
-    result = bi;
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
   }
-  return result;
+  if ((threadIdx.x & 63) == 0) { smax[threadIdx.x >> 6] = best; sidx[threadIdx.x >> 6] = bi; }
+  __syncthreads();
+  best = smax[0];
+  bi = sidx[0];
+  for (int w = 1; w < 16; ++w)
+    if (smax[w] > best || (smax[w] == best && sidx[w] < bi)) { best = smax[w]; bi = sidx[w]; }
+  return bi;
 }
 
-__global__ __launch_bounds__(1024) void greedy_next_kernel(float* logits, int vocab, const int* img_ids, int n_img,
-                                                           const int* prev_id, int* next_id, int* out_ids,
-                                                           const int* step_dev, int ld_logits, int ld_out) {
-  // one block per sequence
-  logits += (size_t)blockIdx.x * ld_logits;
-  prev_id += blockIdx.x;
-  next_id += blockIdx.x;
-  if (out_ids) out_ids += (size_t)blockIdx.x * ld_out;
-  if (step_dev) step_dev += blockIdx.x;
-  const int result = greedy_next_id(logits, vocab, img_ids, n_img, *prev_id);
-  if (threadIdx.x == 0) {
-    *next_id = result;
-    if (out_ids) {
-      const int st = *step_dev;
-      if (st >= 0 && (ld_out <= 0 || st < ld_out)) out_ids[st] = result;   // ld_out doubles as the row capacity
-    }
-  }
+__device__ __forceinline__ int greedy_next_id(float* logits, int vocab, const int* img_ids, int n_img, int prev) {
+  const int f = image_chain_index(logits, img_ids, n_img, prev);
+  return f >= 0 ? img_ids[f + 1] : row_argmax(logits, vocab);
 }
 
-// ---- in-flight batching: next token + stop rule + slot advance, one launch (sx_greedy_next_slots) --------------------------------
+// ---- the tail of the token step: next id, and in the in-flight form stop rule + slot advance, one launch ------------------------
+// Two forms of one kernel (next_token_kernel; the kernel-statistics files under profiles/ list its ancestors greedy_next_kernel and
+// greedy_next_slots_kernel). LOCK-STEP (live == NULL; sx_greedy_next, sx_greedy_next_b, sx_sample_next_b): every row takes its next
+// id and stores it; the host-side step advances the counters. IN-FLIGHT (sx_greedy_next_slots, sx_sample_next_slots):
 // Slot g of the lock-step decode step is either LIVE (a request occupies it) or PARKED (free: the host has not refilled it yet).
 // A parked slot keeps stepping through the GEMVs with the others (the weights stream once for all rows anyway) but must leave no
 // trace: its counters hold the idle values
@@ -939,53 +930,24 @@ __global__ __launch_bounds__(1024) void greedy_next_kernel(float* logits, int vo
 // and this kernel returns for it before it touches anything, the in-place zeroing of its logits row included.
 // A live slot takes the next id by the shared rule, stores it, advances its four counters and tests the stop rule (EOS or budget) on
 // the device; a slot that stops parks itself here, so the very next replay of the captured step already treats it as idle.
-struct SlotStepP {
+struct TailP {
   float* logits;
   const int* img_ids;
-  int* cur;
+  const int* prev;     // [G] the token just fed; in-flight: cur
+  int* next;           // [G] the next token (may alias prev); in-flight: cur
+  int* out_ids;
+  int* step;           // lock-step: read only, may be NULL without out_ids
+  int ld_logits, vocab, n_img, ld_out, G;
+  // in-flight form only
   int* live;
   int* n_new;
   const int* max_new;
   const int* force_at;
   int* pos;
   int* ctx;
-  int* step;
-  int* out_ids;
   int* status;
-  int ld_logits, vocab, n_img, ld_out, force_id, eos_id;
+  int force_id, eos_id;
 };
-
-__global__ __launch_bounds__(1024) void greedy_next_slots_kernel(const SlotStepP p) {
-  const int g = blockIdx.x;
-  if (p.live[g] == 0) return;                       // parked (uniform over the workgroup: no barrier is skipped by a part of it)
-  // every thread reads cur[g] before the first barrier of greedy_next_id; thread 0 stores to it after the last one
-  int result = greedy_next_id(p.logits + (size_t)g * p.ld_logits, p.vocab, p.img_ids, p.n_img, p.cur[g]);
-  if (threadIdx.x != 0) return;
-  int n = p.n_new[g];
-  const int fa = p.force_at[g];
-  if (fa >= 0 && n == fa) result = p.force_id;      // synthetic weights only: replaced AFTER the full arg-max (no work skipped)
-  const int st = p.step[g];
-  if (p.out_ids && st >= 0 && st < p.ld_out) p.out_ids[(size_t)g * p.ld_out + st] = result;   // ld_out is the row capacity
-  p.cur[g] = result;
-  n += 1;
-  p.n_new[g] = n;
-  const bool stop = (p.eos_id >= 0 && result == p.eos_id) || n >= p.max_new[g];
-  if (stop) {
-    p.live[g] = 0;
-    p.step[g] = -1;
-    p.pos[g] = -1;
-    p.ctx[g] = 0;
-  } else {
-    p.step[g] = st + 1;
-    p.pos[g] += 1;
-    p.ctx[g] += 1;
-  }
-  int* s = p.status + 4 * g;
-  s[0] = result;
-  s[1] = stop ? 0 : 1;
-  s[2] = n;
-  s[3] = stop ? n : -1;
-}
 
 // ---- seeded sampling: temperature → top-k → top-p → draw, one workgroup per row (sx_sample_next_b / sx_sample_next_slots) -------------
 // transformers' sample() order (processors, then TemperatureLogitsWarper → TopKLogitsWarper → TopPLogitsWarper) in one launch, without a
@@ -1112,39 +1074,24 @@ __device__ __forceinline__ unsigned smp_select(const unsigned (&key)[SMP_NPT], c
 
 // The next id of row g by the rule above; every thread returns it. n: 0-based index of the generated token within its request.
 // Greedy rows (do_sample = 0) and rows inside the forced image chain take greedy_next_id's path and value.
-// NOTE: this function is inlined into sample_next_kernel and into sample_next_slots_kernel, and the translation unit is built with
-// -ffast-math: that a request draws the same ids in the lock-step and in the in-flight step rests on the compiler lowering the weight
-// arithmetic (subtract, divide, exp) alike in both copies. Everything after the weights is integer and cannot differ. The two forms are
-// held bit-equal by tests/test_sampling_gpu.py (test_slots_form_samples_with_step_as_the_token_index, test_neighbours_do_not_matter);
-// if they ever part, give the weight its own __noinline__ function.
+// There is ONE copy of this function in the library (next_token_kernel<true> serves the lock-step and the in-flight form), so a
+// request draws the same ids in both by construction, whatever -ffast-math makes of the weight arithmetic.
 __device__ __forceinline__ int sample_next_id(float* logits, int vocab, const int* img_ids, int n_img, int prev, const SampleP& s,
                                               int g, int n) {
   __shared__ smp_u64 hist[4096];
   __shared__ smp_u64 wsum[16];
   __shared__ smp_u64 sel[2];
   __shared__ unsigned wmax[16];
-  __shared__ int forced, chosen;
+  __shared__ int chosen;
   __shared__ float chosen_p;
-  if (s.do_sample[g] == 0) {
+  const int f = image_chain_index(logits, img_ids, n_img, prev);
+  if (f >= 0 || s.do_sample[g] == 0) {                      // the next chain id or the arg-max: nothing is drawn (probability 1)
     if (threadIdx.x == 0) {
       if (s.n_kept) s.n_kept[g] = -1;
       if (s.p_chosen) s.p_chosen[g] = 1.0f;
     }
-    return greedy_next_id(logits, vocab, img_ids, n_img, prev);
+    return f >= 0 ? img_ids[f + 1] : row_argmax(logits, vocab);
   }
-  if (threadIdx.x == 0) forced = -1;
-  __syncthreads();
-  if ((int)threadIdx.x < n_img - 1 && img_ids[threadIdx.x] == prev) atomicMax(&forced, (int)threadIdx.x);
-  __syncthreads();
-  if (forced >= 0) {                                       // inside the chain: the next chain id, nothing is drawn (probability 1)
-    if (threadIdx.x == 0) {
-      if (s.n_kept) s.n_kept[g] = -1;
-      if (s.p_chosen) s.p_chosen[g] = 1.0f;
-    }
-    return img_ids[forced + 1];
-  }
-  if ((int)threadIdx.x < n_img - 1) logits[img_ids[1 + threadIdx.x]] = 0.0f;    // the only edit of the row, as in greedy_next_id
-  __syncthreads();
   // ---- the row, once ----
   unsigned key[SMP_NPT];
   float w[SMP_NPT];
@@ -1222,33 +1169,23 @@ __device__ __forceinline__ int sample_next_id(float* logits, int vocab, const in
   return chosen;
 }
 
-__global__ __launch_bounds__(1024) void sample_next_kernel(float* logits, int vocab, const int* img_ids, int n_img, const int* prev_id,
-                                                           int* next_id, int* out_ids, const int* step_dev, int ld_logits, int ld_out,
-                                                           const SampleP s) {
-  const int g = blockIdx.x;
-  const int result = sample_next_id(logits + (size_t)g * ld_logits, vocab, img_ids, n_img, prev_id[g], s, g, s.token_index[g]);
-  if (threadIdx.x == 0) {
-    next_id[g] = result;
-    if (out_ids) {
-      const int st = step_dev[g];
-      if (st >= 0 && (ld_out <= 0 || st < ld_out)) out_ids[(size_t)g * ld_out + st] = result;   // ld_out doubles as the row capacity
-    }
+// the lock-step store: ld_out is the row stride of out_ids and doubles as the row capacity (<= 0: no bound — the G = 1 call)
+__device__ __forceinline__ void lockstep_store(const TailP& p, int g, int result) {
+  p.next[g] = result;
+  if (p.out_ids) {
+    const int st = p.step[g];
+    if (st >= 0 && (p.ld_out <= 0 || st < p.ld_out)) p.out_ids[(size_t)g * p.ld_out + st] = result;
   }
 }
 
-// greedy_next_slots_kernel with the sampled id: parking, stop rule, counters and status are the same; the token index is step[g]
-__global__ __launch_bounds__(1024) void sample_next_slots_kernel(const SlotStepP p, const SampleP s) {
-  const int g = blockIdx.x;
-  if (p.live[g] == 0) return;                       // parked (uniform over the workgroup: no barrier is skipped by a part of it)
-  // every thread reads cur[g] and step[g] before the first barrier of sample_next_id; thread 0 stores to them after the last one
-  int result = sample_next_id(p.logits + (size_t)g * p.ld_logits, p.vocab, p.img_ids, p.n_img, p.cur[g], s, g, p.step[g]);
-  if (threadIdx.x != 0) return;
+// the slot advance of a live slot (thread 0): force_at, the id log, the counters, the stop rule, parking, the status row
+__device__ __forceinline__ void slot_advance(const TailP& p, int g, int result) {
   int n = p.n_new[g];
   const int fa = p.force_at[g];
-  if (fa >= 0 && n == fa) result = p.force_id;      // synthetic weights only: replaced AFTER the draw (no work skipped)
+  if (fa >= 0 && n == fa) result = p.force_id;      // synthetic weights only: replaced AFTER the full arg-max / draw (no work skipped)
   const int st = p.step[g];
   if (p.out_ids && st >= 0 && st < p.ld_out) p.out_ids[(size_t)g * p.ld_out + st] = result;   // ld_out is the row capacity
-  p.cur[g] = result;
+  p.next[g] = result;
   n += 1;
   p.n_new[g] = n;
   const bool stop = (p.eos_id >= 0 && result == p.eos_id) || n >= p.max_new[g];
@@ -1267,6 +1204,28 @@ __global__ __launch_bounds__(1024) void sample_next_slots_kernel(const SlotStepP
   q[1] = stop ? 0 : 1;
   q[2] = n;
   q[3] = stop ? n : -1;
+}
+
+struct NoSampleP {};
+
+// SAMPLE: the id by the seeded rule (token index: token_index[g] in the lock-step form, step[g] in the in-flight form), else the
+// greedy id; the greedy instantiation holds nothing of the sampler.
+template <bool SAMPLE>
+__global__ __launch_bounds__(1024) void next_token_kernel(const TailP p, const std::conditional_t<SAMPLE, SampleP, NoSampleP> s) {
+  const int g = blockIdx.x;
+  const bool slots = p.live != nullptr;
+  if (slots && p.live[g] == 0) return;              // parked (uniform over the workgroup: no barrier is skipped by a part of it)
+  float* row = p.logits + (size_t)g * p.ld_logits;
+  // every thread reads prev[g] and the token index before the first barrier of the id functions; thread 0 stores to next[g] (which
+  // may be prev[g]) and step[g] after the last one
+  int result;
+  if constexpr (SAMPLE)
+    result = sample_next_id(row, p.vocab, p.img_ids, p.n_img, p.prev[g], s, g, slots ? p.step[g] : s.token_index[g]);
+  else
+    result = greedy_next_id(row, p.vocab, p.img_ids, p.n_img, p.prev[g]);
+  if (threadIdx.x != 0) return;
+  if (slots) slot_advance(p, g, result);
+  else lockstep_store(p, g, result);
 }
 
 inline dim3 gs_grid(int64_t n) {
@@ -1503,40 +1462,6 @@ extern "C" int sx_scatter_rows(const float* src, const int32_t* rows, float* dst
   return SX_OK;
 }
 
-extern "C" int sx_greedy_next_b(float* logits, int ld_logits, int vocab, const int32_t* img_ids_dev, int n_img,
-                                const int32_t* prev_id_dev, int32_t* next_id_dev, int32_t* out_ids, int ld_out,
-                                const int32_t* step_dev, int G, void* stream) {
-  SX_CHECK(logits && img_ids_dev && prev_id_dev && next_id_dev, "sx_greedy_next: null pointer");
-  SX_CHECK(n_img >= 2 && n_img <= 1024 && G >= 1, "sx_greedy_next: n_img=%d G=%d", n_img, G);
-  SX_CHECK(!out_ids || step_dev, "sx_greedy_next: out_ids needs step_dev");
-  hipLaunchKernelGGL(greedy_next_kernel, dim3(G), dim3(1024), 0, ST, logits, vocab, img_ids_dev, n_img, prev_id_dev,
-                     next_id_dev, out_ids, step_dev, ld_logits, ld_out);
-  SX_HIP_LAUNCH_CHECK();
-  return SX_OK;
-}
-extern "C" int sx_greedy_next(float* logits, int vocab, const int32_t* img_ids_dev, int n_img,
-                              const int32_t* prev_id_dev, int32_t* next_id_dev, int32_t* out_ids,
-                              const int32_t* step_dev, void* stream) {
-  return sx_greedy_next_b(logits, 0, vocab, img_ids_dev, n_img, prev_id_dev, next_id_dev, out_ids, 0, step_dev, 1, stream);
-}
-
-extern "C" int sx_greedy_next_slots(const sx_slot_step_args* a, void* stream) {
-  SX_CHECK(a && a->logits && a->img_ids_dev && a->cur && a->live && a->n_new && a->max_new && a->force_at && a->pos && a->ctx &&
-           a->step && a->status, "sx_greedy_next_slots: null pointer");
-  SX_CHECK(a->n_img >= 2 && a->n_img <= 1024 && a->G >= 1, "sx_greedy_next_slots: n_img=%d G=%d", a->n_img, a->G);
-  SX_CHECK(a->vocab >= 1 && a->ld_logits >= a->vocab, "sx_greedy_next_slots: vocab=%d ld_logits=%d", a->vocab, a->ld_logits);
-  SX_CHECK(!a->out_ids || a->ld_out >= 1, "sx_greedy_next_slots: out_ids needs ld_out >= 1 (the row capacity)");
-  SlotStepP p;
-  p.logits = a->logits; p.img_ids = a->img_ids_dev; p.cur = a->cur; p.live = a->live; p.n_new = a->n_new;
-  p.max_new = a->max_new; p.force_at = a->force_at; p.pos = a->pos; p.ctx = a->ctx; p.step = a->step;
-  p.out_ids = a->out_ids; p.status = a->status;
-  p.ld_logits = a->ld_logits; p.vocab = a->vocab; p.n_img = a->n_img; p.ld_out = a->ld_out;
-  p.force_id = a->force_id; p.eos_id = a->eos_id;
-  hipLaunchKernelGGL(greedy_next_slots_kernel, dim3(a->G), dim3(1024), 0, ST, p);
-  SX_HIP_LAUNCH_CHECK();
-  return SX_OK;
-}
-
 static int sample_params(const sx_sample_args* s, int vocab, const char* who, SampleP* out) {
   SX_CHECK(s && s->do_sample && s->temperature && s->top_k && s->top_p && s->seed, "%s: null pointer in sx_sample_args", who);
   SX_CHECK(vocab >= 1 && vocab <= SMP_MAX_VOCAB, "%s: vocab=%d (a sampled row holds at most %d columns)", who, vocab, SMP_MAX_VOCAB);
@@ -1545,39 +1470,61 @@ static int sample_params(const sx_sample_args* s, int vocab, const char* who, Sa
   return SX_OK;
 }
 
-extern "C" int sx_sample_next_b(float* logits, int ld_logits, int vocab, const int32_t* img_ids_dev, int n_img,
-                                const int32_t* prev_id_dev, int32_t* next_id_dev, int32_t* out_ids, int ld_out,
-                                const int32_t* step_dev, int G, const sx_sample_args* sample, void* stream) {
-  SX_CHECK(logits && img_ids_dev && prev_id_dev && next_id_dev, "sx_sample_next_b: null pointer");
-  SX_CHECK(n_img >= 2 && n_img <= 1024 && G >= 1, "sx_sample_next_b: n_img=%d G=%d", n_img, G);
-  SX_CHECK(!out_ids || step_dev, "sx_sample_next_b: out_ids needs step_dev");
-  SX_CHECK(G == 1 || ld_logits >= vocab, "sx_sample_next_b: vocab=%d ld_logits=%d", vocab, ld_logits);
-  SampleP s;
-  if (int rc = sample_params(sample, vocab, "sx_sample_next_b", &s)) return rc;
-  SX_CHECK(s.token_index, "sx_sample_next_b: token_index is required");
-  hipLaunchKernelGGL(sample_next_kernel, dim3(G), dim3(1024), 0, ST, logits, vocab, img_ids_dev, n_img, prev_id_dev, next_id_dev,
-                     out_ids, step_dev, ld_logits, ld_out, s);
+// sx_slot_step_args as the kernel's parameters: prev and next are both cur. A null struct gives null pointers, which the launcher refuses.
+static TailP slot_tail(const sx_slot_step_args* a) {
+  if (!a) return TailP{};
+  return TailP{a->logits, a->img_ids_dev, a->cur, a->cur, a->out_ids, a->step, a->ld_logits, a->vocab, a->n_img, a->ld_out, a->G,
+               a->live, a->n_new, a->max_new, a->force_at, a->pos, a->ctx, a->status, a->force_id, a->eos_id};
+}
+
+// The one launcher behind the five entry points. slots: the in-flight form (every pointer but out_ids is required, ld_out is the row
+// capacity), else the lock-step form. sampled: the entry point takes a sx_sample_args, which must then be there.
+static int launch_next_token(const char* who, const TailP& p, bool slots, const sx_sample_args* sample, bool sampled, void* stream) {
+  SX_CHECK(p.logits && p.img_ids && p.prev && p.next, "%s: null pointer", who);
+  SX_CHECK(p.n_img >= 2 && p.n_img <= 1024 && p.G >= 1, "%s: n_img=%d G=%d", who, p.n_img, p.G);
+  if (slots) {
+    SX_CHECK(p.live && p.n_new && p.max_new && p.force_at && p.pos && p.ctx && p.step && p.status, "%s: null pointer", who);
+    SX_CHECK(p.vocab >= 1 && p.ld_logits >= p.vocab, "%s: vocab=%d ld_logits=%d", who, p.vocab, p.ld_logits);
+    SX_CHECK(!p.out_ids || p.ld_out >= 1, "%s: out_ids needs ld_out >= 1 (the row capacity)", who);
+  } else {
+    SX_CHECK(!p.out_ids || p.step, "%s: out_ids needs step_dev", who);
+    SX_CHECK(!sampled || p.G == 1 || p.ld_logits >= p.vocab, "%s: vocab=%d ld_logits=%d", who, p.vocab, p.ld_logits);
+  }
+  if (sampled) {
+    SampleP s;
+    if (int rc = sample_params(sample, p.vocab, who, &s)) return rc;
+    SX_CHECK(slots || s.token_index, "%s: token_index is required", who);
+    hipLaunchKernelGGL(next_token_kernel<true>, dim3(p.G), dim3(1024), 0, ST, p, s);
+  } else {
+    hipLaunchKernelGGL(next_token_kernel<false>, dim3(p.G), dim3(1024), 0, ST, p, NoSampleP{});
+  }
   SX_HIP_LAUNCH_CHECK();
   return SX_OK;
 }
 
+// the lock-step forms never write step_dev (TailP.step is writable for the in-flight form)
+extern "C" int sx_greedy_next_b(float* logits, int ld_logits, int vocab, const int32_t* img_ids_dev, int n_img,
+                                const int32_t* prev_id_dev, int32_t* next_id_dev, int32_t* out_ids, int ld_out,
+                                const int32_t* step_dev, int G, void* stream) {
+  return launch_next_token("sx_greedy_next_b", TailP{logits, img_ids_dev, prev_id_dev, next_id_dev, out_ids, const_cast<int32_t*>(step_dev),
+                                                     ld_logits, vocab, n_img, ld_out, G}, false, nullptr, false, stream);
+}
+extern "C" int sx_greedy_next(float* logits, int vocab, const int32_t* img_ids_dev, int n_img,
+                              const int32_t* prev_id_dev, int32_t* next_id_dev, int32_t* out_ids,
+                              const int32_t* step_dev, void* stream) {
+  return sx_greedy_next_b(logits, 0, vocab, img_ids_dev, n_img, prev_id_dev, next_id_dev, out_ids, 0, step_dev, 1, stream);
+}
+extern "C" int sx_sample_next_b(float* logits, int ld_logits, int vocab, const int32_t* img_ids_dev, int n_img,
+                                const int32_t* prev_id_dev, int32_t* next_id_dev, int32_t* out_ids, int ld_out,
+                                const int32_t* step_dev, int G, const sx_sample_args* sample, void* stream) {
+  return launch_next_token("sx_sample_next_b", TailP{logits, img_ids_dev, prev_id_dev, next_id_dev, out_ids, const_cast<int32_t*>(step_dev),
+                                                     ld_logits, vocab, n_img, ld_out, G}, false, sample, true, stream);
+}
+extern "C" int sx_greedy_next_slots(const sx_slot_step_args* a, void* stream) {
+  return launch_next_token("sx_greedy_next_slots", slot_tail(a), true, nullptr, false, stream);
+}
 extern "C" int sx_sample_next_slots(const sx_slot_step_args* a, const sx_sample_args* sample, void* stream) {
-  SX_CHECK(a && a->logits && a->img_ids_dev && a->cur && a->live && a->n_new && a->max_new && a->force_at && a->pos && a->ctx &&
-           a->step && a->status, "sx_sample_next_slots: null pointer");
-  SX_CHECK(a->n_img >= 2 && a->n_img <= 1024 && a->G >= 1, "sx_sample_next_slots: n_img=%d G=%d", a->n_img, a->G);
-  SX_CHECK(a->vocab >= 1 && a->ld_logits >= a->vocab, "sx_sample_next_slots: vocab=%d ld_logits=%d", a->vocab, a->ld_logits);
-  SX_CHECK(!a->out_ids || a->ld_out >= 1, "sx_sample_next_slots: out_ids needs ld_out >= 1 (the row capacity)");
-  SampleP s;
-  if (int rc = sample_params(sample, a->vocab, "sx_sample_next_slots", &s)) return rc;
-  SlotStepP p;
-  p.logits = a->logits; p.img_ids = a->img_ids_dev; p.cur = a->cur; p.live = a->live; p.n_new = a->n_new;
-  p.max_new = a->max_new; p.force_at = a->force_at; p.pos = a->pos; p.ctx = a->ctx; p.step = a->step;
-  p.out_ids = a->out_ids; p.status = a->status;
-  p.ld_logits = a->ld_logits; p.vocab = a->vocab; p.n_img = a->n_img; p.ld_out = a->ld_out;
-  p.force_id = a->force_id; p.eos_id = a->eos_id;
-  hipLaunchKernelGGL(sample_next_slots_kernel, dim3(a->G), dim3(1024), 0, ST, p, s);
-  SX_HIP_LAUNCH_CHECK();
-  return SX_OK;
+  return launch_next_token("sx_sample_next_slots", slot_tail(a), true, sample, true, stream);
 }
 
 extern "C" int sx_scatter_rows_step(const float* src, const int32_t* step_dev, float* dst, int G, int dim, int seq_rows,

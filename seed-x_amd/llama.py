@@ -241,12 +241,14 @@ class LlamaForCausalLM:
         self.decode_nsplit_f32 = 1 if self.G * self.nh >= 512 else min(16, max(1, -(-1024 // (self.G * self.nh))))
         self.device, self.dtype = None, torch.float16
         self._sd, self._P = None, None
-        self._graph = None
-        self._slot_graph = None         # the captured in-flight token step (decode_step(..., slots=...)): one per engine lifetime
-        self._sample_graph = None       # the sampled forms of the two (a greedy step and a sampled step never share a graph)
-        self._slot_sample_graph = None
+        self._drop_graphs()
         self._sample_state = None
         self.kv_epoch = 0               # bumped whenever the KV cache is reset or written outside generate_batch
+
+    def _drop_graphs(self):
+        """No captured token step: the lock-step one, the in-flight one (decode_step(..., slots=...): one per engine lifetime) and the
+        sampled forms of the two (a greedy step and a sampled step never share a graph)."""
+        self._graph = self._slot_graph = self._sample_graph = self._slot_sample_graph = None
 
     def memory_footprint(self):
         """Bytes this module will hold on its GPU once packed (per rank): 16-bit weights, their decode-tile copy (precise mode: always;
@@ -445,10 +447,7 @@ class LlamaForCausalLM:
             if (self.precise and self.decode_nsplit_f32 > 1) else None
         self._P = P
         self._sd = None
-        self._graph = None
-        self._slot_graph = None
-        self._sample_graph = None
-        self._slot_sample_graph = None
+        self._drop_graphs()
         return P
 
     # ---- core passes ---------------------------------------------------------------------------------------------------
@@ -824,22 +823,18 @@ class LlamaForCausalLM:
                               w_tiles=P["lm_head_t"])                                  # [G, Vpad / tp]
         if self.tp > 1:
             logits = self.comm.all_gather(logits).permute(1, 0, 2).reshape(self.G, self.Vpad).contiguous()
+        # sampled step: same tail, the id by the seeded rule (token index = step[g]); on tensor-parallel ranks every rank draws from the
+        # same gathered logits with the same seed and index
+        ss = sampling if slots is None else slots.sampling
+        sample = {} if ss is None else dict(sample=ss, n_kept=ss.n_kept, p_chosen=ss.p_chosen)
         if slots is not None:
-            if slots.sampling is not None:      # the sampled step: same tail, the id by the seeded rule (token index = step[g])
-                ss = slots.sampling
-                ops.sample_next_slots(logits, self.V, img_ids_dev, P["cur"], slots.live, slots.n_new, slots.max_new, slots.force_at,
-                                      P["pos"], P["ctx"], P["step"], out_ids, slots.status, ss, slots.force_id, slots.eos_id,
-                                      n_kept=ss.n_kept, p_chosen=ss.p_chosen)
-            else:
-                ops.greedy_next_slots(logits, self.V, img_ids_dev, P["cur"], slots.live, slots.n_new, slots.max_new, slots.force_at,
-                                      P["pos"], P["ctx"], P["step"], out_ids, slots.status, slots.force_id, slots.eos_id)
+            tail = ops.sample_next_slots if sample else ops.greedy_next_slots
+            tail(logits, self.V, img_ids_dev, P["cur"], slots.live, slots.n_new, slots.max_new, slots.force_at, P["pos"], P["ctx"],
+                 P["step"], out_ids, slots.status, force_id=slots.force_id, eos_id=slots.eos_id, **sample)
             slots.logits = logits
             return
-        if sampling is not None:                # every rank draws from the same gathered logits with the same seed and index
-            ops.sample_next_b(logits, self.V, img_ids_dev, P["cur"], out_ids, P["step"], sampling, n_kept=sampling.n_kept,
-                              p_chosen=sampling.p_chosen)
-        else:
-            ops.greedy_next_b(logits, self.V, img_ids_dev, P["cur"], out_ids, P["step"])
+        tail = ops.sample_next_b if sample else ops.greedy_next_b
+        tail(logits, self.V, img_ids_dev, P["cur"], out_ids, P["step"], **sample)
         ops.add_i32(P["step"], 1)
 
     def decode_step(self, img_ids_dev, out_ids, hid_buf, use_graph=True, slots=None, sampling=None):

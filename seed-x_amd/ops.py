@@ -781,14 +781,41 @@ def attn_decode_fused(qkv, kcache, vcache, pos_dev, cos_tab, sin_tab, scale, H, 
     return ot if out_tiled else out
 
 
-def greedy_next_b(logits, vocab, img_ids_dev, cur_dev, out_ids, step_dev):
-    """logits fp32 [G, ld]; cur_dev int32 [G] (in: previous id, out: next id); out_ids int32 [G, ld_out]; step_dev [G]."""
+def _next_lockstep(logits, vocab, img_ids_dev, cur_dev, out_ids, step_dev, sample=None):
+    """The lock-step tail of the token step: sx_greedy_next_b, or sx_sample_next_b when ``sample`` (a filled SampleArgs) is given."""
     lib = _lib.load()
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1
+    args = (_p(logits), logits.stride(0), vocab, _p(img_ids_dev), img_ids_dev.numel(), _p(cur_dev), _p(cur_dev), _p(out_ids),
+            out_ids.stride(0) if out_ids is not None else 0, _p(step_dev), logits.shape[0])
+    if sample is None:
+        check(lib.sx_greedy_next_b(*args, _stream()), "sx_greedy_next_b")
+    else:
+        check(lib.sx_sample_next_b(*args, C.byref(sample), _stream()), "sx_sample_next_b")
+
+
+def _slot_step_args(who, logits, vocab, img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, out_ids, status, force_id,
+                    eos_id):
+    """sx_slot_step_args from the slot tensors, checked: logits fp32 [G, ld], the rest contiguous int32 on the device."""
     G = logits.shape[0]
     assert logits.dtype == torch.float32 and logits.stride(1) == 1
-    check(lib.sx_greedy_next_b(_p(logits), logits.stride(0), vocab, _p(img_ids_dev), img_ids_dev.numel(), _p(cur_dev),
-                               _p(cur_dev), _p(out_ids), out_ids.stride(0) if out_ids is not None else 0, _p(step_dev), G,
-                               _stream()), "sx_greedy_next_b")
+    for t in (img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, status) + ((out_ids,) if out_ids is not None else ()):
+        assert t.dtype == torch.int32 and t.is_contiguous(), f"{who}: contiguous int32 tensors"
+    for t in (cur, live, n_new, max_new, force_at, pos, ctx, step):
+        assert t.numel() == G
+    assert status.numel() == 4 * G and (out_ids is None or out_ids.shape[0] == G)
+    for t in (logits, img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, status):
+        _p(t)                                   # (GPU tensors only: no CPU fallback)
+    return _lib.SlotStepArgs(
+        logits=logits.data_ptr(), img_ids_dev=img_ids_dev.data_ptr(), cur=cur.data_ptr(), live=live.data_ptr(),
+        n_new=n_new.data_ptr(), max_new=max_new.data_ptr(), force_at=force_at.data_ptr(), pos=pos.data_ptr(), ctx=ctx.data_ptr(),
+        step=step.data_ptr(), out_ids=out_ids.data_ptr() if out_ids is not None else None, status=status.data_ptr(),
+        ld_logits=logits.stride(0), vocab=int(vocab), n_img=img_ids_dev.numel(), ld_out=out_ids.shape[1] if out_ids is not None else 0,
+        force_id=int(force_id), eos_id=int(eos_id), G=G, reserved=0)
+
+
+def greedy_next_b(logits, vocab, img_ids_dev, cur_dev, out_ids, step_dev):
+    """logits fp32 [G, ld]; cur_dev int32 [G] (in: previous id, out: next id); out_ids int32 [G, ld_out]; step_dev [G]."""
+    _next_lockstep(logits, vocab, img_ids_dev, cur_dev, out_ids, step_dev)
 
 
 def greedy_next_slots(logits, vocab, img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, out_ids, status,
@@ -796,23 +823,9 @@ def greedy_next_slots(logits, vocab, img_ids_dev, cur, live, n_new, max_new, for
     """In-flight batching tail of the token step (sx_greedy_next_slots): logits fp32 [G, ld]; every other tensor int32 [G] on the
     device, out_ids [G, rows] or None, status [G, 4]. Live slots take their next id, advance n_new / step / pos / ctx and park
     themselves when the id is ``eos_id`` or their budget is reached; parked slots are not touched."""
-    lib = _lib.load()
-    G = logits.shape[0]
-    assert logits.dtype == torch.float32 and logits.stride(1) == 1
-    for t in (img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, status) + ((out_ids,) if out_ids is not None else ()):
-        assert t.dtype == torch.int32 and t.is_contiguous(), "greedy_next_slots: contiguous int32 tensors"
-    for t in (cur, live, n_new, max_new, force_at, pos, ctx, step):
-        assert t.numel() == G
-    assert status.numel() == 4 * G and (out_ids is None or out_ids.shape[0] == G)
-    a = _lib.SlotStepArgs(
-        logits=logits.data_ptr(), img_ids_dev=img_ids_dev.data_ptr(), cur=cur.data_ptr(), live=live.data_ptr(),
-        n_new=n_new.data_ptr(), max_new=max_new.data_ptr(), force_at=force_at.data_ptr(), pos=pos.data_ptr(), ctx=ctx.data_ptr(),
-        step=step.data_ptr(), out_ids=out_ids.data_ptr() if out_ids is not None else None, status=status.data_ptr(),
-        ld_logits=logits.stride(0), vocab=int(vocab), n_img=img_ids_dev.numel(), ld_out=out_ids.shape[1] if out_ids is not None else 0,
-        force_id=int(force_id), eos_id=int(eos_id), G=G, reserved=0)
-    for t in (logits, img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, status):
-        _p(t)                                   # (GPU tensors only: no CPU fallback)
-    check(lib.sx_greedy_next_slots(C.byref(a), _stream()), "sx_greedy_next_slots")
+    a = _slot_step_args("greedy_next_slots", logits, vocab, img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, out_ids,
+                        status, force_id, eos_id)
+    check(_lib.load().sx_greedy_next_slots(C.byref(a), _stream()), "sx_greedy_next_slots")
 
 
 def _sample_args(sample, G, token_index=None, n_kept=None, p_chosen=None):
@@ -833,38 +846,19 @@ def sample_next_b(logits, vocab, img_ids_dev, cur_dev, out_ids, step_dev, sample
     parameters on the device (do_sample / top_k int32 [G], temperature / top_p fp32 [G], seed int32 [G, 2] = low, high word);
     ``token_index`` int32 [G] is the index of the generated token within its request (default: ``step_dev``). Rows with do_sample = 0
     take the greedy id. Optional outputs n_kept int32 [G], p_chosen fp32 [G]."""
-    lib = _lib.load()
-    G = logits.shape[0]
-    assert logits.dtype == torch.float32 and logits.stride(1) == 1
     token_index = step_dev if token_index is None else token_index
     assert token_index is not None, "sample_next_b: token_index (or step_dev) is required"
-    a = _sample_args(sample, G, token_index, n_kept, p_chosen)
-    check(lib.sx_sample_next_b(_p(logits), logits.stride(0), vocab, _p(img_ids_dev), img_ids_dev.numel(), _p(cur_dev),
-                               _p(cur_dev), _p(out_ids), out_ids.stride(0) if out_ids is not None else 0, _p(step_dev), G,
-                               C.byref(a), _stream()), "sx_sample_next_b")
+    _next_lockstep(logits, vocab, img_ids_dev, cur_dev, out_ids, step_dev,
+                   _sample_args(sample, logits.shape[0], token_index, n_kept, p_chosen))
 
 
 def sample_next_slots(logits, vocab, img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, out_ids, status, sample,
                       force_id=-1, eos_id=-1, n_kept=None, p_chosen=None):
     """greedy_next_slots with the seeded sampling rule (sx_sample_next_slots): the token index of slot g is ``step[g]``."""
-    lib = _lib.load()
-    G = logits.shape[0]
-    assert logits.dtype == torch.float32 and logits.stride(1) == 1
-    for t in (img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, status) + ((out_ids,) if out_ids is not None else ()):
-        assert t.dtype == torch.int32 and t.is_contiguous(), "sample_next_slots: contiguous int32 tensors"
-    for t in (cur, live, n_new, max_new, force_at, pos, ctx, step):
-        assert t.numel() == G
-    assert status.numel() == 4 * G and (out_ids is None or out_ids.shape[0] == G)
-    a = _lib.SlotStepArgs(
-        logits=logits.data_ptr(), img_ids_dev=img_ids_dev.data_ptr(), cur=cur.data_ptr(), live=live.data_ptr(),
-        n_new=n_new.data_ptr(), max_new=max_new.data_ptr(), force_at=force_at.data_ptr(), pos=pos.data_ptr(), ctx=ctx.data_ptr(),
-        step=step.data_ptr(), out_ids=out_ids.data_ptr() if out_ids is not None else None, status=status.data_ptr(),
-        ld_logits=logits.stride(0), vocab=int(vocab), n_img=img_ids_dev.numel(), ld_out=out_ids.shape[1] if out_ids is not None else 0,
-        force_id=int(force_id), eos_id=int(eos_id), G=G, reserved=0)
-    for t in (logits, img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, status):
-        _p(t)                                   # (GPU tensors only: no CPU fallback)
-    s = _sample_args(sample, G, None, n_kept, p_chosen)
-    check(lib.sx_sample_next_slots(C.byref(a), C.byref(s), _stream()), "sx_sample_next_slots")
+    a = _slot_step_args("sample_next_slots", logits, vocab, img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, out_ids,
+                        status, force_id, eos_id)
+    s = _sample_args(sample, logits.shape[0], None, n_kept, p_chosen)
+    check(_lib.load().sx_sample_next_slots(C.byref(a), C.byref(s), _stream()), "sx_sample_next_slots")
 
 
 def scatter_rows_step(src, step_dev, dst):

@@ -165,11 +165,7 @@ class ContinuousLVLM:
         dev, H, G = llm.device, llm.H, len(requests)
         P = llm._pack()
         assert G == llm.G, f"the LLM was built for max_batch={llm.G} lock-step sequences, got {G} requests"
-        img_ids = tokenizer.encode(''.join([BOI_TOKEN] + [IMG_TOKEN.format(i) for i in range(num_img_gen_tokens)]
-                                           + [EOI_TOKEN]), add_special_tokens=False)        # generation.py:15-17
-        boi_id, eoi_id = img_ids[0], img_ids[-1]
-        if eos_token_id == "auto":
-            eos_token_id = getattr(tokenizer, "eos_token_id", None)
+        img_ids, boi_id, eoi_id, eos_token_id = self._special_ids(tokenizer, num_img_gen_tokens, eos_token_id)
         img_ids_dev = torch.tensor(img_ids, dtype=torch.int32, device=dev)
         nchunk = num_img_gen_tokens + 1
         rows = 2 * max_new_tokens + nchunk + 8          # finished sequences keep stepping until the slowest one ends
@@ -227,15 +223,8 @@ class ContinuousLVLM:
             hit = [g for g in range(G) if not done[g] and self.chunk_forced_image_tokens and cur[g] == boi_id
                    and n_new[g] + nchunk <= max_new_tokens]
             if hit:
-                # inputs [<img>, <img_0> … <img_63>] as one causal chunk per sequence, all such sequences in ONE pass;
-                # the outputs are forced (generation.py:23-26)
-                chunk = torch.tensor([boi_id] + img_ids[1:-1], dtype=torch.int32, device=dev)
-                xe = ops.embedding(chunk, P["embed"])
-                _, hns = llm.forward_embeds_batch([xe] * len(hit), hit, need_logits=False)
-                forced = torch.tensor(img_ids[1:], dtype=torch.int32, device=dev)
-                for g, hn in zip(hit, hns):
-                    hid[g, n_new[g]:n_new[g] + nchunk] = hn                                  # plumbing copy
-                    out_ids[g, n_new[g]:n_new[g] + nchunk] = forced
+                self._forced_image_chunk(hit, n_new, img_ids, hid, out_ids)
+                for g in hit:
                     n_new[g] += nchunk
                     P["step"][g] = n_new[g]
                     P["cur"][g] = eoi_id
@@ -261,28 +250,35 @@ class ContinuousLVLM:
             generate_ids = out_ids[g, :n].cpu().long()
             if reuse_cache:
                 self._remember(g, prompts[g], generate_ids[:n - 1].tolist())          # the last new token was never fed
-            last_hidden = hid[g, 1:n]                                                        # seed_x.py:196-197
-            eoi_indices = torch.where(generate_ids == eoi_id)[0].tolist()                    # :199
-            text_mask = torch.ones_like(generate_ids, dtype=torch.bool)
-            img_gen_feat = None
-            if eoi_indices:
-                feats = []
-                for e in eoi_indices:
-                    feats.append(last_hidden[e - num_img_gen_tokens:e])                      # :204
-                    text_mask[e - num_img_gen_tokens:e] = False
-                img_gen_feat = self.output_resampler(torch.stack(feats))                     # :209-210
-                img_gen_feat = ops.cast(img_gen_feat.contiguous(), self.dtype)
-            text_mask[generate_ids == boi_id] = False
-            text = tokenizer.decode(generate_ids[text_mask], skip_special_tokens=False)      # :214-216
-            results.append({'text': text, 'has_img_output': len(eoi_indices) > 0, 'img_gen_feat': img_gen_feat,
-                            'num_gen_imgs': len(eoi_indices), 'generate_ids': generate_ids,
-                            'last_hidden_states': last_hidden})
+            results.append(self._result(tokenizer, generate_ids, hid[g, 1:n], boi_id, eoi_id, num_img_gen_tokens))
             if params[g] is not None:
                 results[-1]['seed'] = params[g].seed
         return results
 
+    @staticmethod
+    def _special_ids(tokenizer, num_img_gen_tokens, eos_token_id):
+        """(img_ids, boi_id, eoi_id, eos): the ids of [<img>, <img_0> …, </img>] (generation.py:15-17), its two ends, and the EOS id
+        ("auto" → tokenizer.eos_token_id; None: no EOS stop)."""
+        img_ids = tokenizer.encode(''.join([BOI_TOKEN] + [IMG_TOKEN.format(i) for i in range(num_img_gen_tokens)]
+                                           + [EOI_TOKEN]), add_special_tokens=False)
+        if eos_token_id == "auto":
+            eos_token_id = getattr(tokenizer, "eos_token_id", None)
+        return img_ids, img_ids[0], img_ids[-1], eos_token_id
+
+    def _forced_image_chunk(self, hit, n_new, img_ids, hid, out_ids):
+        """The forced image block of the sequences ``hit`` (their current token is <img>): inputs [<img>, <img_0> … <img_63>] as one
+        causal chunk per sequence, all of them in ONE pass; the outputs are forced (generation.py:23-26). Sequence g's hidden states
+        and ids [<img_0> …, </img>] go to rows n_new[g] … of ``hid`` / ``out_ids``; the caller advances its counters."""
+        llm, dev = self.llm, self.llm.device
+        xe = ops.embedding(torch.tensor(img_ids[:-1], dtype=torch.int32, device=dev), llm._P["embed"])
+        _, hns = llm.forward_embeds_batch([xe] * len(hit), hit, need_logits=False)
+        forced = torch.tensor(img_ids[1:], dtype=torch.int32, device=dev)
+        for g, hn in zip(hit, hns):
+            hid[g, n_new[g]:n_new[g] + len(img_ids) - 1] = hn                                # plumbing copy
+            out_ids[g, n_new[g]:n_new[g] + len(img_ids) - 1] = forced
+
     def _result(self, tokenizer, generate_ids, last_hidden, boi_id, eoi_id, num_img_gen_tokens):
-        """The reference-style result dict of one finished request (seed_x.py:196-234), as generate_batch builds it."""
+        """The reference-style result dict of one finished request (seed_x.py:196-234; last_hidden: :196-197)."""
         eoi_indices = torch.where(generate_ids == eoi_id)[0].tolist()                        # :199
         text_mask = torch.ones_like(generate_ids, dtype=torch.bool)
         img_gen_feat = None
@@ -322,11 +318,7 @@ class ContinuousLVLM:
         assert N >= 1, "generate_inflight needs at least one request"
         dev, H, G = llm.device, llm.H, llm.G
         P = llm._pack()
-        img_ids = tokenizer.encode(''.join([BOI_TOKEN] + [IMG_TOKEN.format(i) for i in range(num_img_gen_tokens)]
-                                           + [EOI_TOKEN]), add_special_tokens=False)        # generation.py:15-17
-        boi_id, eoi_id = img_ids[0], img_ids[-1]
-        if eos_token_id == "auto":
-            eos_token_id = getattr(tokenizer, "eos_token_id", None)
+        img_ids, boi_id, eoi_id, eos_token_id = self._special_ids(tokenizer, num_img_gen_tokens, eos_token_id)
         eos = -1 if eos_token_id is None else int(eos_token_id)
         nchunk = num_img_gen_tokens + 1
         budget = [int(req.get("max_new_tokens") or max_new_tokens) for req in requests]
@@ -421,15 +413,8 @@ class ContinuousLVLM:
             hit = [g for g in live if self.chunk_forced_image_tokens and cur[g] == boi_id
                    and n_new[g] + nchunk <= budget[sched.slot_req[g]]]
             if hit:
-                # inputs [<img>, <img_0> … <img_63>] as one causal chunk per slot, all such slots in ONE pass; the outputs are
-                # forced (generation.py:23-26). The other slots wait, as in generate_batch.
-                chunk = torch.tensor([boi_id] + img_ids[1:-1], dtype=torch.int32, device=dev)
-                xe = ops.embedding(chunk, P["embed"])
-                _, hns = llm.forward_embeds_batch([xe] * len(hit), hit, need_logits=False)
-                forced = torch.tensor(img_ids[1:], dtype=torch.int32, device=dev)
-                for g, hn in zip(hit, hns):
-                    hid[g, n_new[g]:n_new[g] + nchunk] = hn                                  # plumbing copy
-                    out_ids[g, n_new[g]:n_new[g] + nchunk] = forced
+                self._forced_image_chunk(hit, n_new, img_ids, hid, out_ids)                  # the other slots wait, as in generate_batch
+                for g in hit:
                     n_new[g] += nchunk
                     cur[g] = eoi_id
                 llm._slot_write(st.n_new, hit, [n_new[g] for g in hit])

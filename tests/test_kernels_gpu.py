@@ -514,6 +514,35 @@ def test_embedding_scatter_greedy(dev):
     assert cur.item() == 10
 
 
+def test_greedy_next_single_row_contract(dev):
+    """The G = 1 lock-step entry on a [500] row (ops.greedy_next: ld_logits = 0, distinct prev / next tensors): id and in-place row edit
+    equal greedy_next_b on the same row, for a free row and a chain row; the id goes to out_ids[step[0]] for 0 <= step < capacity and
+    nowhere otherwise. sx_greedy_next itself passes ld_out = 0, which means no bound."""
+    from seedx_amd import _lib, ops
+    vocab, i32 = 500, lambda v: torch.tensor(v, dtype=torch.int32, device=dev)
+    img = torch.arange(400, 466, dtype=torch.int32, device=dev)
+    row = rnd((vocab,), torch.float32, dev, scale=3.0, seed=50)
+    row[401:465] += 6.0                                              # image columns that the rule zeroes before the arg-max
+    for prev_id in (7, 431):                                         # a free row, a row inside the chain
+        ref, cur = row.clone().view(1, vocab), i32([prev_id])
+        ops.greedy_next_b(ref, vocab, img, cur, None, None)
+        got, prev, nxt = row.clone(), i32([prev_id]), i32([-3])
+        ops.greedy_next(got, vocab, img, prev, nxt)                   # out_ids = None, step = None: ld_out = 0
+        assert nxt.item() == cur.item() and prev.item() == prev_id and torch.equal(got, ref[0])
+    assert cur.item() == 432 and torch.equal(got, row)               # the chain row is not edited
+    want = cur.item()
+    for st, hits in ((2, [2]), (0, [0]), (-1, []), (4, []), (12345, [])):
+        outs, nxt = torch.full((4,), -1, dtype=torch.int32, device=dev), i32([-3])
+        ops.greedy_next(row.clone(), vocab, img, i32([431]), nxt, outs, i32([st]))
+        assert nxt.item() == want and outs.tolist() == [want if i in hits else -1 for i in range(4)], (st, outs.tolist())
+    outs, nxt, got, prev = torch.full((4,), -1, dtype=torch.int32, device=dev), i32([-3]), row.clone(), i32([431])
+    for st in (-1, 3):                                               # the C entry: ld_out = 0, only a negative step is dropped
+        step = i32([st])
+        rc = _lib.load().sx_greedy_next(ops._p(got), vocab, ops._p(img), img.numel(), ops._p(prev), ops._p(nxt), ops._p(outs),
+                                        ops._p(step), ops._stream())
+        assert rc == 0 and nxt.item() == want and outs.tolist() == [-1, -1, -1, want if st == 3 else -1]
+
+
 def test_elementwise(dev):
     from seedx_amd import ops
     x = rnd((3, 1001), torch.float32, dev, seed=47)

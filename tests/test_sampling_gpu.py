@@ -168,12 +168,14 @@ def test_slots_form_all_greedy_equals_greedy_next_slots(dev):
         assert torch.equal(a, b)
 
 
-def test_slots_form_samples_with_step_as_the_token_index(dev):
+@pytest.mark.parametrize("vocab,ld", [(500, 512), (1031, 1088), (32330, 32384)])
+def test_slots_form_samples_with_step_as_the_token_index(dev, vocab, ld):
     """Sampled live slots: the id equals sx_sample_next_b's with token_index = step; force_at replaces it after the draw; the stop rule,
-    the counters and the status follow the id; a parked slot keeps everything."""
+    the counters and the status follow the id; a parked slot keeps everything. At every row width of this file: 1031 and 32330 bring
+    the float4 row read, its scalar tail and partly filled threads into play."""
     from seedx_amd import ops
-    G, rows, vocab = 5, 16, 500
-    logits = torch.from_numpy((np.random.default_rng(3).normal(size=(G, 512)) * 3.0).astype(np.float32)).to(dev)
+    G, rows = 5, 16
+    logits = torch.from_numpy((np.random.default_rng(3).normal(size=(G, ld)) * 3.0).astype(np.float32)).to(dev)
     img = _i32(IMG_IDS, dev)
     mk = lambda: Params(dev, [1, 1, 1, 1, 0], [0.7, 1.0, 1.3, 1.0, 1.0], [50, 0, 8, 50, 0], [0.5, 0.9, 1.0, 0.95, 1.0], [5, 6, 7, 8, 9])
     step0, cur0 = [3, 9, 1, 12345, 6], [11, 12, 13, -7, 14]
