@@ -32,6 +32,8 @@ extern "C" {
 #define SX_BF16X3 3 /* sx_groupnorm* outputs only: bf16 planes [hi | hi | lo] per row, 3*C columns (see sx_split_bf16) */
 #define SX_F16X2 4  /* sx_groupnorm* outputs only: fp16 planes [hi | lo] per row, 2*C columns (sx_split16's row layout): the A operand
                      * of the fp32-grade VAE convs whose weights are exact in fp16 (W duplicated per tap: A.W = Ah.W + Al.W) */
+#define SX_FP8_E4M3 5 /* sx_gemv_args.w_dtype only: OCP e4m3fn weight codes (1-4-3, bias 7, no infinities; the NaN codes 0x7f / 0xff never
+                       * occur) with one fp32 scale per weight row, W[n][k] = decode(code[n][k]) * w_scale[n] */
 /* OR-ed into a 16-bit OUTPUT dtype of the decode-step producers (sx_layernorm with rows <= 32, sx_attn_decode_b, sx_gemv):
  * the [rows <= 32][cols] result is written as MFMA operand tiles [rows/16][cols/32][16][32] — what sx_gemv reads with x_layout = 1
  * (tile t = columns 32t .. 32t+31 of all 16 rows, 1 KB contiguous; rows >= `rows` of a tile are not written). */
@@ -177,6 +179,18 @@ typedef struct sx_gemv_args {
   const float* x16_gamma; /* optional fp32 [N] with x16_out: x16_out holds o * gamma (the NEXT LlamaRMSNorm's weight applied on the
                         * activation side, so that the next projection keeps its exact checkpoint weights and only scales by rstd from
                         * row_ssq_in — the RMSNorm fold of the precise mode; row_ssq_out is still the sum of squares of o itself) */
+  int32_t w_dtype;     /* 0: W has the activation dtype. SX_FP8_E4M3: W holds one-byte e4m3 codes in the FP8 form of w_layout 1 or 2 (MFMA path
+                        * only, any other combination is SX_ERR_INVALID):
+                        *   w_layout 1: [N/16][K/64][16][64] — a 64-k slab of 16 rows is one 1-KB tile; inside a row the 64 codes are ordered
+                        *     so that byte 16 g + 8 h + j holds k = 64 t + 32 h + 8 g + j (g = 0..3, h = 0..1, j = 0..7): lane (row r, group g)
+                        *     of the 16x16x32 MFMA finds its eight k-slots of BOTH 32-k halves in the one 16-B load at byte 64 r + 16 g,
+                        *   w_layout 2: [N/20][K/64][20][64] — the same 1-KB tile of rows 0..15, then rows 16..19 (256 B) in the same byte order.
+                        * The codes are converted to the activation dtype in registers (exact for every code) and feed the same MFMAs as
+                        * 16-bit tiles; the products are summed in fp32 exactly as for 16-bit weights of value decode(code). */
+  const float* w_scale; /* with SX_FP8_E4M3 (else NULL): fp32 [N], 16-B aligned, in the row order of W as passed (GLU-packed rows: packed
+                        * order). Multiplies the summed accumulators of row n once — after the wave, split-K and plane sums, before rstd
+                        * (row_ssq_in), activation, GLU, residual and the plane / sum-of-squares outputs. A power-of-two scale commutes with
+                        * every fp32 rounding: the result then has the bits of the 16-bit kernel on the weights code * scale. */
 } sx_gemv_args;
 /* workgroups in x (= partial rows of row_ssq_out) sx_gemv launches for an M x N x K problem with / without GLU on the MFMA path */
 int sx_gemv_ssq_parts(int N, int glu, int w_layout);

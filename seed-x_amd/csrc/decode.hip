@@ -29,6 +29,7 @@ struct GemvP {
                 // blocks' results are added ahead of the epilogue
   int out_planes;          // the 16-bit tiled output (y_tiled) or x16_out is written as two planes: block 0 = hi, block 1 = lo (rows <= 16)
   const float* x16_gamma;  // x16_out holds o * gamma[col] (the NEXT RMSNorm's gamma applied on the activation side: the weights stay exact)
+  const float* w_scale;    // FP8 weight tiles (W8 kernels): fp32 [N], row n of W as passed is e4m3 code * w_scale[n]
 };
 
 template <typename TT, int MR>
@@ -146,10 +147,38 @@ __device__ __forceinline__ u32x2_t lo_plane(f32x4_t x, u32x2_t hi, bool bf16) {
   return lo;
 }
 
+// Eight e4m3 codes (two dwords = one lane's k-slots of one 32-k half) → the eight 16-bit MFMA operand elements, exactly: every
+// non-NaN code is a normal fp16 number (>= 2^-9) and has 3 mantissa bits (bf16 keeps 7). fp16: one packed convert per pair
+// (v_cvt_scalef32_pk_f16_fp8 with scale 1); bf16: packed convert to fp32, then one v_perm_b32 keeps the two upper halves.
+template <typename TT>
+__device__ __forceinline__ typename TT::vec8 fp8x8_to16(unsigned d0, unsigned d1) {
+  u32x4_t o;
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (std::is_same<TT, F16>::value) {
+    o[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(d0, 1.0f, false));
+    o[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(d0, 1.0f, true));
+    o[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(d1, 1.0f, false));
+    o[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(d1, 1.0f, true));
+  } else {
+    const f32x2_t a = __builtin_amdgcn_cvt_pk_f32_fp8(d0, false), b = __builtin_amdgcn_cvt_pk_f32_fp8(d0, true);
+    const f32x2_t c = __builtin_amdgcn_cvt_pk_f32_fp8(d1, false), d = __builtin_amdgcn_cvt_pk_f32_fp8(d1, true);
+    o[0] = __builtin_amdgcn_perm(__float_as_uint(a[1]), __float_as_uint(a[0]), 0x07060302u);
+    o[1] = __builtin_amdgcn_perm(__float_as_uint(b[1]), __float_as_uint(b[0]), 0x07060302u);
+    o[2] = __builtin_amdgcn_perm(__float_as_uint(c[1]), __float_as_uint(c[0]), 0x07060302u);
+    o[3] = __builtin_amdgcn_perm(__float_as_uint(d[1]), __float_as_uint(d[0]), 0x07060302u);
+  }
+#endif
+  return __builtin_bit_cast(typename TT::vec8, o);
+}
+
 // MB = 2 (17..32 activation rows, lock-step batch 32): the x operand is two 16-row blocks — tiles [2][K/32][16][32] or rows 16..31 of
 // the row-major x — and every weight fragment feeds two MFMAs, so the weights still stream ONCE for all 32 sequences. Outputs, the
 // 16-bit tiled output, x16_out and the sums of squares follow the same block structure (row m = 16 b + r).
-template <typename TT, int R, int NWV, int U, bool TAIL = false, int MB = 1>
+// W8 (sx_gemv_args.w_dtype = SX_FP8_E4M3, w_layout 1 / 2 only): the weight tiles hold e4m3 codes, a 64-k slab of 16 rows is ONE 1-KB
+// tile [16][64] whose rows are ordered so that lane (r, g) finds its eight k-slots of both 32-k halves in one 16-B load (include/
+// seedx_hip.h) — half the bytes and half the weight loads per k-step. The codes become 16-bit operand elements in registers (exact,
+// fp8x8_to16) in front of the same MFMAs; the fp32 row scale multiplies the summed accumulators once in wave 0's epilogue.
+template <typename TT, int R, int NWV, int U, bool TAIL = false, int MB = 1, bool W8 = false>
 __global__ __launch_bounds__(NWV * 64) void gemm_skinny_kernel(const GemvP p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef typename TT::vec8 vec8;
@@ -182,16 +211,17 @@ __global__ __launch_bounds__(NWV * 64) void gemm_skinny_kernel(const GemvP p) {
   // row-major W: a load instruction covers one 64-B half line of 16 rows (row stride 2K bytes). Decode layout: the same
   // instruction covers one contiguous 1-KB operand tile, a wave's k range is one contiguous stream.
   const unsigned short* wp[R];
-  const size_t kstep = TAIL ? 1280 : (p.packed ? 1024 : 64), khalf = TAIL ? 640 : (p.packed ? 512 : 32);   // elements per 64-wide k-step / to its 2nd half
+  constexpr int WD = W8 ? 2 : 1;   // FP8 tiles: every tile stride is half as many 16-bit units (lane offset r * 32 + 8 g units = byte r * 64 + 16 g: the same)
+  const size_t kstep = (TAIL ? 1280 : (p.packed ? 1024 : 64)) / WD, khalf = TAIL ? 640 : (p.packed ? 512 : 32);   // elements per 64-wide k-step / to its 2nd half (16-bit tiles)
   size_t kstep_q[R], khalf_q[R];
 #pragma unroll
   for (int q = 0; q < R; ++q) {
     kstep_q[q] = kstep; khalf_q[q] = khalf;
-    wp[q] = p.packed ? p.W + (size_t)(n0 / 16 + q) * (size_t)(p.K >> 5) * 512 + r * 32 + 8 * g
+    wp[q] = p.packed ? p.W + (size_t)(n0 / 16 + q) * (size_t)(p.K >> 5) * (512 / WD) + r * 32 + 8 * g
                      : p.W + (size_t)(n0 + q * 16 + r) * p.K + 8 * g;
   }
   if (TAIL) {   // [N/20][K/32][20 rows][32 k]: a 32-k slab of the group is 1280 B = rows 0..15 (the 1-KB MFMA tile) + rows 16..19
-    wp[0] = p.W + (size_t)blockIdx.x * (size_t)(p.K >> 5) * 640 + r * 32 + 8 * g;
+    wp[0] = p.W + (size_t)blockIdx.x * (size_t)(p.K >> 5) * (640 / WD) + r * 32 + 8 * g;   // (FP8: [N/20][K/64][20][64], rows 16..19 behind the 1-KB tile)
     if (r < 4) wp[R - 1] = wp[0] + 512;
     else { wp[R - 1] = (const unsigned short*)g_zero_line; kstep_q[R - 1] = 0; khalf_q[R - 1] = 0; }   // operand rows 4..15 of block 1 = 0
   }
@@ -249,7 +279,7 @@ __global__ __launch_bounds__(NWV * 64) void gemm_skinny_kernel(const GemvP p) {
 #pragma unroll
         for (int q = 0; q < R; ++q) {
           f.wa[u][q] = __builtin_nontemporal_load((const u32x4_t*)(wp[q] + (size_t)(ks + u) * kstep_q[q]));
-          f.wb[u][q] = __builtin_nontemporal_load((const u32x4_t*)(wp[q] + (size_t)(ks + u) * kstep_q[q] + khalf_q[q]));
+          if (!W8) f.wb[u][q] = __builtin_nontemporal_load((const u32x4_t*)(wp[q] + (size_t)(ks + u) * kstep_q[q] + khalf_q[q]));
         }
 #pragma unroll
         for (int b = 0; b < MB; ++b) {
@@ -267,12 +297,16 @@ __global__ __launch_bounds__(NWV * 64) void gemm_skinny_kernel(const GemvP p) {
         // on its own B column only — no select on the loaded registers (a VALU op on them at the top of the round makes the
         // waitcnt pass drain every load in flight)
 #pragma unroll
-        for (int q = 0; q < R; ++q)
+        for (int q = 0; q < R; ++q) {
+          // FP8: the conversion is VALU work on loaded registers too — here, for the k-step being consumed, never at the top of the round
+          const vec8 wa = W8 ? fp8x8_to16<TT>(f.wa[u][q][0], f.wa[u][q][1]) : __builtin_bit_cast(vec8, f.wa[u][q]);
+          const vec8 wb = W8 ? fp8x8_to16<TT>(f.wa[u][q][2], f.wa[u][q][3]) : __builtin_bit_cast(vec8, f.wb[u][q]);
 #pragma unroll
           for (int b = 0; b < MB; ++b) {
-            acc[q][b] = TT::mfma16(__builtin_bit_cast(vec8, f.wa[u][q]), __builtin_bit_cast(vec8, f.xa[u][b]), acc[q][b]);
-            acc[q][b] = TT::mfma16(__builtin_bit_cast(vec8, f.wb[u][q]), __builtin_bit_cast(vec8, f.xb[u][b]), acc[q][b]);
+            acc[q][b] = TT::mfma16(wa, __builtin_bit_cast(vec8, f.xa[u][b]), acc[q][b]);
+            acc[q][b] = TT::mfma16(wb, __builtin_bit_cast(vec8, f.xb[u][b]), acc[q][b]);
           }
+        }
       }
     }
   };
@@ -320,6 +354,14 @@ __global__ __launch_bounds__(NWV * 64) void gemm_skinny_kernel(const GemvP p) {
   }
   __syncthreads();
   if (wave != 0) return;
+  // FP8: the lane's four row scales per row group, asked for ahead of the LDS / split-K sums that hide the round trip (the 20-row
+  // tail's block 1 is rows 16..19 = lane group 0 only: the others would read past the group, at the last one past N)
+  f32x4_t wsc[R];
+  if (W8) {
+#pragma unroll
+    for (int q = 0; q < R; ++q)
+      wsc[q] = (TAIL && q == 1 && g != 0) ? (f32x4_t){0.f, 0.f, 0.f, 0.f} : *(const f32x4_t*)(p.w_scale + n0 + q * 16 + 4 * g);
+  }
   // lane holds y[m = 16 b + r][n0 + q*16 + 4g + e], e = 0..3; the waves' partial sums are added in wave order (0 + w0 == w0: the same bits as
   // when wave 0 went through LDS too)
   f32x4_t v[R][MB];
@@ -376,6 +418,13 @@ __global__ __launch_bounds__(NWV * 64) void gemm_skinny_kernel(const GemvP p) {
     for (int q = 0; q < R; ++q)
 #pragma unroll
       for (int b = 0; b < MB / 2; ++b) v[q][b] += v[q][MB / 2 + b];
+  }
+  if (W8) {   // code sums → weights: once per output, behind every sum and ahead of rstd / activation / GLU (whose two rows differ in scale)
+#pragma unroll
+    for (int q = 0; q < R; ++q)
+#pragma unroll
+      for (int b = 0; b < MB; ++b)
+        if (b < RB) v[q][b] *= wsc[q];
   }
   if (p.ssq_in) {
 #pragma unroll
@@ -1291,6 +1340,14 @@ extern "C" int sx_gemv(const sx_gemv_args* a, void* stream) {
   SX_CHECK(a->w_layout != 2 || (!a->glu && a->N % 20 == 0 && a->N % 32 == 0), "sx_gemv: w_layout 2 needs N %% 20 == 0, N %% 32 == 0, no GLU");
   // MI355X (tools/bench_gemv.py, 13B shapes): VALU path 6.5 / 4.7 / 3.0 TB/s at M = 1 / 4 / 8, MFMA path 4.0-4.4 TB/s at any M
   const bool mfma_ok = (a->M >= 2 || planes2) && a->K % 64 == 0 && a->K >= 256 && a->N % 32 == 0;
+  // FP8 weight tiles: codes + fp32 row scales, tiled layouts and the MFMA kernel only (the VALU kernel has no FP8 form)
+  SX_CHECK(a->w_dtype == 0 || a->w_dtype == SX_FP8_E4M3, "sx_gemv: w_dtype must be 0 (the activation dtype) or SX_FP8_E4M3");
+  const bool w8 = a->w_dtype == SX_FP8_E4M3;
+  SX_CHECK(!w8 || ((a->w_layout == 1 || a->w_layout == 2) && mfma_ok),
+           "sx_gemv: SX_FP8_E4M3 weights need w_layout 1 or 2 and the MFMA path (M >= 2, K %% 64 == 0, K >= 256, N %% 32 == 0)");
+  SX_CHECK(!w8 || (a->w_scale && ((uintptr_t)a->w_scale & 15) == 0), "sx_gemv: SX_FP8_E4M3 weights need w_scale (16-B aligned fp32 [N])");
+  SX_CHECK(w8 || !a->w_scale, "sx_gemv: w_scale belongs to SX_FP8_E4M3 weights");
+  p.w_scale = a->w_scale;
   SX_CHECK(!a->w_layout || (mfma_ok && a->K % 64 == 0), "sx_gemv: the decode-tile layout needs M >= 2, K %% 64 == 0, K >= 256, N %% 32 == 0");
   // the decode-tile layout only exists for the MFMA kernel: it overrides the VALU test hook
   SX_CHECK(!p.y_tiled || mfma_ok, "sx_gemv: a tiled output needs the MFMA path (M >= 2, K %% 64 == 0, K >= 256, N %% 32 == 0)");
@@ -1320,29 +1377,30 @@ extern "C" int sx_gemv(const sx_gemv_args* a, void* stream) {
       p.ws_part = (float*)((char*)a->workspace + cnt_bytes);
     }
     const dim3 grid(gx, S);
-#define SX_SK_GO(TT)                                                                                          \
+#define SX_SK_GO(TT, W8)                                                                                          \
     if (a->M > 16 && planes2 && r4) {                                                                          \
-      hipLaunchKernelGGL((gemm_skinny_kernel<TT, 4, 4, 1, false, 4>), grid, dim3(256), 0, ST, p);              \
+      hipLaunchKernelGGL((gemm_skinny_kernel<TT, 4, 4, 1, false, 4, W8>), grid, dim3(256), 0, ST, p);              \
     } else if (a->M > 16 && planes2) {    /* round 6: 17..32 fp32-grade rows = four operand blocks per weight fragment */      \
-      if (tail20) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 1, true, 4>), grid, dim3(256), 0, ST, p);      \
-      else if (r2) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 1, false, 4>), grid, dim3(256), 0, ST, p);    \
-      else hipLaunchKernelGGL((gemm_skinny_kernel<TT, 1, 4, 2, false, 4>), grid, dim3(256), 0, ST, p);            \
+      if (tail20) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 1, true, 4, W8>), grid, dim3(256), 0, ST, p);      \
+      else if (r2) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 1, false, 4, W8>), grid, dim3(256), 0, ST, p);    \
+      else hipLaunchKernelGGL((gemm_skinny_kernel<TT, 1, 4, 2, false, 4, W8>), grid, dim3(256), 0, ST, p);            \
     } else if (r4) {                                                                                           \
-      if (a->M > 16 || planes2) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 4, 4, 1, false, 2>), grid, dim3(256), 0, ST, p); \
-      else hipLaunchKernelGGL((gemm_skinny_kernel<TT, 4, 4, 2, false, 1>), grid, dim3(256), 0, ST, p);         \
+      if (a->M > 16 || planes2) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 4, 4, 1, false, 2, W8>), grid, dim3(256), 0, ST, p); \
+      else hipLaunchKernelGGL((gemm_skinny_kernel<TT, 4, 4, 2, false, 1, W8>), grid, dim3(256), 0, ST, p);         \
     } else if (a->M > 16 || planes2) {                                                                                \
       if (g_skinny_var[1] == 1) {       /* lab: 4 k-steps per round (256 VGPRs + AGPR copies, one wave per SIMD) */ \
-        if (tail20) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 4, true, 2>), grid, dim3(256), 0, ST, p);   \
-        else if (r2) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 4, false, 2>), grid, dim3(256), 0, ST, p); \
-        else hipLaunchKernelGGL((gemm_skinny_kernel<TT, 1, 4, 4, false, 2>), grid, dim3(256), 0, ST, p);         \
-      } else if (tail20 && g_skinny_var[1] == 2) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 4, true, 2>), grid, dim3(256), 0, ST, p); \
-      else if (tail20) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 2, true, 2>), grid, dim3(256), 0, ST, p); \
-      else if (r2) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 2, false, 2>), grid, dim3(256), 0, ST, p);   \
-      else hipLaunchKernelGGL((gemm_skinny_kernel<TT, 1, 4, 4, false, 2>), grid, dim3(256), 0, ST, p);           \
-    } else if (tail20) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 4, true>), grid, dim3(256), 0, ST, p); \
-    else if (r2) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 4>), grid, dim3(256), 0, ST, p);             \
-    else hipLaunchKernelGGL((gemm_skinny_kernel<TT, 1, 4, 4>), grid, dim3(256), 0, ST, p);
-    if (a->dtype == SX_BF16) { SX_SK_GO(BF16) } else { SX_SK_GO(F16) }
+        if (tail20) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 4, true, 2, W8>), grid, dim3(256), 0, ST, p);   \
+        else if (r2) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 4, false, 2, W8>), grid, dim3(256), 0, ST, p); \
+        else hipLaunchKernelGGL((gemm_skinny_kernel<TT, 1, 4, 4, false, 2, W8>), grid, dim3(256), 0, ST, p);         \
+      } else if (tail20 && g_skinny_var[1] == 2) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 4, true, 2, W8>), grid, dim3(256), 0, ST, p); \
+      else if (tail20) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 2, true, 2, W8>), grid, dim3(256), 0, ST, p); \
+      else if (r2) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 2, false, 2, W8>), grid, dim3(256), 0, ST, p);   \
+      else hipLaunchKernelGGL((gemm_skinny_kernel<TT, 1, 4, 4, false, 2, W8>), grid, dim3(256), 0, ST, p);           \
+    } else if (tail20) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 4, true, 1, W8>), grid, dim3(256), 0, ST, p); \
+    else if (r2) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 4, false, 1, W8>), grid, dim3(256), 0, ST, p);             \
+    else hipLaunchKernelGGL((gemm_skinny_kernel<TT, 1, 4, 4, false, 1, W8>), grid, dim3(256), 0, ST, p);
+    if (w8) { if (a->dtype == SX_BF16) { SX_SK_GO(BF16, true) } else { SX_SK_GO(F16, true) } }
+    else if (a->dtype == SX_BF16) { SX_SK_GO(BF16, false) } else { SX_SK_GO(F16, false) }
 #undef SX_SK_GO
     SX_HIP_LAUNCH_CHECK();
     return SX_OK;

@@ -193,7 +193,7 @@ class SampleState:
 
 
 class LlamaForCausalLM:
-    def __init__(self, config, max_cache_len=None, max_batch=1, comm=None, precise=None, kv_v16=None):
+    def __init__(self, config, max_cache_len=None, max_batch=1, comm=None, precise=None, kv_v16=None, weight_format=None):
         self.config = config if not isinstance(config, dict) else LlamaConfigLite(**config)
         c = self.config
         self.H, self.nh, self.L = c.hidden_size, c.num_attention_heads, c.num_hidden_layers
@@ -227,6 +227,27 @@ class LlamaForCausalLM:
         # contract) — decided in _pack once the dtype is known; ``kv_v16=False`` / ``SX_LLM_V16=0`` keep the all-fp32 cache.
         self._kv_v16_arg = kv_v16
         self.kv_v16 = False
+        # weight-only FP8 of the decode step (quant.py; opt-in: ``weight_format="fp8_e4m3"`` or SX_LLM_WEIGHTS=fp8_e4m3): the seven projection
+        # matrices of every layer are quantised to e4m3 codes with a power-of-two scale per row; the decode tiles hold the codes (half the
+        # bytes of a token step's weight stream), the row-major 16-bit weights hold their exact dequantised values. The 1e-3 contract
+        # then holds against the QUANTISED model (bit-identical to the default mode loaded with the dequantised weights); against the
+        # original checkpoint the mode costs the quantisation itself (2.7 % per projection on Gaussian rows, llm.weight_quant_report).
+        if weight_format is None:
+            weight_format = os.environ.get("SX_LLM_WEIGHTS") or None
+        if weight_format not in (None, "fp8_e4m3"):
+            raise ValueError(f"LlamaForCausalLM: weight_format must be None or 'fp8_e4m3', not {weight_format!r}")
+        self.weight_format = weight_format
+        self.weight_quant_report = None
+        if weight_format is not None:
+            # only where the raw matrices ARE the decode tiles: the precise mode's RMSNorm fold keeps gamma on the activation side; the
+            # plain flow folds gamma into its tiles, which would be a second, different quantisation of the same weights
+            if not self.precise:
+                raise ValueError("LlamaForCausalLM: weight_format='fp8_e4m3' needs the precise mode (the plain 16-bit flow folds the RMSNorm "
+                                 "gamma into its decode tiles: those are not the checkpoint's matrices and would be quantised a second, different time)")
+            if not self._skinny_shapes_ok():
+                raise ValueError("LlamaForCausalLM: weight_format='fp8_e4m3' needs the tiled precise decode path: hidden / per-rank head and FFN "
+                                 f"widths that are multiples of 64 and >= 256, output widths that are multiples of 32 (H {self.H}, "
+                                 f"heads x dim {self.H_l}, FFN {self.I_l}, vocab rows {self.V_l}): FP8 tiles exist for the MFMA skinny GEMM only")
         # Decode attention (tools/bench_decode_attention_ab.py, 16 sequences x 40 heads, ms per token of the graph-replayed step):
         # three launches (RoPE + append, split-KV attention, combine) with 8 / 2 / 1 KV splits 6.70 / 6.46 / 6.52; ONE launch
         # (sx_attn_decode_fused, bit-identical) with 8 splits 6.80 — its arrival-counter tail costs more than two graph
@@ -245,6 +266,20 @@ class LlamaForCausalLM:
         self._sample_state = None
         self.kv_epoch = 0               # bumped whenever the KV cache is reset or written outside generate_batch
 
+    def _precise_tiled_ok(self):
+        """Every projection shape of the precise decode step satisfies the MFMA skinny GEMM (_pack's P["precise_tiled"])."""
+        return all(k % 64 == 0 and k >= 256 for k in (self.H, self.H_l, self.I_l)) and \
+            all(n % 32 == 0 for n in (3 * self.H_l, self.H, 2 * self.I_l, self.V_l))
+
+    def _skinny_shapes_ok(self):
+        """precise_tiled and decode_tiled of _pack, from the dims alone (the attention output travels as operand tiles too)."""
+        return self._precise_tiled_ok() and self.H_l % 32 == 0
+
+    def _bal20(self, n_rows):
+        """o / down projections run from 20-row decode tiles where that gives 256 equal workgroups (N = 5120): the one rule for the
+        16-bit tiles, the FP8 tiles and the workgroup count of the RMSNorm fold, which must agree on the layout (SX_GEMV_BAL20=0: A/B switch)."""
+        return (self.G >= 5 or self.precise) and os.environ.get("SX_GEMV_BAL20", "1") != "0" and n_rows % 20 == 0 and n_rows // 20 == 256
+
     def _drop_graphs(self):
         """No captured token step: the lock-step one, the in-flight one (decode_step(..., slots=...): one per engine lifetime) and the
         sampled forms of the two (a greedy step and a sampled step never share a graph)."""
@@ -256,6 +291,11 @@ class LlamaForCausalLM:
         per_layer = (3 * self.H_l * self.H + self.H * self.H_l + 2 * self.I_l * self.H + self.H * self.I_l) * 2
         w = self.L * per_layer + (self.V + self.V_l) * self.H * 2
         tiles = self.L * per_layer + self.V_l * self.H * 2 if (self.G >= 5 or self.precise) else 0
+        if self.weight_format == "fp8_e4m3":
+            # one byte per weight + one fp32 scale per row, in exactly one layout per projection (o / down: 20-row OR 16-row tiles);
+            # lm_head's tiles stay 16-bit. "weights" is unchanged: the row-major matrices hold the dequantised values for prefill
+            rows = 3 * self.H_l + self.H + 2 * self.I_l + self.H
+            tiles = self.L * (per_layer // 2 + rows * 4) + self.V_l * self.H * 2
         kv = self.L * self.G * self.nh_l * self.Tmax * self.hd * ((4 + (2 if self.kv_v16 else 4)) if self.precise else 4)
         return {"weights": w, "decode_tiles": tiles, "kv_cache": kv, "total": w + tiles + kv}
 
@@ -349,7 +389,8 @@ class LlamaForCausalLM:
         free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)   # + the allocator's cached blocks
         logging.getLogger("seedx_amd").info(
             "LlamaForCausalLM._pack (%s, %d sequences, Tmax %d): weights %.1f GB + decode tiles %.1f GB + KV cache %.1f GB (%s)",
-            "precise" if self.precise else "plain 16-bit", self.G, self.Tmax, fp["weights"] / 1e9, fp["decode_tiles"] / 1e9,
+            ("precise" if self.precise else "plain 16-bit") + (", FP8 e4m3 decode tiles" if self.weight_format else ""), self.G, self.Tmax,
+            fp["weights"] / 1e9, fp["decode_tiles"] / 1e9,
             fp["kv_cache"] / 1e9, ("k fp32 + v 16-bit" if self.kv_v16 else "fp32") if self.precise else "16-bit")
         if fp["total"] > free:
             raise RuntimeError(
@@ -382,30 +423,58 @@ class LlamaForCausalLM:
         # of the projections that FOLLOW a norm carry that norm's gamma (W' = W · diag(gamma), product rounded once to 16 bits) —
         # wgu of every layer (post_attention_layernorm) and wqkv of layers >= 1 (input_layernorm; layer 0's input comes from the
         # embedding, not from a GEMV). Prefill keeps the row-major, unfolded weights and the norm kernel.
-        bal20 = (self.G >= 5 or self.precise) and os.environ.get("SX_GEMV_BAL20", "1") != "0"
         # the consumer adds the producer's per-workgroup sums of squares 64 at a time: the o / down launches (N = H) must have a
         # multiple of 64 workgroups (H = 5120: 256 with 20-row tiles, 320 without)
         # (asked from the library, not re-derived here: sx_gemv's own workgroup count for an N = H launch in that weight layout)
         from . import _lib
-        parts = _lib.load().sx_gemv_ssq_parts(self.H, 0, 2 if (bal20 and self.H % 20 == 0 and self.H // 20 == 256) else 1)
+        parts = _lib.load().sx_gemv_ssq_parts(self.H, 0, 2 if self._bal20(self.H) else 1)
         fold = self.G >= 5 and tp == 1 and parts % 64 == 0 and os.environ.get("SX_RMS_FOLD", "1") != "0" \
             and not self.precise      # (SX_RMS_FOLD=0: A/B switch, tools/; the precise mode norms in fp32 with its own kernel)
+        fp8 = self.weight_format == "fp8_e4m3"
+        if fp8:
+            from . import quant
+            qerr = {n.split(".")[1]: torch.zeros(2, dtype=torch.float64, device=dev) for n in quant.LLAMA_PROJECTIONS}   # [|W - Wq|^2, |W|^2]
         for i in range(self.L):
             p = f"model.layers.{i}."
-            sh = llama_tp_shard(sd, p, r, tp, self.nh, self.hd)
+            if fp8:
+                # the FULL matrices are quantised (after the LoRA merge, before the tensor-parallel slicing): every rank holds slices of
+                # one quantised model. From here on "the weights" are the dequantised values; codes and scales are sliced the same way
+                ql = quant.quantize_llama_layer(sd, p, dt, dev)
+                for k, (_, _, wq) in ql.items():
+                    w0 = sd[k].detach().to(dev, dt).double()
+                    qerr[k[len(p):].split(".")[1]] += torch.stack([(w0 - wq.double()).square().sum(), w0.square().sum()])
+                sh8 = llama_tp_shard({k: v[0] for k, v in ql.items()}, p, r, tp, self.nh, self.hd)
+                sc8 = quant.llama_tp_shard_scales({k: v[1] for k, v in ql.items()}, p, r, tp, self.nh, self.hd)
+                lsd = {k: v[2] for k, v in ql.items()}
+                del ql
+            sh = llama_tp_shard(lsd if fp8 else sd, p, r, tp, self.nh, self.hd)
             qkv = torch.cat([sh["q"].detach(), sh["k"].detach(), sh["v"].detach()], dim=0)
             gu = glu_pack_rows(sh["up"].detach().to(dev, dt), sh["gate"].detach().to(dev, dt))
             P["layers"].append(dict(
                 ln1=f32(sd[p + "input_layernorm.weight"]), ln2=f32(sd[p + "post_attention_layernorm.weight"]),
                 wqkv=w16(qkv), wo=w16(sh["o"]), wgu=gu, wd=w16(sh["down"])))
             lw = P["layers"][-1]
+            if fp8:
+                # decode tiles = the codes (one layout per projection: 20-row tiles where o / down use them, else 16-row) + row scales;
+                # GLU row packing moves the codes and the scales alike. No 16-bit tile copy at all.
+                c8 = {"wqkv": torch.cat([sh8["q"], sh8["k"], sh8["v"]], dim=0), "wo": sh8["o"], "wd": sh8["down"],
+                      "wgu": glu_pack_rows(sh8["up"], sh8["gate"])}
+                s8 = {"wqkv": torch.cat([sc8["q"], sc8["k"], sc8["v"]]), "wo": sc8["o"], "wd": sc8["down"],
+                      "wgu": glu_pack_rows(sc8["up"][:, None], sc8["gate"][:, None]).reshape(-1)}
+                for k in ("wqkv", "wo", "wgu", "wd"):
+                    lw[k + "_t"] = lw[k + "_t20"] = None
+                    t20 = k in ("wo", "wd") and self._bal20(c8[k].shape[0])
+                    lw[k + "_f8"] = ((ops.pack_decode_tiles20_fp8 if t20 else ops.pack_decode_tiles_fp8)(c8[k].contiguous()),
+                                     s8[k].contiguous().clone())
+                del sh8, sc8, c8, s8, lsd
+                continue
             for k in ("wqkv", "wo", "wgu", "wd"):
                 lw[k + "_t"] = tiles(lw[k])
             # N = 5120 output rows are 320 16-row groups on 256 CUs; as 256 groups of 20 rows every CU streams the same bytes
             # (sx_gemv w_layout 2) — the o and down projections of the 13B geometry
             for k in ("wo", "wd"):
                 lw[k + "_t20"] = None
-                if bal20 and lw[k + "_t"] is not None and lw[k].shape[0] % 20 == 0 and lw[k].shape[0] // 20 == 256:
+                if lw[k + "_t"] is not None and self._bal20(lw[k].shape[0]):
                     lw[k + "_t20"] = ops.pack_decode_tiles20(lw[k])
             if fold and lw["wgu_t"] is not None and lw["wqkv_t"] is not None:
                 g2 = lw["ln2"][None, :]
@@ -414,8 +483,20 @@ class LlamaForCausalLM:
                 if i > 0:
                     lw["wqkv_t"] = tiles((qkv.to(dev, torch.float32) * lw["ln1"][None, :]).to(dt).contiguous())
         # every decode GEMV has the decode-tile weight copy → its 16-bit inputs travel as operand tiles too (_layers_single)
-        P["decode_tiled"] = all(lw[k + "_t"] is not None for lw in P["layers"] for k in ("wqkv", "wo", "wgu", "wd")) \
+        P["decode_tiled"] = all((lw.get(k + "_f8") if fp8 else lw[k + "_t"]) is not None for lw in P["layers"] for k in ("wqkv", "wo", "wgu", "wd")) \
             and (self.nh_l * self.hd) % 32 == 0
+        if fp8:
+            held = sum(t.numel() * t.element_size() for lw in P["layers"] for k in ("wqkv", "wo", "wgu", "wd") for t in lw[k + "_f8"]) \
+                + P["lm_head_t"].numel() * P["lm_head_t"].element_size()
+            assert held == fp["decode_tiles"], (held, fp["decode_tiles"])      # memory_footprint() prices what is held, nothing else
+            err = {k: math.sqrt(float(v[0] / v[1])) if float(v[1]) > 0 else 0.0 for k, v in qerr.items()}
+            tiles16 = sum(2 * lw[k].numel() for lw in P["layers"] for k in ("wqkv", "wo", "wgu", "wd")) + 2 * P["lm_head_t"].numel()
+            self.weight_quant_report = {"weight_format": self.weight_format, "decode_tile_bytes": held, "decode_tile_bytes_16bit": tiles16,
+                                        "rel_frobenius_error": err}
+            logging.getLogger("seedx_amd").info(
+                "LlamaForCausalLM._pack: FP8 e4m3 weight tiles, %.2f GB of decode tiles (16-bit: %.2f GB); relative Frobenius error of the "
+                "quantisation against the %s checkpoint: %s", held / 1e9, self.weight_quant_report["decode_tile_bytes_16bit"] / 1e9,
+                str(dt).replace("torch.", ""), ", ".join(f"{k} {v:.4f}" for k, v in err.items()))
         P["rms_fold"] = fold and P["decode_tiled"] and self.H % 32 == 0
         assert P["rms_fold"] or not fold or not any(lw["wgu_t"] is not None for lw in P["layers"]), \
             "folded decode tiles without the tiled decode path"
@@ -423,13 +504,14 @@ class LlamaForCausalLM:
         P["gemv_ws"] = torch.zeros(16384 + 8 * 16 * ((2 if self.precise else 1) * ((self.G + 15) // 16)) * self.H * 4, dtype=torch.uint8,
                                    device=dev) if P["decode_tiled"] else None
         # precise decode step on the skinny GEMM (operand tiles, two planes): every projection shape must satisfy its MFMA path
-        P["precise_tiled"] = all(k % 64 == 0 and k >= 256 for k in (self.H, self.H_l, self.I_l)) and \
-            all(n % 32 == 0 for n in (3 * self.H_l, self.H, 2 * self.I_l, self.V_l))
+        P["precise_tiled"] = self._precise_tiled_ok()
         # RMSNorm fold of the precise decode step (single rank, decode tiles, a multiple of 64 workgroups in the o / down launches —
         # the plain fold's conditions): the residual GEMV writes the two planes of x * gamma_next and the rows' sums of squares, the
         # projection behind the norm scales by rstd. gamma sits on the ACTIVATION here: the checkpoint's weights stay exact.
         P["rms_fold_precise"] = self.precise and P["precise_tiled"] and P["decode_tiled"] and tp == 1 and parts % 64 == 0 \
             and self.H % 32 == 0 and self.I_l % 32 == 0 and os.environ.get("SX_RMS_FOLD", "1") != "0"
+        if fp8 and not (P["precise_tiled"] and P["decode_tiled"]):
+            raise ValueError("LlamaForCausalLM: weight_format='fp8_e4m3' needs the tiled precise decode path (FP8 tiles exist for the MFMA skinny GEMM only)")
         inv = 1.0 / (self.config.rope_base ** (torch.arange(0, self.hd, 2).float() / self.hd))
         fr = torch.outer(torch.arange(self.Tmax).float(), inv)           # [Tmax, hd/2] fp32 (:97-113)
         P["cos"], P["sin"] = fr.cos().to(dev).contiguous(), fr.sin().to(dev).contiguous()
@@ -606,7 +688,7 @@ class LlamaForCausalLM:
         def lin(xp, lw, k, **kw):
             if tl:
                 return ops.gemv(xp, lw[k], w_tiles=lw[k + "_t"] if dtl else None, workspace=ws if dtl else None,
-                                w_tiles20=lw.get(k + "_t20") if dtl else None, out_dtype=f32, **kw)
+                                w_tiles20=lw.get(k + "_t20") if dtl else None, w_fp8=lw.get(k + "_f8"), out_dtype=f32, **kw)
             return ops.gemm(xp, lw[k], a_planes=2, out_dtype=f32, **kw)
         fold = P["rms_fold_precise"]
         fuse_rope = hd == 128 and os.environ.get("SX_LLM_FUSE_ROPE", "1") != "0"
@@ -628,7 +710,7 @@ class LlamaForCausalLM:
             if fold:
                 # residual GEMV: fp32 x, the planes of x * gamma of the NEXT norm, the rows' sums of squares; GLU epilogue: planes directly
                 x, x16, ssq = lin(att, lw, "wo", residual=x, emit_norm=True, planes_out=True, norm_gamma=lw["ln2"])
-                g = ops.gemv(x16, lw["wgu"], act="silu", glu=True, w_tiles=lw["wgu_t"], y_tiled=True, planes_out=True,
+                g = ops.gemv(x16, lw["wgu"], act="silu", glu=True, w_tiles=lw["wgu_t"], w_fp8=lw.get("wgu_f8"), y_tiled=True, planes_out=True,
                              ssq_in=(ssq, self.H, eps))
                 if li + 1 < nl:
                     x, x16, ssq = lin(g, lw, "wd", residual=x, emit_norm=True, planes_out=True, norm_gamma=P["layers"][li + 1]["ln1"])
@@ -638,7 +720,8 @@ class LlamaForCausalLM:
             x = comm.all_reduce(lin(att, lw, "wo", residual=x if lead else None))
             h, _ = ops.rmsnorm_planes(x, lw["ln2"], eps, dt, tiled=tl)
             if tl:                           # SiLU-GLU epilogue writes the two planes of its result itself (no sx_split16 launch)
-                g = ops.gemv(h, lw["wgu"], act="silu", glu=True, w_tiles=lw["wgu_t"] if dtl else None, y_tiled=True, planes_out=True)
+                g = ops.gemv(h, lw["wgu"], act="silu", glu=True, w_tiles=lw["wgu_t"] if dtl else None, w_fp8=lw.get("wgu_f8"), y_tiled=True,
+                             planes_out=True)
             else:
                 g = ops.split16(lin(h, lw, "wgu", act="silu", glu=True), dt)
             x = comm.all_reduce(lin(g, lw, "wd", residual=x if lead else None))

@@ -231,6 +231,29 @@ def pack_decode_tiles20(w):
     return w.view(N // 20, 20, K // 32, 32).permute(0, 2, 1, 3).contiguous().view(N, K)
 
 
+def _fp8_row_order(codes):
+    """[..., K] → [..., K/64, 64] with the 64 codes of a k-slab in the skinny GEMM's lane order: byte 16 g + 8 h + j holds
+    k = 32 h + 8 g + j (g = 0..3 lane group, h = 0..1 32-k half, j = 0..7) — sx_gemv_args.w_dtype in include/seedx_hip.h."""
+    K = codes.shape[-1]
+    return codes.reshape(*codes.shape[:-1], K // 64, 2, 4, 8).transpose(-3, -2).reshape(*codes.shape[:-1], K // 64, 64)
+
+
+def pack_decode_tiles_fp8(codes):
+    """Row-major e4m3 codes uint8 [N, K] (quant.quantize_rows) → FP8 decode tiles [N/16][K/64][16][64]: a 64-k slab of 16 rows is one
+    contiguous 1-KB tile, ONE 16-B load per lane and k-step (the 16-bit layout of pack_decode_tiles needs two)."""
+    N, K = codes.shape
+    assert codes.dtype == torch.uint8 and N % 16 == 0 and K % 64 == 0
+    return _fp8_row_order(codes).view(N // 16, 16, K // 64, 64).permute(0, 2, 1, 3).contiguous()
+
+
+def pack_decode_tiles20_fp8(codes):
+    """Row-major e4m3 codes uint8 [N, K] → 20-row FP8 decode tiles [N/20][K/64][20][64] (sx_gemv w_layout 2): the 1-KB tile of rows
+    0..15, then rows 16..19, per 64-k slab."""
+    N, K = codes.shape
+    assert codes.dtype == torch.uint8 and N % 20 == 0 and K % 64 == 0
+    return _fp8_row_order(codes).view(N // 20, 20, K // 64, 64).permute(0, 2, 1, 3).contiguous()
+
+
 class Tiled16:
     """A [rows <= 32, cols] 16-bit activation of the decode step held as MFMA operand tiles [rows/16][cols/32][16][32] (SX_TILED16
     in include/seedx_hip.h): what the skinny GEMM reads with one contiguous 1-KB load per operand. Rows 16..31 (lock-step batches
@@ -259,7 +282,7 @@ class Tiled16:
 
 
 def gemv(x, w, residual=None, act=None, glu=False, out_dtype=None, w_tiles=None, y_tiled=False, workspace=None,
-         emit_norm=False, ssq_in=None, w_tiles20=None, planes_out=False, norm_gamma=None):
+         emit_norm=False, ssq_in=None, w_tiles20=None, planes_out=False, norm_gamma=None, w_fp8=None):
     """w_tiles: the same weight in the decode layout (pack_decode_tiles); used instead of w when the MFMA path runs.
     x may be a Tiled16 (then w_tiles is required); y_tiled returns the 16-bit result as a Tiled16 for the next gemv.
     workspace: zero-initialised uint8 scratch enabling split-K over workgroups for shapes that need it (sx_gemv_args.workspace).
@@ -269,12 +292,15 @@ def gemv(x, w, residual=None, act=None, glu=False, out_dtype=None, w_tiles=None,
     w_tiles20: the weight as 20-row decode tiles (pack_decode_tiles20) instead of w_tiles: one workgroup per 20 rows.
     planes_out (M <= 16): the tiled 16-bit result (y_tiled) or the emit_norm x16 is written as two planes (Tiled16 planes = 2) for a next
     gemv with fp32-grade x; norm_gamma (with emit_norm): x16 = planes of y * gamma — the NEXT RMSNorm's weight on the activation side, so
-    the projection behind the norm keeps exact weights and only applies rstd (ssq_in)."""
+    the projection behind the norm keeps exact weights and only applies rstd (ssq_in).
+    w_fp8 = (tiles, scale): the weight as e4m3 codes in FP8 decode tiles (pack_decode_tiles_fp8 → 16-row, pack_decode_tiles20_fp8 →
+    20-row; the shape says which) with its fp32 row scales [N], in the row order of ``w``; replaces w_tiles / w_tiles20. ``w`` (the
+    dequantised 16-bit matrix) only gives shape and dtype. MFMA path only: any other shape is an error, never a fall-back."""
     lib = _lib.load()
     xt = isinstance(x, Tiled16)
     if xt:
         M, K = x.rows, x.cols
-        assert x.dtype == w.dtype and (x.planes == 2 or w_tiles is not None or w_tiles20 is not None)
+        assert x.dtype == w.dtype and (x.planes == 2 or w_tiles is not None or w_tiles20 is not None or w_fp8 is not None)
     else:
         assert x.dim() == 2 and x.is_contiguous() and w.is_contiguous() and x.dtype == w.dtype
         M, K = x.shape
@@ -309,6 +335,13 @@ def gemv(x, w, residual=None, act=None, glu=False, out_dtype=None, w_tiles=None,
     if w_tiles20 is not None and not glu and (xt or y_tiled or M >= 5) and K % 64 == 0 and K >= 256 and N % 32 == 0 and N % 20 == 0:
         assert w_tiles20.shape == w.shape and w_tiles20.dtype == w.dtype and w_tiles20.is_contiguous()
         args.W, args.w_layout = w_tiles20.data_ptr(), 2
+    if w_fp8 is not None:
+        t8, sc = w_fp8
+        assert t8.dtype == torch.uint8 and t8.is_contiguous() and t8.dim() == 4 and t8.shape[2] in (16, 20) and t8.shape[3] == 64
+        assert t8.shape[0] * t8.shape[2] == N and t8.shape[1] * 64 == K and t8.device == dev, "FP8 tiles do not match the weight's shape"
+        assert sc.dtype == torch.float32 and sc.is_contiguous() and sc.shape == (N,) and sc.device == dev
+        args.W, args.w_layout = t8.data_ptr(), 1 if t8.shape[2] == 16 else 2
+        args.w_dtype, args.w_scale = _lib.SX_FP8_E4M3, sc.data_ptr()
     x16 = ssq = None
     if emit_norm:
         assert args.w_layout in (1, 2) and out_dtype == torch.float32 and not glu and not y_tiled

@@ -1,0 +1,113 @@
+"""Weight-only FP8 (OCP e4m3fn) codec of the LLM decode step: one power-of-two scale per output row.
+
+Per row n of a 16-bit weight W[N, K]:  s[n] = clamp(ceil(log2(max|W[n, :]| / 448)), -15, 7)  (0 for an all-zero row),
+code = e4m3fn(rne(clamp(W · 2^-s, -448, 448))),  scale[n] = 2^s[n]  (fp32).  The NaN codes 0x7f / 0xff are never produced.
+Every code · 2^s with s in [-15, 7] is exactly representable in fp16 AND bf16 (smallest: 2^-9 · 2^-15 = 2^-24, the smallest fp16
+subnormal; largest: 448 · 2^7 < 65504; three mantissa bits), so the dequantised 16-bit matrix IS the quantised model: prefill runs
+the ordinary GEMMs on it, the decode step streams the codes (sx_gemv w_dtype = SX_FP8_E4M3) and computes the same bits.
+
+Everything here is integer / exact fp32 arithmetic in plain torch ops (no float8 cast, no pow / log2 whose last bit could depend on
+the device): the same codes on the CPU and on the GPU.
+"""
+import torch
+
+FP8_MAX = 448.0
+S_MIN, S_MAX = -15, 7
+LLAMA_PROJECTIONS = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj",
+                     "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj")
+
+
+def _pow2(e):
+    """2^e as fp32 for an int32 tensor e in [-126, 127], built from the exponent field (exact on every device)."""
+    return ((e.to(torch.int32) + 127) << 23).view(torch.float32)
+
+
+def _exponent(v):
+    """floor(log2 |v|) of a normal fp32 tensor as int32 (zero → -127)."""
+    return ((v.contiguous().view(torch.int32) >> 23) & 0xff) - 127
+
+
+def row_exponents(w):
+    """s[n] = clamp(ceil(log2(amax[n] / 448)), -15, 7) as int32 [N]; 0 for an all-zero row. No division: with amax = 1.f · 2^E,
+    amax <= 448 · 2^s = 1.75 · 2^(8 + s)  ⇔  s >= E - 8 (fraction <= .75) or s >= E - 7 (fraction > .75)."""
+    amax = w.detach().abs().amax(dim=1).to(torch.float32).contiguous()
+    bits = amax.view(torch.int32)
+    s = _exponent(amax) - 8 + ((bits & 0x7fffff) > 0x600000).to(torch.int32)
+    s = s.clamp(S_MIN, S_MAX)
+    return torch.where(amax == 0, torch.zeros_like(s), s)
+
+
+def encode_e4m3(v):
+    """fp32 tensor → e4m3fn codes (uint8): clamp to ±448, round to nearest even. Bit-identical to
+    ``v.clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8)`` for every finite input, -0 included."""
+    v = v.to(torch.float32)
+    a = v.abs().clamp(max=FP8_MAX)
+    e = _exponent(a).clamp(min=-6)                       # normal codes: 2^e <= a < 2^(e+1), quantum 2^(e-3); subnormal: quantum 2^-9
+    y = torch.round(a * _pow2(3 - e))                    # 0 .. 16 in units of the quantum (torch.round = half to even); 16 = next binade
+    # code = (e + 6) · 8 + y: subnormals (e = -6) y = 0..7 → codes 0..7, y = 8 → code 8 = 2^-6; normals y = 8 + mantissa; y = 16 carries
+    code = (e + 6) * 8 + y.to(torch.int32)
+    code = torch.where(a == 0, torch.zeros_like(code), code)
+    code = code | (torch.signbit(v).to(torch.int32) << 7)
+    return code.to(torch.uint8)
+
+
+def decode_table(device=None):
+    """fp32 [256]: the value of every e4m3fn code (0x7f / 0xff = NaN)."""
+    c = torch.arange(256, dtype=torch.int32, device=device)
+    e, m = (c >> 3) & 15, (c & 7).to(torch.float32)
+    val = torch.where(e == 0, m * 2.0 ** -9, (8.0 + m) * _pow2(e - 10))
+    val = torch.where((c & 0x7f) == 0x7f, torch.full_like(val, float("nan")), val)
+    return torch.where((c & 0x80) != 0, -val, val)
+
+
+def quantize_rows(w):
+    """16-bit (or fp32) W[N, K] → (codes uint8 [N, K], scale fp32 [N] = 2^s)."""
+    assert w.dim() == 2
+    s = row_exponents(w)
+    codes = encode_e4m3(w.detach().to(torch.float32) * _pow2(-s)[:, None])
+    return codes, _pow2(s)
+
+
+def dequantize_rows(codes, scale, dtype=torch.float32):
+    """codes uint8 [N, K], scale fp32 [N] → decode(code) · scale in ``dtype`` (exact in fp16 / bf16 for quantize_rows' scales)."""
+    assert codes.dtype == torch.uint8 and codes.dim() == 2 and scale.shape == (codes.shape[0],)
+    val = torch.index_select(decode_table(codes.device), 0, codes.reshape(-1).to(torch.int32)).view(codes.shape)
+    return (val * scale.to(torch.float32)[:, None]).to(dtype)
+
+
+def quantize_llama_layer(sd, prefix, dtype, device=None):
+    """The seven projection matrices of one decoder layer (FULL matrices: after the LoRA merge, before any tensor-parallel slicing) →
+    {key: (codes, scale, dequantised weight in ``dtype``)}. The checkpoint value is first rounded to ``dtype`` — what the 16-bit model
+    would have held."""
+    out = {}
+    for n in LLAMA_PROJECTIONS:
+        k = prefix + n + ".weight"
+        w = sd[k].detach().to(device=device, dtype=dtype)
+        codes, scale = quantize_rows(w)
+        out[k] = (codes, scale, dequantize_rows(codes, scale, dtype))
+    return out
+
+
+def quantize_llama_state_dict(sd, cfg, dtype=torch.float16):
+    """→ (state dict with the seven projection matrices of every layer replaced by their dequantised values, {key: codes}, {key: scale}).
+    Embedding, norms and lm_head stay as they are. ``cfg``: dict or config object with num_hidden_layers."""
+    L = cfg["num_hidden_layers"] if isinstance(cfg, dict) else cfg.num_hidden_layers
+    out, codes, scales = dict(sd), {}, {}
+    for i in range(L):
+        for k, (c, s, w) in quantize_llama_layer(sd, f"model.layers.{i}.", dtype).items():
+            out[k], codes[k], scales[k] = (w.float() if sd[k].dtype == torch.float32 else w), c, s   # (exact either way)
+    return out, codes, scales
+
+
+def llama_tp_shard_scales(scales, layer_prefix, rank, tp, nh, hd):
+    """Rank ``rank``'s row scales of one layer, keyed like parallel.llama_tp_shard: the row-sharded q / k / v / gate / up slice theirs,
+    the column-sharded o / down keep every row (each rank holds columns of ALL rows) — the ranks hold slices of ONE quantised model."""
+    hl = nh // tp * hd
+    hs = slice(rank * hl, (rank + 1) * hl)
+    p = layer_prefix
+    il = scales[p + "mlp.gate_proj.weight"].shape[0] // tp
+    isl = slice(rank * il, (rank + 1) * il)
+    return {"q": scales[p + "self_attn.q_proj.weight"][hs], "k": scales[p + "self_attn.k_proj.weight"][hs],
+            "v": scales[p + "self_attn.v_proj.weight"][hs], "o": scales[p + "self_attn.o_proj.weight"],
+            "gate": scales[p + "mlp.gate_proj.weight"][isl], "up": scales[p + "mlp.up_proj.weight"][isl],
+            "down": scales[p + "mlp.down_proj.weight"]}
