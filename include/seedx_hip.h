@@ -444,6 +444,16 @@ int sx_rope_kv_append_f32(float* qkv, float* kcache, float* vcache, const float*
 int sx_rope_kv_append_f32_v16(float* qkv, float* kcache, void* vcache16, const float* cos_tab, const float* sin_tab,
                               const int32_t* pos0_dev, int G, int T, int H, int D, int Tmax, int64_t cache_seq_stride,
                               int table_dtype, void* stream);
+/* the same with the FP8 KV cache (LlamaForCausalLM(kv_format="fp8_e4m3"), head_dim 128 only): the rotated k row and the v row of every
+ * (token, head) are quantised to OCP e4m3fn codes with ONE power-of-two scale per row — s = clamp(ceil(log2(amax / 448)), -64, 64), 0 for a
+ * zero row, code = e4m3fn(rne(clamp(x * 2^-s, +-448))), never a NaN code (seedx_amd.quant.quantize_kv_rows states the rule on the host, bit
+ * for bit) — and appended to kcodes / vcodes uint8 [G][H][Tmax][128] (sequences cache_seq_stride BYTES apart) and kscale / vscale fp32
+ * [G][H][Tmax] (sequences scale_seq_stride floats apart): 264 B per (head, token) instead of 768. q is rotated in place.
+ * emulate = 1, the bit-reference twin: kcodes / vcodes are the FP32 caches of sx_rope_kv_append_f32 (cache_seq_stride in floats) and
+ * receive decode(code) * 2^s; the scale pointers are unused (NULL). Positions outside [0, Tmax) write nothing. */
+int sx_rope_kv_append_f32_q8(float* qkv, void* kcodes, void* vcodes, float* kscale, float* vscale, const float* cos_tab,
+                             const float* sin_tab, const int32_t* pos0_dev, int G, int T, int H, int D, int Tmax,
+                             int64_t cache_seq_stride, int64_t scale_seq_stride, int table_dtype, int emulate, void* stream);
 /* Causal attention of a T-token chunk per sequence over the fp32 cache, fp32 FMA arithmetic and softmax
  * (modeling_llama_xformer.py:204-239: prefill causal, q_len == 1 sees the whole cache): row t sees keys 0 .. pos0[g] + t.
  * Device-resident positions → graph-capturable for the decode step (T = 1). Output = the planes of the context rows [G*T][H*D].
@@ -472,6 +482,16 @@ typedef struct sx_attn_f32_args {
   const float* rope_sin;
   const float* k_new;
   const float* v_new;
+  /* FP8 KV cache (head_dim 128, causal, the cache layout; excludes v16). 0 (default, also a zero-initialised struct): off.
+   * 1: kcache / vcache hold e4m3fn codes (uint8, the same ELEMENT strides) and k_scale / v_scale one power-of-two fp32 scale per key row
+   *    [G][H][Tmax], sequences scale_seq_stride floats apart; the result equals, bit for bit, the fp32 call on a cache holding
+   *    decode(code) * scale. In the fused RoPE form the new token's rows are quantised (sx_rope_kv_append_f32_q8's rule) and appended.
+   * 2: meaningful in the fused RoPE form only — fp32 caches, the new token's k / v stored (and attended to) as their quantised and
+   *    dequantised values: the bit-reference twin of 1. Without rope_cos it is the plain fp32 call. */
+  int32_t kv_fp8;
+  const float* k_scale;
+  const float* v_scale;
+  int64_t scale_seq_stride;
 } sx_attn_f32_args;
 int sx_attention_f32(const sx_attn_f32_args* args, void* stream);
 /* tuning / test hook: 1 (default) = causal chunks above 8 tokens at head_dim 128 run on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32)

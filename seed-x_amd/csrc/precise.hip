@@ -6,6 +6,9 @@
 //     K twice over the same weight tiles, sx_gemv x_planes = 2 feeds every weight fragment to two MFMAs — no extra weight bytes;
 //   * q, k, v never become 16-bit: the qkv GEMM stores fp32, RoPE runs in fp32 into an fp32 KV cache (rope_kv_f32_kernel), and
 //     attention (attn_f32_kernel) is fp32 FMA work — T <= a few hundred keys per head on this path, 1 % of the LLM's FLOPs.
+//   * opt-in, lossy: the FP8 (e4m3) KV cache (kv_format="fp8_e4m3") — k after RoPE and v rounded ONCE, at append, to 128 codes + one
+//     power-of-two scale per (token, head) row (quant_row8); attention reads the codes and computes, bit for bit, what the fp32 kernels
+//     compute on a cache holding the dequantised values (KV8 template arguments below).
 // This file holds the kernels that only exist for that mode. It is compiled WITHOUT -ffast-math (csrc/build.sh): x - float(rn16(x))
 // and the softmax bookkeeping must not be re-associated.
 // Reference being matched: modeling_llama_xformer.py:95 (RMSNorm), :141-149 (RoPE), :204-239 (attention), run by the fp32 oracle.
@@ -143,6 +146,127 @@ __global__ void rope_kv_f32_kernel(float* qkv, float* kc, void* vc_, const float
   }
 }
 
+// ---- FP8 (e4m3fn) KV cache: LlamaForCausalLM(kv_format="fp8_e4m3") -----------------------------------------------------------------
+// The ONE quantiser of every append path (quant.py quantize_kv_rows is its host statement). A 16-lane group owns a row of D = 128 values,
+// lane dl the dims 8 dl .. 8 dl + 7 (the mapping of attn_f32_kernel's fused RoPE block). Row amax by four xor shuffles; s = ceil(log2(amax
+// / 448)) from the float's exponent and mantissa bits, clamped to [-64, 64], 0 for a zero row; x · 2^-s is exact; clamp to +-448;
+// v_cvt_pk_fp8_f32 rounds to nearest even (gfx950 FP8 is OCP e4m3fn). Returns the lane's 8 codes and the row's 2^s.
+__device__ __forceinline__ void quant_row8(const float (&x)[8], u32x2_t& codes, float& scale) {
+  float am = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) am = fmaxf(am, fabsf(x[e]));
+  am = fmaxf(am, __shfl_xor(am, 1, 64));
+  am = fmaxf(am, __shfl_xor(am, 2, 64));
+  am = fmaxf(am, __shfl_xor(am, 4, 64));
+  am = fmaxf(am, __shfl_xor(am, 8, 64));
+  const unsigned bits = __float_as_uint(am);
+  int s = (int)((bits >> 23) & 0xffu) - 127 - 8 + ((bits & 0x7fffffu) > 0x600000u ? 1 : 0);
+  s = min(64, max(-64, s));
+  if (am == 0.f) s = 0;
+  const float inv = __uint_as_float((unsigned)(127 - s) << 23);
+  scale = __uint_as_float((unsigned)(127 + s) << 23);
+  float y[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) y[e] = __builtin_amdgcn_fmed3f(x[e] * inv, -448.f, 448.f);
+#if defined(__HIP_DEVICE_COMPILE__)
+  int w0 = 0, w1 = 0;
+  w0 = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], w0, false);
+  w0 = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], w0, true);
+  w1 = __builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], w1, false);
+  w1 = __builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], w1, true);
+  codes[0] = (unsigned)w0;
+  codes[1] = (unsigned)w1;
+#endif
+}
+
+// 8 e4m3fn codes → their fp32 values (exact)
+__device__ __forceinline__ void decode8(const u32x2_t w, float* f) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false);
+    const auto b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
+    f[4 * i] = a[0]; f[4 * i + 1] = a[1]; f[4 * i + 2] = b[0]; f[4 * i + 3] = b[1];
+  }
+#endif
+}
+
+// quant_row8, and x REPLACED by the dequantised values decode(code) · 2^s (exact): what the cache will give back, so a value attended to
+// from registers equals the one read later
+__device__ __forceinline__ void quant_dequant_row8(float (&x)[8], u32x2_t& codes, float& scale) {
+  quant_row8(x, codes, scale);
+  decode8(codes, x);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) x[e] *= scale;
+}
+
+// rope_kv_f32_kernel with the FP8 cache (D = 128): one 16-lane group per (sequence, token, head) row. q is rotated in place; the rotated
+// k row and the v row are quantised and appended as codes [G][H][Tmax][128] + one fp32 scale per row [G][H][Tmax] (EMUL: as their
+// dequantised fp32 values into fp32 caches, the bit-reference twin). A position outside [0, Tmax) writes nothing.
+template <typename TT, bool EMUL>
+__global__ __launch_bounds__(256) void rope_kv_q8_kernel(float* qkv, void* kc_, void* vc_, float* ks, float* vs, const float* cos_t,
+                                                         const float* sin_t, const int* pos0_dev, int T, int H, int Tmax, int G,
+                                                         long long seq_stride, long long sc_seq_stride) {
+  constexpr int D = 128, half = 64;
+  const long long rows = (long long)G * T * H;
+  const int dl = threadIdx.x & 15;
+  const long long r_ = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
+  const bool valid = r_ < rows;                       // uniform over the 16-lane group
+  const long long rr = valid ? r_ : rows - 1;
+  const int h = (int)(rr % H);
+  const long long r = rr / H;                         // qkv row = g*T + t
+  const int g = (int)(r / T), t = (int)(r - (long long)g * T);
+  const int praw = pos0_dev[g] + t;
+  const bool pos_ok = praw >= 0 && praw < Tmax;
+  const int pt = pos_ok ? praw : 0;
+  const int jb = (dl & 7) * 8;
+  float* row = qkv + (size_t)r * 3 * H * D;
+  float* qo = row + (size_t)h * D + dl * 8;
+  const float* ko = row + (size_t)(H + h) * D + dl * 8;
+  const float* vo = row + (size_t)(2 * H + h) * D + dl * 8;
+  const f32x4_t q0 = *(const f32x4_t*)qo, q1 = *(const f32x4_t*)(qo + 4);
+  const f32x4_t k0 = *(const f32x4_t*)ko, k1 = *(const f32x4_t*)(ko + 4);
+  const f32x4_t v0 = *(const f32x4_t*)vo, v1 = *(const f32x4_t*)(vo + 4);
+  const float qa[8] = {q0[0], q0[1], q0[2], q0[3], q1[0], q1[1], q1[2], q1[3]};
+  const float ka[8] = {k0[0], k0[1], k0[2], k0[3], k1[0], k1[1], k1[2], k1[3]};
+  float va[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+  const float sg = (dl < 8) ? -1.0f : 1.0f;           // first half: x1 c - x2 s; second half: x2 c + x1 s
+  float qr[8], kr[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float c = TT::to_f32(TT::from_f32(cos_t[(size_t)pt * half + jb + e]));
+    const float s = TT::to_f32(TT::from_f32(sin_t[(size_t)pt * half + jb + e]));
+    const float qp = __shfl_xor(qa[e], 8, 64), kp = __shfl_xor(ka[e], 8, 64);   // the rotation partner's dims: lane dl ^ 8
+    qr[e] = qa[e] * c + sg * (qp * s);
+    kr[e] = ka[e] * c + sg * (kp * s);
+  }
+  u32x2_t kcod, vcod;
+  float ksc, vsc;
+  quant_dequant_row8(kr, kcod, ksc);
+  quant_dequant_row8(va, vcod, vsc);
+  if (!valid) return;
+  *(f32x4_t*)qo = (f32x4_t){qr[0], qr[1], qr[2], qr[3]};
+  *(f32x4_t*)(qo + 4) = (f32x4_t){qr[4], qr[5], qr[6], qr[7]};
+  if (!pos_ok) return;                                // a device-resident position past the cache never writes outside it
+  const size_t ro = (size_t)g * seq_stride + ((size_t)h * Tmax + praw) * D + dl * 8;
+  if constexpr (EMUL) {
+    float* kd = (float*)kc_ + ro;
+    float* vd = (float*)vc_ + ro;
+    *(f32x4_t*)kd = (f32x4_t){kr[0], kr[1], kr[2], kr[3]};
+    *(f32x4_t*)(kd + 4) = (f32x4_t){kr[4], kr[5], kr[6], kr[7]};
+    *(f32x4_t*)vd = (f32x4_t){va[0], va[1], va[2], va[3]};
+    *(f32x4_t*)(vd + 4) = (f32x4_t){va[4], va[5], va[6], va[7]};
+  } else {
+    *(u32x2_t*)((unsigned char*)kc_ + ro) = kcod;
+    *(u32x2_t*)((unsigned char*)vc_ + ro) = vcod;
+    if (dl == 0) {
+      const size_t so = (size_t)g * sc_seq_stride + (size_t)h * Tmax + praw;
+      ks[so] = ksc;
+      vs[so] = vsc;
+    }
+  }
+}
+
 // Causal attention over the fp32 cache, fp32 FMA arithmetic (modeling_llama_xformer.py:204-239: prefill is causal, a q_len == 1 step
 // sees the whole cache — both are "row t of the chunk sees keys 0 .. pos0 + t"). Workgroup = (QB query rows of the chunk, head,
 // sequence), 16 groups of 16 lanes: a group owns keys grp, grp + 16, ...; a lane owns 8 of the D <= 128 head dims; every key row is
@@ -168,6 +292,11 @@ struct AttnF32P {
   const float* sin_t;
   const float* knew;
   const float* vnew;
+  // FP8 cache (KV8 = 1 kernels): kc / vc hold e4m3fn codes with the SAME element strides, ks / vs one fp32 power-of-two scale per key row,
+  // [G][H][Tmax] with sequences sc_seq_stride floats apart
+  const float* ks;
+  const float* vs;
+  long long sc_seq_stride;
 };
 
 // QB query rows per workgroup: 4 for the decode step and short chunks, 8 for prefill (every key row is loaded once per QB rows: the
@@ -177,10 +306,19 @@ struct AttnF32P {
 // 4 sequences x 40 heads = 160 workgroups on 256 CUs, each walking 1.5k keys in 94 dependent iterations) is latency-bound, not
 // byte-bound; with the keys of a head spread over nsplit workgroups the walk is nsplit times shorter and the chip is full. Every split
 // writes (sum of p v, running max, sum of p) to `part`, attn_f32_combine_kernel merges them in split order (deterministic).
-template <typename TT, int QB, int DC, bool V16 = false, bool SPLIT = false>
+// KV8 (the FP8 cache, D = 128): 1 = k and v are e4m3fn codes with one power-of-two scale per key row: 8 code bytes per lane and key row
+// each, decoded exactly (v_cvt_pk_f32_fp8). The k scale multiplies the finished score (one multiply per query row instead of eight per key
+// row) and the v scale the decoded values: a power of two commutes with every fp32 rounding of the fma chains as long as nothing leaves
+// the normal range — the scores and v · 2^s do not (s in [-64, 64]); a probability times 2^s could, so p is never scaled. The result is,
+// bit for bit, the KV8 = 0 kernel's on a cache holding the dequantised values. 2 = the bit-reference twin of the fused RoPE form: fp32
+// caches, the new token's k / v quantised and dequantised on append. In both, the new token's own key / value (attended to from
+// registers) are the dequantised values — the reason vnew is rounded under V16.
+template <typename TT, int QB, int DC, bool V16 = false, bool SPLIT = false, int KV8 = 0>
 __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnF32P p) {
   constexpr int DW = 8 * DC, DMAX = 128 * DC;
   static_assert(!SPLIT || (QB == 1 && DC == 1), "key splits: the single-row decode form");
+  static_assert(KV8 == 0 || (DC == 1 && !V16), "the FP8 cache: head_dim 128, no 16-bit v");
+  static_assert(KV8 != 2 || QB == 1, "KV8 = 2 only differs in the fused RoPE form");
   __shared__ float red[4][QB][DMAX + 4];
   const int q0 = SPLIT ? 0 : blockIdx.x * QB, h = blockIdx.y, g = blockIdx.z, D = p.D;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -208,8 +346,11 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnF32P p) {
       }
     }
   }
-  const float* kh = p.kc + (size_t)g * p.seq_stride + (size_t)h * p.head_stride;
+  const float* kh = p.kc + (size_t)g * p.seq_stride + (size_t)h * p.head_stride;       // (KV8 = 1: unused, see kc8)
   const size_t vbase = (size_t)g * p.seq_stride + (size_t)h * p.head_stride;
+  const unsigned char* kc8 = (const unsigned char*)p.kc + vbase;                        // KV8 = 1: codes, same element strides
+  const unsigned char* vc8 = (const unsigned char*)p.vc + vbase;
+  const size_t sbase = (size_t)g * p.sc_seq_stride + (size_t)h * p.Tmax;                // KV8 = 1: the row scales of this (sequence, head)
   int kend = min(p.Tmax, pos0 + q0 + nq);       // keys 0 .. kend-1 are visible to the block's last row
   int kbeg = 0;
   int chunk = kend;
@@ -246,20 +387,35 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnF32P p) {
         knew[e] = ko[e] * cs[e] + sg * (kp[e] * sn[e]);
         vnew[e] = V16 ? TT::to_f32(TT::from_f32(vo[e])) : vo[e];
       }
+      u32x2_t kcod, vcod;
+      float ksc, vsc;
+      if constexpr (KV8 != 0) {                       // every group holds the whole row: all of them quantise (uniform shuffles)
+        quant_dequant_row8(knew, kcod, ksc);
+        quant_dequant_row8(vnew, vcod, vsc);
+      }
       own_new = pos_ok && (SPLIT ? (praw / chunk == (int)blockIdx.x) : true);
       if (own_new && grp == 0) {                      // append: one 16-lane group covers the 128 dims
-        float* kd = const_cast<float*>(kh) + (size_t)praw * p.row_stride + dl * 8;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) kd[e] = knew[e];
         const size_t vo_c = vbase + (size_t)praw * p.row_stride + dl * 8;
-        if constexpr (V16) {
-          unsigned short* vd = (unsigned short*)const_cast<void*>(p.vc) + vo_c;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) vd[e] = TT::from_f32(vo[e]);
+        if constexpr (KV8 == 1) {                     // codes: one 8-byte store per lane, one lane stores the two scales
+          *(u32x2_t*)(const_cast<unsigned char*>(kc8) + (size_t)praw * p.row_stride + dl * 8) = kcod;
+          *(u32x2_t*)(const_cast<unsigned char*>(vc8) + (size_t)praw * p.row_stride + dl * 8) = vcod;
+          if (dl == 0) {
+            const_cast<float*>(p.ks)[sbase + praw] = ksc;
+            const_cast<float*>(p.vs)[sbase + praw] = vsc;
+          }
         } else {
-          float* vd = (float*)const_cast<void*>(p.vc) + vo_c;
+          float* kd = const_cast<float*>(kh) + (size_t)praw * p.row_stride + dl * 8;
 #pragma unroll
-          for (int e = 0; e < 8; ++e) vd[e] = vo[e];
+          for (int e = 0; e < 8; ++e) kd[e] = knew[e];
+          if constexpr (V16) {
+            unsigned short* vd = (unsigned short*)const_cast<void*>(p.vc) + vo_c;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) vd[e] = TT::from_f32(vo[e]);
+          } else {
+            float* vd = (float*)const_cast<void*>(p.vc) + vo_c;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) vd[e] = KV8 == 2 ? vnew[e] : vo[e];     // (KV8 = 2: the dequantised row)
+          }
         }
       }
       if (pos_ok) kend = min(kend, praw);             // the cache rows below pos; the new key comes from registers
@@ -267,11 +423,22 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnF32P p) {
   }
   for (int t = kbeg + grp; t < kend; t += 16) {
     float kf[DW], vf[DW];
+    float ksc = 1.f;
 #pragma unroll
     for (int e = 0; e < DW; ++e) { kf[e] = 0.f; vf[e] = 0.f; }
+    if constexpr (KV8 == 1) {
+      const u32x2_t kw = *(const u32x2_t*)(kc8 + (size_t)t * p.row_stride + dl * 8);
+      const u32x2_t vw = *(const u32x2_t*)(vc8 + (size_t)t * p.row_stride + dl * 8);
+      ksc = p.ks[sbase + t];
+      const float vsc = p.vs[sbase + t];
+      decode8(kw, kf);
+      decode8(vw, vf);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) vf[e] *= vsc;
+    }
 #pragma unroll
     for (int c = 0; c < DC; ++c) {
-      if (dvalid[c]) {
+      if (KV8 != 1 && dvalid[c]) {
         const float* kr = kh + (size_t)t * p.row_stride + c * 128 + dl * 8;
         const size_t vo = vbase + (size_t)t * p.row_stride + c * 128 + dl * 8;
         const f32x4_t k0 = *(const f32x4_t*)kr, k1 = *(const f32x4_t*)(kr + 4);
@@ -301,6 +468,7 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnF32P p) {
       s += __shfl_xor(s, 2, 64);
       s += __shfl_xor(s, 4, 64);
       s += __shfl_xor(s, 8, 64);
+      if constexpr (KV8 == 1) s *= ksc;
       if (i < nq && t <= pos0 + q0 + i) {               // uniform over the 16-lane group
         const float m_new = fmaxf(m_run[i], s);
         const float alpha = __expf(m_run[i] - m_new);   // exp(-inf) = 0 on the first key
@@ -447,7 +615,10 @@ __global__ __launch_bounds__(128) void attn_f32_combine_kernel(const AttnF32P p)
 //     4 CONSECUTIVE head dims of its query row → 8-byte plane stores.
 // D = 128 only (the decoder's head_dim); everything else keeps the VALU kernel.
 typedef float f32x16v_t __attribute__((ext_vector_type(16)));
-template <typename TT, bool V16>
+// KV8 (the FP8 cache): the K tile is 64 code bytes of the lane's half row (four 16-byte loads), a V step 4 code bytes; the k scale
+// multiplies the key's score row, the v scale the decoded operand (exact, see attn_f32_kernel) — the same bits as the fp32 kernel on the
+// dequantised cache.
+template <typename TT, bool V16, bool KV8 = false>
 __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const AttnF32P p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int D = 128;
@@ -473,6 +644,9 @@ __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const AttnF32P p) {
   }
   const float* kh = p.kc + (size_t)g * p.seq_stride + (size_t)h * p.head_stride;
   const size_t vbase = (size_t)g * p.seq_stride + (size_t)h * p.head_stride;
+  const unsigned char* kc8 = (const unsigned char*)p.kc + vbase;                        // KV8: codes, same element strides
+  const unsigned char* vc8 = (const unsigned char*)p.vc + vbase;
+  const size_t sbase = (size_t)g * p.sc_seq_stride + (size_t)h * p.Tmax;                // KV8: the row scales of this (sequence, head)
   f32x16v_t o[4];
 #pragma unroll
   for (int b = 0; b < 4; ++b)
@@ -489,13 +663,33 @@ __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const AttnF32P p) {
     f32x16v_t sacc;
 #pragma unroll
     for (int j = 0; j < 16; ++j) sacc[j] = 0.f;
-    f32x4_t kq[16];
+    if constexpr (KV8) {                                         // decoded four values at a time, right in front of their MFMAs: the tile
+      const unsigned char* kr8 = kc8 + (size_t)kr_ * p.row_stride + half * 64;      // lives in 16 registers of codes, not 64 of floats
+      u32x4_t kw[4];
 #pragma unroll
-    for (int e = 0; e < 16; ++e) kq[e] = *(const f32x4_t*)(kr + 4 * e);
+      for (int e = 0; e < 4; ++e) kw[e] = *(const u32x4_t*)(kr8 + 16 * e);
 #pragma unroll
-    for (int e = 0; e < 16; ++e)
+      for (int e = 0; e < 16; ++e) {
+        const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)kw[e >> 2][e & 3], false);
+        const auto b = __builtin_amdgcn_cvt_pk_f32_fp8((int)kw[e >> 2][e & 3], true);
+        sacc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[0], qv[4 * e], sacc, 0, 0, 0);
+        sacc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[1], qv[4 * e + 1], sacc, 0, 0, 0);
+        sacc = __builtin_amdgcn_mfma_f32_32x32x2f32(b[0], qv[4 * e + 2], sacc, 0, 0, 0);
+        sacc = __builtin_amdgcn_mfma_f32_32x32x2f32(b[1], qv[4 * e + 3], sacc, 0, 0, 0);
+      }
+    } else {
+      f32x4_t kq[16];
 #pragma unroll
-      for (int c = 0; c < 4; ++c) sacc = __builtin_amdgcn_mfma_f32_32x32x2f32(kq[e][c], qv[4 * e + c], sacc, 0, 0, 0);
+      for (int e = 0; e < 16; ++e) kq[e] = *(const f32x4_t*)(kr + 4 * e);
+#pragma unroll
+      for (int e = 0; e < 16; ++e)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) sacc = __builtin_amdgcn_mfma_f32_32x32x2f32(kq[e][c], qv[4 * e + c], sacc, 0, 0, 0);
+    }
+    if constexpr (KV8) {                                         // score row j belongs to key k0 + 8 (j >> 2) + 4 half + (j & 3)
+#pragma unroll
+      for (int j = 0; j < 16; ++j) sacc[j] *= p.ks[sbase + min(k0 + (j >> 2) * 8 + half * 4 + (j & 3), p.Tmax - 1)];
+    }
     // ---- online softmax of the lane's column (16 local keys + the partner's 16) ----
     float mx = -INFINITY;
 #pragma unroll
@@ -527,7 +721,13 @@ __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const AttnF32P p) {
       const int key = min(k0 + (t >> 2) * 8 + half * 4 + (t & 3), p.Tmax - 1);
       const size_t vo = vbase + (size_t)key * p.row_stride + 4 * l32;
       float vv[4];
-      if constexpr (V16) {
+      if constexpr (KV8) {
+        const unsigned w = *(const unsigned*)(vc8 + (size_t)key * p.row_stride + 4 * l32);
+        const float vsc = p.vs[sbase + key];
+        const auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+        const auto b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+        vv[0] = a[0] * vsc; vv[1] = a[1] * vsc; vv[2] = b[0] * vsc; vv[3] = b[1] * vsc;
+      } else if constexpr (V16) {
         const u32x2_t w = *(const u32x2_t*)((const unsigned short*)p.vc + vo);
         vv[0] = TT::to_f32((unsigned short)(w[0] & 0xffffu)); vv[1] = TT::to_f32((unsigned short)(w[0] >> 16));
         vv[2] = TT::to_f32((unsigned short)(w[1] & 0xffffu)); vv[3] = TT::to_f32((unsigned short)(w[1] >> 16));
@@ -630,6 +830,30 @@ extern "C" int sx_rope_kv_append_f32_v16(float* qkv, float* kcache, void* vcache
   return rope_kv_f32_impl(qkv, kcache, vcache16, 1, cos_tab, sin_tab, pos0_dev, G, T, H, D, Tmax, cache_seq_stride, table_dtype, stream);
 }
 
+extern "C" int sx_rope_kv_append_f32_q8(float* qkv, void* kcodes, void* vcodes, float* kscale, float* vscale, const float* cos_tab,
+                                        const float* sin_tab, const int32_t* pos0_dev, int G, int T, int H, int D, int Tmax,
+                                        int64_t cache_seq_stride, int64_t scale_seq_stride, int table_dtype, int emulate, void* stream) {
+  SX_CHECK(qkv && kcodes && vcodes && cos_tab && sin_tab && pos0_dev, "sx_rope_kv_append_f32_q8: null pointer");
+  SX_CHECK(D == 128, "sx_rope_kv_append_f32_q8: head_dim %d (the FP8 KV cache exists for head_dim 128 only)", D);
+  SX_CHECK(G >= 1 && T >= 1 && H >= 1 && Tmax >= 1, "sx_rope_kv_append_f32_q8: G/T/H/Tmax");
+  SX_CHECK(table_dtype == SX_F16 || table_dtype == SX_BF16, "sx_rope_kv_append_f32_q8: table_dtype");
+  SX_CHECK(emulate == 0 || emulate == 1, "sx_rope_kv_append_f32_q8: emulate must be 0 (codes + scales) or 1 (dequantised values into fp32 caches)");
+  SX_CHECK(emulate || (kscale && vscale && (((uintptr_t)kscale) & 3) == 0 && (((uintptr_t)vscale) & 3) == 0 && scale_seq_stride >= (int64_t)H * Tmax),
+           "sx_rope_kv_append_f32_q8: kscale / vscale (fp32 [G][H][Tmax], scale_seq_stride >= H*Tmax) are missing or misaligned");
+  SX_CHECK((((uintptr_t)qkv) & 15) == 0 && (((uintptr_t)kcodes) & 15) == 0 && (((uintptr_t)vcodes) & 15) == 0 && cache_seq_stride % 8 == 0 &&
+           cache_seq_stride >= (int64_t)H * Tmax * D, "sx_rope_kv_append_f32_q8: qkv / cache pointers and cache_seq_stride must keep 16-B alignment");
+  const int64_t rows = (int64_t)G * T * H;
+  const dim3 grid((unsigned)((rows + 15) / 16));
+#define SX_ROPE_Q8_GO(TT, EM)                                                                                                          \
+  hipLaunchKernelGGL((rope_kv_q8_kernel<TT, EM>), grid, dim3(256), 0, ST, qkv, kcodes, vcodes, kscale, vscale, cos_tab, sin_tab, pos0_dev, T, \
+                     H, Tmax, G, (long long)cache_seq_stride, (long long)scale_seq_stride)
+  if (table_dtype == SX_BF16) { if (emulate) SX_ROPE_Q8_GO(BF16, true); else SX_ROPE_Q8_GO(BF16, false); }
+  else { if (emulate) SX_ROPE_Q8_GO(F16, true); else SX_ROPE_Q8_GO(F16, false); }
+#undef SX_ROPE_Q8_GO
+  SX_HIP_LAUNCH_CHECK();
+  return SX_OK;
+}
+
 static int g_attn_f32_mfma = 1;    // 0: chunks above 8 tokens keep the VALU kernel (A/B and the bit-reference of the tests)
 extern "C" int sx_attention_f32_variant(int v) {
   SX_CHECK(v == 0 || v == 1, "sx_attention_f32_variant: 0 (VALU kernels only) or 1 (fp32 MFMA kernel for chunks above 8 tokens)");
@@ -656,6 +880,21 @@ extern "C" int sx_attention_f32(const sx_attn_f32_args* a, void* stream) {
   p.T = a->T; p.H = a->H; p.D = a->D; p.Tmax = a->Tmax; p.tiled = tiled; p.scale = a->scale; p.causal = a->causal ? 1 : 0;
   p.part = a->scratch; p.nsplit = a->nsplit;
   p.cos_t = a->rope_cos; p.sin_t = a->rope_sin; p.knew = a->k_new; p.vnew = a->v_new;
+  p.ks = a->k_scale; p.vs = a->v_scale; p.sc_seq_stride = a->scale_seq_stride;
+  // the FP8 KV cache: 1 = codes + row scales, 2 = fp32 caches with quantise-dequantise on append (only the fused RoPE form appends:
+  // without it 2 IS the fp32 call, on a cache that already holds dequantised values)
+  SX_CHECK(a->kv_fp8 >= 0 && a->kv_fp8 <= 2, "sx_attention_f32: kv_fp8 must be 0 (off), 1 (e4m3 codes + row scales) or 2 (fp32 caches, quantise-dequantise on append)");
+  const int kv8 = (a->kv_fp8 == 2 && !a->rope_cos) ? 0 : a->kv_fp8;
+  if (a->kv_fp8) {
+    SX_CHECK(a->D == 128, "sx_attention_f32: kv_fp8 needs head_dim 128, not %d", a->D);
+    SX_CHECK(!a->v16, "sx_attention_f32: kv_fp8 and v16 exclude each other (the FP8 cache holds k AND v as codes)");
+    SX_CHECK(a->causal && a->kv_row_stride <= 0 && a->kv_head_stride <= 0, "sx_attention_f32: kv_fp8 is the causal form over the cache layout (no K / V strides)");
+  }
+  if (kv8 == 1) {
+    SX_CHECK(a->k_scale && a->v_scale && (((uintptr_t)a->k_scale) & 3) == 0 && (((uintptr_t)a->v_scale) & 3) == 0 &&
+             a->scale_seq_stride >= (int64_t)a->H * a->Tmax, "sx_attention_f32: kv_fp8 = 1 needs k_scale / v_scale (fp32 [G][H][Tmax], 4-B aligned, scale_seq_stride >= H*Tmax)");
+    SX_CHECK(p.seq_stride % 16 == 0, "sx_attention_f32: kv_fp8 = 1 needs cache_seq_stride %% 16 == 0 (16-B aligned code rows)");
+  }
   if (a->rope_cos) {
     SX_CHECK(a->T == 1 && a->causal && a->D == 128 && a->rope_sin && a->k_new && a->v_new && a->kv_row_stride <= 0 + (int64_t)a->D,
              "sx_attention_f32: the fused RoPE form is the T = 1 causal step at head_dim 128 over the cache layout (rope_sin, k_new, v_new set)");
@@ -668,9 +907,15 @@ extern "C" int sx_attention_f32(const sx_attn_f32_args* a, void* stream) {
     p.vc = a->vcache;
     const dim3 grid(a->nsplit, a->H, a->G);
 #define SX_SPLIT_GO(TT, V16) hipLaunchKernelGGL((attn_f32_kernel<TT, 1, 1, V16, true>), grid, dim3(256), 0, ST, p)
+#define SX_SPLIT8_GO(TT, KV8) hipLaunchKernelGGL((attn_f32_kernel<TT, 1, 1, false, true, KV8>), grid, dim3(256), 0, ST, p)
+    if (kv8) {
+      if (dt == SX_BF16) { if (kv8 == 1) SX_SPLIT8_GO(BF16, 1); else SX_SPLIT8_GO(BF16, 2); }
+      else { if (kv8 == 1) SX_SPLIT8_GO(F16, 1); else SX_SPLIT8_GO(F16, 2); }
+    } else
     if (dt == SX_BF16) { if (a->v16) SX_SPLIT_GO(BF16, true); else SX_SPLIT_GO(BF16, false); }
     else { if (a->v16) SX_SPLIT_GO(F16, true); else SX_SPLIT_GO(F16, false); }
 #undef SX_SPLIT_GO
+#undef SX_SPLIT8_GO
     SX_HIP_LAUNCH_CHECK();
     if (dt == SX_BF16) hipLaunchKernelGGL(attn_f32_combine_kernel<BF16>, dim3(a->H, a->G), dim3(128), 0, ST, p);
     else hipLaunchKernelGGL(attn_f32_combine_kernel<F16>, dim3(a->H, a->G), dim3(128), 0, ST, p);
@@ -682,7 +927,10 @@ extern "C" int sx_attention_f32(const sx_attn_f32_args* a, void* stream) {
   if (mfma) {
     p.vc = a->vcache;
     const dim3 grid((a->T + 127) / 128, a->H, a->G);
-    if (a->v16) {
+    if (kv8 == 1) {
+      if (dt == SX_BF16) hipLaunchKernelGGL((attn_f32_mfma_kernel<BF16, false, true>), grid, dim3(256), 0, ST, p);
+      else hipLaunchKernelGGL((attn_f32_mfma_kernel<F16, false, true>), grid, dim3(256), 0, ST, p);
+    } else if (a->v16) {
       SX_CHECK(p.row_stride % 8 == 0 && p.head_stride % 8 == 0 && p.seq_stride % 8 == 0, "sx_attention_f32: 16-bit V rows must be 16-B aligned");
       if (dt == SX_BF16) hipLaunchKernelGGL((attn_f32_mfma_kernel<BF16, true>), grid, dim3(256), 0, ST, p);
       else hipLaunchKernelGGL((attn_f32_mfma_kernel<F16, true>), grid, dim3(256), 0, ST, p);
@@ -690,6 +938,22 @@ extern "C" int sx_attention_f32(const sx_attn_f32_args* a, void* stream) {
       if (dt == SX_BF16) hipLaunchKernelGGL((attn_f32_mfma_kernel<BF16, false>), grid, dim3(256), 0, ST, p);
       else hipLaunchKernelGGL((attn_f32_mfma_kernel<F16, false>), grid, dim3(256), 0, ST, p);
     }
+    SX_HIP_LAUNCH_CHECK();
+    return SX_OK;
+  }
+  if (kv8) {
+    // the FP8 cache (1), or the fused RoPE form of its fp32 twin (2: T == 1 by the check above)
+#define SX_KV8_GO(TT, QB, KV8) hipLaunchKernelGGL((attn_f32_kernel<TT, QB, 1, false, false, KV8>), dim3((a->T + QB - 1) / QB, a->H, a->G), dim3(256), 0, ST, p)
+    if (kv8 == 2) {
+      if (dt == SX_BF16) SX_KV8_GO(BF16, 1, 2); else SX_KV8_GO(F16, 1, 2);
+    } else if (a->T > 8) {
+      if (dt == SX_BF16) SX_KV8_GO(BF16, 8, 1); else SX_KV8_GO(F16, 8, 1);
+    } else if (a->T == 1) {
+      if (dt == SX_BF16) SX_KV8_GO(BF16, 1, 1); else SX_KV8_GO(F16, 1, 1);
+    } else {
+      if (dt == SX_BF16) SX_KV8_GO(BF16, 4, 1); else SX_KV8_GO(F16, 4, 1);
+    }
+#undef SX_KV8_GO
     SX_HIP_LAUNCH_CHECK();
     return SX_OK;
   }

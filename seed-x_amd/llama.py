@@ -20,12 +20,26 @@ logits, past_key_values, hidden_states with the LAST entry = post-final-norm sta
     headline step — the LLM phases themselves + 49 % (462 → 688 ms: prefill 2.3x, token step 6.0 → 7.7 ms at 16 sequences).
     MEMORY: the KV cache is fp32 for K and — round 6, fp16 models — 16-bit for V ("mixed" cache, ``kv_v16``; bf16 models and
     ``kv_v16=False`` keep fp32 V) — L·G·heads·Tmax·hd·(4 + 2 | 4) B = 5.0 | 6.7 GB per sequence at 13B dims with
-    Tmax = 4096 (pass ``max_cache_len``: the cache is sized from it, 0.63 | 0.84 GB per sequence at 512) — and the decode-tile copy of the
+    Tmax = 4096, 1.26 | 1.68 GB at Tmax = 1024 (pass ``max_cache_len``: the cache is sized from it, 0.63 | 0.84 GB per sequence at 512;
+    ``kv_format="fp8_e4m3"``, below, holds 0.43 GB at 1024) — and the decode-tile copy of the
     weights (+ 25.7 GB at 13B) exists for every batch size, not only G >= 5; ``memory_footprint()`` returns the figures before
     anything is allocated, ``_pack`` logs them. The ``past_key_values`` views ``forward`` returns are fp32 in this mode (the reference
     returns the model dtype; they are views of the module's own cache and only meant to be handed back to ``forward``).
     Lock-step batches of 17..32 sequences stay in precise mode (round 6: four operand blocks per weight fragment, 10.9 ms per 32-sequence
     token step); ``SX_LLM_PRECISE32=0`` sends them to the plain 16-bit flow instead (2.0e-3 at 40 layers) — logged once at construction
+  * ``kv_format="fp8_e4m3"`` (opt-in, lossy; or ``SX_LLM_KV=fp8_e4m3``; precise mode, head_dim 128, single rank): the KV cache holds OCP
+    e4m3fn codes with one power-of-two fp32 scale per (token, head) row of k (after RoPE) and of v — uint8 [L][G][heads][Tmax][128] +
+    fp32 [L][G][heads][Tmax], 264 B per (layer, head, token) instead of 768 (0.344 of the mixed cache). A row is rounded ONCE, when it is
+    appended (quant.quantize_kv_rows is the rule, csrc/precise.hip quant_row8 the kernel); everything else is the fp32-grade path: the
+    model computes, bit for bit, what the fp32-cache kernels compute on a cache holding the dequantised values.
+    ``kv_format="fp8_e4m3_emulated"`` is that statement's other half, the bit-reference twin and test hook (in the spirit of
+    sx_attention_f32_variant): ordinary all-fp32 caches, every append stores dequantise(quantise(row)), attention runs the existing fp32
+    kernels — the same bits, no byte saving. The mode is NOT inside the 1e-3 contract: on the random-weight miniatures (sharp softmaxes)
+    logits move 5e-2 to 6e-2 from the unquantised model and 78-95 % of the arg-maxes survive (profiles/fp8_kv.md); the cost on a real
+    checkpoint is not known. A last-bit difference in one k can flip a code, so two different evaluation orders of the same prompt
+    (one prefill / prefill + decode, other prefill chunkings) agree only to ~1e-3: cross-turn ``reuse_cache=True`` is NOT claimed to
+    reproduce the ids of a fresh prefill under this mode. ``past_key_values`` are dequantised fp32 copies. Independent of
+    ``weight_format``
   * ``comm`` with world > 1: Megatron tensor parallelism (parallel.py) — this rank owns nh/tp heads (their q/k/v rows, KV
     cache and o_proj columns), I/tp FFN rows (gate/up rows, down_proj columns) and Vpad/tp lm_head rows; the fp32
     residual stream is all-reduced after o_proj and down_proj (rank 0's GEMM epilogue adds the residual), the logits are
@@ -193,7 +207,9 @@ class SampleState:
 
 
 class LlamaForCausalLM:
-    def __init__(self, config, max_cache_len=None, max_batch=1, comm=None, precise=None, kv_v16=None, weight_format=None):
+    KV_FORMATS = (None, "fp8_e4m3", "fp8_e4m3_emulated")
+
+    def __init__(self, config, max_cache_len=None, max_batch=1, comm=None, precise=None, kv_v16=None, weight_format=None, kv_format=None):
         self.config = config if not isinstance(config, dict) else LlamaConfigLite(**config)
         c = self.config
         self.H, self.nh, self.L = c.hidden_size, c.num_attention_heads, c.num_hidden_layers
@@ -248,6 +264,24 @@ class LlamaForCausalLM:
                 raise ValueError("LlamaForCausalLM: weight_format='fp8_e4m3' needs the tiled precise decode path: hidden / per-rank head and FFN "
                                  f"widths that are multiples of 64 and >= 256, output widths that are multiples of 32 (H {self.H}, "
                                  f"heads x dim {self.H_l}, FFN {self.I_l}, vocab rows {self.V_l}): FP8 tiles exist for the MFMA skinny GEMM only")
+        # FP8 (e4m3) KV cache (module docstring; opt-in: ``kv_format="fp8_e4m3"`` or SX_LLM_KV=fp8_e4m3). Never a silent fall-back: a
+        # configuration the FP8 kernels do not cover is refused here, like weight_format
+        if kv_format is None:
+            kv_format = os.environ.get("SX_LLM_KV") or None
+        if kv_format not in self.KV_FORMATS:
+            raise ValueError(f"LlamaForCausalLM: kv_format must be None, 'fp8_e4m3' or 'fp8_e4m3_emulated', not {kv_format!r}")
+        self.kv_format = kv_format
+        if kv_format is not None:
+            if not self.precise:
+                raise ValueError(f"LlamaForCausalLM: kv_format={kv_format!r} needs the precise mode (the FP8 cache is read by the fp32 attention "
+                                 "kernels; the plain 16-bit flow's cache has no FP8 form)")
+            if self.hd != 128:
+                raise ValueError(f"LlamaForCausalLM: kv_format={kv_format!r} needs head_dim 128, not {self.hd} (one 16-lane group quantises a row)")
+            if kv_v16:
+                raise ValueError(f"LlamaForCausalLM: kv_v16=True and kv_format={kv_format!r} exclude each other (the FP8 cache holds k AND v "
+                                 "as codes; its fp32 twin holds both in fp32)")
+            if tp > 1:
+                raise NotImplementedError("kv_format is single-rank: tensor-parallel ranks are not supported")
         # Decode attention (tools/bench_decode_attention_ab.py, 16 sequences x 40 heads, ms per token of the graph-replayed step):
         # three launches (RoPE + append, split-KV attention, combine) with 8 / 2 / 1 KV splits 6.70 / 6.46 / 6.52; ONE launch
         # (sx_attn_decode_fused, bit-identical) with 8 splits 6.80 — its arrival-counter tail costs more than two graph
@@ -265,6 +299,25 @@ class LlamaForCausalLM:
         self._drop_graphs()
         self._sample_state = None
         self.kv_epoch = 0               # bumped whenever the KV cache is reset or written outside generate_batch
+
+    def _kv_name(self):
+        """The KV cache's format in words (log line and fit guard)."""
+        if not self.precise:
+            return "16-bit"
+        if self.kv_format == "fp8_e4m3":
+            return "FP8 e4m3 codes + fp32 row scales"
+        if self.kv_format == "fp8_e4m3_emulated":
+            return "fp32 holding FP8-e4m3-rounded rows (the reference twin)"
+        return "k fp32 + v 16-bit" if self.kv_v16 else "fp32"
+
+    def _kv_kw(self, li, s=slice(None)):
+        """What ops.rope_kv_append_f32 / attention_f32 take beyond the caches under ``kv_format``: layer li's row scales of the sequences
+        ``s``, or the emulate flag."""
+        if self.kv_format == "fp8_e4m3":
+            return {"kv_scales": (self._P["ks"][li][s], self._P["vs"][li][s])}
+        if self.kv_format == "fp8_e4m3_emulated":
+            return {"kv_emulate": True}
+        return {}
 
     def _precise_tiled_ok(self):
         """Every projection shape of the precise decode step satisfies the MFMA skinny GEMM (_pack's P["precise_tiled"])."""
@@ -297,6 +350,8 @@ class LlamaForCausalLM:
             rows = 3 * self.H_l + self.H + 2 * self.I_l + self.H
             tiles = self.L * (per_layer // 2 + rows * 4) + self.V_l * self.H * 2
         kv = self.L * self.G * self.nh_l * self.Tmax * self.hd * ((4 + (2 if self.kv_v16 else 4)) if self.precise else 4)
+        if self.kv_format == "fp8_e4m3":        # one byte per k and per v value + the two fp32 row scales (the emulated twin: all fp32, above)
+            kv = self.L * self.G * self.nh_l * self.Tmax * (2 * self.hd + 8)
         return {"weights": w, "decode_tiles": tiles, "kv_cache": kv, "total": w + tiles + kv}
 
     # ---- reference-compatible plumbing ---------------------------------------------------------------------
@@ -384,19 +439,19 @@ class LlamaForCausalLM:
         sd, dev, dt = self._sd, self.device, self.dtype
         want_v16 = self._kv_v16_arg if self._kv_v16_arg is not None else \
             (os.environ.get("SX_LLM_V16", "1") != "0" and dt == torch.float16)
-        self.kv_v16 = bool(want_v16) and self.precise and self.hd <= 128 and self.hd % 8 == 0
+        self.kv_v16 = bool(want_v16) and self.precise and self.hd <= 128 and self.hd % 8 == 0 and self.kv_format is None
         fp = self.memory_footprint()
         free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)   # + the allocator's cached blocks
         logging.getLogger("seedx_amd").info(
             "LlamaForCausalLM._pack (%s, %d sequences, Tmax %d): weights %.1f GB + decode tiles %.1f GB + KV cache %.1f GB (%s)",
             ("precise" if self.precise else "plain 16-bit") + (", FP8 e4m3 decode tiles" if self.weight_format else ""), self.G, self.Tmax,
             fp["weights"] / 1e9, fp["decode_tiles"] / 1e9,
-            fp["kv_cache"] / 1e9, ("k fp32 + v 16-bit" if self.kv_v16 else "fp32") if self.precise else "16-bit")
+            fp["kv_cache"] / 1e9, self._kv_name())
         if fp["total"] > free:
             raise RuntimeError(
                 f"LlamaForCausalLM: {fp['total'] / 1e9:.1f} GB needed ({fp['weights'] / 1e9:.1f} weights + {fp['decode_tiles'] / 1e9:.1f} decode "
                 f"tiles + {fp['kv_cache'] / 1e9:.1f} KV cache at max_cache_len {self.Tmax}, {self.G} sequences"
-                f"{', fp32 (precise mode)' if self.precise else ''}) but {free / 1e9:.1f} GB are free: lower max_cache_len / max_batch"
+                f"{(', ' + self._kv_name() if self.kv_format else ', fp32 (precise mode)') if self.precise else ''}) but {free / 1e9:.1f} GB are free: lower max_cache_len / max_batch"
                 + (", or pass precise=False (16-bit cache, no decode tiles below 5 sequences)" if self.precise else ""))
         if self.tp > 1:     # the captured decode step all-reduces [G, H] and all-gathers [G, Vpad/tp] fp32 (see _decode_step_body)
             self.comm.require_capacity(self.G * max(self.H, self.V_l))
@@ -516,9 +571,19 @@ class LlamaForCausalLM:
         fr = torch.outer(torch.arange(self.Tmax).float(), inv)           # [Tmax, hd/2] fp32 (:97-113)
         P["cos"], P["sin"] = fr.cos().to(dev).contiguous(), fr.sin().to(dev).contiguous()
         G = self.G
-        P["kc"] = torch.zeros((self.L, G, self.nh_l, self.Tmax, self.hd), dtype=torch.float32 if self.precise else dt,
-                              device=dev)                                                          # this rank's heads
-        P["vc"] = torch.zeros_like(P["kc"], dtype=dt) if self.kv_v16 else torch.zeros_like(P["kc"])
+        if self.kv_format == "fp8_e4m3":
+            # codes + one scale per (token, head) row, all zeros: a never-written row decodes to 0 · 0 and no code is NaN, so what the
+            # in-flight step reads from parked slots stays finite
+            P["kc"] = torch.zeros((self.L, G, self.nh_l, self.Tmax, self.hd), dtype=torch.uint8, device=dev)
+            P["vc"] = torch.zeros_like(P["kc"])
+            P["ks"] = torch.zeros((self.L, G, self.nh_l, self.Tmax), dtype=torch.float32, device=dev)
+            P["vs"] = torch.zeros_like(P["ks"])
+            held = sum(P[k].numel() * P[k].element_size() for k in ("kc", "vc", "ks", "vs"))
+            assert held == fp["kv_cache"], (held, fp["kv_cache"])          # memory_footprint() prices what is held
+        else:
+            P["kc"] = torch.zeros((self.L, G, self.nh_l, self.Tmax, self.hd), dtype=torch.float32 if self.precise else dt,
+                                  device=dev)                                                      # this rank's heads
+            P["vc"] = torch.zeros_like(P["kc"], dtype=dt) if self.kv_v16 else torch.zeros_like(P["kc"])
         # device-resident loop state, one entry per sequence
         P["pos"] = torch.zeros(G, dtype=torch.int32, device=dev)         # position of the next input token
         P["ctx"] = torch.ones(G, dtype=torch.int32, device=dev)          # pos + 1 (keys visible to that token)
@@ -569,18 +634,22 @@ class LlamaForCausalLM:
                 # fp32-grade activations: operand planes into a_planes = 2 GEMMs with fp32 outputs, fp32 RoPE / cache / attention
                 h, _ = ops.rmsnorm_planes(x, lw["ln1"], eps, dt)
                 qkv = ops.gemm(h, lw["wqkv"], a_planes=2, out_dtype=torch.float32)    # [M, 3H] fp32
+                # (kv_format: the append quantises; the emulated twin's attention is the plain fp32 call on its rounded rows)
                 if uniform:
+                    kw = self._kv_kw(li, slice(g0, g0 + n))
                     ops.rope_kv_append_f32(qkv, kc_l[g0:g0 + n], vc_l[g0:g0 + n], P["cos"], P["sin"], P["pos"][g0:g0 + n], n, Ts[0],
-                                           nh, hd, dt)
-                    att = ops.attention_f32(qkv, kc_l[g0:g0 + n], vc_l[g0:g0 + n], P["pos"][g0:g0 + n], n, Ts[0], nh, hd, scale, dt)
+                                           nh, hd, dt, **kw)
+                    att = ops.attention_f32(qkv, kc_l[g0:g0 + n], vc_l[g0:g0 + n], P["pos"][g0:g0 + n], n, Ts[0], nh, hd, scale, dt,
+                                            kv_scales=kw.get("kv_scales"))
                 else:
                     att = torch.empty((M, 2 * H), dtype=dt, device=x.device)
                     for i, g in enumerate(seqs):
                         rows = qkv[offs[i]:offs[i + 1]]
+                        kw = self._kv_kw(li, slice(g, g + 1))
                         ops.rope_kv_append_f32(rows, kc_l[g:g + 1], vc_l[g:g + 1], P["cos"], P["sin"], P["pos"][g:g + 1], 1, Ts[i], nh,
-                                               hd, dt)
+                                               hd, dt, **kw)
                         att[offs[i]:offs[i + 1]] = ops.attention_f32(rows, kc_l[g:g + 1], vc_l[g:g + 1], P["pos"][g:g + 1], 1, Ts[i],
-                                                                     nh, hd, scale, dt)
+                                                                     nh, hd, scale, dt, kv_scales=kw.get("kv_scales"))
                 x = comm.all_reduce(ops.gemm(att, lw["wo"], a_planes=2, residual=x if lead else None, out_dtype=torch.float32))
                 h, _ = ops.rmsnorm_planes(x, lw["ln2"], eps, dt)
                 g_ = ops.split16(ops.gemm(h, lw["wgu"], a_planes=2, act="silu", glu=True, out_dtype=torch.float32), dt)
@@ -700,13 +769,14 @@ class LlamaForCausalLM:
             else:
                 h, _ = ops.rmsnorm_planes(x, lw["ln1"], eps, dt, tiled=tl)
                 qkv = lin(h, lw, "wqkv")                                              # [G, 3H] fp32
+            kw = self._kv_kw(li)    # kv_format: the row scales of the FP8 cache, or the emulate flag of its fp32 twin
             if fuse_rope:           # RoPE + KV append inside the attention launch (one graph node per layer instead of two)
                 att = ops.attention_f32(qkv, P["kc"][li], P["vc"][li], P["pos"], G, 1, nh, hd, scale, dt, tiled=tl,
-                                        nsplit=self.decode_nsplit_f32, scratch=P["attn_f32_part"], rope=(P["cos"], P["sin"]))
+                                        nsplit=self.decode_nsplit_f32, scratch=P["attn_f32_part"], rope=(P["cos"], P["sin"]), **kw)
             else:
-                ops.rope_kv_append_f32(qkv, P["kc"][li], P["vc"][li], P["cos"], P["sin"], P["pos"], G, 1, nh, hd, dt)
+                ops.rope_kv_append_f32(qkv, P["kc"][li], P["vc"][li], P["cos"], P["sin"], P["pos"], G, 1, nh, hd, dt, **kw)
                 att = ops.attention_f32(qkv, P["kc"][li], P["vc"][li], P["pos"], G, 1, nh, hd, scale, dt, tiled=tl,
-                                        nsplit=self.decode_nsplit_f32, scratch=P["attn_f32_part"])
+                                        nsplit=self.decode_nsplit_f32, scratch=P["attn_f32_part"], kv_scales=kw.get("kv_scales"))
             if fold:
                 # residual GEMV: fp32 x, the planes of x * gamma of the NEXT norm, the rows' sums of squares; GLU epilogue: planes directly
                 x, x16, ssq = lin(att, lw, "wo", residual=x, emit_norm=True, planes_out=True, norm_gamma=lw["ln2"])
@@ -836,8 +906,15 @@ class LlamaForCausalLM:
                 logits = self.comm.all_gather(logits).permute(1, 0, 2).reshape(T, self.Vpad)
             logits = logits[:, : self.V].unsqueeze(0)
         Tk = int(P["pos"][0].item())
-        pkv = tuple((P["kc"][li][0][:, :Tk].unsqueeze(0), P["vc"][li][0][:, :Tk].unsqueeze(0)) for li in range(self.L)) \
-            if use_cache else None
+        if use_cache and self.kv_format == "fp8_e4m3":
+            # dequantised fp32 COPIES (plumbing: the contract only hands them back and reads shape[2])
+            from . import quant
+            tab = quant.decode_table(self.device)
+            deq = lambda c, sc: (tab[c[0][:, :Tk].long()] * sc[0][:, :Tk, None]).unsqueeze(0)
+            pkv = tuple((deq(P["kc"][li], P["ks"][li]), deq(P["vc"][li], P["vs"][li])) for li in range(self.L))
+        else:
+            pkv = tuple((P["kc"][li][0][:, :Tk].unsqueeze(0), P["vc"][li][0][:, :Tk].unsqueeze(0)) for li in range(self.L)) \
+                if use_cache else None
         hs = ((None,) * self.L + (hn.view(1, -1, self.H),)) if output_hidden_states else None
         out = CausalLMOutputWithPast(loss=None, logits=logits, past_key_values=pkv, hidden_states=hs, attentions=None)
         return out if return_dict else out.to_tuple()

@@ -548,31 +548,63 @@ def rmsnorm_planes(x, gamma, eps, dtype, tiled=False, want_f32=False, want_plane
     return ret, y32
 
 
-def rope_kv_append_f32(qkv, kcache, vcache, cos_tab, sin_tab, pos_dev, G, T, H, D, table_dtype):
+def _kv_scales_ok(kv_scales, kcache, vcache):
+    """The FP8 cache's tensors: codes uint8 [G, H, Tmax, 128] and one fp32 scale per row [G, H, Tmax], k and v laid out alike."""
+    ks, vs = kv_scales
+    assert kcache.dtype == torch.uint8 and vcache.dtype == torch.uint8 and kcache.shape[3] == 128
+    assert ks.dtype == torch.float32 and vs.dtype == torch.float32 and ks.shape == kcache.shape[:3] and vs.shape == ks.shape \
+        and ks[0].is_contiguous() and vs.stride() == ks.stride()
+    return ks, vs
+
+
+def rope_kv_append_f32(qkv, kcache, vcache, cos_tab, sin_tab, pos_dev, G, T, H, D, table_dtype, kv_scales=None, kv_emulate=False):
     """qkv fp32 [G*T, 3HD] (q rotated in place); caches [G, H, Tmax, D]: k fp32, v fp32 or — the mixed cache — the model's 16-bit dtype
-    (= table_dtype); pos_dev int32 [G]."""
+    (= table_dtype); pos_dev int32 [G].
+    kv_scales=(kscale, vscale) fp32 [G, H, Tmax]: the FP8 cache — kcache / vcache are uint8 e4m3 codes, every appended row is quantised
+    with one power-of-two scale (quant.quantize_kv_rows' rule). kv_emulate: fp32 caches receive the dequantised values instead (the
+    bit-reference twin of the FP8 cache)."""
     assert qkv.dtype == torch.float32 and qkv.is_contiguous() and qkv.shape == (G * T, 3 * H * D)
-    assert kcache.dtype == torch.float32 and vcache.dtype in (torch.float32, table_dtype) and kcache.dim() == 4 and kcache.shape[0] == G \
-        and kcache[0].is_contiguous() and vcache.stride() == kcache.stride()
+    assert kcache.dim() == 4 and kcache.shape[0] == G and kcache[0].is_contiguous() and vcache.stride() == kcache.stride()
+    if kv_scales is not None or kv_emulate:
+        assert not (kv_scales is not None and kv_emulate)
+        if kv_emulate:
+            assert kcache.dtype == torch.float32 and vcache.dtype == torch.float32
+            ks = vs = None
+        else:
+            ks, vs = _kv_scales_ok(kv_scales, kcache, vcache)
+        check(_lib.load().sx_rope_kv_append_f32_q8(_p(qkv), _p(kcache), _p(vcache), _p(ks), _p(vs), _p(cos_tab), _p(sin_tab), _p(pos_dev),
+                                                   G, T, H, D, kcache.shape[2], kcache.stride(0), 0 if ks is None else ks.stride(0),
+                                                   _DT[table_dtype], 1 if kv_emulate else 0, _stream()), "sx_rope_kv_append_f32_q8")
+        return
+    assert kcache.dtype == torch.float32 and vcache.dtype in (torch.float32, table_dtype)
     fn = "sx_rope_kv_append_f32" if vcache.dtype == torch.float32 else "sx_rope_kv_append_f32_v16"
     check(getattr(_lib.load(), fn)(_p(qkv), _p(kcache), _p(vcache), _p(cos_tab), _p(sin_tab), _p(pos_dev), G, T, H, D,
                                    kcache.shape[2], kcache.stride(0), _DT[table_dtype], _stream()), fn)
 
 
-def attention_f32(qkv, kcache, vcache, pos_dev, G, T, H, D, scale, dtype, tiled=False, nsplit=1, scratch=None, rope=None):
+def attention_f32(qkv, kcache, vcache, pos_dev, G, T, H, D, scale, dtype, tiled=False, nsplit=1, scratch=None, rope=None, kv_scales=None,
+                  kv_emulate=False):
     """Causal fp32 attention of a T-token chunk per sequence over the fp32 cache (row t sees keys 0 .. pos[g] + t); q = the rotated
     head rows at the front of qkv's rows. Returns the planes of the context [G*T, H*D] (see split16).
     rope=(cos, sin) (T == 1, D == 128): qkv holds the UNROTATED q | k | v rows of the new token; the launch rotates q and k, appends k / v
-    to the caches at pos[g] and attends — rope_kv_append_f32 + attention_f32 in one launch per layer."""
+    to the caches at pos[g] and attends — rope_kv_append_f32 + attention_f32 in one launch per layer.
+    kv_scales=(kscale, vscale): the FP8 cache (uint8 codes + row scales, see rope_kv_append_f32) — the same bits as this call on a cache
+    holding the dequantised values. kv_emulate (with rope): fp32 caches, the new token's rows quantised and dequantised on append."""
     assert qkv.dtype == torch.float32 and qkv.is_contiguous() and qkv.shape[0] == G * T and qkv.shape[1] >= H * D
-    assert kcache.dtype == torch.float32 and kcache.shape[0] == G and kcache.shape[1] == H and kcache.shape[3] == D
-    assert vcache.dtype in (torch.float32, dtype) and vcache.stride() == kcache.stride()
+    assert kcache.shape[0] == G and kcache.shape[1] == H and kcache.shape[3] == D and vcache.stride() == kcache.stride()
     ret, buf, code = _planes_out(G * T, H * D, dtype, qkv.device, tiled)
     a = _lib.AttnF32Args()
+    if kv_scales is not None:
+        assert not kv_emulate
+        ks, vs = _kv_scales_ok(kv_scales, kcache, vcache)
+        a.kv_fp8, a.k_scale, a.v_scale, a.scale_seq_stride = 1, _p(ks), _p(vs), ks.stride(0)
+    else:
+        assert kcache.dtype == torch.float32 and vcache.dtype in ((torch.float32,) if kv_emulate else (torch.float32, dtype))
+        a.kv_fp8 = 2 if kv_emulate else 0
     a.q, a.kcache, a.vcache, a.out, a.pos0_dev = _p(qkv), _p(kcache), _p(vcache), _p(buf), _p(pos_dev)
     a.q_row_stride, a.cache_seq_stride = qkv.stride(0), kcache.stride(0)
     a.G, a.T, a.H, a.D, a.Tmax, a.dtype, a.scale, a.causal = G, T, H, D, kcache.shape[2], code, float(scale), 1
-    a.v16 = 0 if vcache.dtype == torch.float32 else 1
+    a.v16 = 0 if vcache.dtype in (torch.float32, torch.uint8) else 1
     if nsplit > 1 and T == 1:         # decode step of few sequences: key splits (scratch: fp32 [G, H, nsplit, D + 2])
         if scratch is None:
             scratch = torch.empty((G, H, nsplit, D + 2), dtype=torch.float32, device=qkv.device)

@@ -27,13 +27,14 @@ def _exponent(v):
     return ((v.contiguous().view(torch.int32) >> 23) & 0xff) - 127
 
 
-def row_exponents(w):
-    """s[n] = clamp(ceil(log2(amax[n] / 448)), -15, 7) as int32 [N]; 0 for an all-zero row. No division: with amax = 1.f · 2^E,
+def row_exponents(w, s_min=S_MIN, s_max=S_MAX):
+    """s[n] = clamp(ceil(log2(amax[n] / 448)), s_min, s_max) as int32 (the weights' [-15, 7] by default), amax over the LAST dim;
+    0 for an all-zero row. No division: with amax = 1.f · 2^E,
     amax <= 448 · 2^s = 1.75 · 2^(8 + s)  ⇔  s >= E - 8 (fraction <= .75) or s >= E - 7 (fraction > .75)."""
-    amax = w.detach().abs().amax(dim=1).to(torch.float32).contiguous()
+    amax = w.detach().abs().amax(dim=-1).to(torch.float32).contiguous()
     bits = amax.view(torch.int32)
     s = _exponent(amax) - 8 + ((bits & 0x7fffff) > 0x600000).to(torch.int32)
-    s = s.clamp(S_MIN, S_MAX)
+    s = s.clamp(s_min, s_max)
     return torch.where(amax == 0, torch.zeros_like(s), s)
 
 
@@ -73,6 +74,28 @@ def dequantize_rows(codes, scale, dtype=torch.float32):
     assert codes.dtype == torch.uint8 and codes.dim() == 2 and scale.shape == (codes.shape[0],)
     val = torch.index_select(decode_table(codes.device), 0, codes.reshape(-1).to(torch.int32)).view(codes.shape)
     return (val * scale.to(torch.float32)[:, None]).to(dtype)
+
+
+# ---- FP8 KV cache (LlamaForCausalLM(kv_format="fp8_e4m3")): the same row rule on fp32 activations ------------------------------
+# One row = the head_dim values of one (token, head), k after RoPE or v. The exponent clamp is [-64, 64] instead of the weights'
+# [-15, 7]: that clamp makes dequantised WEIGHTS fp16-exact, which means nothing for fp32 activations and would cost precision on rows
+# whose amax is below 448 · 2^-15 = 0.014; +-64 keeps every dequantised value, and its product with O(1) operands, a normal fp32.
+# The device quantiser (csrc/precise.hip, quant_row8) computes the same codes and scales; non-finite inputs are outside the rule.
+KV_S_MIN, KV_S_MAX = -64, 64
+
+
+def quantize_kv_rows(x):
+    """fp32 [..., D] → (codes uint8 [..., D], scale fp32 [...] = 2^s), s = clamp(ceil(log2(amax / 448)), -64, 64), 0 for a zero row."""
+    x = x.detach().to(torch.float32)
+    s = row_exponents(x, KV_S_MIN, KV_S_MAX)
+    return encode_e4m3(x * _pow2(-s)[..., None]), _pow2(s)
+
+
+def dequantize_kv_rows(codes, scale):
+    """codes uint8 [..., D], scale fp32 [...] → decode(code) · scale, fp32 (exact: the scale is a power of two)."""
+    assert codes.dtype == torch.uint8 and scale.shape == codes.shape[:-1]
+    val = torch.index_select(decode_table(codes.device), 0, codes.reshape(-1).to(torch.int32)).view(codes.shape)
+    return val * scale.to(torch.float32)[..., None]
 
 
 def quantize_llama_layer(sd, prefix, dtype, device=None):
