@@ -151,8 +151,10 @@ typedef struct sx_gemv_args {
                         * only on its own operand column and columns >= M are never stored; 16 * K elements in all): MFMA path only */
   void* workspace;     /* optional, MFMA path: device scratch for split-K over workgroups (shapes whose N / 16 row groups do not
                         * fill the chip). Layout: 16 KB of arrival counters, then the partial sums. Must be ZERO when first used
-                        * and is left with its counters at zero; bytes >= 16384 + 8 * 16 * N * 4 allows every split factor
-                        * (smaller: no split). One launch at a time per
+                        * and is left with its counters at zero. A split into S workgroups (S <= 8) needs
+                        * bytes >= 16384 + S * 16 * MB * N * 4, MB = the 16-row x blocks per weight fragment: 1 for M <= 16, 2 for
+                        * M = 17..32 or x_planes = 2, 4 for both — so 16384 + 8 * 16 * MB * N * 4 allows every split factor (smaller than
+                        * the chosen factor needs: no split, nothing past workspace_bytes is touched). One launch at a time per
                         * workspace (launches on one stream are fine). NULL: never split. Results are deterministic either way
                         * (partials are added in split order by the last workgroup to arrive). */
   uint64_t workspace_bytes;

@@ -991,6 +991,70 @@ def test_gemm_matrix_covers_every_launched_kernel():
         assert all(gm.kernel_of(c)[0] == "ls" or gm.kernel_of(c) in set(pp) for c in gm.CASES if c["dt"] == dt)
 
 
+def test_gemv_matrix_covers_every_launched_kernel():
+    """tests/test_gemv_matrix_gpu.py's case table mirrors sx_gemv's dispatch: FAMILIES is exactly the set of gemm_skinny_kernel
+    instantiations of SX_SK_GO, VALU_MR that of gemv_kernel in SX_GEMV_GO, and every one of them has cases for both dtypes and
+    (skinny) both weight formats; every case reaches the family it was written for."""
+    from tests import test_gemv_matrix_gpu as gv
+    sk, sk_tt, mr, tt = gv.source_kernels()
+    assert len(sk) == 14 and sk == set(gv.FAMILIES) and len(gv.FAMILIES) == 14, sk ^ set(gv.FAMILIES)
+    assert sk_tt == {("F16", False), ("F16", True), ("BF16", False), ("BF16", True)} and tt == {"F16", "BF16"}
+    assert mr == set(gv.VALU_MR)
+    ids = [c["id"] for c in gv.SKINNY + gv.VALU + gv.BOTH]
+    assert len(ids) == len(set(ids))
+    for c in gv.SKINNY:
+        assert gv.kernel_of(c) == ("sk",) + c["fam"] + (c["w8"],), c["id"]
+    for dt in gv.DTYPES:
+        have = {gv.kernel_of(c) for c in gv.SKINNY if c["dt"] == dt}
+        assert have == {("sk",) + f + (w8,) for f in gv.FAMILIES for w8 in (False, True)}, dt
+        assert {gv.kernel_of(c) for c in gv.VALU if c["dt"] == dt} == {("valu", m) for m in gv.VALU_MR}, dt
+        # M < MR inside a VALU case, odd N, K % 64 != 0
+        assert {c["M"] for c in gv.VALU if c["dt"] == dt} >= {1, 2, 3, 4, 5, 7, 8}
+        assert {c["K"] for c in gv.VALU} == {8, 264, 520} and {131, 1001, 32} == {c["N"] for c in gv.VALU}
+        # the lab variants and the 64-row workgroups are reached through their hooks
+        assert {c["var1"] for c in gv.SKINNY} == {0, 1, 2} and {c["var3"] for c in gv.SKINNY} == {1, 2}
+    # one workspace-threshold case per MB value, forced split factors 2 and 8 per MB value
+    assert {gv.n_blocks(c) for c in gv.SKINNY if c["ws"] == "short"} == {1, 2, 4}
+    assert {(gv.n_blocks(c), c["S"]) for c in gv.SKINNY if c["S"] and c["ws"] == "full"} == {(mb, s) for mb in (1, 2, 4) for s in (2, 8)}
+
+
+def test_gemv_matrix_k_values_reach_every_peeled_round():
+    """For every skinny instantiation, dtype and weight format, the four waves' (full, rem) of its unsplit cases — by the kernel's own
+    k-slice formula — cover full in {0, 1, 2, odd >= 3, even >= 4} with every rem in 0 .. U-1 (all but the wave without k-steps), the
+    waves of a case never all have the same length, and the forced split-K cases of every MB value include waves without any k-step."""
+    from tests import test_gemv_matrix_gpu as gv
+    assert gv.wave_rounds(5, 4) == [(0, 1), (0, 1), (0, 1), (0, 2)] and gv.wave_rounds(73, 4) == [(4, 2), (4, 2), (4, 2), (4, 3)]
+    assert len(gv.required_classes(1)) == 4 and len(gv.required_classes(2)) == 9 and len(gv.required_classes(4)) == 19
+    for fam in gv.FAMILIES:
+        U = fam[1]
+        for dt in gv.DTYPES:
+            for w8 in (False, True):
+                cases = [c for c in gv.SKINNY if c["fam"] == fam and c["dt"] == dt and c["w8"] == w8 and not c["S"]]
+                seen = set()
+                for c in cases:
+                    assert c["K"] % 64 == 0 and 320 <= c["K"] <= 4672
+                    rounds = gv.wave_rounds(c["K"] // 64, U)
+                    assert len({f * U + r for f, r in rounds}) > 1, c["id"]
+                    seen |= {gv.round_class(f, r) for f, r in rounds}
+                assert seen >= gv.required_classes(U), (fam, dt, w8, gv.required_classes(U) - seen)
+    for mb in (1, 2, 4):
+        split = [c for c in gv.SKINNY if c["S"] and c["ws"] == "full" and gv.n_blocks(c) == mb]
+        assert any((0, 0) in gv.wave_rounds(c["K"] // 64, c["fam"][1], c["S"]) for c in split), mb
+    # the largest weight: 8192 rows, at short K only outside the 64-row workgroups
+    for c in gv.SKINNY:
+        assert c["N"] * c["K"] <= 8192 * 4672
+        if c["N"] == 8192 and c["fam"][0] == 2:
+            assert c["K"] in (320, 832)
+
+
+def test_gemv_matrix_dispatch_block_unchanged():
+    """kernel_of in tests/test_gemv_matrix_gpu.py restates sx_gemv's dispatch by hand; the block it restates is pinned here."""
+    from tests import test_gemv_matrix_gpu as gv
+    assert gv.dispatch_crc() == 0x14246dd8, \
+        "csrc/decode.hip: the dispatch block of sx_gemv (from `const bool tail20` to `#undef SX_SK_GO`) changed — re-read kernel_of, " \
+        "FAMILIES and the case table of tests/test_gemv_matrix_gpu.py against it, then record the new CRC here"
+
+
 def test_layernorm_fold_host_algebra_and_tile_gate():
     """ops.fold_layernorm: rstd (x W'^T - mu colsum) + bias' == LayerNorm(x) W^T + bias (fp32 weights: exact algebra up to rounding);
     GLU-packed rows fold row by row. ops.ln_fold_ok / sx_gemm_ln: the fold exists only where every neighbour GEMM runs on a
