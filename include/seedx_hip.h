@@ -410,6 +410,26 @@ int sx_sample_next_b(float* logits, int ld_logits, int vocab, const int32_t* img
 /* sx_greedy_next_slots (parking, force_at after the draw, stop rule, counters, status — all unchanged) with the id by the rule above. */
 int sx_sample_next_slots(const sx_slot_step_args* args, const sx_sample_args* sample, void* stream);
 
+/* KV-cache prefix fork (prefix reuse of in-flight batching, inflight.py): copies the first rows of one slot's cache to other slots,
+ * every layer and head in ONE launch. The cache is addressed as bytes, so one entry serves every cache tensor and format: the fp32 K
+ * cache (row_bytes 512 at head_dim 128), the 16-bit caches (256), the FP8 codes (128) and their fp32 row scales (row_bytes 4).
+ * For every pair i and every (o < outer, h < inner) the n_rows[i] * row_bytes contiguous bytes at
+ *     cache + o * outer_stride + src[i] * slot_stride + h * inner_stride
+ * are copied to the same offset of slot dst[i]. A pair is SKIPPED (nothing is written) when src[i] or dst[i] lies outside [0, G),
+ * when src[i] == dst[i] or when n_rows[i] <= 0; n_rows[i] above Tmax is CLAMPED to Tmax. The pairs of one launch are not ordered:
+ * no slot may be written twice, and no slot may be read and written (ops.kv_fork refuses both). 16-byte accesses wherever the two
+ * spans share their alignment modulo 16, 4-byte accesses for the head and tail of such spans and for spans that do not (scale rows;
+ * an odd Tmax): cache, the strides and row_bytes must be multiples of 4. outer * inner and n_pairs are at most 65535 each. */
+typedef struct sx_kv_fork_args {
+  void* cache;             /* bytes, viewed as [outer][G][inner][Tmax][row_bytes]                       */
+  const int32_t* src;      /* device [n_pairs] donor slot                                               */
+  const int32_t* dst;      /* device [n_pairs] receiving slot                                           */
+  const int32_t* n_rows;   /* device [n_pairs] rows [0, n) to copy                                      */
+  int64_t outer_stride, slot_stride, inner_stride;   /* bytes                                           */
+  int32_t n_pairs, outer, G, inner, Tmax, row_bytes;
+} sx_kv_fork_args;
+int sx_kv_fork(const sx_kv_fork_args* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Elementwise / layout helpers
  * ------------------------------------------------------------------------------------------------ */

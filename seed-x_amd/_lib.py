@@ -77,6 +77,12 @@ class SampleArgs(C.Structure):
                 ("token_index", c_vp), ("n_kept", c_vp), ("p_chosen", c_vp)]
 
 
+class KvForkArgs(C.Structure):
+    _fields_ = [("cache", c_vp), ("src", c_vp), ("dst", c_vp), ("n_rows", c_vp),
+                ("outer_stride", c_i64), ("slot_stride", c_i64), ("inner_stride", c_i64),
+                ("n_pairs", c_i32), ("outer", c_i32), ("G", c_i32), ("inner", c_i32), ("Tmax", c_i32), ("row_bytes", c_i32)]
+
+
 class AttnArgs(C.Structure):
     _fields_ = [("Q", c_vp), ("K", c_vp), ("V", c_vp), ("O", c_vp),
                 ("B", c_i32), ("H", c_i32), ("Sq", c_i32), ("Skv", c_i32), ("D", c_i32), ("reserved", c_i32),
@@ -135,6 +141,7 @@ SIGNATURES = {
     "sx_greedy_next_slots": [C.POINTER(SlotStepArgs), c_vp],
     "sx_sample_next_b": [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, C.POINTER(SampleArgs), c_vp],
     "sx_sample_next_slots": [C.POINTER(SlotStepArgs), C.POINTER(SampleArgs), c_vp],
+    "sx_kv_fork": [C.POINTER(KvForkArgs), c_vp],
     "sx_scatter_rows_step": [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp],
     "sx_add_i32_n": [c_vp, c_i32, c_i32, c_vp],
     "sx_embedding": [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp],

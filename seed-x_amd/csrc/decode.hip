@@ -1593,3 +1593,66 @@ extern "C" int sx_scatter_rows_step(const float* src, const int32_t* step_dev, f
   SX_HIP_LAUNCH_CHECK();
   return SX_OK;
 }
+
+// ---- KV-cache prefix fork (include/seedx_hip.h: sx_kv_fork) ---------------------------------------------------------------------------
+// Block (x, y, z) = (byte chunk, outer * inner, pair). The span of one (pair, outer, inner) is n_rows * row_bytes contiguous bytes in
+// both slots. Where source and destination share their alignment modulo 16 the body moves as 16-byte vectors (lane i at base + 16 i: 1 KiB
+// per wave instruction, four independent loads per lane ahead of their stores) and only the head / tail words move as dwords; otherwise the whole span moves as
+// dwords. The blocks of one span stride over it, so a long prefix spreads over gridDim.x blocks per (pair, outer, inner).
+__global__ void __launch_bounds__(256) kv_fork_kernel(sx_kv_fork_args a) {
+  const int pair = blockIdx.z;
+  const int s = a.src[pair], d = a.dst[pair];
+  int n = a.n_rows[pair];
+  if (s < 0 || s >= a.G || d < 0 || d >= a.G || s == d || n <= 0) return;          // block-uniform: the skip rules
+  n = n > a.Tmax ? a.Tmax : n;
+  const int o = blockIdx.y / a.inner, h = blockIdx.y - o * a.inner;
+  const int64_t base = (int64_t)o * a.outer_stride + (int64_t)h * a.inner_stride;
+  const char* sp = (const char*)a.cache + base + (int64_t)s * a.slot_stride;
+  char* dp = (char*)a.cache + base + (int64_t)d * a.slot_stride;
+  const int64_t nbytes = (int64_t)n * a.row_bytes;
+  int64_t head = nbytes, body = 0;
+  if ((((uintptr_t)sp ^ (uintptr_t)dp) & 15) == 0) {
+    head = (int64_t)((16 - ((uintptr_t)sp & 15)) & 15);
+    head = head < nbytes ? head : nbytes;
+    body = (nbytes - head) & ~(int64_t)15;
+  }
+  const int64_t stride = (int64_t)gridDim.x * 256, t0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint4* sv = (const uint4*)(sp + head);
+  uint4* dv = (uint4*)(dp + head);
+  const int64_t nvec = body >> 4;
+  int64_t v = t0;
+  for (; v + 3 * stride < nvec; v += 4 * stride) {                                  // full quads: four loads issued, then four stores
+    const uint4 r0 = sv[v], r1 = sv[v + stride], r2 = sv[v + 2 * stride], r3 = sv[v + 3 * stride];
+    dv[v] = r0;
+    dv[v + stride] = r1;
+    dv[v + 2 * stride] = r2;
+    dv[v + 3 * stride] = r3;
+  }
+  for (; v < nvec; v += stride) dv[v] = sv[v];                                      // the last, partial quad
+  const int64_t hw = head >> 2, nw = (nbytes - body) >> 2;                          // head words, then tail words
+  for (int64_t w = t0; w < nw; w += stride) {
+    const int64_t off = w < hw ? w * 4 : head + body + (w - hw) * 4;
+    *(uint32_t*)(dp + off) = *(const uint32_t*)(sp + off);
+  }
+}
+
+extern "C" int sx_kv_fork(const sx_kv_fork_args* a, void* stream) {
+  SX_CHECK(a && a->cache && a->src && a->dst && a->n_rows, "sx_kv_fork: null pointer");
+  SX_CHECK(a->n_pairs >= 0 && a->n_pairs <= 65535, "sx_kv_fork: n_pairs=%d must be 0..65535", a->n_pairs);
+  SX_CHECK(a->outer >= 1 && a->G >= 1 && a->inner >= 1 && a->Tmax >= 1 && a->row_bytes >= 4, "sx_kv_fork: bad dims");
+  SX_CHECK((int64_t)a->outer * a->inner <= 65535, "sx_kv_fork: outer * inner = %lld exceeds 65535", (long long)a->outer * a->inner);
+  SX_CHECK(a->row_bytes % 4 == 0 && ((uintptr_t)a->cache & 3) == 0 && a->outer_stride % 4 == 0 && a->slot_stride % 4 == 0 &&
+               a->inner_stride % 4 == 0, "sx_kv_fork: cache, strides and row_bytes must be multiples of 4 bytes");
+  const int64_t span = (int64_t)a->Tmax * a->row_bytes;
+  SX_CHECK(a->inner_stride >= span && a->slot_stride >= (a->inner - 1) * a->inner_stride + span &&
+               a->outer_stride >= (a->G - 1) * a->slot_stride + (a->inner - 1) * a->inner_stride + span,
+           "sx_kv_fork: strides do not describe [outer][G][inner][Tmax][row_bytes]");
+  if (a->n_pairs == 0) return SX_OK;
+  // chunks of 16 KB (256 lanes x 4 vectors), as many blocks per span as fill the machine (~4096 in all) and no more than the span has chunks
+  const int64_t spans = (int64_t)a->n_pairs * a->outer * a->inner, chunks = (span + 16383) / 16384;
+  int64_t gx = (4096 + spans - 1) / spans;
+  gx = gx < 1 ? 1 : (gx > chunks ? chunks : gx);
+  hipLaunchKernelGGL(kv_fork_kernel, dim3((unsigned)gx, (unsigned)(a->outer * a->inner), (unsigned)a->n_pairs), dim3(256), 0, ST, *a);
+  SX_HIP_LAUNCH_CHECK();
+  return SX_OK;
+}

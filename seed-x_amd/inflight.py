@@ -10,6 +10,11 @@
     later round of the same pass may refill it while the pass has quota left,
   * a decode step runs whenever at least one slot is live.
 
+With ``prefix_cache=True`` the engine also remembers what every slot's KV cache holds (``PrefixIndex``) and lets ``plan_admission``
+choose the slots of a round: a request whose prompt starts like a slot's record keeps those rows (in place, when the slot is free) or
+gets them copied from the donor slot by one sx_kv_fork launch, and prefills only the rest. The requests admitted per pass, hence the
+decode-step counts, are those of the plain schedule; ``simulate_prefix`` is ``simulate``'s counterpart with the token counts.
+
 ``SlotScheduler`` turns finish events into admissions; ``simulate`` drives it with known lengths and counts steps, which is what
 the tests compare the engine's ``last_inflight_stats`` with and what tools/bench_inflight.py prints next to its wall clocks. A forced
 image block is a host-driven chunk that takes no decode step: give ``simulate`` a request's length minus its chunk tokens.
@@ -41,6 +46,21 @@ class SlotScheduler:
                 self.quota -= 1
                 out.append((g, self.slot_req[g]))
         return out
+
+    def candidates(self):
+        """The requests the next ``admit()`` would take, in queue order, without taking them (prefix planning: plan_admission)."""
+        n = min(sum(r is None for r in self.slot_req), len(self.queue), max(self.quota, 0))
+        return [self.queue[i] for i in range(n)]
+
+    def free_slots(self):
+        return [g for g, r in enumerate(self.slot_req) if r is None]
+
+    def place(self, slot, request):
+        """Admits ``request`` (one of ``candidates()``) into the free ``slot``: what ``admit()`` does, with the slot chosen by the caller."""
+        assert self.slot_req[slot] is None and self.quota > 0, f"slot {slot} is not free or the pass has no quota left"
+        self.queue.remove(request)
+        self.slot_req[slot] = request
+        self.quota -= 1
 
     def finish(self, slot):
         """The request in ``slot`` ended: frees the slot, returns the request index."""
@@ -94,3 +114,169 @@ def lockstep_wave_steps(lengths, n_slots):
     """Decode steps of the lock-step alternative: FIFO waves of ``n_slots`` requests, every wave as long as its longest member."""
     lengths = [int(n) for n in lengths]
     return sum(max(lengths[i:i + n_slots]) - 1 for i in range(0, len(lengths), n_slots))
+
+
+# ---- prefix reuse: what a slot's cache holds, and who may take it ------------------------------------------------------------------
+def _common_prefix(ids_a, sigs_a, ids_b, sigs_b, cap):
+    """Rows [0, p), p <= cap, on which the token ids AND the row signatures agree."""
+    m = min(len(ids_a), len(ids_b), cap)
+    p = 0
+    while p < m and ids_a[p] == ids_b[p] and sigs_a[p] == sigs_b[p]:
+        p += 1
+    return p
+
+
+class PrefixIndex:
+    """What the KV cache of each of ``n_slots`` slots holds: the token ids of its rows, one opaque hashable signature per row (the
+    engine: a fingerprint of the row's input embedding, so that image rows with equal ids and different features differ), the KV epoch
+    the record was made under and a last-use stamp from a clock that only moves forward (0: never used)."""
+
+    def __init__(self, n_slots):
+        self.n_slots = int(n_slots)
+        self.rec = [None] * self.n_slots               # (ids, sigs, epoch) or None
+        self.stamp = [0] * self.n_slots
+        self.clock = 0
+
+    def touch(self, slot):
+        self.clock += 1
+        self.stamp[slot] = self.clock
+
+    def record(self, slot, ids, sigs, epoch):
+        ids, sigs = list(ids), list(sigs)
+        assert len(ids) == len(sigs), "one signature per row"
+        self.rec[slot] = (ids, sigs, epoch)
+        self.touch(slot)
+
+    def invalidate(self, slot):
+        self.rec[slot] = None
+
+    def restamp(self, old_epoch, new_epoch):
+        """The owner of the cache moved the epoch from ``old_epoch`` to ``new_epoch`` itself, without touching a recorded row: records
+        made under ``old_epoch`` stay valid. Records of any other epoch stay stale."""
+        self.rec = [None if r is None else ((r[0], r[1], new_epoch) if r[2] == old_epoch else r) for r in self.rec]
+
+    def match(self, ids, sigs, epoch):
+        """[(slot, p)] with p >= 1, longest first (lowest slot on ties): the slot's record agrees with the prompt on ids and signatures of
+        rows [0, p). p is capped at len(ids) - 1: at least one token must be forwarded. Records of another epoch never match."""
+        out = []
+        for g, r in enumerate(self.rec):
+            if r is None or r[2] != epoch:
+                continue
+            p = _common_prefix(r[0], r[1], ids, sigs, len(ids) - 1)
+            if p >= 1:
+                out.append((g, p))
+        return sorted(out, key=lambda t: (-t[1], t[0]))
+
+
+def plan_admission(index, free_slots, live_slots, requests, min_tokens, epoch=0):
+    """One admission round with prefix reuse. ``requests``: [(request, ids, sigs)] in queue order — exactly the requests
+    ``SlotScheduler.admit`` would take, so at most len(free_slots). Returns (plan, deferred): plan = [(slot, request, start, donor)] in
+    queue order — the request goes to ``slot``, rows [0, start) of its prompt are already there (donor None) or are to be copied from
+    slot ``donor`` BEFORE the round's prefill, rows [start, len) are to be prefilled — and ``deferred`` = the requests left for the next
+    round of the same pass. The rules:
+      * in place first: the longest match in a free slot nobody took yet is taken as it is (any length, no copy; among free slots that
+        tie on a match shorter than ``min_tokens`` — every prompt starts with the same BOS id — the least recently used one, so that
+        a one-row match does not pick the slot with the youngest record); of two requests that
+        want one free slot the earlier gets it,
+      * fork otherwise: a match of >= ``min_tokens`` rows in a live slot (rows below a live request's prompt length are never rewritten)
+        or in a free slot an earlier request of the round took IN PLACE is copied into another free slot — of the second kind only the
+        rows that request keeps (its ``start``), so no donor is handed to a request that overwrites the forked rows,
+      * a shorter match is dropped: start 0, no donor,
+      * same-round sharing: a request that shares >= ``min_tokens`` rows with an EARLIER request of the round, and more than with any
+        slot, is deferred (and so is every request behind one it shares most with); next round it forks from its leader's slot,
+      * victims: a request without a slot of its own overwrites the free slot with the oldest last-use stamp, lowest index on ties —
+        chosen after every in-place claim, never a slot the round reads from.
+    The index is only read: whoever carries the plan out stamps the donors (``index.touch``) and records the slots."""
+    free, live = list(free_slots), set(live_slots)
+    assert len(requests) <= len(free), "more requests than free slots"
+    placed, deferred, seen = [], [], []             # placed: [request, slot | None, start, donor]
+    kept = {}                                       # free slot taken in place -> rows it keeps
+    for r, ids, sigs in requests:
+        ids, sigs = list(ids), list(sigs)
+        matches = [(g, p) for g, p in index.match(ids, sigs, epoch) if g in live or g in free]
+        # longest first; a free slot before a live one; short ties by last use (equal lengths are all short or all long)
+        matches.sort(key=lambda t: (-t[1], t[0] in live, index.stamp[t[0]] if t[1] < min_tokens else 0, t[0]))
+        best = matches[0][1] if matches else 0
+        shared = max([_common_prefix(i2, s2, ids, sigs, len(ids) - 1) for i2, s2 in seen], default=0)
+        seen.append((ids, sigs))
+        if shared >= min_tokens and shared > best:
+            deferred.append(r)
+            continue
+        choice = [r, None, 0, None]
+        for g, p in matches:
+            if g in free and g not in kept and all(c[1] != g for c in placed):
+                choice = [r, g, p, None]
+                kept[g] = p
+                break
+            rows = p if g in live else min(p, kept.get(g, 0))
+            if rows >= min_tokens:
+                choice = [r, None, rows, g]
+                break
+        placed.append(choice)
+    donors = {c[3] for c in placed if c[3] is not None}
+    pool = sorted((g for g in free if g not in kept), key=lambda g: (index.stamp[g], g))
+    assert not donors & set(pool), "a donor slot must not be overwritten in its own round"
+    for c in placed:
+        if c[1] is None:
+            c[1] = pool.pop(0)
+    return [(c[1], c[0], c[2], c[3]) for c in placed], deferred
+
+
+def simulate_prefix(prompts, lengths, n_slots, max_admit=None, min_tokens=16, sigs=None, generated=None, index=None):
+    """``simulate`` with prefix reuse: request i has the prompt ids ``prompts[i]`` (row signatures ``sigs[i]``; None: the ids themselves)
+    and produces ``lengths[i]`` tokens by decode steps (a forced image chunk's tokens left out, as for ``simulate``). ``generated[i]``
+    (optional) are ALL the ids it produced: a finished slot then holds its prompt and every produced id but the last, which later
+    turns may match; without it only the prompt. ``index``: a PrefixIndex to start from and leave behind (None: empty). Returns
+    ``simulate``'s dict — same decode_steps, live_slot_steps, parked_slot_steps and admissions: only the slots differ — with
+    prefill_passes counting the rounds actually run, plus prefill_tokens (rows forwarded at admission), prefix_hit_tokens (rows not
+    forwarded), forked_tokens (those of them that were copied) and fork_launches (rounds with at least one copy)."""
+    lengths = [int(n) for n in lengths]
+    prompts = [list(p) for p in prompts]
+    sigs = prompts if sigs is None else [list(s) for s in sigs]
+    assert len(prompts) == len(lengths) == len(sigs) and all(n >= 1 for n in lengths)
+    sch = SlotScheduler(n_slots, len(lengths), max_admit)
+    index = PrefixIndex(n_slots) if index is None else index
+    made = {}
+    stats = dict(decode_steps=0, live_slot_steps=0, parked_slot_steps=0, admissions=0, prefill_passes=0, finish_order=[],
+                 prefill_tokens=0, prefix_hit_tokens=0, forked_tokens=0, fork_launches=0)
+
+    def finish(g):
+        r = sch.finish(g)
+        stats["finish_order"].append(r)
+        fed = list(generated[r])[:-1] if generated is not None else []
+        index.record(g, prompts[r] + fed, sigs[r] + fed, 0)
+
+    while not sch.done:
+        sch.new_pass()
+        while True:
+            cand = sch.candidates()
+            if not cand:
+                break
+            plan, _ = plan_admission(index, sch.free_slots(), sch.live_slots(), [(r, prompts[r], sigs[r]) for r in cand], min_tokens)
+            stats["admissions"] += len(plan)
+            stats["prefill_passes"] += 1
+            stats["fork_launches"] += any(d is not None for _, _, _, d in plan)
+            for g, r, start, donor in plan:
+                if donor is not None:
+                    index.touch(donor)
+            for g, r, start, donor in plan:
+                sch.place(g, r)
+                index.record(g, prompts[r], sigs[r], 0)
+                stats["prefill_tokens"] += len(prompts[r]) - start
+                stats["prefix_hit_tokens"] += start
+                stats["forked_tokens"] += start if donor is not None else 0
+            for g, r, _, _ in plan:
+                made[g] = 1
+                if made[g] >= lengths[r]:
+                    finish(g)
+        live = sch.live_slots()
+        if not live:
+            continue
+        stats["decode_steps"] += 1
+        stats["live_slot_steps"] += len(live)
+        stats["parked_slot_steps"] += n_slots - len(live)
+        for g in live:
+            made[g] += 1
+            if made[g] >= lengths[sch.slot_req[g]]:
+                finish(g)
+    return stats

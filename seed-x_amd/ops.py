@@ -939,3 +939,45 @@ def cfg_euler_step(eps, latents, scaled_next, sigmas_dev, step_dev, nb, C_lat, l
     n = latents.numel()
     check(lib.sx_cfg_euler_step(_p(eps), _p(latents), _p(scaled_next), _p(sigmas_dev), _p(step_dev), nb, n, C_lat,
                                 ld_scaled, float(gs), float(igs), mode, _stream()), "sx_cfg_euler_step")
+
+
+# ---- KV-cache prefix fork (prefix reuse of in-flight batching) --------------------------------------------------------
+KV_CACHE_KEYS = ("kc", "vc", "ks", "vs")
+
+
+def kv_fork(caches, pairs):
+    """Copies cache rows [0, n) of slot ``src`` to slot ``dst`` for every (src, dst, n) of ``pairs``, all layers and heads of a cache
+    tensor in ONE sx_kv_fork launch. ``caches``: the LLM's pack (its "kc" / "vc" and, under the FP8 format, "ks" / "vs" tensors: one
+    launch each), one cache tensor, or a list of them — [L, G, heads, Tmax, hd] of any dtype, or [L, G, heads, Tmax] (row scales);
+    the [Tmax, hd] block of a head must be contiguous, the other axes may be strided. The kernel skips a pair whose src or dst is
+    outside [0, G), whose src == dst or whose n <= 0 (include/seedx_hip.h); such pairs are passed on and take no part in the checks
+    below. The pairs of a launch are not ordered, so among the others a dst that occurs twice, a slot that is both read and written, and
+    n > Tmax raise ValueError. Returns the number of launches."""
+    if isinstance(caches, dict):
+        caches = [caches[k] for k in KV_CACHE_KEYS if caches.get(k) is not None]
+    elif isinstance(caches, torch.Tensor):
+        caches = [caches]
+    pairs = [(int(s), int(d), int(n)) for s, d, n in pairs]
+    assert caches, "kv_fork: no cache tensor"
+    G, Tmax = caches[0].shape[1], caches[0].shape[3]
+    live = [(s, d, n) for s, d, n in pairs if 0 <= s < G and 0 <= d < G and s != d and n > 0]
+    dsts = [d for _, d, _ in live]
+    if len(set(dsts)) != len(dsts):
+        raise ValueError(f"kv_fork: a slot receives two prefixes in one call: {pairs}")
+    if set(dsts) & {s for s, _, _ in live}:
+        raise ValueError(f"kv_fork: a slot is both read and written in one call: {pairs}")
+    if any(n > Tmax for _, _, n in live):
+        raise ValueError(f"kv_fork: a prefix is longer than the cache ({Tmax} rows): {pairs}")
+    if not pairs:
+        return 0
+    lib = _lib.load()
+    dev = caches[0].device
+    tab = torch.tensor(pairs, dtype=torch.int32).t().contiguous().to(dev)               # [3, n_pairs]: src, dst, n
+    for t in caches:
+        assert t.is_cuda and t.dim() in (4, 5) and t.shape[1] == G and t.shape[3] == Tmax, "kv_fork: caches of one model"
+        es, row = t.element_size(), (t.shape[4] if t.dim() == 5 else 1)
+        assert t.stride(3) == row and (t.dim() == 4 or t.stride(4) == 1), "kv_fork: a head's [Tmax, hd] block must be contiguous"
+        a = _lib.KvForkArgs(_p(t), _p(tab[0]), _p(tab[1]), _p(tab[2]), t.stride(0) * es, t.stride(1) * es, t.stride(2) * es,
+                            len(pairs), t.shape[0], G, t.shape[2], Tmax, row * es)
+        check(lib.sx_kv_fork(C.byref(a), _stream()), "sx_kv_fork")
+    return len(caches)

@@ -8,12 +8,14 @@ When ``<img>`` is emitted the 64 forced ``<img_i>`` tokens are run as ONE 65-tok
 (identical math, 64× the arithmetic intensity).
 ``generate_batch`` runs G independent requests in lock step (one weight stream from HBM per token step for all G).
 ``generate_inflight`` serves a queue of any length on those G slots: the stop rule runs on the device, a finished slot idles
-inside the captured step and is refilled from the queue before the next one (inflight.py holds the schedule).
+inside the captured step and is refilled from the queue before the next one (inflight.py holds the schedule). With
+``agent.prefix_cache = True`` an admitted request keeps, or gets copied from another slot by one sx_kv_fork launch, the cache rows of the
+longest prompt prefix some slot already holds, and prefills only the rest.
 """
 import torch
 
 from . import ops
-from .inflight import SlotScheduler
+from .inflight import PrefixIndex, SlotScheduler, plan_admission
 from .sampling import SamplingParams
 
 BOI_TOKEN = '<img>'
@@ -22,6 +24,10 @@ IMG_TOKEN = '<img_{:05d}>'
 
 
 class ContinuousLVLM:
+    # default of ``prefix_min_tokens``: the fork / prefill crossover measured on the 40-layer model. Repeated runs put it at 4 or at 8
+    # rows (at 4 the gain is below the run-to-run spread): the larger one (profiles/prefix_cache.md, prefix_cache_crossover_runs.md)
+    PREFIX_MIN_TOKENS = 8
+
     def __init__(self, llm, input_resampler, output_resampler, lm_loss_scale=1.0, rec_loss_scale=1.0,
                  add_patch_pos=False, vit_down=False, mse=False):
         self.llm = llm
@@ -33,6 +39,8 @@ class ContinuousLVLM:
         self.device, self.dtype = None, torch.float16
         self.use_graph = True
         self.chunk_forced_image_tokens = True
+        self.prefix_cache = False        # generate_inflight: reuse the cache rows of a prompt prefix some slot already holds (opt-in)
+        self.prefix_min_tokens = self.PREFIX_MIN_TOKENS   # shortest prefix worth a slot-to-slot copy, or worth waiting one round for
         self._conv = {}                  # sequence → (token ids, row fingerprints, LLM cache epoch) held by its KV cache
         self._sig_w = {}
         self.last_prefill_tokens = []
@@ -178,6 +186,8 @@ class ContinuousLVLM:
         if any(p is not None for p in params):          # per-row parameters on the device; greedy rows keep the arg-max
             ss = llm.sample_state()
             ss.set_rows(range(G), params)
+        if self._inflight is not None:
+            self._inflight["prefix"] = None             # generate_inflight's slot records: this call rewrites the slots
         starts = self._reuse_prefix(prompts) if reuse_cache else [0] * G
         if not reuse_cache:
             llm.reset()
@@ -308,11 +318,27 @@ class ContinuousLVLM:
         one such request runs the sampled token step (sx_sample_next_slots: same stop rule, the parameters are read per slot from
         device memory, greedy requests keep the arg-max); a queue without one runs the greedy step as before. A request's ids depend
         on its own logits, parameters, seed and token indices only — never on its slot or its neighbours.
-        Forced image blocks stay host-driven chunks as in generate_batch (the other slots wait). Cross-turn cache reuse is not
-        offered here: the call clears those records. Slots are reused without zeroing: keys at or above ``pos`` are never visible."""
+        Forced image blocks stay host-driven chunks as in generate_batch (the other slots wait). Slots are reused without zeroing:
+        keys at or above ``pos`` are never visible. generate_batch's cross-turn records (``reuse_cache``) are cleared by this call.
+        Prefix reuse is switched on the engine, like ``use_graph``: ``agent.prefix_cache = True`` (off by default: the call then takes
+        the lowest free slot and prefills every prompt from row 0, as ever) and ``agent.prefix_min_tokens``. With it the engine
+        remembers what each slot's cache holds — token ids and ``_row_sig`` fingerprints of the prompt rows, image rows included, and of
+        the generated tokens that were fed back — across admissions AND across calls. The records are validated by
+        ``llm.kv_epoch``: ``llm.forward``, ``forward_embeds``, ``reset`` and ``park_slots`` move it and so end the records, and
+        generate_batch drops them itself. ``llm.forward_embeds_batch``, ``decode_step`` and ``set_position`` do NOT move the epoch (the
+        engines are built from them): whoever calls those directly between two cached calls must ``llm.reset()`` afterwards. An admitted request
+        whose prompt starts like a record keeps those rows where the slot is free, or has them copied from the live or just-claimed
+        donor slot (>= ``prefix_min_tokens`` rows; ops.kv_fork: one launch per cache tensor and round, issued before the round's
+        prefill), and prefills only its suffix; requests that share a prefix with an earlier request of their own round (one prompt
+        under several seeds) wait one round and fork from it (inflight.plan_admission states the rules). Which requests a pass
+        admits does not change, so the step counts stay inflight.simulate's; ``last_prefill_tokens`` lists the suffix lengths and
+        ``last_inflight_stats`` also counts prefix_hit_tokens, forked_tokens and fork_launches (inflight.simulate_prefix predicts them).
+        Reused rows are the rows an earlier pass wrote: results agree with the uncached call like generate_batch's ``reuse_cache``
+        (identical ids, states within the prefill-shape rounding)."""
         llm = self.llm
         if llm.comm.world > 1:
             raise NotImplementedError("generate_inflight is single-rank: tensor-parallel ranks are not supported")
+        prefix_cache, prefix_min_tokens = bool(self.prefix_cache), int(self.prefix_min_tokens)
         requests = list(requests)
         N = len(requests)
         assert N >= 1, "generate_inflight needs at least one request"
@@ -334,23 +360,49 @@ class ContinuousLVLM:
                 img_ids_dev=torch.tensor(img_ids, dtype=torch.int32, device=dev),
                 out_ids=torch.full((G, rows), -1, dtype=torch.int32, device=dev),
                 hid=torch.zeros((G, rows, H), dtype=torch.float32, device=dev),              # row k = state at input new[k-1]
-                state=None, state_sampled=None)
-        llm.reset()                                      # bumps kv_epoch: the cross-turn records no longer describe the cache
+                state=None, state_sampled=None,
+                prefix=keep["prefix"] if keep is not None and keep["key"] == (tuple(img_ids), eos, G, id(P)) else None)
+        index = None
+        if prefix_cache:                                 # what each slot's cache holds; lives next to the buffers, across calls
+            index = keep["prefix"] = keep["prefix"] or PrefixIndex(G)
+
+        def owned(fn, *a):
+            # a step of this call that moves kv_epoch without touching a recorded row: the records move with it. A write from outside
+            # moves the epoch alone, and the records made under the old one never match again
+            e0 = llm.kv_epoch
+            out = fn(*a)
+            if index is not None:
+                index.restamp(e0, llm.kv_epoch)
+            return out
+
+        owned(llm.reset)                                 # bumps kv_epoch: the cross-turn records no longer describe the cache
         self._conv = {}
         which = "state_sampled" if sampled else "state"        # two slot states, two captured steps: neither disturbs the other
         if keep[which] is None:
-            keep[which] = llm.slot_state(force_id=boi_id, eos_id=eos, sampling=sampled)
+            keep[which] = owned(lambda: llm.slot_state(force_id=boi_id, eos_id=eos, sampling=sampled))
         st, img_ids_dev, out_ids, hid = keep[which], keep["img_ids_dev"], keep["out_ids"], keep["hid"]
-        llm.park_slots(range(G), st)
+        owned(llm.park_slots, range(G), st)
         sched = SlotScheduler(G, N, max_admit)
         results = [None] * N
         n_new, cur = [0] * G, [0] * G                    # host mirrors of the live slots' state
         stats = dict(decode_steps=0, live_slot_steps=0, parked_slot_steps=0, admissions=0, prefill_passes=0, prefill_tokens=0)
+        if prefix_cache:
+            stats.update(prefix_hit_tokens=0, forked_tokens=0, fork_launches=0)
         self.last_prefill_tokens = []
+        prompts, held = {}, {}                           # prefix_cache: request -> (ids, x, row signatures); slot -> (ids, signatures)
+
+        def sigs_of(x):
+            return [tuple(s) for s in self._row_sig(x).tolist()]
 
         def harvest(g, n):
             r = sched.finish(g)
             generate_ids = out_ids[g, :n].cpu().long()
+            if index is not None:                        # the slot now holds its prompt and the generated ids that were fed back
+                ids, sig = held.pop(g)
+                fed = generate_ids[:n - 1].tolist()
+                if fed:
+                    sig = sig + sigs_of(ops.embedding(torch.tensor(fed, dtype=torch.int32, device=dev), P["embed"]))
+                index.record(g, ids + fed, sig, llm.kv_epoch)
             last_hidden = hid[g, 1:n].clone()                                                # the slot's rows are reused
             results[r] = self._result(tokenizer, generate_ids, last_hidden, boi_id, eoi_id, num_img_gen_tokens)
             if params[r] is not None:
@@ -361,18 +413,22 @@ class ContinuousLVLM:
         def stopped(g):
             return n_new[g] >= budget[sched.slot_req[g]] or (eos >= 0 and cur[g] == eos)
 
-        def admit_round(adm):
-            # ONE batched prefill over the admitted slots; token 1 of each comes from it (host-side stop test: not in the graph)
+        def admit_round(adm, starts=None):
+            # ONE batched prefill over the admitted slots; token 1 of each comes from it (host-side stop test: not in the graph).
+            # ``starts`` (prefix_cache): rows [0, starts[i]) of slot i's prompt are in its cache already, the rest is forwarded
             slots = [g for g, _ in adm]
             xs, last_ids = [], []
-            for g, r in adm:
-                ids, x = self._prompt_embeds(tokenizer, requests[r])
+            for i, (g, r) in enumerate(adm):
+                ids, x = prompts.pop(r)[:2] if starts is not None else self._prompt_embeds(tokenizer, requests[r])
                 assert len(ids) + budget[r] <= llm.Tmax, "KV cache too small for prompt + max_new_tokens"
-                xs.append(x)
+                xs.append(x if starts is None else x[starts[i]:])
                 last_ids.append(ids[-1])
-            llm._slot_write(P["pos"], slots, 0)
-            llm._slot_write(P["ctx"], slots, 1)
+            llm._slot_write(P["pos"], slots, 0 if starts is None else list(starts))
+            llm._slot_write(P["ctx"], slots, 1 if starts is None else [s + 1 for s in starts])
             logits, _ = llm.forward_embeds_batch(xs, slots)
+            if starts is not None:                       # the slots hold their prompts now
+                for g in slots:
+                    index.record(g, held[g][0], held[g][1], llm.kv_epoch)
             first = torch.tensor(last_ids, dtype=torch.int32, device=dev)
             if sampled:                                  # the slots take their requests' parameters; token index 0 is drawn here
                 st.sampling.set_rows(slots, [params[r] for _, r in adm])
@@ -398,17 +454,42 @@ class ContinuousLVLM:
             llm._slot_write(st.live, slots, 1)
             fin = [g for g in slots if stopped(g)]
             if fin:
-                llm.park_slots(fin, st)
+                owned(llm.park_slots, fin, st)
                 for g in fin:
                     harvest(g, n_new[g])
+
+        def admit_round_prefix(cand):
+            # plan → fork → suffix prefill. The forks of a round are issued before its prefill: a donor's rows are read as they were
+            for r in cand:
+                if r not in prompts:                     # (a deferred request keeps its embeddings for the next round)
+                    ids, x = self._prompt_embeds(tokenizer, requests[r])
+                    prompts[r] = (ids, x, sigs_of(x))
+            plan, _ = plan_admission(index, sched.free_slots(), sched.live_slots(), [(r, prompts[r][0], prompts[r][2]) for r in cand],
+                                     prefix_min_tokens, llm.kv_epoch)
+            forks = [(d, g, start) for g, _, start, d in plan if d is not None]
+            if forks:
+                ops.kv_fork(P, forks)
+                stats["fork_launches"] += 1
+                for d, _, _ in forks:
+                    index.touch(d)
+            for g, r, start, d in plan:
+                sched.place(g, r)
+                held[g] = (list(prompts[r][0]), prompts[r][2])
+                index.invalidate(g)                      # rows [start, ...) are about to be rewritten: recorded again after the prefill
+                stats["prefix_hit_tokens"] += start
+                stats["forked_tokens"] += start if d is not None else 0
+            admit_round([(g, r) for g, r, _, _ in plan], [start for _, _, start, _ in plan])
 
         while not sched.done:
             sched.new_pass()
             while True:
-                adm = sched.admit()
+                adm = sched.candidates() if prefix_cache else sched.admit()
                 if not adm:
                     break
-                admit_round(adm)
+                if prefix_cache:
+                    admit_round_prefix(adm)
+                else:
+                    admit_round(adm)
             live = sched.live_slots()
             hit = [g for g in live if self.chunk_forced_image_tokens and cur[g] == boi_id
                    and n_new[g] + nchunk <= budget[sched.slot_req[g]]]
@@ -422,7 +503,7 @@ class ContinuousLVLM:
                 llm._slot_write(P["cur"], hit, eoi_id)
                 fin = [g for g in hit if stopped(g)]
                 if fin:
-                    llm.park_slots(fin, st)
+                    owned(llm.park_slots, fin, st)
                     for g in fin:
                         harvest(g, n_new[g])
                 live = sched.live_slots()
@@ -438,7 +519,7 @@ class ContinuousLVLM:
                 cur[g], alive, n_new[g], fin_n = status[g]
                 if not alive:
                     harvest(g, fin_n)
-        llm.reset()                                      # pos / ctx / step leave their idle values
+        owned(llm.reset)                                 # pos / ctx / step leave their idle values
         self.last_inflight_stats = stats
         return results
 
