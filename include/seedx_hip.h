@@ -34,6 +34,8 @@ extern "C" {
                      * of the fp32-grade VAE convs whose weights are exact in fp16 (W duplicated per tap: A.W = Ah.W + Al.W) */
 #define SX_FP8_E4M3 5 /* sx_gemv_args.w_dtype only: OCP e4m3fn weight codes (1-4-3, bias 7, no infinities; the NaN codes 0x7f / 0xff never
                        * occur) with one fp32 scale per weight row, W[n][k] = decode(code[n][k]) * w_scale[n] */
+#define SX_FP4_E2M1 6 /* sx_gemv_args.w_dtype only: OCP MXFP4 weight codes (e2m1: sign + magnitudes 0, .5, 1, 1.5, 2, 3, 4, 6; two per byte)
+                       * with one E8M0 scale byte per block of 32 consecutive k of a row, W[n][k] = decode(code[n][k]) * 2^(byte - 127) */
 /* OR-ed into a 16-bit OUTPUT dtype of the decode-step producers (sx_layernorm with rows <= 32, sx_attn_decode_b, sx_gemv):
  * the [rows <= 32][cols] result is written as MFMA operand tiles [rows/16][cols/32][16][32] — what sx_gemv reads with x_layout = 1
  * (tile t = columns 32t .. 32t+31 of all 16 rows, 1 KB contiguous; rows >= `rows` of a tile are not written). */
@@ -193,10 +195,27 @@ typedef struct sx_gemv_args {
                         * order). Multiplies the summed accumulators of row n once — after the wave, split-K and plane sums, before rstd
                         * (row_ssq_in), activation, GLU, residual and the plane / sum-of-squares outputs. A power-of-two scale commutes with
                         * every fp32 rounding: the result then has the bits of the 16-bit kernel on the weights code * scale. */
+  const void* w_block_scale; /* with w_dtype = SX_FP4_E2M1 (else NULL; w_scale must then be NULL): the E8M0 block scales of the MXFP4 form
+                        * of w_layout 1 or 2 (MFMA path only; row-major W, a missing or not 16-B aligned scale array, a shape outside the
+                        * MFMA path or w_scale set are SX_ERR_INVALID, never a fall-back). The kernel keeps its 64-k step:
+                        *   W, w_layout 1: [N/16][K/64][16][32 B] — a 64-k slab of 16 rows is one 512-B tile; byte 8 g + 4 h + i of a row
+                        *     holds k = 64 t + 32 h + 8 g + 2 i in its low nibble and k + 1 in its high one (g = 0..3, h = 0..1, i = 0..3):
+                        *     lane (row r, group g) of the 16x16x32 MFMA loads the 8 bytes at 32 r + 8 g, dword h = its eight k-slots of
+                        *     32-k half h in nibble order, all in ONE 32-k block — one scale per dword,
+                        *   W, w_layout 2: [N/20][K/64][20][32 B] — the 512-B tile of rows 0..15, then rows 16..19 (128 B), same byte order,
+                        *   w_block_scale, w_layout 1: [N/16][K/64][16][2] bytes, byte h of (row r, k-step t) = the E8M0 byte of block 2 t + h
+                        *     of that row (one 2-B load per lane and k-step); w_layout 2: [N/20][K/64][20][2], rows 16..19 behind rows 0..15.
+                        * Rows are in the order of W as passed (GLU-packed rows: packed order). Each dword becomes four packed converts
+                        * (v_cvt_scalef32_pk_{f16,bf16}_fp4, the block scale applied in the convert: every code * 2^e with e in [-13, 13] is
+                        * a normal fp16 / bf16 number, so the operand is exact) in front of the same MFMAs, k-slices and epilogue as the
+                        * 16-bit tiles: the result has the bits of the 16-bit kernel on the dequantised weights. No row scale. */
 } sx_gemv_args;
 /* workgroups in x (= partial rows of row_ssq_out) sx_gemv launches for an M x N x K problem with / without GLU on the MFMA path */
 int sx_gemv_ssq_parts(int N, int glu, int w_layout);
 int sx_gemv(const sx_gemv_args* args, void* stream);
+/* host only, nothing is launched: the launch sx_gemv would make for these SX_FP4_E2M1 args (same checks, same status) —
+ * plan[0..5] = workgroups in x, split-K factor, then the kernel family (R, U, TAIL, MB) of gemm_skinny_kernel */
+int sx_gemv_fp4_plan(const sx_gemv_args* args, int32_t* plan);
 /* test hook: 1 = always take the VALU path (lets the tests compare both), 0 = automatic */
 int sx_gemv_force_valu(int on);
 /* tuning hook (tools/lab/gemv_lab): key 2 = split-K factor of the MFMA skinny GEMM when a workspace is given:

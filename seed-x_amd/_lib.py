@@ -12,6 +12,7 @@ SX_F16, SX_BF16, SX_F32 = 0, 1, 2
 SX_BF16X3 = 3          # sx_groupnorm* output only: bf16 planes [hi | hi | lo] per row
 SX_F16X2 = 4           # sx_groupnorm* output only: fp16 planes [hi | lo] per row
 SX_FP8_E4M3 = 5        # sx_gemv_args.w_dtype only: e4m3fn weight codes + fp32 row scales
+SX_FP4_E2M1 = 6        # sx_gemv_args.w_dtype only: MXFP4 (e2m1) weight codes + E8M0 block scales (w_block_scale)
 SX_TILED16 = 0x100     # OR-ed into a 16-bit out dtype: decode operand tiles [cols/32][16][32] (include/seedx_hip.h)
 SX_ACT_NONE, SX_ACT_GELU, SX_ACT_SILU = 0, 1, 2
 SX_A_LINEAR, SX_A_CONV3X3 = 0, 1
@@ -40,7 +41,7 @@ class GemvArgs(C.Structure):
                 ("w_layout", c_i32), ("x_layout", c_i32), ("workspace", c_vp), ("workspace_bytes", C.c_uint64),
                 ("x16_out", c_vp), ("row_ssq_out", c_vp), ("row_ssq_in", c_vp), ("ssq_in_parts", c_i32), ("ssq_dim", c_i32),
                 ("ssq_eps", c_f32), ("x_planes", c_i32), ("out_planes", c_i32), ("x16_gamma", c_vp),
-                ("w_dtype", c_i32), ("w_scale", c_vp)]
+                ("w_dtype", c_i32), ("w_scale", c_vp), ("w_block_scale", c_vp)]
 
 
 class AttnF32Args(C.Structure):
@@ -114,6 +115,7 @@ SIGNATURES = {
     "sx_gemm_pick_tile": [c_i32, c_i32, c_i32, c_i32, c_i32],
     "sx_gemv": [C.POINTER(GemvArgs), c_vp],
     "sx_gemv_ssq_parts": [c_i32, c_i32, c_i32],
+    "sx_gemv_fp4_plan": [C.POINTER(GemvArgs), C.POINTER(c_i32)],
     "sx_gemv_force_valu": [c_i32],
     "sx_layernorm": [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_f32, c_i32, c_vp],
     "sx_softmax_rows": [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_f32, c_i32, c_vp],

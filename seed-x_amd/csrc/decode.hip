@@ -30,6 +30,7 @@ struct GemvP {
   int out_planes;          // the 16-bit tiled output (y_tiled) or x16_out is written as two planes: block 0 = hi, block 1 = lo (rows <= 16)
   const float* x16_gamma;  // x16_out holds o * gamma[col] (the NEXT RMSNorm's gamma applied on the activation side: the weights stay exact)
   const float* w_scale;    // FP8 weight tiles (W8 kernels): fp32 [N], row n of W as passed is e4m3 code * w_scale[n]
+  const unsigned char* w_bscale;   // MXFP4 weight tiles (W4 kernels): E8M0 bytes [N/16][K/64][16][2] (20-row tiles: [N/20][K/64][20][2])
 };
 
 template <typename TT, int MR>
@@ -171,6 +172,28 @@ __device__ __forceinline__ typename TT::vec8 fp8x8_to16(unsigned d0, unsigned d1
   return __builtin_bit_cast(typename TT::vec8, o);
 }
 
+// Eight e2m1 codes (one dword = one lane's k-slots of one 32-k half, nibble j = slot j, all in one 32-k block) times that block's scale
+// 2^e → the eight 16-bit MFMA operand elements: one packed convert per byte, the scale applied inside it. Exact: every code * 2^e with
+// e in [-13, 13] is a normal fp16 number with one mantissa bit (and one of bf16).
+template <typename TT>
+__device__ __forceinline__ typename TT::vec8 fp4x8_to16(unsigned d, float sc) {
+  u32x4_t o;
+#if defined(__HIP_DEVICE_COMPILE__)
+  if (std::is_same<TT, F16>::value) {
+    o[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(d, sc, 0));
+    o[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(d, sc, 1));
+    o[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(d, sc, 2));
+    o[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(d, sc, 3));
+  } else {
+    o[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 0));
+    o[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 1));
+    o[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 2));
+    o[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, sc, 3));
+  }
+#endif
+  return __builtin_bit_cast(typename TT::vec8, o);
+}
+
 // MB = 2 (17..32 activation rows, lock-step batch 32): the x operand is two 16-row blocks — tiles [2][K/32][16][32] or rows 16..31 of
 // the row-major x — and every weight fragment feeds two MFMAs, so the weights still stream ONCE for all 32 sequences. Outputs, the
 // 16-bit tiled output, x16_out and the sums of squares follow the same block structure (row m = 16 b + r).
@@ -178,11 +201,16 @@ __device__ __forceinline__ typename TT::vec8 fp8x8_to16(unsigned d0, unsigned d1
 // tile [16][64] whose rows are ordered so that lane (r, g) finds its eight k-slots of both 32-k halves in one 16-B load (include/
 // seedx_hip.h) — half the bytes and half the weight loads per k-step. The codes become 16-bit operand elements in registers (exact,
 // fp8x8_to16) in front of the same MFMAs; the fp32 row scale multiplies the summed accumulators once in wave 0's epilogue.
-template <typename TT, int R, int NWV, int U, bool TAIL = false, int MB = 1, bool W8 = false>
+// W4 (w_dtype = SX_FP4_E2M1, w_layout 1 / 2 only): MXFP4 tiles — a 64-k slab of 16 rows is one 512-B tile [16][32 B], lane (r, g) loads
+// the 8 bytes at 32 r + 8 g (dword h = its eight k-slots of 32-k half h) and the two E8M0 bytes of (row, k-step) from w_bscale; the same
+// 64-k step and the same k-slices per wave as the 16-bit kernel. fp4x8_to16 makes the exact operand code * 2^e in front of the same
+// MFMAs, so there is no scale in the epilogue: it is the 16-bit one.
+template <typename TT, int R, int NWV, int U, bool TAIL = false, int MB = 1, bool W8 = false, bool W4 = false>
 __global__ __launch_bounds__(NWV * 64) void gemm_skinny_kernel(const GemvP p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef typename TT::vec8 vec8;
   static_assert(!TAIL || R == 2, "the 20-row variant is two MFMA row blocks");
+  static_assert(!(W8 && W4), "one weight format");
   __shared__ float red[NWV - 1][R * MB][64][4];   // waves 1 .. NWV-1 hand their partial sums to wave 0 (which keeps its own in registers)
   // the wave index as a SCALAR: everything derived from it (k range, round counts) then lives in SGPRs and the guards below
   // are scalar branches. With a VGPR-derived count the compiler predicates the guarded MFMAs through EXEC instead — and
@@ -224,6 +252,27 @@ __global__ __launch_bounds__(NWV * 64) void gemm_skinny_kernel(const GemvP p) {
     wp[0] = p.W + (size_t)blockIdx.x * (size_t)(p.K >> 5) * (640 / WD) + r * 32 + 8 * g;   // (FP8: [N/20][K/64][20][64], rows 16..19 behind the 1-KB tile)
     if (r < 4) wp[R - 1] = wp[0] + 512;
     else { wp[R - 1] = (const unsigned short*)g_zero_line; kstep_q[R - 1] = 0; khalf_q[R - 1] = 0; }   // operand rows 4..15 of block 1 = 0
+  }
+  // MXFP4 tiles: 512 B (20-row: 640 B) of codes and 32 B (40 B) of scales per 64-k step; lane offset 32 r + 8 g bytes / 2 r bytes
+  const unsigned char* sp[R];
+  size_t sstep_q[R];
+  if constexpr (W4) {
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+      kstep_q[q] = TAIL ? 320 : 256;
+      sstep_q[q] = TAIL ? 40 : 32;
+      wp[q] = p.W + (size_t)(n0 / 16 + q) * (size_t)(p.K >> 6) * 256 + r * 16 + 4 * g;
+      sp[q] = p.w_bscale + (size_t)(n0 / 16 + q) * (size_t)(p.K >> 6) * 32 + 2 * r;
+    }
+    if (TAIL) {   // [N/20][K/64][20][32 B]: rows 16..19 behind the 512-B tile; scales [N/20][K/64][20][2] alike
+      wp[0] = p.W + (size_t)blockIdx.x * (size_t)(p.K >> 6) * 320 + r * 16 + 4 * g;
+      sp[0] = p.w_bscale + (size_t)blockIdx.x * (size_t)(p.K >> 6) * 40 + 2 * r;
+      if (r < 4) { wp[R - 1] = wp[0] + 256; sp[R - 1] = sp[0] + 32; }
+      else {      // operand rows 4..15 of block 1: code 0 from the zero line, whatever the scale bits (0 * 2^e = 0)
+        wp[R - 1] = (const unsigned short*)g_zero_line; kstep_q[R - 1] = 0;
+        sp[R - 1] = (const unsigned char*)g_zero_line; sstep_q[R - 1] = 0;
+      }
+    }
   }
   f32x4_t acc[R][MB];
 #pragma unroll
@@ -270,7 +319,9 @@ __global__ __launch_bounds__(NWV * 64) void gemm_skinny_kernel(const GemvP p) {
   // rounds and the < U remainder are peeled. Measured (tools/lab/gemv_lab, profiles/r3_ab_experiments.md §6): the deeper
   // flight alone changes nothing (+-1 %) — the wide shapes already stream at 6.5-6.9 TB/s net of the 3-4 us launch cost;
   // what moved the numbers was the x layout (L2 channel conflicts) and, for K = 13824, split-K.
-  struct Frag { u32x4_t wa[U][R], wb[U][R], xa[U][MB], xb[U][MB]; };
+  struct Frag16 { u32x4_t wa[U][R], wb[U][R], xa[U][MB], xb[U][MB]; };
+  struct Frag4 { u32x2_t wa[U][R]; unsigned short ws[U][R]; u32x4_t xa[U][MB], xb[U][MB]; };   // MXFP4: 8 B of codes + the two E8M0 bytes of (row, k-step)
+  typedef std::conditional_t<W4, Frag4, Frag16> Frag;
   auto load_round = [&](Frag& f, int ks, int cnt) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -278,8 +329,13 @@ __global__ __launch_bounds__(NWV * 64) void gemm_skinny_kernel(const GemvP p) {
         const size_t k = (size_t)(ks + u) * xstep;
 #pragma unroll
         for (int q = 0; q < R; ++q) {
-          f.wa[u][q] = __builtin_nontemporal_load((const u32x4_t*)(wp[q] + (size_t)(ks + u) * kstep_q[q]));
-          if (!W8) f.wb[u][q] = __builtin_nontemporal_load((const u32x4_t*)(wp[q] + (size_t)(ks + u) * kstep_q[q] + khalf_q[q]));
+          if constexpr (W4) {
+            f.wa[u][q] = __builtin_nontemporal_load((const u32x2_t*)(wp[q] + (size_t)(ks + u) * kstep_q[q]));
+            f.ws[u][q] = *(const unsigned short*)(sp[q] + (size_t)(ks + u) * sstep_q[q]);
+          } else {
+            f.wa[u][q] = __builtin_nontemporal_load((const u32x4_t*)(wp[q] + (size_t)(ks + u) * kstep_q[q]));
+            if (!W8) f.wb[u][q] = __builtin_nontemporal_load((const u32x4_t*)(wp[q] + (size_t)(ks + u) * kstep_q[q] + khalf_q[q]));
+          }
         }
 #pragma unroll
         for (int b = 0; b < MB; ++b) {
@@ -299,12 +355,23 @@ __global__ __launch_bounds__(NWV * 64) void gemm_skinny_kernel(const GemvP p) {
 #pragma unroll
         for (int q = 0; q < R; ++q) {
           // FP8: the conversion is VALU work on loaded registers too — here, for the k-step being consumed, never at the top of the round
+          if constexpr (W4) {   // MXFP4: dword h = the eight k-slots of half h, byte h of ws = its block's E8M0 scale (fp32 bits: byte << 23)
+            const unsigned sc = f.ws[u][q];
+            const vec8 wa = fp4x8_to16<TT>(f.wa[u][q][0], __uint_as_float((sc & 0xffu) << 23));
+            const vec8 wb = fp4x8_to16<TT>(f.wa[u][q][1], __uint_as_float((sc >> 8) << 23));
+#pragma unroll
+            for (int b = 0; b < MB; ++b) {
+              acc[q][b] = TT::mfma16(wa, __builtin_bit_cast(vec8, f.xa[u][b]), acc[q][b]);
+              acc[q][b] = TT::mfma16(wb, __builtin_bit_cast(vec8, f.xb[u][b]), acc[q][b]);
+            }
+          } else {
           const vec8 wa = W8 ? fp8x8_to16<TT>(f.wa[u][q][0], f.wa[u][q][1]) : __builtin_bit_cast(vec8, f.wa[u][q]);
           const vec8 wb = W8 ? fp8x8_to16<TT>(f.wa[u][q][2], f.wa[u][q][3]) : __builtin_bit_cast(vec8, f.wb[u][q]);
 #pragma unroll
           for (int b = 0; b < MB; ++b) {
             acc[q][b] = TT::mfma16(wa, __builtin_bit_cast(vec8, f.xa[u][b]), acc[q][b]);
             acc[q][b] = TT::mfma16(wb, __builtin_bit_cast(vec8, f.xb[u][b]), acc[q][b]);
+          }
           }
         }
       }
@@ -1305,7 +1372,10 @@ extern "C" int sx_gemv_ssq_parts(int N, int glu, int w_layout) {
   return (glu || N / 32 >= 256) ? N / 32 : N / 16;
 }
 
-extern "C" int sx_gemv(const sx_gemv_args* a, void* stream) {
+// the MXFP4 launcher (behind sx_gemv): plan != nullptr → only reports the launch it would make
+static int gemv_fp4_go(const sx_gemv_args* a, GemvP& p, bool planes2, void* stream, int32_t* plan);
+
+static int gemv_entry(const sx_gemv_args* a, void* stream, int32_t* plan) {
   SX_CHECK(a && a->x && a->W && a->y, "sx_gemv: null pointer");
   SX_CHECK(a->dtype == SX_F16 || a->dtype == SX_BF16, "sx_gemv: dtype");
   SX_CHECK(a->M >= 1 && a->M <= 32, "sx_gemv: M=%d must be 1..32", a->M);
@@ -1341,17 +1411,28 @@ extern "C" int sx_gemv(const sx_gemv_args* a, void* stream) {
   // MI355X (tools/bench_gemv.py, 13B shapes): VALU path 6.5 / 4.7 / 3.0 TB/s at M = 1 / 4 / 8, MFMA path 4.0-4.4 TB/s at any M
   const bool mfma_ok = (a->M >= 2 || planes2) && a->K % 64 == 0 && a->K >= 256 && a->N % 32 == 0;
   // FP8 weight tiles: codes + fp32 row scales, tiled layouts and the MFMA kernel only (the VALU kernel has no FP8 form)
-  SX_CHECK(a->w_dtype == 0 || a->w_dtype == SX_FP8_E4M3, "sx_gemv: w_dtype must be 0 (the activation dtype) or SX_FP8_E4M3");
+  SX_CHECK(a->w_dtype == 0 || a->w_dtype == SX_FP8_E4M3 || a->w_dtype == SX_FP4_E2M1,
+           "sx_gemv: w_dtype must be 0 (the activation dtype), SX_FP8_E4M3 or SX_FP4_E2M1");
   const bool w8 = a->w_dtype == SX_FP8_E4M3;
   SX_CHECK(!w8 || ((a->w_layout == 1 || a->w_layout == 2) && mfma_ok),
            "sx_gemv: SX_FP8_E4M3 weights need w_layout 1 or 2 and the MFMA path (M >= 2, K %% 64 == 0, K >= 256, N %% 32 == 0)");
   SX_CHECK(!w8 || (a->w_scale && ((uintptr_t)a->w_scale & 15) == 0), "sx_gemv: SX_FP8_E4M3 weights need w_scale (16-B aligned fp32 [N])");
   SX_CHECK(w8 || !a->w_scale, "sx_gemv: w_scale belongs to SX_FP8_E4M3 weights");
   p.w_scale = a->w_scale;
+  // MXFP4 weight tiles: codes + E8M0 block scales, tiled layouts and the MFMA kernel only, no row scale
+  const bool w4 = a->w_dtype == SX_FP4_E2M1;
+  SX_CHECK(!w4 || ((a->w_layout == 1 || a->w_layout == 2) && mfma_ok),
+           "sx_gemv: SX_FP4_E2M1 weights need w_layout 1 or 2 and the MFMA path (M >= 2, K %% 64 == 0, K >= 256, N %% 32 == 0)");
+  SX_CHECK(!w4 || (a->w_block_scale && ((uintptr_t)a->w_block_scale & 15) == 0),
+           "sx_gemv: SX_FP4_E2M1 weights need w_block_scale (16-B aligned E8M0 bytes)");
+  SX_CHECK(w4 || !a->w_block_scale, "sx_gemv: w_block_scale belongs to SX_FP4_E2M1 weights");
+  p.w_bscale = (const unsigned char*)a->w_block_scale;
   SX_CHECK(!a->w_layout || (mfma_ok && a->K % 64 == 0), "sx_gemv: the decode-tile layout needs M >= 2, K %% 64 == 0, K >= 256, N %% 32 == 0");
   // the decode-tile layout only exists for the MFMA kernel: it overrides the VALU test hook
   SX_CHECK(!p.y_tiled || mfma_ok, "sx_gemv: a tiled output needs the MFMA path (M >= 2, K %% 64 == 0, K >= 256, N %% 32 == 0)");
   SX_CHECK(!a->x_layout || mfma_ok, "sx_gemv: tiled x needs the MFMA path (M >= 2, K %% 64 == 0, K >= 256, N %% 32 == 0)");
+  if (w4) return gemv_fp4_go(a, p, planes2, stream, plan);
+  SX_CHECK(!plan, "sx_gemv_fp4_plan: w_dtype must be SX_FP4_E2M1");
   if (mfma_ok && (a->w_layout || a->x_layout || p.y_tiled || (g_force_valu_gemv != 1 && (a->M >= 5 || g_force_valu_gemv == 2)))) {
     // MFMA skinny GEMM: R = 2 row groups per wave for GLU (one packed group) or when that still gives >= 256 blocks
     const bool tail20 = a->w_layout == 2;
@@ -1422,6 +1503,62 @@ extern "C" int sx_gemv(const sx_gemv_args* a, void* stream) {
 #undef SX_GEMV_GO
   SX_HIP_LAUNCH_CHECK();
   return SX_OK;
+}
+
+extern "C" int sx_gemv(const sx_gemv_args* a, void* stream) { return gemv_entry(a, stream, nullptr); }
+extern "C" int sx_gemv_fp4_plan(const sx_gemv_args* a, int32_t* plan) {
+  SX_CHECK(plan, "sx_gemv_fp4_plan: null pointer");
+  return gemv_entry(a, nullptr, plan);
+}
+
+// MXFP4 tiles: sx_gemv's MFMA dispatch restated for the W4 kernels — the same tail20 / r2 / r4 / gx / S rules and the same (R, U, TAIL, MB)
+// family per case as the 16-bit / FP8 block above (tests/test_fp4_weights_cpu.py compares the two texts and, through sx_gemv_fp4_plan,
+// the workgroup counts with sx_gemv_ssq_parts): an MXFP4 launch has the grid, the k-slices and the split factor of its 16-bit twin.
+static int gemv_fp4_go(const sx_gemv_args* a, GemvP& p, bool planes2, void* stream, int32_t* plan) {
+    const bool tail20 = a->w_layout == 2;
+    const bool r2 = !tail20 && (a->glu || a->N / 32 >= 256);
+    const bool r4 = r2 && g_skinny_var[3] > 0 && a->N % 64 == 0 && !a->x16_out && (a->N / 64 >= (g_skinny_var[3] == 2 ? 64 : 200));
+    const int gx = tail20 ? a->N / 20 : (r4 ? a->N / 64 : (r2 ? a->N / 32 : a->N / 16));
+    int S = 1;
+    if (a->workspace && !(tail20 && g_skinny_var[2] <= 0)) {
+      if (g_skinny_var[2] > 0) S = g_skinny_var[2];
+      else if (g_skinny_var[2] == 0 && a->K >= 8192) while (S < 8 && gx * S < 1024 && (a->K / 64) / (2 * S * 4) >= 4) S *= 2;
+      const uint64_t cnt_bytes = 16384;
+      if (S > 1 && (gx > 4096 || cnt_bytes + (uint64_t)S * (a->M > 16 ? (planes2 ? 64 : 32) : (planes2 ? 32 : 16)) * a->N * 4 > a->workspace_bytes)) S = 1;
+      p.ws_cnt = (unsigned*)a->workspace;
+      p.ws_part = (float*)((char*)a->workspace + cnt_bytes);
+    }
+    const dim3 grid(gx, S);
+#define SX_SK4_K(R_, U_, TAIL_, MB_)                                                                               \
+    { if (plan) { plan[2] = R_; plan[3] = U_; plan[4] = TAIL_; plan[5] = MB_; }                                     \
+      else if (a->dtype == SX_BF16) hipLaunchKernelGGL((gemm_skinny_kernel<BF16, R_, 4, U_, TAIL_, MB_, false, true>), grid, dim3(256), 0, ST, p); \
+      else hipLaunchKernelGGL((gemm_skinny_kernel<F16, R_, 4, U_, TAIL_, MB_, false, true>), grid, dim3(256), 0, ST, p); }
+    if (plan) { plan[0] = gx; plan[1] = S; }
+    if (a->M > 16 && planes2 && r4) {
+      SX_SK4_K(4, 1, false, 4)
+    } else if (a->M > 16 && planes2) {
+      if (tail20) SX_SK4_K(2, 1, true, 4)
+      else if (r2) SX_SK4_K(2, 1, false, 4)
+      else SX_SK4_K(1, 2, false, 4)
+    } else if (r4) {
+      if (a->M > 16 || planes2) SX_SK4_K(4, 1, false, 2)
+      else SX_SK4_K(4, 2, false, 1)
+    } else if (a->M > 16 || planes2) {
+      if (g_skinny_var[1] == 1) {
+        if (tail20) SX_SK4_K(2, 4, true, 2)
+        else if (r2) SX_SK4_K(2, 4, false, 2)
+        else SX_SK4_K(1, 4, false, 2)
+      } else if (tail20 && g_skinny_var[1] == 2) SX_SK4_K(2, 4, true, 2)
+      else if (tail20) SX_SK4_K(2, 2, true, 2)
+      else if (r2) SX_SK4_K(2, 2, false, 2)
+      else SX_SK4_K(1, 4, false, 2)
+    } else if (tail20) SX_SK4_K(2, 4, true, 1)
+    else if (r2) SX_SK4_K(2, 4, false, 1)
+    else SX_SK4_K(1, 4, false, 1)
+#undef SX_SK4_K
+    if (plan) return SX_OK;
+    SX_HIP_LAUNCH_CHECK();
+    return SX_OK;
 }
 
 extern "C" int sx_attn_decode_b(const void* q, const void* kcache, const void* vcache, void* out, float* scratch,

@@ -208,6 +208,7 @@ class SampleState:
 
 class LlamaForCausalLM:
     KV_FORMATS = (None, "fp8_e4m3", "fp8_e4m3_emulated")
+    WEIGHT_FORMATS = (None, "fp8_e4m3", "mxfp4")
 
     def __init__(self, config, max_cache_len=None, max_batch=1, comm=None, precise=None, kv_v16=None, weight_format=None, kv_format=None):
         self.config = config if not isinstance(config, dict) else LlamaConfigLite(**config)
@@ -248,22 +249,25 @@ class LlamaForCausalLM:
         # bytes of a token step's weight stream), the row-major 16-bit weights hold their exact dequantised values. The 1e-3 contract
         # then holds against the QUANTISED model (bit-identical to the default mode loaded with the dequantised weights); against the
         # original checkpoint the mode costs the quantisation itself (2.7 % per projection on Gaussian rows, llm.weight_quant_report).
+        # ``weight_format="mxfp4"`` (SX_LLM_WEIGHTS=mxfp4) is the same contract at four bits: OCP MXFP4 codes (e2m1, two per byte) with one
+        # power-of-two E8M0 scale per 32-k block — 0.53 B per weight in the decode tiles, 11.4 % per projection on Gaussian rows
+        # (round to nearest, no calibration); same requirements and refusals.
         if weight_format is None:
             weight_format = os.environ.get("SX_LLM_WEIGHTS") or None
-        if weight_format not in (None, "fp8_e4m3"):
-            raise ValueError(f"LlamaForCausalLM: weight_format must be None or 'fp8_e4m3', not {weight_format!r}")
+        if weight_format not in self.WEIGHT_FORMATS:
+            raise ValueError(f"LlamaForCausalLM: weight_format must be None, 'fp8_e4m3' or 'mxfp4', not {weight_format!r}")
         self.weight_format = weight_format
         self.weight_quant_report = None
         if weight_format is not None:
             # only where the raw matrices ARE the decode tiles: the precise mode's RMSNorm fold keeps gamma on the activation side; the
             # plain flow folds gamma into its tiles, which would be a second, different quantisation of the same weights
             if not self.precise:
-                raise ValueError("LlamaForCausalLM: weight_format='fp8_e4m3' needs the precise mode (the plain 16-bit flow folds the RMSNorm "
+                raise ValueError(f"LlamaForCausalLM: weight_format={weight_format!r} needs the precise mode (the plain 16-bit flow folds the RMSNorm "
                                  "gamma into its decode tiles: those are not the checkpoint's matrices and would be quantised a second, different time)")
             if not self._skinny_shapes_ok():
-                raise ValueError("LlamaForCausalLM: weight_format='fp8_e4m3' needs the tiled precise decode path: hidden / per-rank head and FFN "
+                raise ValueError(f"LlamaForCausalLM: weight_format={weight_format!r} needs the tiled precise decode path: hidden / per-rank head and FFN "
                                  f"widths that are multiples of 64 and >= 256, output widths that are multiples of 32 (H {self.H}, "
-                                 f"heads x dim {self.H_l}, FFN {self.I_l}, vocab rows {self.V_l}): FP8 tiles exist for the MFMA skinny GEMM only")
+                                 f"heads x dim {self.H_l}, FFN {self.I_l}, vocab rows {self.V_l}): FP8 / MXFP4 tiles exist for the MFMA skinny GEMM only")
         # FP8 (e4m3) KV cache (module docstring; opt-in: ``kv_format="fp8_e4m3"`` or SX_LLM_KV=fp8_e4m3). Never a silent fall-back: a
         # configuration the FP8 kernels do not cover is refused here, like weight_format
         if kv_format is None:
@@ -349,6 +353,9 @@ class LlamaForCausalLM:
             # lm_head's tiles stay 16-bit. "weights" is unchanged: the row-major matrices hold the dequantised values for prefill
             rows = 3 * self.H_l + self.H + 2 * self.I_l + self.H
             tiles = self.L * (per_layer // 2 + rows * 4) + self.V_l * self.H * 2
+        if self.weight_format == "mxfp4":
+            # half a byte per weight + one E8M0 byte per 32 weights, one layout per projection; lm_head's tiles stay 16-bit
+            tiles = self.L * (per_layer // 4 + per_layer // 64) + self.V_l * self.H * 2
         kv = self.L * self.G * self.nh_l * self.Tmax * self.hd * ((4 + (2 if self.kv_v16 else 4)) if self.precise else 4)
         if self.kv_format == "fp8_e4m3":        # one byte per k and per v value + the two fp32 row scales (the emulated twin: all fp32, above)
             kv = self.L * self.G * self.nh_l * self.Tmax * (2 * self.hd + 8)
@@ -444,7 +451,7 @@ class LlamaForCausalLM:
         free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)   # + the allocator's cached blocks
         logging.getLogger("seedx_amd").info(
             "LlamaForCausalLM._pack (%s, %d sequences, Tmax %d): weights %.1f GB + decode tiles %.1f GB + KV cache %.1f GB (%s)",
-            ("precise" if self.precise else "plain 16-bit") + (", FP8 e4m3 decode tiles" if self.weight_format else ""), self.G, self.Tmax,
+            ("precise" if self.precise else "plain 16-bit") + ({"fp8_e4m3": ", FP8 e4m3 decode tiles", "mxfp4": ", MXFP4 decode tiles"}.get(self.weight_format, "")), self.G, self.Tmax,
             fp["weights"] / 1e9, fp["decode_tiles"] / 1e9,
             fp["kv_cache"] / 1e9, self._kv_name())
         if fp["total"] > free:
@@ -485,7 +492,9 @@ class LlamaForCausalLM:
         parts = _lib.load().sx_gemv_ssq_parts(self.H, 0, 2 if self._bal20(self.H) else 1)
         fold = self.G >= 5 and tp == 1 and parts % 64 == 0 and os.environ.get("SX_RMS_FOLD", "1") != "0" \
             and not self.precise      # (SX_RMS_FOLD=0: A/B switch, tools/; the precise mode norms in fp32 with its own kernel)
-        fp8 = self.weight_format == "fp8_e4m3"
+        fp8 = self.weight_format is not None         # a quantised weight format: FP8 row codes or MXFP4 block codes
+        fp4 = self.weight_format == "mxfp4"
+        fkey = "_f4" if fp4 else "_f8"
         if fp8:
             from . import quant
             qerr = {n.split(".")[1]: torch.zeros(2, dtype=torch.float64, device=dev) for n in quant.LLAMA_PROJECTIONS}   # [|W - Wq|^2, |W|^2]
@@ -494,12 +503,16 @@ class LlamaForCausalLM:
             if fp8:
                 # the FULL matrices are quantised (after the LoRA merge, before the tensor-parallel slicing): every rank holds slices of
                 # one quantised model. From here on "the weights" are the dequantised values; codes and scales are sliced the same way
-                ql = quant.quantize_llama_layer(sd, p, dt, dev)
+                ql = quant.quantize_llama_layer(sd, p, dt, dev, weight_format=self.weight_format)
                 for k, (_, _, wq) in ql.items():
                     w0 = sd[k].detach().to(dev, dt).double()
                     qerr[k[len(p):].split(".")[1]] += torch.stack([(w0 - wq.double()).square().sum(), w0.square().sum()])
-                sh8 = llama_tp_shard({k: v[0] for k, v in ql.items()}, p, r, tp, self.nh, self.hd)
-                sc8 = quant.llama_tp_shard_scales({k: v[1] for k, v in ql.items()}, p, r, tp, self.nh, self.hd)
+                if fp4:     # packed codes and block scales: o / down are sliced along K in both
+                    sh8, sc8 = quant.llama_tp_shard_mxfp4({k: v[0] for k, v in ql.items()}, {k: v[1] for k, v in ql.items()}, p, r, tp,
+                                                          self.nh, self.hd)
+                else:
+                    sh8 = llama_tp_shard({k: v[0] for k, v in ql.items()}, p, r, tp, self.nh, self.hd)
+                    sc8 = quant.llama_tp_shard_scales({k: v[1] for k, v in ql.items()}, p, r, tp, self.nh, self.hd)
                 lsd = {k: v[2] for k, v in ql.items()}
                 del ql
             sh = llama_tp_shard(lsd if fp8 else sd, p, r, tp, self.nh, self.hd)
@@ -514,11 +527,19 @@ class LlamaForCausalLM:
                 # GLU row packing moves the codes and the scales alike. No 16-bit tile copy at all.
                 c8 = {"wqkv": torch.cat([sh8["q"], sh8["k"], sh8["v"]], dim=0), "wo": sh8["o"], "wd": sh8["down"],
                       "wgu": glu_pack_rows(sh8["up"], sh8["gate"])}
-                s8 = {"wqkv": torch.cat([sc8["q"], sc8["k"], sc8["v"]]), "wo": sc8["o"], "wd": sc8["down"],
-                      "wgu": glu_pack_rows(sc8["up"][:, None], sc8["gate"][:, None]).reshape(-1)}
+                if fp4:     # block scales [rows, K/32]: the GLU packing moves whole rows of them
+                    s8 = {"wqkv": torch.cat([sc8["q"], sc8["k"], sc8["v"]], dim=0), "wo": sc8["o"], "wd": sc8["down"],
+                          "wgu": glu_pack_rows(sc8["up"], sc8["gate"])}
+                else:
+                    s8 = {"wqkv": torch.cat([sc8["q"], sc8["k"], sc8["v"]]), "wo": sc8["o"], "wd": sc8["down"],
+                          "wgu": glu_pack_rows(sc8["up"][:, None], sc8["gate"][:, None]).reshape(-1)}
                 for k in ("wqkv", "wo", "wgu", "wd"):
                     lw[k + "_t"] = lw[k + "_t20"] = None
                     t20 = k in ("wo", "wd") and self._bal20(c8[k].shape[0])
+                    if fp4:
+                        lw[k + "_f4"] = ((ops.pack_decode_tiles20_fp4 if t20 else ops.pack_decode_tiles_fp4)(c8[k].contiguous()),
+                                         ops.pack_block_scales_fp4(s8[k].contiguous(), rows=20 if t20 else 16))
+                        continue
                     lw[k + "_f8"] = ((ops.pack_decode_tiles20_fp8 if t20 else ops.pack_decode_tiles_fp8)(c8[k].contiguous()),
                                      s8[k].contiguous().clone())
                 del sh8, sc8, c8, s8, lsd
@@ -538,10 +559,10 @@ class LlamaForCausalLM:
                 if i > 0:
                     lw["wqkv_t"] = tiles((qkv.to(dev, torch.float32) * lw["ln1"][None, :]).to(dt).contiguous())
         # every decode GEMV has the decode-tile weight copy → its 16-bit inputs travel as operand tiles too (_layers_single)
-        P["decode_tiled"] = all((lw.get(k + "_f8") if fp8 else lw[k + "_t"]) is not None for lw in P["layers"] for k in ("wqkv", "wo", "wgu", "wd")) \
+        P["decode_tiled"] = all((lw.get(k + fkey) if fp8 else lw[k + "_t"]) is not None for lw in P["layers"] for k in ("wqkv", "wo", "wgu", "wd")) \
             and (self.nh_l * self.hd) % 32 == 0
         if fp8:
-            held = sum(t.numel() * t.element_size() for lw in P["layers"] for k in ("wqkv", "wo", "wgu", "wd") for t in lw[k + "_f8"]) \
+            held = sum(t.numel() * t.element_size() for lw in P["layers"] for k in ("wqkv", "wo", "wgu", "wd") for t in lw[k + fkey]) \
                 + P["lm_head_t"].numel() * P["lm_head_t"].element_size()
             assert held == fp["decode_tiles"], (held, fp["decode_tiles"])      # memory_footprint() prices what is held, nothing else
             err = {k: math.sqrt(float(v[0] / v[1])) if float(v[1]) > 0 else 0.0 for k, v in qerr.items()}
@@ -549,8 +570,8 @@ class LlamaForCausalLM:
             self.weight_quant_report = {"weight_format": self.weight_format, "decode_tile_bytes": held, "decode_tile_bytes_16bit": tiles16,
                                         "rel_frobenius_error": err}
             logging.getLogger("seedx_amd").info(
-                "LlamaForCausalLM._pack: FP8 e4m3 weight tiles, %.2f GB of decode tiles (16-bit: %.2f GB); relative Frobenius error of the "
-                "quantisation against the %s checkpoint: %s", held / 1e9, self.weight_quant_report["decode_tile_bytes_16bit"] / 1e9,
+                "LlamaForCausalLM._pack: %s weight tiles, %.2f GB of decode tiles (16-bit: %.2f GB); relative Frobenius error of the "
+                "quantisation against the %s checkpoint: %s", "MXFP4" if fp4 else "FP8 e4m3", held / 1e9, self.weight_quant_report["decode_tile_bytes_16bit"] / 1e9,
                 str(dt).replace("torch.", ""), ", ".join(f"{k} {v:.4f}" for k, v in err.items()))
         P["rms_fold"] = fold and P["decode_tiled"] and self.H % 32 == 0
         assert P["rms_fold"] or not fold or not any(lw["wgu_t"] is not None for lw in P["layers"]), \
@@ -566,7 +587,7 @@ class LlamaForCausalLM:
         P["rms_fold_precise"] = self.precise and P["precise_tiled"] and P["decode_tiled"] and tp == 1 and parts % 64 == 0 \
             and self.H % 32 == 0 and self.I_l % 32 == 0 and os.environ.get("SX_RMS_FOLD", "1") != "0"
         if fp8 and not (P["precise_tiled"] and P["decode_tiled"]):
-            raise ValueError("LlamaForCausalLM: weight_format='fp8_e4m3' needs the tiled precise decode path (FP8 tiles exist for the MFMA skinny GEMM only)")
+            raise ValueError(f"LlamaForCausalLM: weight_format={self.weight_format!r} needs the tiled precise decode path (FP8 / MXFP4 tiles exist for the MFMA skinny GEMM only)")
         inv = 1.0 / (self.config.rope_base ** (torch.arange(0, self.hd, 2).float() / self.hd))
         fr = torch.outer(torch.arange(self.Tmax).float(), inv)           # [Tmax, hd/2] fp32 (:97-113)
         P["cos"], P["sin"] = fr.cos().to(dev).contiguous(), fr.sin().to(dev).contiguous()
@@ -757,7 +778,7 @@ class LlamaForCausalLM:
         def lin(xp, lw, k, **kw):
             if tl:
                 return ops.gemv(xp, lw[k], w_tiles=lw[k + "_t"] if dtl else None, workspace=ws if dtl else None,
-                                w_tiles20=lw.get(k + "_t20") if dtl else None, w_fp8=lw.get(k + "_f8"), out_dtype=f32, **kw)
+                                w_tiles20=lw.get(k + "_t20") if dtl else None, w_fp8=lw.get(k + "_f8"), w_fp4=lw.get(k + "_f4"), out_dtype=f32, **kw)
             return ops.gemm(xp, lw[k], a_planes=2, out_dtype=f32, **kw)
         fold = P["rms_fold_precise"]
         fuse_rope = hd == 128 and os.environ.get("SX_LLM_FUSE_ROPE", "1") != "0"
@@ -780,7 +801,7 @@ class LlamaForCausalLM:
             if fold:
                 # residual GEMV: fp32 x, the planes of x * gamma of the NEXT norm, the rows' sums of squares; GLU epilogue: planes directly
                 x, x16, ssq = lin(att, lw, "wo", residual=x, emit_norm=True, planes_out=True, norm_gamma=lw["ln2"])
-                g = ops.gemv(x16, lw["wgu"], act="silu", glu=True, w_tiles=lw["wgu_t"], w_fp8=lw.get("wgu_f8"), y_tiled=True, planes_out=True,
+                g = ops.gemv(x16, lw["wgu"], act="silu", glu=True, w_tiles=lw["wgu_t"], w_fp8=lw.get("wgu_f8"), w_fp4=lw.get("wgu_f4"), y_tiled=True, planes_out=True,
                              ssq_in=(ssq, self.H, eps))
                 if li + 1 < nl:
                     x, x16, ssq = lin(g, lw, "wd", residual=x, emit_norm=True, planes_out=True, norm_gamma=P["layers"][li + 1]["ln1"])
@@ -790,7 +811,7 @@ class LlamaForCausalLM:
             x = comm.all_reduce(lin(att, lw, "wo", residual=x if lead else None))
             h, _ = ops.rmsnorm_planes(x, lw["ln2"], eps, dt, tiled=tl)
             if tl:                           # SiLU-GLU epilogue writes the two planes of its result itself (no sx_split16 launch)
-                g = ops.gemv(h, lw["wgu"], act="silu", glu=True, w_tiles=lw["wgu_t"] if dtl else None, w_fp8=lw.get("wgu_f8"), y_tiled=True,
+                g = ops.gemv(h, lw["wgu"], act="silu", glu=True, w_tiles=lw["wgu_t"] if dtl else None, w_fp8=lw.get("wgu_f8"), w_fp4=lw.get("wgu_f4"), y_tiled=True,
                              planes_out=True)
             else:
                 g = ops.split16(lin(h, lw, "wgu", act="silu", glu=True), dt)

@@ -254,6 +254,38 @@ def pack_decode_tiles20_fp8(codes):
     return _fp8_row_order(codes).view(N // 20, 20, K // 64, 64).permute(0, 2, 1, 3).contiguous()
 
 
+def _fp4_row_order(codes):
+    """Packed e2m1 codes [..., K/2] (byte i = k 2i | k 2i + 1 << 4) → [..., K/64, 32] with the 32 bytes of a k-slab in the skinny GEMM's
+    lane order: byte 8 g + 4 h + i holds k = 32 h + 8 g + 2 i (low nibble) and k + 1 (g = 0..3 lane group, h = 0..1 32-k half,
+    i = 0..3) — sx_gemv_args.w_block_scale in include/seedx_hip.h."""
+    K2 = codes.shape[-1]
+    return codes.reshape(*codes.shape[:-1], K2 // 32, 2, 4, 4).transpose(-3, -2).reshape(*codes.shape[:-1], K2 // 32, 32)
+
+
+def pack_decode_tiles_fp4(codes):
+    """Row-major packed e2m1 codes uint8 [N, K/2] (quant.quantize_blocks_mxfp4) → MXFP4 decode tiles [N/16][K/64][16][32]: a 64-k slab
+    of 16 rows is one contiguous 512-B tile, ONE 8-B load per lane and k-step (dword h = the lane's eight k-slots of 32-k half h)."""
+    N, K2 = codes.shape
+    assert codes.dtype == torch.uint8 and N % 16 == 0 and K2 % 32 == 0
+    return _fp4_row_order(codes).view(N // 16, 16, K2 // 32, 32).permute(0, 2, 1, 3).contiguous()
+
+
+def pack_decode_tiles20_fp4(codes):
+    """Row-major packed e2m1 codes uint8 [N, K/2] → 20-row MXFP4 decode tiles [N/20][K/64][20][32] (sx_gemv w_layout 2): the 512-B tile
+    of rows 0..15, then rows 16..19, per 64-k slab."""
+    N, K2 = codes.shape
+    assert codes.dtype == torch.uint8 and N % 20 == 0 and K2 % 32 == 0
+    return _fp4_row_order(codes).view(N // 20, 20, K2 // 32, 32).permute(0, 2, 1, 3).contiguous()
+
+
+def pack_block_scales_fp4(scale, rows=16):
+    """E8M0 block scales uint8 [N, K/32] (quant.quantize_blocks_mxfp4, rows in the order of the code matrix) → scale tiles
+    [N/rows][K/64][rows][2], rows = 16 or 20 like the code tiles they belong to: byte h of (row, k-step t) is the scale of block 2 t + h."""
+    N, B = scale.shape
+    assert scale.dtype == torch.uint8 and rows in (16, 20) and N % rows == 0 and B % 2 == 0
+    return scale.view(N // rows, rows, B // 2, 2).permute(0, 2, 1, 3).contiguous()
+
+
 class Tiled16:
     """A [rows <= 32, cols] 16-bit activation of the decode step held as MFMA operand tiles [rows/16][cols/32][16][32] (SX_TILED16
     in include/seedx_hip.h): what the skinny GEMM reads with one contiguous 1-KB load per operand. Rows 16..31 (lock-step batches
@@ -282,7 +314,7 @@ class Tiled16:
 
 
 def gemv(x, w, residual=None, act=None, glu=False, out_dtype=None, w_tiles=None, y_tiled=False, workspace=None,
-         emit_norm=False, ssq_in=None, w_tiles20=None, planes_out=False, norm_gamma=None, w_fp8=None):
+         emit_norm=False, ssq_in=None, w_tiles20=None, planes_out=False, norm_gamma=None, w_fp8=None, w_fp4=None):
     """w_tiles: the same weight in the decode layout (pack_decode_tiles); used instead of w when the MFMA path runs.
     x may be a Tiled16 (then w_tiles is required); y_tiled returns the 16-bit result as a Tiled16 for the next gemv.
     workspace: zero-initialised uint8 scratch enabling split-K over workgroups for shapes that need it (sx_gemv_args.workspace).
@@ -295,12 +327,14 @@ def gemv(x, w, residual=None, act=None, glu=False, out_dtype=None, w_tiles=None,
     the projection behind the norm keeps exact weights and only applies rstd (ssq_in).
     w_fp8 = (tiles, scale): the weight as e4m3 codes in FP8 decode tiles (pack_decode_tiles_fp8 → 16-row, pack_decode_tiles20_fp8 →
     20-row; the shape says which) with its fp32 row scales [N], in the row order of ``w``; replaces w_tiles / w_tiles20. ``w`` (the
-    dequantised 16-bit matrix) only gives shape and dtype. MFMA path only: any other shape is an error, never a fall-back."""
+    dequantised 16-bit matrix) only gives shape and dtype. MFMA path only: any other shape is an error, never a fall-back.
+    w_fp4 = (code_tiles, scale_tiles): the weight as MXFP4 decode tiles (pack_decode_tiles_fp4 / pack_decode_tiles20_fp4; the shape says
+    which) with its E8M0 block-scale tiles (pack_block_scales_fp4 with the same rows); replaces w_tiles / w_tiles20 in the same way."""
     lib = _lib.load()
     xt = isinstance(x, Tiled16)
     if xt:
         M, K = x.rows, x.cols
-        assert x.dtype == w.dtype and (x.planes == 2 or w_tiles is not None or w_tiles20 is not None or w_fp8 is not None)
+        assert x.dtype == w.dtype and (x.planes == 2 or w_tiles is not None or w_tiles20 is not None or w_fp8 is not None or w_fp4 is not None)
     else:
         assert x.dim() == 2 and x.is_contiguous() and w.is_contiguous() and x.dtype == w.dtype
         M, K = x.shape
@@ -342,6 +376,14 @@ def gemv(x, w, residual=None, act=None, glu=False, out_dtype=None, w_tiles=None,
         assert sc.dtype == torch.float32 and sc.is_contiguous() and sc.shape == (N,) and sc.device == dev
         args.W, args.w_layout = t8.data_ptr(), 1 if t8.shape[2] == 16 else 2
         args.w_dtype, args.w_scale = _lib.SX_FP8_E4M3, sc.data_ptr()
+    if w_fp4 is not None:
+        assert w_fp8 is None
+        t4, sc = w_fp4
+        assert t4.dtype == torch.uint8 and t4.is_contiguous() and t4.dim() == 4 and t4.shape[2] in (16, 20) and t4.shape[3] == 32
+        assert t4.shape[0] * t4.shape[2] == N and t4.shape[1] * 64 == K and t4.device == dev, "MXFP4 tiles do not match the weight's shape"
+        assert sc.dtype == torch.uint8 and sc.is_contiguous() and sc.shape == t4.shape[:3] + (2,) and sc.device == dev
+        args.W, args.w_layout = t4.data_ptr(), 1 if t4.shape[2] == 16 else 2
+        args.w_dtype, args.w_block_scale = _lib.SX_FP4_E2M1, sc.data_ptr()
     x16 = ssq = None
     if emit_norm:
         assert args.w_layout in (1, 2) and out_dtype == torch.float32 and not glu and not y_tiled
