@@ -449,6 +449,27 @@ typedef struct sx_kv_fork_args {
 } sx_kv_fork_args;
 int sx_kv_fork(const sx_kv_fork_args* args, void* stream);
 
+/* Decode tiles → the row-major matrix (LlamaForCausalLM(weight_residency="tiles"): the quantised tiles are the only copy of a
+ * projection, prefill rebuilds it into a shared scratch buffer in front of its sx_gemm). The exact inverse of the packers of ops.py:
+ * out[n][k] (16-bit, `dtype`, row-major [N][K]) = the value the skinny GEMM feeds its MFMAs for weight (n, k) —
+ *   SX_FP8_E4M3: decode(code) * w_scale[n] (the power-of-two row scale: the product is exact in fp32 and, for the quantiser's exponents
+ *     [-15, 7], exactly representable in fp16 and bf16), tiles [N/16][K/64][16][64] (w_layout 1) or [N/20][K/64][20][64] (w_layout 2),
+ *   SX_FP4_E2M1: decode(code) * 2^(E8M0 byte - 127) by the packed converts of sx_gemv (scale bits = byte << 23), tiles
+ *     [N/16][K/64][16][32] + scale tiles [N/16][K/64][16][2] (w_layout 1) or the 20-row forms (w_layout 2),
+ * byte order inside a 64-k slab as under sx_gemv_args.w_dtype / w_block_scale. Rows are in the order of the tiles (GLU-packed rows stay
+ * packed). Every store instruction of a wave covers whole 128-byte row segments. SX_ERR_INVALID, never a fall-back: another w_dtype,
+ * w_layout 0, K % 64 != 0, N no multiple of the layout's 16 / 20 rows, a missing or not 16-B aligned scale array, the other format's scale
+ * array set, tiles / out not 16-B aligned, out_bytes < N * K * 2. Nothing beyond the first N * K * 2 bytes of out is written. */
+typedef struct sx_dequant_tiles_args {
+  const void* tiles;          /* the code tiles                                                               */
+  const float* w_scale;       /* SX_FP8_E4M3: fp32 [N] row scales (else NULL)                                 */
+  const void* w_block_scale;  /* SX_FP4_E2M1: E8M0 scale tiles (else NULL)                                    */
+  void* out;                  /* 16-bit [N][K], row-major                                                     */
+  uint64_t out_bytes;         /* bytes the caller owns at out (>= N * K * 2)                                  */
+  int32_t w_dtype, w_layout, N, K, dtype, reserved;
+} sx_dequant_tiles_args;
+int sx_dequant_tiles(const sx_dequant_tiles_args* args, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Elementwise / layout helpers
  * ------------------------------------------------------------------------------------------------ */

@@ -11,8 +11,8 @@ LIB_PATH = os.path.join(_HERE, "lib", "libseedx_hip.so")
 SX_F16, SX_BF16, SX_F32 = 0, 1, 2
 SX_BF16X3 = 3          # sx_groupnorm* output only: bf16 planes [hi | hi | lo] per row
 SX_F16X2 = 4           # sx_groupnorm* output only: fp16 planes [hi | lo] per row
-SX_FP8_E4M3 = 5        # sx_gemv_args.w_dtype only: e4m3fn weight codes + fp32 row scales
-SX_FP4_E2M1 = 6        # sx_gemv_args.w_dtype only: MXFP4 (e2m1) weight codes + E8M0 block scales (w_block_scale)
+SX_FP8_E4M3 = 5        # sx_gemv_args / sx_dequant_tiles_args.w_dtype only: e4m3fn weight codes + fp32 row scales
+SX_FP4_E2M1 = 6        # sx_gemv_args / sx_dequant_tiles_args.w_dtype only: MXFP4 (e2m1) weight codes + E8M0 block scales (w_block_scale)
 SX_TILED16 = 0x100     # OR-ed into a 16-bit out dtype: decode operand tiles [cols/32][16][32] (include/seedx_hip.h)
 SX_ACT_NONE, SX_ACT_GELU, SX_ACT_SILU = 0, 1, 2
 SX_A_LINEAR, SX_A_CONV3X3 = 0, 1
@@ -84,6 +84,11 @@ class KvForkArgs(C.Structure):
                 ("n_pairs", c_i32), ("outer", c_i32), ("G", c_i32), ("inner", c_i32), ("Tmax", c_i32), ("row_bytes", c_i32)]
 
 
+class DequantTilesArgs(C.Structure):
+    _fields_ = [("tiles", c_vp), ("w_scale", c_vp), ("w_block_scale", c_vp), ("out", c_vp), ("out_bytes", C.c_uint64),
+                ("w_dtype", c_i32), ("w_layout", c_i32), ("N", c_i32), ("K", c_i32), ("dtype", c_i32), ("reserved", c_i32)]
+
+
 class AttnArgs(C.Structure):
     _fields_ = [("Q", c_vp), ("K", c_vp), ("V", c_vp), ("O", c_vp),
                 ("B", c_i32), ("H", c_i32), ("Sq", c_i32), ("Skv", c_i32), ("D", c_i32), ("reserved", c_i32),
@@ -144,6 +149,7 @@ SIGNATURES = {
     "sx_sample_next_b": [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, C.POINTER(SampleArgs), c_vp],
     "sx_sample_next_slots": [C.POINTER(SlotStepArgs), C.POINTER(SampleArgs), c_vp],
     "sx_kv_fork": [C.POINTER(KvForkArgs), c_vp],
+    "sx_dequant_tiles": [C.POINTER(DequantTilesArgs), c_vp],
     "sx_scatter_rows_step": [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp],
     "sx_add_i32_n": [c_vp, c_i32, c_i32, c_vp],
     "sx_embedding": [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp],

@@ -1793,3 +1793,166 @@ extern "C" int sx_kv_fork(const sx_kv_fork_args* a, void* stream) {
   SX_HIP_LAUNCH_CHECK();
   return SX_OK;
 }
+
+// ---- decode tiles → row-major 16-bit matrix (include/seedx_hip.h: sx_dequant_tiles) ---------------------------------------------------
+// The skinny GEMM's weight fragment load, run backwards: a wave takes one 64-k slab of a row group per step. The two half-waves own rows
+// 0..7 and 8..15 of the 16-row tile: lane (s = lane >> 5, r8 = (lane >> 2) & 7, g = lane & 3) loads what lane (row r8 + 8 s, group g) of
+// the MFMA loads — 16 B of FP8 codes at 64 r + 16 g, or 8 B of MXFP4 codes at 32 r + 8 g plus the row's two E8M0 bytes — and converts it
+// with the GEMM's own converts to the eight k-slots of 32-k half 0 (A: k = 8 g ..) and of half 1 (B: k = 32 + 8 g ..). Writes are four
+// times the reads, so the store side decides the mapping: as loaded, a store instruction would cover 64-B pieces of 16 rows (the four g
+// of a row are one half of its 128-B segment). One v_permlane32_swap per dword hands the lower half-wave's B to the upper one and the
+// upper's A down: then the first store (A') covers rows 0..7 and the second (B') rows 8..15, each row's whole 128-B segment = 16 B x the
+// eight lanes (g, s) — no LDS. Rows 16..19 of a 20-row tile (behind the 16-row tile) are done 32 lanes per slab, lane = (row, 16-B piece):
+// an 8-B (MXFP4: 4-B) load per lane, the same whole segments. U slabs per wave are loaded ahead of their converts; consecutive waves take
+// consecutive slabs, so a row's segments are written in address order.
+struct DequantP {
+  const unsigned char* tiles;
+  const float* rscale;
+  const unsigned char* bscale;
+  unsigned short* out;
+  int K, nks;
+};
+
+// eight e4m3 codes times the row's power-of-two scale → eight 16-bit values: the code → fp32 convert of fp8x8_to16's bf16 path, the scale
+// in fp32 (exact: a power of two), one rounding-free convert down (the product has 4 significant bits and lies in the format's range)
+template <typename TT>
+__device__ __forceinline__ u32x4_t fp8x8_scaled_to16(unsigned d0, unsigned d1, float sc) {
+  u32x4_t o = {0u, 0u, 0u, 0u};
+#if defined(__HIP_DEVICE_COMPILE__)
+  const f32x2_t a = __builtin_amdgcn_cvt_pk_f32_fp8(d0, false), b = __builtin_amdgcn_cvt_pk_f32_fp8(d0, true);
+  const f32x2_t c = __builtin_amdgcn_cvt_pk_f32_fp8(d1, false), d = __builtin_amdgcn_cvt_pk_f32_fp8(d1, true);
+  o[0] = pack2<TT>(a[0] * sc, a[1] * sc);
+  o[1] = pack2<TT>(b[0] * sc, b[1] * sc);
+  o[2] = pack2<TT>(c[0] * sc, c[1] * sc);
+  o[3] = pack2<TT>(d[0] * sc, d[1] * sc);
+#endif
+  return o;
+}
+
+template <typename TT, bool W4, bool TAIL>
+__global__ __launch_bounds__(256) void dequant_tiles_kernel(const DequantP p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr int U = 4;                        // 64-k slabs per wave
+  constexpr int ROWS = TAIL ? 20 : 16;
+  constexpr int RB = W4 ? 32 : 64;            // bytes of one row in a slab's tile
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int t0 = (blockIdx.y * 4 + wave) * U;
+  if (t0 >= p.nks) return;                    // wave-uniform
+  const int nu = p.nks - t0 < U ? p.nks - t0 : U;
+  const int n0 = blockIdx.x * ROWS;
+  const size_t slab0 = (size_t)blockIdx.x * p.nks + t0;            // this wave's first slab: tiles, scale tiles and k are indexed by it
+  const unsigned char* tile = p.tiles + slab0 * (ROWS * RB);
+  const unsigned char* stile = W4 ? p.bscale + slab0 * (ROWS * 2) : nullptr;
+  {
+    const int s = lane >> 5, r = ((lane >> 2) & 7) + 8 * s, g = lane & 3;
+    u32x4_t w[U];
+    unsigned short ws[U];
+    float rs = 0.f;
+    if constexpr (!W4) rs = p.rscale[n0 + r];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (u < nu) {
+        const unsigned char* q = tile + (size_t)u * (ROWS * RB) + r * RB + g * (RB / 4);
+        if constexpr (W4) {
+          const u32x2_t d = *(const u32x2_t*)q;
+          w[u] = (u32x4_t){d[0], d[1], 0u, 0u};
+          ws[u] = *(const unsigned short*)(stile + (size_t)u * (ROWS * 2) + 2 * r);
+        } else {
+          w[u] = *(const u32x4_t*)q;
+        }
+      }
+    }
+    // first store: row n0 + r8, second: row n0 + 8 + r8; this lane's 16-B piece of the 128-B segment is g + 4 s in both
+    unsigned short* o0 = p.out + (size_t)(n0 + (r & 7)) * p.K + (size_t)t0 * 64 + 8 * (g + 4 * s);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (u < nu) {
+        u32x4_t A, B;
+        if constexpr (W4) {
+          A = __builtin_bit_cast(u32x4_t, fp4x8_to16<TT>(w[u][0], __uint_as_float(((unsigned)ws[u] & 0xffu) << 23)));
+          B = __builtin_bit_cast(u32x4_t, fp4x8_to16<TT>(w[u][1], __uint_as_float(((unsigned)ws[u] >> 8) << 23)));
+        } else {
+          A = fp8x8_scaled_to16<TT>(w[u][0], w[u][1], rs);
+          B = fp8x8_scaled_to16<TT>(w[u][2], w[u][3], rs);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {   // lanes 32..63 of A <-> lanes 0..31 of B
+          const auto x = __builtin_amdgcn_permlane32_swap(A[i], B[i], false, false);
+          A[i] = x[0];
+          B[i] = x[1];
+        }
+        *(u32x4_t*)(o0 + u * 64) = A;
+        *(u32x4_t*)(o0 + (size_t)8 * p.K + u * 64) = B;
+      }
+    }
+  }
+  if constexpr (TAIL) {   // rows 16..19: two slabs per pass, lane = (slab u2 + (lane >> 5), row rr, 16-B piece c = 4 h + g)
+    const int rr = (lane >> 3) & 3, c = lane & 7, g = c & 3, h = c >> 2;
+    float rs = 0.f;
+    if constexpr (!W4) rs = p.rscale[n0 + 16 + rr];
+#pragma unroll
+    for (int u2 = 0; u2 < U; u2 += 2) {
+      const int u = u2 + (lane >> 5);
+      if (u < nu) {
+        const unsigned char* q = tile + (size_t)u * (ROWS * RB) + 16 * RB + rr * RB + g * (RB / 4) + h * (RB / 8);
+        u32x4_t v;
+        if constexpr (W4) {
+          const unsigned sc = stile[(size_t)u * (ROWS * 2) + 32 + 2 * rr + h];
+          v = __builtin_bit_cast(u32x4_t, fp4x8_to16<TT>(*(const unsigned*)q, __uint_as_float(sc << 23)));
+        } else {
+          const u32x2_t d = *(const u32x2_t*)q;
+          v = fp8x8_scaled_to16<TT>(d[0], d[1], rs);
+        }
+        *(u32x4_t*)(p.out + (size_t)(n0 + 16 + rr) * p.K + (size_t)(t0 + u) * 64 + 8 * c) = v;
+      }
+    }
+  }
+#endif
+}
+
+template <typename TT>
+static void dequant_tiles_launch(const DequantP& p, bool w4, bool tail, dim3 grid, void* stream) {
+  if (w4) {
+    if (tail) hipLaunchKernelGGL((dequant_tiles_kernel<TT, true, true>), grid, dim3(256), 0, ST, p);
+    else hipLaunchKernelGGL((dequant_tiles_kernel<TT, true, false>), grid, dim3(256), 0, ST, p);
+  } else {
+    if (tail) hipLaunchKernelGGL((dequant_tiles_kernel<TT, false, true>), grid, dim3(256), 0, ST, p);
+    else hipLaunchKernelGGL((dequant_tiles_kernel<TT, false, false>), grid, dim3(256), 0, ST, p);
+  }
+}
+
+extern "C" int sx_dequant_tiles(const sx_dequant_tiles_args* a, void* stream) {
+  SX_CHECK(a && a->tiles && a->out, "sx_dequant_tiles: null pointer");
+  SX_CHECK(a->dtype == SX_F16 || a->dtype == SX_BF16, "sx_dequant_tiles: dtype must be SX_F16 or SX_BF16");
+  SX_CHECK(a->w_dtype == SX_FP8_E4M3 || a->w_dtype == SX_FP4_E2M1, "sx_dequant_tiles: w_dtype must be SX_FP8_E4M3 or SX_FP4_E2M1");
+  SX_CHECK(a->w_layout == 1 || a->w_layout == 2, "sx_dequant_tiles: w_layout must be 1 (16-row decode tiles) or 2 (20-row decode tiles)");
+  const int rows = a->w_layout == 1 ? 16 : 20;
+  SX_CHECK(a->N > 0 && a->K > 0 && a->K % 64 == 0 && a->N % rows == 0,
+           "sx_dequant_tiles: N=%d K=%d need K %% 64 == 0 and N %% %d == 0 (w_layout %d)", a->N, a->K, rows, a->w_layout);
+  SX_CHECK(((uintptr_t)a->tiles & 15) == 0 && ((uintptr_t)a->out & 15) == 0, "sx_dequant_tiles: tiles and out must be 16-B aligned");
+  const bool w4 = a->w_dtype == SX_FP4_E2M1;
+  if (w4) {
+    SX_CHECK(a->w_block_scale && ((uintptr_t)a->w_block_scale & 15) == 0,
+             "sx_dequant_tiles: SX_FP4_E2M1 tiles need w_block_scale (16-B aligned E8M0 scale tiles)");
+    SX_CHECK(!a->w_scale, "sx_dequant_tiles: w_scale belongs to SX_FP8_E4M3 tiles");
+  } else {
+    SX_CHECK(a->w_scale && ((uintptr_t)a->w_scale & 15) == 0, "sx_dequant_tiles: SX_FP8_E4M3 tiles need w_scale (16-B aligned fp32 [N])");
+    SX_CHECK(!a->w_block_scale, "sx_dequant_tiles: w_block_scale belongs to SX_FP4_E2M1 tiles");
+  }
+  SX_CHECK(a->out_bytes >= (uint64_t)a->N * (uint64_t)a->K * 2, "sx_dequant_tiles: out_bytes=%llu is less than N * K * 2 = %llu",
+           (unsigned long long)a->out_bytes, (unsigned long long)a->N * (unsigned long long)a->K * 2);
+  DequantP p;
+  p.tiles = (const unsigned char*)a->tiles;
+  p.rscale = a->w_scale;
+  p.bscale = (const unsigned char*)a->w_block_scale;
+  p.out = (unsigned short*)a->out;
+  p.K = a->K;
+  p.nks = a->K / 64;
+  const int gy = (p.nks + 15) / 16;            // 4 waves x 4 slabs per workgroup
+  SX_CHECK(gy <= 65535, "sx_dequant_tiles: K=%d is too large", a->K);
+  const dim3 grid((unsigned)(a->N / rows), (unsigned)gy);
+  if (a->dtype == SX_F16) dequant_tiles_launch<F16>(p, w4, a->w_layout == 2, grid, stream);
+  else dequant_tiles_launch<BF16>(p, w4, a->w_layout == 2, grid, stream);
+  SX_HIP_LAUNCH_CHECK();
+  return SX_OK;
+}

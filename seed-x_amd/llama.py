@@ -40,6 +40,16 @@ logits, past_key_values, hidden_states with the LAST entry = post-final-norm sta
     (one prefill / prefill + decode, other prefill chunkings) agree only to ~1e-3: cross-turn ``reuse_cache=True`` is NOT claimed to
     reproduce the ids of a fresh prefill under this mode. ``past_key_values`` are dequantised fp32 copies. Independent of
     ``weight_format``
+  * ``weight_residency="tiles"`` (opt-in; or ``SX_LLM_WEIGHT_RESIDENCY=tiles``; needs a ``weight_format``): the quantised decode tiles are
+    the ONLY copy of the seven projections. By default a quantised model still keeps every projection as a row-major 16-bit matrix of
+    the dequantised values (25.7 GB at 13B dims) that only prefill reads; in this mode ``_pack`` frees each layer's matrices once its
+    tiles are built (peak load-time memory: one layer), and prefill rebuilds one projection at a time into one shared scratch buffer
+    (the largest per-rank projection, gate|up: 283 MB at 13B) with sx_dequant_tiles in front of the unchanged GEMM — the same bits as
+    the default residency, prefill and decode. The decode step never touches the scratch buffer. CHOOSING: the mode buys the memory
+    (more KV slots / a longer ``max_cache_len`` beside the other models, or a smaller part) and pays one extra pass over the layer's
+    weights per prefill pass (0.53 / 1.03 B read + 2 B written per weight). Measured at 13B dims (profiles/weight_residency.md): 25.1 GB
+    less held; + 4.3 .. 8.2 ms per pass, which is + 5 % of a 2048-row prefill (150 ms) but + 31 .. 35 % of the 8-row suffix prefills
+    (14.5 ms) that in-flight batching with prefix reuse lives on; the token step is unchanged.
   * ``comm`` with world > 1: Megatron tensor parallelism (parallel.py) — this rank owns nh/tp heads (their q/k/v rows, KV
     cache and o_proj columns), I/tp FFN rows (gate/up rows, down_proj columns) and Vpad/tp lm_head rows; the fp32
     residual stream is all-reduced after o_proj and down_proj (rank 0's GEMM epilogue adds the residual), the logits are
@@ -209,8 +219,10 @@ class SampleState:
 class LlamaForCausalLM:
     KV_FORMATS = (None, "fp8_e4m3", "fp8_e4m3_emulated")
     WEIGHT_FORMATS = (None, "fp8_e4m3", "mxfp4")
+    WEIGHT_RESIDENCIES = (None, "tiles")
 
-    def __init__(self, config, max_cache_len=None, max_batch=1, comm=None, precise=None, kv_v16=None, weight_format=None, kv_format=None):
+    def __init__(self, config, max_cache_len=None, max_batch=1, comm=None, precise=None, kv_v16=None, weight_format=None, kv_format=None,
+                 weight_residency=None):
         self.config = config if not isinstance(config, dict) else LlamaConfigLite(**config)
         c = self.config
         self.H, self.nh, self.L = c.hidden_size, c.num_attention_heads, c.num_hidden_layers
@@ -268,6 +280,16 @@ class LlamaForCausalLM:
                 raise ValueError(f"LlamaForCausalLM: weight_format={weight_format!r} needs the tiled precise decode path: hidden / per-rank head and FFN "
                                  f"widths that are multiples of 64 and >= 256, output widths that are multiples of 32 (H {self.H}, "
                                  f"heads x dim {self.H_l}, FFN {self.I_l}, vocab rows {self.V_l}): FP8 / MXFP4 tiles exist for the MFMA skinny GEMM only")
+        # residency of the quantised projections (module docstring; opt-in: ``weight_residency="tiles"`` or SX_LLM_WEIGHT_RESIDENCY=tiles):
+        # None keeps the row-major 16-bit copy of the dequantised values for prefill, "tiles" holds the decode tiles alone
+        if weight_residency is None:
+            weight_residency = os.environ.get("SX_LLM_WEIGHT_RESIDENCY") or None
+        if weight_residency not in self.WEIGHT_RESIDENCIES:
+            raise ValueError(f"LlamaForCausalLM: weight_residency must be None or 'tiles', not {weight_residency!r}")
+        if weight_residency is not None and weight_format is None:
+            raise ValueError(f"LlamaForCausalLM: weight_residency={weight_residency!r} needs a weight_format ('fp8_e4m3' or 'mxfp4'): only "
+                             "quantised decode tiles can stand in for the row-major 16-bit matrices")
+        self.weight_residency = weight_residency
         # FP8 (e4m3) KV cache (module docstring; opt-in: ``kv_format="fp8_e4m3"`` or SX_LLM_KV=fp8_e4m3). Never a silent fall-back: a
         # configuration the FP8 kernels do not cover is refused here, like weight_format
         if kv_format is None:
@@ -359,7 +381,16 @@ class LlamaForCausalLM:
         kv = self.L * self.G * self.nh_l * self.Tmax * self.hd * ((4 + (2 if self.kv_v16 else 4)) if self.precise else 4)
         if self.kv_format == "fp8_e4m3":        # one byte per k and per v value + the two fp32 row scales (the emulated twin: all fp32, above)
             kv = self.L * self.G * self.nh_l * self.Tmax * (2 * self.hd + 8)
+        if self.weight_residency == "tiles":
+            # no row-major projection is held: embedding + lm_head + the one prefill scratch buffer (the largest per-rank projection)
+            scratch = self._scratch_elems() * 2
+            w = (self.V + self.V_l) * self.H * 2 + scratch
+            return {"weights": w, "prefill_scratch": scratch, "decode_tiles": tiles, "kv_cache": kv, "total": w + tiles + kv}
         return {"weights": w, "decode_tiles": tiles, "kv_cache": kv, "total": w + tiles + kv}
+
+    def _scratch_elems(self):
+        """Elements of the tiles residency's prefill scratch buffer: max over the four per-rank projections of N * K (gate|up at 13B)."""
+        return max(3 * self.H_l * self.H, self.H * self.H_l, 2 * self.I_l * self.H, self.H * self.I_l)
 
     # ---- reference-compatible plumbing ---------------------------------------------------------------------
     @classmethod
@@ -451,7 +482,9 @@ class LlamaForCausalLM:
         free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)   # + the allocator's cached blocks
         logging.getLogger("seedx_amd").info(
             "LlamaForCausalLM._pack (%s, %d sequences, Tmax %d): weights %.1f GB + decode tiles %.1f GB + KV cache %.1f GB (%s)",
-            ("precise" if self.precise else "plain 16-bit") + ({"fp8_e4m3": ", FP8 e4m3 decode tiles", "mxfp4": ", MXFP4 decode tiles"}.get(self.weight_format, "")), self.G, self.Tmax,
+            ("precise" if self.precise else "plain 16-bit") + ({"fp8_e4m3": ", FP8 e4m3 decode tiles", "mxfp4": ", MXFP4 decode tiles"}.get(self.weight_format, ""))
+            + (", tiles residency: no row-major projections, prefill dequantises into a %.2f GB scratch buffer" % (fp["prefill_scratch"] / 1e9)
+               if self.weight_residency == "tiles" else ""), self.G, self.Tmax,
             fp["weights"] / 1e9, fp["decode_tiles"] / 1e9,
             fp["kv_cache"] / 1e9, self._kv_name())
         if fp["total"] > free:
@@ -543,6 +576,12 @@ class LlamaForCausalLM:
                     lw[k + "_f8"] = ((ops.pack_decode_tiles20_fp8 if t20 else ops.pack_decode_tiles_fp8)(c8[k].contiguous()),
                                      s8[k].contiguous().clone())
                 del sh8, sc8, c8, s8, lsd
+                if self.weight_residency == "tiles":
+                    # the tiles are the only copy: this layer's row-major matrices existed while the tiles were built and go now (peak
+                    # load-time memory is one layer); what stays is the shape / dtype handle ops.gemv asks for
+                    del sh, qkv, gu
+                    for k in ("wqkv", "wo", "wgu", "wd"):
+                        lw[k] = ops.WeightShape(lw[k].shape, dt)
                 continue
             for k in ("wqkv", "wo", "wgu", "wd"):
                 lw[k + "_t"] = tiles(lw[k])
@@ -568,7 +607,14 @@ class LlamaForCausalLM:
             err = {k: math.sqrt(float(v[0] / v[1])) if float(v[1]) > 0 else 0.0 for k, v in qerr.items()}
             tiles16 = sum(2 * lw[k].numel() for lw in P["layers"] for k in ("wqkv", "wo", "wgu", "wd")) + 2 * P["lm_head_t"].numel()
             self.weight_quant_report = {"weight_format": self.weight_format, "decode_tile_bytes": held, "decode_tile_bytes_16bit": tiles16,
-                                        "rel_frobenius_error": err}
+                                        "rel_frobenius_error": err, "weight_residency": self.weight_residency}
+            if self.weight_residency == "tiles":
+                # ONE buffer for all four projections of every layer. Prefill runs on one stream: the GEMM on projection k finishes
+                # before the dequantisation of projection k + 1 overwrites the buffer (_layers_multi). The decode step never reads it.
+                P["w_scratch"] = torch.empty(self._scratch_elems(), dtype=dt, device=dev)
+                rowmajor = P["embed"].numel() * 2 + P["lm_head"].numel() * 2 + P["w_scratch"].numel() * 2 \
+                    + sum(lw[k].numel() * 2 for lw in P["layers"] for k in ("wqkv", "wo", "wgu", "wd") if torch.is_tensor(lw[k]))
+                assert rowmajor == fp["weights"] and P["w_scratch"].numel() * 2 == fp["prefill_scratch"], (rowmajor, fp)
             logging.getLogger("seedx_amd").info(
                 "LlamaForCausalLM._pack: %s weight tiles, %.2f GB of decode tiles (16-bit: %.2f GB); relative Frobenius error of the "
                 "quantisation against the %s checkpoint: %s", "MXFP4" if fp4 else "FP8 e4m3", held / 1e9, self.weight_quant_report["decode_tile_bytes_16bit"] / 1e9,
@@ -637,6 +683,14 @@ class LlamaForCausalLM:
         comm, lead = self.comm, self.comm.rank == 0
         pr = self.precise
         n = len(seqs)
+        if self.weight_residency == "tiles":
+            # the tiles are the only copy of a projection: rebuild it (exactly: sx_dequant_tiles) into the shared scratch buffer right in
+            # front of its GEMM. Everything here runs on ONE stream, so the GEMM on projection k has finished before the dequantisation
+            # of projection k + 1 overwrites the buffer; nothing else reads it (the decode step runs from the tiles).
+            fkey = "_f4" if self.weight_format == "mxfp4" else "_f8"
+            wmat = lambda lw, k: ops.dequant_tiles(dtype=dt, out=P["w_scratch"], **{"w_fp4" if fkey == "_f4" else "w_fp8": lw[k + fkey]})
+        else:
+            wmat = lambda lw, k: lw[k]
         pos_all = P["pos"].tolist()                                              # one host read per pass
         pos0 = [pos_all[g] for g in seqs]
         for T, p0 in zip(Ts, pos0):
@@ -654,7 +708,7 @@ class LlamaForCausalLM:
             if pr:
                 # fp32-grade activations: operand planes into a_planes = 2 GEMMs with fp32 outputs, fp32 RoPE / cache / attention
                 h, _ = ops.rmsnorm_planes(x, lw["ln1"], eps, dt)
-                qkv = ops.gemm(h, lw["wqkv"], a_planes=2, out_dtype=torch.float32)    # [M, 3H] fp32
+                qkv = ops.gemm(h, wmat(lw, "wqkv"), a_planes=2, out_dtype=torch.float32)    # [M, 3H] fp32
                 # (kv_format: the append quantises; the emulated twin's attention is the plain fp32 call on its rounded rows)
                 if uniform:
                     kw = self._kv_kw(li, slice(g0, g0 + n))
@@ -671,10 +725,10 @@ class LlamaForCausalLM:
                                                hd, dt, **kw)
                         att[offs[i]:offs[i + 1]] = ops.attention_f32(rows, kc_l[g:g + 1], vc_l[g:g + 1], P["pos"][g:g + 1], 1, Ts[i],
                                                                      nh, hd, scale, dt, kv_scales=kw.get("kv_scales"))
-                x = comm.all_reduce(ops.gemm(att, lw["wo"], a_planes=2, residual=x if lead else None, out_dtype=torch.float32))
+                x = comm.all_reduce(ops.gemm(att, wmat(lw, "wo"), a_planes=2, residual=x if lead else None, out_dtype=torch.float32))
                 h, _ = ops.rmsnorm_planes(x, lw["ln2"], eps, dt)
-                g_ = ops.split16(ops.gemm(h, lw["wgu"], a_planes=2, act="silu", glu=True, out_dtype=torch.float32), dt)
-                x = comm.all_reduce(ops.gemm(g_, lw["wd"], a_planes=2, residual=x if lead else None, out_dtype=torch.float32))
+                g_ = ops.split16(ops.gemm(h, wmat(lw, "wgu"), a_planes=2, act="silu", glu=True, out_dtype=torch.float32), dt)
+                x = comm.all_reduce(ops.gemm(g_, wmat(lw, "wd"), a_planes=2, residual=x if lead else None, out_dtype=torch.float32))
                 continue
             h = ops.rmsnorm(x, lw["ln1"], eps, dt)
             qkv = ops.gemm(h, lw["wqkv"])                                             # [M, 3H]

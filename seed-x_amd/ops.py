@@ -286,6 +286,79 @@ def pack_block_scales_fp4(scale, rows=16):
     return scale.view(N // rows, rows, B // 2, 2).permute(0, 2, 1, 3).contiguous()
 
 
+def unpack_decode_tiles_fp8(tiles):
+    """FP8 decode tiles [N/rows][K/64][rows][64] (rows = 16: pack_decode_tiles_fp8, 20: pack_decode_tiles20_fp8; the shape says which) →
+    the row-major e4m3 codes uint8 [N, K]: the host inverse of the packer, the reference sx_dequant_tiles is tested against."""
+    assert tiles.dtype == torch.uint8 and tiles.dim() == 4 and tiles.shape[2] in (16, 20) and tiles.shape[3] == 64
+    G, T, R, _ = tiles.shape
+    rows = tiles.permute(0, 2, 1, 3).reshape(G * R, T, 4, 2, 8)           # byte 16 g + 8 h + j of a slab → [g][h][j]
+    return rows.transpose(-3, -2).reshape(G * R, T * 64).contiguous()      # k = 32 h + 8 g + j
+
+
+def unpack_decode_tiles_fp4(tiles):
+    """MXFP4 decode tiles [N/rows][K/64][rows][32] (rows = 16 or 20) → the row-major packed e2m1 codes uint8 [N, K/2] (byte i = k 2i |
+    k 2i + 1 << 4): the host inverse of pack_decode_tiles_fp4 / pack_decode_tiles20_fp4."""
+    assert tiles.dtype == torch.uint8 and tiles.dim() == 4 and tiles.shape[2] in (16, 20) and tiles.shape[3] == 32
+    G, T, R, _ = tiles.shape
+    rows = tiles.permute(0, 2, 1, 3).reshape(G * R, T, 4, 2, 4)           # byte 8 g + 4 h + i of a slab → [g][h][i]
+    return rows.transpose(-3, -2).reshape(G * R, T * 32).contiguous()      # byte 16 h + 4 g + i of the row's 32 bytes
+
+
+def unpack_block_scales_fp4(scale_tiles):
+    """E8M0 scale tiles [N/rows][K/64][rows][2] (rows = 16 or 20) → the block scales uint8 [N, K/32]: the inverse of pack_block_scales_fp4."""
+    assert scale_tiles.dtype == torch.uint8 and scale_tiles.dim() == 4 and scale_tiles.shape[2] in (16, 20) and scale_tiles.shape[3] == 2
+    G, T, R, _ = scale_tiles.shape
+    return scale_tiles.permute(0, 2, 1, 3).reshape(G * R, T * 2).contiguous()
+
+
+class WeightShape:
+    """Shape and dtype of a weight whose only copy is its quantised decode tiles (LlamaForCausalLM(weight_residency="tiles")): what gemv
+    takes as ``w`` beside w_fp8 / w_fp4. It owns no storage — a kernel that would read it is handed a null pointer and refuses."""
+    __slots__ = ("shape", "dtype")
+
+    def __init__(self, shape, dtype):
+        self.shape, self.dtype = torch.Size(shape), dtype
+
+    def numel(self):
+        return self.shape[0] * self.shape[1]
+
+    def is_contiguous(self):
+        return True
+
+    def data_ptr(self):
+        return 0
+
+
+def dequant_tiles(w_fp8=None, w_fp4=None, dtype=torch.float16, out=None):
+    """The row-major 16-bit [N, K] matrix of a weight held as decode tiles (sx_dequant_tiles; exact: every element is the value
+    quant.dequantize_rows / dequantize_blocks_mxfp4 gives in ``dtype``). w_fp8 = (tiles, scale) / w_fp4 = (code_tiles, scale_tiles) as
+    for gemv; the tile shape says 16- or 20-row. ``out``: a caller-owned contiguous buffer of ``dtype`` with at least N * K elements (the
+    shared prefill scratch of the tiles residency): the matrix is written to its first N * K elements, nothing behind them is touched,
+    and the returned tensor is a view of it. The caller orders its uses of ``out``: on ONE stream the GEMM that reads the view finishes
+    before the next dequant_tiles overwrites it."""
+    assert (w_fp8 is None) != (w_fp4 is None), "dequant_tiles: exactly one of w_fp8 / w_fp4"
+    assert dtype in (torch.float16, torch.bfloat16)
+    t, sc = w_fp8 if w_fp8 is not None else w_fp4
+    rb = 64 if w_fp8 is not None else 32
+    assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 4 and t.shape[2] in (16, 20) and t.shape[3] == rb
+    N, K = t.shape[0] * t.shape[2], t.shape[1] * 64
+    args = _lib.DequantTilesArgs()
+    if w_fp8 is not None:
+        assert sc.dtype == torch.float32 and sc.is_contiguous() and sc.shape == (N,) and sc.device == t.device
+        args.w_dtype, args.w_scale = _lib.SX_FP8_E4M3, sc.data_ptr()
+    else:
+        assert sc.dtype == torch.uint8 and sc.is_contiguous() and sc.shape == t.shape[:3] + (2,) and sc.device == t.device
+        args.w_dtype, args.w_block_scale = _lib.SX_FP4_E2M1, sc.data_ptr()
+    if out is None:
+        out = torch.empty(N * K, dtype=dtype, device=t.device)
+    assert out.dtype == dtype and out.is_contiguous() and out.device == t.device and out.numel() >= N * K, \
+        "dequant_tiles: out must be a contiguous buffer of the target dtype with at least N * K elements"
+    args.tiles, args.out, args.out_bytes = t.data_ptr(), out.data_ptr(), out.numel() * out.element_size()
+    args.w_layout, args.N, args.K, args.dtype = (1 if t.shape[2] == 16 else 2), N, K, _DT[dtype]
+    check(_lib.load().sx_dequant_tiles(C.byref(args), _stream()), "sx_dequant_tiles")
+    return out.view(-1)[:N * K].view(N, K)
+
+
 class Tiled16:
     """A [rows <= 32, cols] 16-bit activation of the decode step held as MFMA operand tiles [rows/16][cols/32][16][32] (SX_TILED16
     in include/seedx_hip.h): what the skinny GEMM reads with one contiguous 1-KB load per operand. Rows 16..31 (lock-step batches
@@ -329,9 +402,11 @@ def gemv(x, w, residual=None, act=None, glu=False, out_dtype=None, w_tiles=None,
     20-row; the shape says which) with its fp32 row scales [N], in the row order of ``w``; replaces w_tiles / w_tiles20. ``w`` (the
     dequantised 16-bit matrix) only gives shape and dtype. MFMA path only: any other shape is an error, never a fall-back.
     w_fp4 = (code_tiles, scale_tiles): the weight as MXFP4 decode tiles (pack_decode_tiles_fp4 / pack_decode_tiles20_fp4; the shape says
-    which) with its E8M0 block-scale tiles (pack_block_scales_fp4 with the same rows); replaces w_tiles / w_tiles20 in the same way."""
+    which) with its E8M0 block-scale tiles (pack_block_scales_fp4 with the same rows); replaces w_tiles / w_tiles20 in the same way.
+    With w_fp8 / w_fp4, ``w`` may be a WeightShape: shape and dtype without storage (the tiles are the weight's only copy)."""
     lib = _lib.load()
     xt = isinstance(x, Tiled16)
+    assert not isinstance(w, WeightShape) or w_fp8 is not None or w_fp4 is not None, "gemv: a weight without storage needs its FP8 / MXFP4 tiles"
     if xt:
         M, K = x.rows, x.cols
         assert x.dtype == w.dtype and (x.planes == 2 or w_tiles is not None or w_tiles20 is not None or w_fp8 is not None or w_fp4 is not None)
