@@ -213,9 +213,11 @@ typedef struct sx_gemv_args {
 /* workgroups in x (= partial rows of row_ssq_out) sx_gemv launches for an M x N x K problem with / without GLU on the MFMA path */
 int sx_gemv_ssq_parts(int N, int glu, int w_layout);
 int sx_gemv(const sx_gemv_args* args, void* stream);
-/* host only, nothing is launched: the launch sx_gemv would make for these SX_FP4_E2M1 args (same checks, same status) —
- * plan[0..5] = workgroups in x, split-K factor, then the kernel family (R, U, TAIL, MB) of gemm_skinny_kernel */
-int sx_gemv_fp4_plan(const sx_gemv_args* args, int32_t* plan);
+/* host only, nothing is launched: the launch sx_gemv would make for these args under the current hooks (same checks, same status), for
+ * every weight format and both paths — plan[0] = path (0 VALU, 1 MFMA skinny), plan[1] = workgroups in x, plan[2] = split-K factor
+ * (grid y), plan[3..6] = the kernel family (R, U, TAIL, MB) of gemm_skinny_kernel (VALU: MR of gemv_kernel, 0, 0, 0), plan[7] = w_dtype
+ * as passed */
+int sx_gemv_plan(const sx_gemv_args* args, int32_t* plan);
 /* test hook: 1 = always take the VALU path (lets the tests compare both), 0 = automatic */
 int sx_gemv_force_valu(int on);
 /* tuning hook (tools/lab/gemv_lab): key 2 = split-K factor of the MFMA skinny GEMM when a workspace is given:

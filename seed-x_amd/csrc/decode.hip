@@ -355,23 +355,19 @@ __global__ __launch_bounds__(NWV * 64) void gemm_skinny_kernel(const GemvP p) {
 #pragma unroll
         for (int q = 0; q < R; ++q) {
           // FP8: the conversion is VALU work on loaded registers too — here, for the k-step being consumed, never at the top of the round
+          vec8 wa, wb;
           if constexpr (W4) {   // MXFP4: dword h = the eight k-slots of half h, byte h of ws = its block's E8M0 scale (fp32 bits: byte << 23)
             const unsigned sc = f.ws[u][q];
-            const vec8 wa = fp4x8_to16<TT>(f.wa[u][q][0], __uint_as_float((sc & 0xffu) << 23));
-            const vec8 wb = fp4x8_to16<TT>(f.wa[u][q][1], __uint_as_float((sc >> 8) << 23));
-#pragma unroll
-            for (int b = 0; b < MB; ++b) {
-              acc[q][b] = TT::mfma16(wa, __builtin_bit_cast(vec8, f.xa[u][b]), acc[q][b]);
-              acc[q][b] = TT::mfma16(wb, __builtin_bit_cast(vec8, f.xb[u][b]), acc[q][b]);
-            }
+            wa = fp4x8_to16<TT>(f.wa[u][q][0], __uint_as_float((sc & 0xffu) << 23));
+            wb = fp4x8_to16<TT>(f.wa[u][q][1], __uint_as_float((sc >> 8) << 23));
           } else {
-          const vec8 wa = W8 ? fp8x8_to16<TT>(f.wa[u][q][0], f.wa[u][q][1]) : __builtin_bit_cast(vec8, f.wa[u][q]);
-          const vec8 wb = W8 ? fp8x8_to16<TT>(f.wa[u][q][2], f.wa[u][q][3]) : __builtin_bit_cast(vec8, f.wb[u][q]);
+            wa = W8 ? fp8x8_to16<TT>(f.wa[u][q][0], f.wa[u][q][1]) : __builtin_bit_cast(vec8, f.wa[u][q]);
+            wb = W8 ? fp8x8_to16<TT>(f.wa[u][q][2], f.wa[u][q][3]) : __builtin_bit_cast(vec8, f.wb[u][q]);
+          }
 #pragma unroll
           for (int b = 0; b < MB; ++b) {
             acc[q][b] = TT::mfma16(wa, __builtin_bit_cast(vec8, f.xa[u][b]), acc[q][b]);
             acc[q][b] = TT::mfma16(wb, __builtin_bit_cast(vec8, f.xb[u][b]), acc[q][b]);
-          }
           }
         }
       }
@@ -1366,14 +1362,79 @@ extern "C" int sx_gemv_tune(int key, int value) {
 static int g_force_valu_gemv = 0;   // test hook (sx_gemv_force_valu): compare the two GEMV paths
 extern "C" int sx_gemv_force_valu(int on) { g_force_valu_gemv = on; return SX_OK; }   // 1 = VALU only, 2 = MFMA whenever legal
 
-// workgroups in x of the MFMA path (must mirror the r2 / gx choice in sx_gemv below)
-extern "C" int sx_gemv_ssq_parts(int N, int glu, int w_layout) {
-  if (w_layout == 2) return N / 20;
-  return (glu || N / 32 >= 256) ? N / 32 : N / 16;
+// Row groups of the MFMA path without 64-row workgroups, as always next to x16_out (row_ssq_out has one column per workgroup:
+// sx_gemv_ssq_parts): 20-row tiles, else R = 2 row groups per wave for GLU (one packed group) or when that still gives >= 256 blocks
+struct SkinnyRows { bool tail20, r2; int gx; };
+static SkinnyRows skinny_rows(int N, int glu, int w_layout) {
+  const bool tail20 = w_layout == 2;
+  const bool r2 = !tail20 && (glu || N / 32 >= 256);
+  return {tail20, r2, tail20 ? N / 20 : (r2 ? N / 32 : N / 16)};
+}
+extern "C" int sx_gemv_ssq_parts(int N, int glu, int w_layout) { return skinny_rows(N, glu, w_layout).gx; }
+
+// The launch of one sx_gemv call, whatever the weight format: path, grid (gx, S) and kernel — the (R, U, TAIL, MB) family of
+// gemm_skinny_kernel, or gemv_kernel with MR = R and U = TAIL = MB = 0 on the VALU path. sx_gemv_plan reports these fields.
+struct SkinnyPlan { int mfma, gx, S, R, U, TAIL, MB, ws_part_off; };   // ws_part_off: 0 = no split-K workspace, else where its partial sums begin
+static SkinnyPlan skinny_plan(const sx_gemv_args* a, bool planes2, bool mfma_ok) {
+  SkinnyPlan pl = {0, 0, 1};
+  // the decode-tile layout only exists for the MFMA kernel: it overrides the VALU test hook
+  pl.mfma = mfma_ok && (a->w_layout || a->x_layout || (a->out_dtype & SX_TILED16) || (g_force_valu_gemv != 1 && (a->M >= 5 || g_force_valu_gemv == 2)));
+  if (!pl.mfma) {
+    pl.gx = ((a->N + 1) / 2 + 3) / 4;     // a wave per pair of rows, four waves per workgroup
+    pl.R = a->M == 1 ? 1 : (a->M == 2 ? 2 : (a->M <= 4 ? 4 : 8));
+    return pl;
+  }
+  const SkinnyRows rows = skinny_rows(a->N, a->glu, a->w_layout);
+  // 64-row workgroups (R = 4, one k-step per round): every workgroup re-reads the whole x operand from L2 (64 B x K per 16-row block) —
+  // with two planes that traffic is as large as the weight stream itself and its time ADDS to it (tools/bench_skinny_shapes.py:
+  // qkv 26 / 32 / 43 us with 1 / 2 / 4 x blocks). Twice the rows per workgroup halve it; only where enough workgroups remain to fill
+  // the chip (qkv at 13B: 240, measured faster than 480 32-row ones), and not together with the RMSNorm-fold producer outputs (20-row
+  // tiles anyway)
+  const bool r4 = rows.r2 && g_skinny_var[3] > 0 && a->N % 64 == 0 && !a->x16_out && (a->N / 64 >= (g_skinny_var[3] == 2 ? 64 : 200));
+  pl.gx = r4 ? a->N / 64 : rows.gx;
+  // x blocks per weight fragment: 17..32 rows are two, fp32-grade rows (two planes) twice as many
+  pl.MB = (a->M > 16 ? 2 : 1) * (planes2 ? 2 : 1);
+  // split-K over workgroups when the row groups alone do not fill the chip (N = 5120: 320 workgroups on 256 CUs, the CUs
+  // with two of them set the time) AND the kernel is long enough to pay for the second pass (publish, count, re-read: ~4 us
+  // at the kernel's tail): tools/lab/gemv_lab — down 5120x13824 36.8 -> 33.0 us with S = 4, o 5120x5120 15.4 -> 17.6 (never)
+  if (a->workspace && !(rows.tail20 && g_skinny_var[2] <= 0)) {      // 256 balanced 20-row groups: no split unless forced (lab)
+    if (g_skinny_var[2] > 0) pl.S = g_skinny_var[2];
+    else if (g_skinny_var[2] == 0 && a->K >= 8192) while (pl.S < 8 && pl.gx * pl.S < 1024 && (a->K / 64) / (2 * pl.S * 4) >= 4) pl.S *= 2;
+    const uint64_t cnt_bytes = 16384;    // fixed, so launches of different N can share one workspace (their partial regions
+                                         // may overlap — launches are serial — but never reach the counters)
+    if (pl.S > 1 && (pl.gx > 4096 || cnt_bytes + (uint64_t)pl.S * 16 * pl.MB * a->N * 4 > a->workspace_bytes)) pl.S = 1;   // too small: no split
+    pl.ws_part_off = (int)cnt_bytes;
+  }
+  // the family: rows per wave, then k-steps per round by what the x blocks leave of the register file
+  pl.R = r4 ? 4 : (rows.tail20 || rows.r2 ? 2 : 1);
+  pl.TAIL = rows.tail20;
+  if (pl.MB == 4) pl.U = pl.R == 1 ? 2 : 1;
+  else if (r4) pl.U = pl.MB == 2 ? 1 : 2;
+  else if (pl.MB == 1) pl.U = 4;
+  else if (g_skinny_var[1] == 1) pl.U = 4;       // lab: 4 k-steps per round (256 VGPRs + AGPR copies, one wave per SIMD)
+  else if (rows.tail20) pl.U = g_skinny_var[1] == 2 ? 4 : 2;
+  else pl.U = rows.r2 ? 2 : 4;
+  return pl;
 }
 
-// the MXFP4 launcher (behind sx_gemv): plan != nullptr → only reports the launch it would make
-static int gemv_fp4_go(const sx_gemv_args* a, GemvP& p, bool planes2, void* stream, int32_t* plan);
+// every gemm_skinny_kernel the library holds: one row per (R, U, TAIL, MB) family, its kernels by [F16, BF16][16-bit, FP8, MXFP4 weights]
+typedef void (*SkinnyKernel)(const GemvP);
+struct SkinnyRow { int R, U, TAIL, MB; SkinnyKernel k[2][3]; };
+#define SX_SK_ROW(R, U, TAIL, MB)                                                                                                        \
+  {R, U, TAIL, MB, {{gemm_skinny_kernel<F16, R, 4, U, TAIL, MB, false, false>, gemm_skinny_kernel<F16, R, 4, U, TAIL, MB, true, false>,   \
+                     gemm_skinny_kernel<F16, R, 4, U, TAIL, MB, false, true>},                                                         \
+                    {gemm_skinny_kernel<BF16, R, 4, U, TAIL, MB, false, false>, gemm_skinny_kernel<BF16, R, 4, U, TAIL, MB, true, false>, \
+                     gemm_skinny_kernel<BF16, R, 4, U, TAIL, MB, false, true>}}}
+static const SkinnyRow g_skinny_table[] = {
+    SX_SK_ROW(1, 4, false, 1), SX_SK_ROW(2, 4, false, 1), SX_SK_ROW(2, 4, true, 1), SX_SK_ROW(4, 2, false, 1),
+    SX_SK_ROW(1, 4, false, 2), SX_SK_ROW(2, 2, false, 2), SX_SK_ROW(2, 2, true, 2), SX_SK_ROW(2, 4, false, 2), SX_SK_ROW(2, 4, true, 2),
+    SX_SK_ROW(4, 1, false, 2),
+    SX_SK_ROW(1, 2, false, 4), SX_SK_ROW(2, 1, false, 4), SX_SK_ROW(2, 1, true, 4), SX_SK_ROW(4, 1, false, 4),
+};
+#undef SX_SK_ROW
+// every gemv_kernel (the VALU path): [F16, BF16][MR = 1, 2, 4, 8]
+static const SkinnyKernel g_gemv_table[2][4] = {{gemv_kernel<F16, 1>, gemv_kernel<F16, 2>, gemv_kernel<F16, 4>, gemv_kernel<F16, 8>},
+                                                {gemv_kernel<BF16, 1>, gemv_kernel<BF16, 2>, gemv_kernel<BF16, 4>, gemv_kernel<BF16, 8>}};
 
 static int gemv_entry(const sx_gemv_args* a, void* stream, int32_t* plan) {
   SX_CHECK(a && a->x && a->W && a->y, "sx_gemv: null pointer");
@@ -1428,137 +1489,41 @@ static int gemv_entry(const sx_gemv_args* a, void* stream, int32_t* plan) {
   SX_CHECK(w4 || !a->w_block_scale, "sx_gemv: w_block_scale belongs to SX_FP4_E2M1 weights");
   p.w_bscale = (const unsigned char*)a->w_block_scale;
   SX_CHECK(!a->w_layout || (mfma_ok && a->K % 64 == 0), "sx_gemv: the decode-tile layout needs M >= 2, K %% 64 == 0, K >= 256, N %% 32 == 0");
-  // the decode-tile layout only exists for the MFMA kernel: it overrides the VALU test hook
   SX_CHECK(!p.y_tiled || mfma_ok, "sx_gemv: a tiled output needs the MFMA path (M >= 2, K %% 64 == 0, K >= 256, N %% 32 == 0)");
   SX_CHECK(!a->x_layout || mfma_ok, "sx_gemv: tiled x needs the MFMA path (M >= 2, K %% 64 == 0, K >= 256, N %% 32 == 0)");
-  if (w4) return gemv_fp4_go(a, p, planes2, stream, plan);
-  SX_CHECK(!plan, "sx_gemv_fp4_plan: w_dtype must be SX_FP4_E2M1");
-  if (mfma_ok && (a->w_layout || a->x_layout || p.y_tiled || (g_force_valu_gemv != 1 && (a->M >= 5 || g_force_valu_gemv == 2)))) {
-    // MFMA skinny GEMM: R = 2 row groups per wave for GLU (one packed group) or when that still gives >= 256 blocks
-    const bool tail20 = a->w_layout == 2;
-    const bool r2 = !tail20 && (a->glu || a->N / 32 >= 256);
-    // 64-row workgroups (R = 4, one k-step per round): every workgroup re-reads the whole x operand from L2 (64 B x K per 16-row block) —
-    // with two planes that traffic is as large as the weight stream itself and its time ADDS to it (tools/bench_skinny_shapes.py:
-    // qkv 26 / 32 / 43 us with 1 / 2 / 4 x blocks). Twice the rows per workgroup halve it; only where enough workgroups remain to fill
-    // the chip (qkv at 13B: 240, measured faster than 480 32-row ones), and not together with the RMSNorm-fold producer outputs (20-row
-    // tiles anyway)
-    const bool r4 = r2 && g_skinny_var[3] > 0 && a->N % 64 == 0 && !a->x16_out && (a->N / 64 >= (g_skinny_var[3] == 2 ? 64 : 200));
-    const int gx = tail20 ? a->N / 20 : (r4 ? a->N / 64 : (r2 ? a->N / 32 : a->N / 16));
-    // split-K over workgroups when the row groups alone do not fill the chip (N = 5120: 320 workgroups on 256 CUs, the CUs
-    // with two of them set the time) AND the kernel is long enough to pay for the second pass (publish, count, re-read: ~4 us
-    // at the kernel's tail): tools/lab/gemv_lab — down 5120x13824 36.8 -> 33.0 us with S = 4, o 5120x5120 15.4 -> 17.6 (never)
-    int S = 1;
-    if (a->workspace && !(tail20 && g_skinny_var[2] <= 0)) {      // 256 balanced 20-row groups: no split unless forced (lab)
-      if (g_skinny_var[2] > 0) S = g_skinny_var[2];
-      else if (g_skinny_var[2] == 0 && a->K >= 8192) while (S < 8 && gx * S < 1024 && (a->K / 64) / (2 * S * 4) >= 4) S *= 2;
-      const uint64_t cnt_bytes = 16384;    // fixed, so launches of different N can share one workspace (their partial regions
-                                           // may overlap — launches are serial — but never reach the counters)
-      if (S > 1 && (gx > 4096 || cnt_bytes + (uint64_t)S * (a->M > 16 ? (planes2 ? 64 : 32) : (planes2 ? 32 : 16)) * a->N * 4 > a->workspace_bytes)) S = 1;   // too small: no split
-      p.ws_cnt = (unsigned*)a->workspace;
-      p.ws_part = (float*)((char*)a->workspace + cnt_bytes);
-    }
-    const dim3 grid(gx, S);
-#define SX_SK_GO(TT, W8)                                                                                          \
-    if (a->M > 16 && planes2 && r4) {                                                                          \
-      hipLaunchKernelGGL((gemm_skinny_kernel<TT, 4, 4, 1, false, 4, W8>), grid, dim3(256), 0, ST, p);              \
-    } else if (a->M > 16 && planes2) {    /* round 6: 17..32 fp32-grade rows = four operand blocks per weight fragment */      \
-      if (tail20) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 1, true, 4, W8>), grid, dim3(256), 0, ST, p);      \
-      else if (r2) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 1, false, 4, W8>), grid, dim3(256), 0, ST, p);    \
-      else hipLaunchKernelGGL((gemm_skinny_kernel<TT, 1, 4, 2, false, 4, W8>), grid, dim3(256), 0, ST, p);            \
-    } else if (r4) {                                                                                           \
-      if (a->M > 16 || planes2) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 4, 4, 1, false, 2, W8>), grid, dim3(256), 0, ST, p); \
-      else hipLaunchKernelGGL((gemm_skinny_kernel<TT, 4, 4, 2, false, 1, W8>), grid, dim3(256), 0, ST, p);         \
-    } else if (a->M > 16 || planes2) {                                                                                \
-      if (g_skinny_var[1] == 1) {       /* lab: 4 k-steps per round (256 VGPRs + AGPR copies, one wave per SIMD) */ \
-        if (tail20) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 4, true, 2, W8>), grid, dim3(256), 0, ST, p);   \
-        else if (r2) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 4, false, 2, W8>), grid, dim3(256), 0, ST, p); \
-        else hipLaunchKernelGGL((gemm_skinny_kernel<TT, 1, 4, 4, false, 2, W8>), grid, dim3(256), 0, ST, p);         \
-      } else if (tail20 && g_skinny_var[1] == 2) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 4, true, 2, W8>), grid, dim3(256), 0, ST, p); \
-      else if (tail20) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 2, true, 2, W8>), grid, dim3(256), 0, ST, p); \
-      else if (r2) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 2, false, 2, W8>), grid, dim3(256), 0, ST, p);   \
-      else hipLaunchKernelGGL((gemm_skinny_kernel<TT, 1, 4, 4, false, 2, W8>), grid, dim3(256), 0, ST, p);           \
-    } else if (tail20) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 4, true, 1, W8>), grid, dim3(256), 0, ST, p); \
-    else if (r2) hipLaunchKernelGGL((gemm_skinny_kernel<TT, 2, 4, 4, false, 1, W8>), grid, dim3(256), 0, ST, p);             \
-    else hipLaunchKernelGGL((gemm_skinny_kernel<TT, 1, 4, 4, false, 1, W8>), grid, dim3(256), 0, ST, p);
-    if (w8) { if (a->dtype == SX_BF16) { SX_SK_GO(BF16, true) } else { SX_SK_GO(F16, true) } }
-    else if (a->dtype == SX_BF16) { SX_SK_GO(BF16, false) } else { SX_SK_GO(F16, false) }
-#undef SX_SK_GO
-    SX_HIP_LAUNCH_CHECK();
+  const SkinnyPlan pl = skinny_plan(a, planes2, mfma_ok);
+  if (!pl.mfma) {
+    SX_CHECK(a->M <= 8, "sx_gemv: M=%d > 8 needs K %% 64 == 0 and N %% 32 == 0 (MFMA path)", a->M);
+    SX_CHECK(p.packed == 0, "sx_gemv: the VALU kernel reads row-major weights only");
+    SX_CHECK(!a->x16_out && !a->row_ssq_in, "sx_gemv: the RMSNorm fold exists on the MFMA path only");
+  }
+  if (plan) {
+    const int32_t out[8] = {pl.mfma, pl.gx, pl.S, pl.R, pl.U, pl.TAIL, pl.MB, a->w_dtype};
+    for (int i = 0; i < 8; ++i) plan[i] = out[i];
     return SX_OK;
   }
-  SX_CHECK(a->M <= 8, "sx_gemv: M=%d > 8 needs K %% 64 == 0 and N %% 32 == 0 (MFMA path)", a->M);
-  SX_CHECK(p.packed == 0, "sx_gemv: the VALU kernel reads row-major weights only");
-  SX_CHECK(!a->x16_out && !a->row_ssq_in, "sx_gemv: the RMSNorm fold exists on the MFMA path only");
-  const int pairs = (a->N + 1) / 2;
-  const dim3 grid((pairs + 3) / 4), block(256);
-  const int mr = a->M == 1 ? 1 : (a->M == 2 ? 2 : (a->M <= 4 ? 4 : 8));
-#define SX_GEMV_GO(TT)                                                                          \
-  switch (mr) {                                                                                 \
-    case 1: hipLaunchKernelGGL((gemv_kernel<TT, 1>), grid, block, 0, ST, p); break;             \
-    case 2: hipLaunchKernelGGL((gemv_kernel<TT, 2>), grid, block, 0, ST, p); break;             \
-    case 4: hipLaunchKernelGGL((gemv_kernel<TT, 4>), grid, block, 0, ST, p); break;             \
-    default: hipLaunchKernelGGL((gemv_kernel<TT, 8>), grid, block, 0, ST, p); break;            \
+  SkinnyKernel kernel = nullptr;
+  if (pl.mfma) {
+    if (pl.ws_part_off) {
+      p.ws_cnt = (unsigned*)a->workspace;
+      p.ws_part = (float*)((char*)a->workspace + pl.ws_part_off);
+    }
+    for (const SkinnyRow& row : g_skinny_table)
+      if (row.R == pl.R && row.U == pl.U && row.TAIL == pl.TAIL && row.MB == pl.MB) kernel = row.k[a->dtype == SX_BF16][w4 ? 2 : (w8 ? 1 : 0)];
+  } else {
+    for (int i = 0; i < 4; ++i)
+      if (pl.R == 1 << i) kernel = g_gemv_table[a->dtype == SX_BF16][i];
   }
-  if (a->dtype == SX_BF16) { SX_GEMV_GO(BF16) } else { SX_GEMV_GO(F16) }
-#undef SX_GEMV_GO
+  SX_CHECK(kernel, "sx_gemv: no kernel for path %d, (R, U, TAIL, MB) = (%d, %d, %d, %d)", pl.mfma, pl.R, pl.U, pl.TAIL, pl.MB);
+  hipLaunchKernelGGL(kernel, dim3(pl.gx, pl.S), dim3(256), 0, ST, p);
   SX_HIP_LAUNCH_CHECK();
   return SX_OK;
 }
 
 extern "C" int sx_gemv(const sx_gemv_args* a, void* stream) { return gemv_entry(a, stream, nullptr); }
-extern "C" int sx_gemv_fp4_plan(const sx_gemv_args* a, int32_t* plan) {
-  SX_CHECK(plan, "sx_gemv_fp4_plan: null pointer");
+extern "C" int sx_gemv_plan(const sx_gemv_args* a, int32_t* plan) {
+  SX_CHECK(plan, "sx_gemv_plan: null pointer");
   return gemv_entry(a, nullptr, plan);
-}
-
-// MXFP4 tiles: sx_gemv's MFMA dispatch restated for the W4 kernels — the same tail20 / r2 / r4 / gx / S rules and the same (R, U, TAIL, MB)
-// family per case as the 16-bit / FP8 block above (tests/test_fp4_weights_cpu.py compares the two texts and, through sx_gemv_fp4_plan,
-// the workgroup counts with sx_gemv_ssq_parts): an MXFP4 launch has the grid, the k-slices and the split factor of its 16-bit twin.
-static int gemv_fp4_go(const sx_gemv_args* a, GemvP& p, bool planes2, void* stream, int32_t* plan) {
-    const bool tail20 = a->w_layout == 2;
-    const bool r2 = !tail20 && (a->glu || a->N / 32 >= 256);
-    const bool r4 = r2 && g_skinny_var[3] > 0 && a->N % 64 == 0 && !a->x16_out && (a->N / 64 >= (g_skinny_var[3] == 2 ? 64 : 200));
-    const int gx = tail20 ? a->N / 20 : (r4 ? a->N / 64 : (r2 ? a->N / 32 : a->N / 16));
-    int S = 1;
-    if (a->workspace && !(tail20 && g_skinny_var[2] <= 0)) {
-      if (g_skinny_var[2] > 0) S = g_skinny_var[2];
-      else if (g_skinny_var[2] == 0 && a->K >= 8192) while (S < 8 && gx * S < 1024 && (a->K / 64) / (2 * S * 4) >= 4) S *= 2;
-      const uint64_t cnt_bytes = 16384;
-      if (S > 1 && (gx > 4096 || cnt_bytes + (uint64_t)S * (a->M > 16 ? (planes2 ? 64 : 32) : (planes2 ? 32 : 16)) * a->N * 4 > a->workspace_bytes)) S = 1;
-      p.ws_cnt = (unsigned*)a->workspace;
-      p.ws_part = (float*)((char*)a->workspace + cnt_bytes);
-    }
-    const dim3 grid(gx, S);
-#define SX_SK4_K(R_, U_, TAIL_, MB_)                                                                               \
-    { if (plan) { plan[2] = R_; plan[3] = U_; plan[4] = TAIL_; plan[5] = MB_; }                                     \
-      else if (a->dtype == SX_BF16) hipLaunchKernelGGL((gemm_skinny_kernel<BF16, R_, 4, U_, TAIL_, MB_, false, true>), grid, dim3(256), 0, ST, p); \
-      else hipLaunchKernelGGL((gemm_skinny_kernel<F16, R_, 4, U_, TAIL_, MB_, false, true>), grid, dim3(256), 0, ST, p); }
-    if (plan) { plan[0] = gx; plan[1] = S; }
-    if (a->M > 16 && planes2 && r4) {
-      SX_SK4_K(4, 1, false, 4)
-    } else if (a->M > 16 && planes2) {
-      if (tail20) SX_SK4_K(2, 1, true, 4)
-      else if (r2) SX_SK4_K(2, 1, false, 4)
-      else SX_SK4_K(1, 2, false, 4)
-    } else if (r4) {
-      if (a->M > 16 || planes2) SX_SK4_K(4, 1, false, 2)
-      else SX_SK4_K(4, 2, false, 1)
-    } else if (a->M > 16 || planes2) {
-      if (g_skinny_var[1] == 1) {
-        if (tail20) SX_SK4_K(2, 4, true, 2)
-        else if (r2) SX_SK4_K(2, 4, false, 2)
-        else SX_SK4_K(1, 4, false, 2)
-      } else if (tail20 && g_skinny_var[1] == 2) SX_SK4_K(2, 4, true, 2)
-      else if (tail20) SX_SK4_K(2, 2, true, 2)
-      else if (r2) SX_SK4_K(2, 2, false, 2)
-      else SX_SK4_K(1, 4, false, 2)
-    } else if (tail20) SX_SK4_K(2, 4, true, 1)
-    else if (r2) SX_SK4_K(2, 4, false, 1)
-    else SX_SK4_K(1, 4, false, 1)
-#undef SX_SK4_K
-    if (plan) return SX_OK;
-    SX_HIP_LAUNCH_CHECK();
-    return SX_OK;
 }
 
 extern "C" int sx_attn_decode_b(const void* q, const void* kcache, const void* vcache, void* out, float* scratch,

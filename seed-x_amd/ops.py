@@ -386,6 +386,11 @@ class Tiled16:
         return d[:self.rows].contiguous()
 
 
+def _mfma_shape(N, K):
+    """The weight shapes sx_gemv's MFMA skinny kernel takes (its tiled operands and 9..32 rows exist on that kernel only)."""
+    return K % 64 == 0 and K >= 256 and N % 32 == 0
+
+
 def gemv(x, w, residual=None, act=None, glu=False, out_dtype=None, w_tiles=None, y_tiled=False, workspace=None,
          emit_norm=False, ssq_in=None, w_tiles20=None, planes_out=False, norm_gamma=None, w_fp8=None, w_fp4=None):
     """w_tiles: the same weight in the decode layout (pack_decode_tiles); used instead of w when the MFMA path runs.
@@ -438,10 +443,10 @@ def gemv(x, w, residual=None, act=None, glu=False, out_dtype=None, w_tiles=None,
     if planes_out:
         assert y_tiled or emit_norm
         args.out_planes = 1
-    if w_tiles is not None and (xt or y_tiled or M >= 5) and K % 64 == 0 and K >= 256 and N % 32 == 0:
+    if w_tiles is not None and (xt or y_tiled or M >= 5) and _mfma_shape(N, K):
         assert w_tiles.shape == w.shape and w_tiles.dtype == w.dtype and w_tiles.is_contiguous()
         args.W, args.w_layout = w_tiles.data_ptr(), 1
-    if w_tiles20 is not None and not glu and (xt or y_tiled or M >= 5) and K % 64 == 0 and K >= 256 and N % 32 == 0 and N % 20 == 0:
+    if w_tiles20 is not None and not glu and (xt or y_tiled or M >= 5) and _mfma_shape(N, K) and N % 20 == 0:
         assert w_tiles20.shape == w.shape and w_tiles20.dtype == w.dtype and w_tiles20.is_contiguous()
         args.W, args.w_layout = w_tiles20.data_ptr(), 2
     if w_fp8 is not None:
@@ -481,7 +486,7 @@ def linear(x, w, **kw):
     """Dispatch M <= 16 rows to the weight-streaming GEMV / skinny GEMM (when the epilogue allows), else the MFMA GEMM."""
     M, K, N = x.shape[0], x.shape[1], w.shape[0]
     # 9..16 rows only exist on the MFMA skinny kernel (K % 64 == 0, K >= 256, N % 32 == 0); other shapes keep the tiled GEMM
-    skinny_ok = M <= 8 or (K % 64 == 0 and K >= 256 and N % 32 == 0)
+    skinny_ok = M <= 8 or _mfma_shape(N, K)
     if M <= 16 and skinny_ok and kw.get("bias") is None and kw.get("bias2d") is None and not kw.get("res_mod") \
             and kw.get("out") is None and not kw.get("n_valid"):
         res = kw.get("residual")
@@ -757,7 +762,7 @@ def linear_planes(x32, w, w_tiles=None, **kw):
     """epilogue(x32 @ w^T) with x32 fp32 carried as two 16-bit planes: <= 16 rows on the weight-streaming skinny GEMM, else the MFMA GEMM."""
     M, K = x32.shape
     N = w.shape[0]
-    if M <= 32 and K % 64 == 0 and K >= 256 and N % 32 == 0:
+    if M <= 32 and _mfma_shape(N, K):
         return gemv(split16(x32, w.dtype, tiled=True), w, w_tiles=w_tiles, **kw)
     return gemm(split16(x32, w.dtype), w, a_planes=2, **kw)
 

@@ -993,12 +993,13 @@ def test_gemm_matrix_covers_every_launched_kernel():
 
 def test_gemv_matrix_covers_every_launched_kernel():
     """tests/test_gemv_matrix_gpu.py's case table mirrors sx_gemv's dispatch: FAMILIES is exactly the set of gemm_skinny_kernel
-    instantiations of SX_SK_GO, VALU_MR that of gemv_kernel in SX_GEMV_GO, and every one of them has cases for both dtypes and
-    (skinny) both weight formats; every case reaches the family it was written for."""
+    rows of g_skinny_table (each instantiated for both dtypes and the 16-bit, FP8 and MXFP4 weight formats), VALU_MR that of gemv_kernel
+    in g_gemv_table, and every one of them has cases for both dtypes and (skinny) both weight formats of the matrix; every case reaches the
+    family it was written for."""
     from tests import test_gemv_matrix_gpu as gv
     sk, sk_tt, mr, tt = gv.source_kernels()
     assert len(sk) == 14 and sk == set(gv.FAMILIES) and len(gv.FAMILIES) == 14, sk ^ set(gv.FAMILIES)
-    assert sk_tt == {("F16", False), ("F16", True), ("BF16", False), ("BF16", True)} and tt == {"F16", "BF16"}
+    assert sk_tt == {(t, w8, w4) for t in ("F16", "BF16") for w8, w4 in ((False, False), (True, False), (False, True))} and tt == {"F16", "BF16"}
     assert mr == set(gv.VALU_MR)
     ids = [c["id"] for c in gv.SKINNY + gv.VALU + gv.BOTH]
     assert len(ids) == len(set(ids))
@@ -1047,12 +1048,50 @@ def test_gemv_matrix_k_values_reach_every_peeled_round():
             assert c["K"] in (320, 832)
 
 
-def test_gemv_matrix_dispatch_block_unchanged():
-    """kernel_of in tests/test_gemv_matrix_gpu.py restates sx_gemv's dispatch by hand; the block it restates is pinned here."""
+def test_gemv_plan_matches_plan_of():
+    """sx_gemv_plan (host only, nothing launched) equals plan_of, the hand-written restatement in tests/test_gemv_matrix_gpu.py — path,
+    grid, split factor, kernel, and what is refused — for every case of the GPU matrix under its own hooks and workspace, and over the
+    full product of a sweep no GPU run affords: shapes on both sides of every threshold of the rule, the three weight layouts, the
+    RMSNorm-fold producer, every hook value, and no workspace / one byte below the forced factor's threshold (none forced: that of 8,
+    the largest automatic factor) / that threshold. Every family and every VALU MR occurs among the accepted combinations."""
+    import collections
+    import itertools
+    from seedx_amd import _lib
     from tests import test_gemv_matrix_gpu as gv
-    assert gv.dispatch_crc() == 0x14246dd8, \
-        "csrc/decode.hip: the dispatch block of sx_gemv (from `const bool tail20` to `#undef SX_SK_GO`) changed — re-read kernel_of, " \
-        "FAMILIES and the case table of tests/test_gemv_matrix_gpu.py against it, then record the new CRC here"
+    lib, accepted = _lib.load(), collections.Counter()             # accepted: (path, R | MR, U, TAIL, MB) -> combinations of the sweep
+    for c in gv.SKINNY + gv.VALU + [dict(c, fv=fv) for c in gv.BOTH for fv in (0, 1, 2)]:
+        ws = 0
+        if gv.kernel_of(c)[0] == "sk" and c["ws"] != "none":
+            ws = gv.ws_extent(c, max(c["S"], 1)) - (1 if c["ws"] == "short" else 0)
+        want = gv.plan_of(c, ws)
+        S = c["S"] if c["S"] > 1 and c["ws"] == "full" else 1
+        assert want is not None and (c["fam"] is None or want[2:] == (S,) + tuple(map(int, c["fam"]))), (c["id"], want)
+        a = gv.plan_args(c, ws)
+        with gv.Hooks(lib, c):
+            got = gv.lib_plan(lib, a)
+        assert got == want + (a.w_dtype,), (c["id"], got, want, lib.sx_last_error().decode())
+    shapes = []
+    for M, planes, N, K, glu, wl, emit in itertools.product((1, 2, 4, 5, 8, 16, 17, 32), (1, 2), (32, 64, 640, 1280, 5120, 8192, 12800, 16384),
+                                                            (256, 320, 8192, 13824), (False, True), (0, 1, 2), (False, True)):
+        c = gv.case("", "f16", M=M, planes=planes, N=N, K=K, glu=glu, w_layout=wl, emit=emit, x_layout=1 if planes == 2 else 0, out="f32")
+        shapes.append((c, gv.plan_args(c), 16 * (2 if M > 16 else 1) * planes * N * 4))
+    for var1, S, var3, fv in itertools.product((0, 1, 2), (-1, 0, 2, 8), (0, 1, 2), (0, 1, 2)):
+        hooks = dict(var1=var1, S=S, var3=var3, fv=fv)
+        with gv.Hooks(lib, hooks):
+            for c, a, part in shapes:
+                c.update(hooks)
+                thr = 16384 + (S if S > 1 else 8) * part
+                for ws in (0, thr - 1, thr):
+                    a.workspace, a.workspace_bytes = (a.x if ws else None), ws
+                    want, got = gv.plan_of(c, ws), gv.lib_plan(lib, a)
+                    if want is None or got is None:
+                        assert want is None and got is None, ("one side refuses", c, ws, want, got, lib.sx_last_error().decode())
+                        continue
+                    assert got == want + (0,), (c, ws, got, want)
+                    accepted[want[:1] + want[3:]] += 1
+    assert sum(accepted.values()) > 100000, accepted
+    assert {k[1:] for k in accepted if k[0] == 1} == {tuple(map(int, f)) for f in gv.FAMILIES}
+    assert {k[1] for k in accepted if k[0] == 0} == set(gv.VALU_MR)
 
 
 def test_layernorm_fold_host_algebra_and_tile_gate():

@@ -1,17 +1,13 @@
 """Host side of the MXFP4 (e2m1, block-32 E8M0 scale) decode mode: the codec (seedx_amd/quant.py) against a table of the sixteen e2m1
 values, exactness of the dequantised values in fp16 and bf16 at both ends of the exponent clamp, idempotence, the error on Gaussian rows,
 the MXFP4 code and scale tile layouts against the index map of include/seedx_hip.h, GLU packing and tensor-parallel consistency, mode
-selection, memory_footprint(), and the restated grid rule of the MXFP4 launcher in csrc/decode.hip against sx_gemv's own. No GPU."""
-import ctypes as C
-import os
-import re
-
+selection, memory_footprint(), and the dispatch plan of an MXFP4 launch (sx_gemv_plan) against that of its 16-bit and FP8 twins. No GPU."""
 import pytest
 import torch
 
 from oracle import weights
+from tests import test_gemv_matrix_gpu as gv
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAGS = [0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0]
 # (N, K, glu, residual, layout): the shapes of tests/test_fp8_weights_gpu.py
 SHAPES = [(1536, 512, False, False, "t"), (5120, 1024, False, True, "t20"), (5120, 5120, False, True, "t"), (2816, 512, True, False, "t"),
@@ -286,116 +282,46 @@ def test_footprint_at_13b_dims(monkeypatch):
     assert k["decode_tiles"] == fq["decode_tiles"] and k["kv_cache"] == L * 16 * 40 * 1024 * (2 * 128 + 8)
 
 
-# ---- the MXFP4 launcher restates sx_gemv's grid rule and kernel choice -------------------------------------------------------------
-def _strip(text):
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    return re.sub(r"[\s\\]+", "", text)
-
-
-def _dispatch_texts():
-    """(grid rule, kernel choice) of sx_gemv's 16-bit / FP8 block and of the MXFP4 launcher, comments and whitespace removed; a kernel
-    launch is written K(R,U,TAIL,MB) on both sides."""
-    src = open(os.path.join(ROOT, "seed-x_amd", "csrc", "decode.hip")).read()
-    a0 = src.index("const bool tail20")
-    a = src[a0:src.index("#undef SX_SK_GO")]
-    b0 = src.index("const bool tail20", a0 + 1)
-    b = src[b0:src.index("#undef SX_SK4_K")]
-    assert src.count("const bool tail20") == 2
-    rule_a, rule_b = a[:a.index("#define SX_SK_GO(")], b[:b.index("#define SX_SK4_K(")]
-    pick_a = a[a.index("\n", a.index("#define SX_SK_GO(")):a.index("if (w8)")]
-    pick_a = re.sub(r"hipLaunchKernelGGL\(\(gemm_skinny_kernel<TT, (\d), 4, (\d), (true|false), (\d), W8>\), grid, dim3\(256\), 0, ST, p\);",
-                    r"K(\1,\2,\3,\4)", pick_a)
-    pick_b = b[b.index("if (plan) { plan[0] = gx; plan[1] = S; }") + len("if (plan) { plan[0] = gx; plan[1] = S; }"):]
-    pick_b = re.sub(r"SX_SK4_K\((\d), (\d), (true|false), (\d)\)", r"K(\1,\2,\3,\4)", pick_b)
-    macro_b = b[b.index("#define SX_SK4_K("):b.index("if (plan) { plan[0] = gx; plan[1] = S; }")]
-    return _strip(rule_a), _strip(rule_b), _strip(pick_a), _strip(pick_b), macro_b
-
-
-def test_fp4_launcher_restates_the_16bit_grid_rule_and_kernel_choice():
-    """Source level: the tail20 / r2 / r4 / gx / S rules and the (R, U, TAIL, MB) chosen per case are, token for token, those of the pinned
-    16-bit / FP8 dispatch block; every MXFP4 launch goes through one macro that instantiates gemm_skinny_kernel<.., false, true>."""
-    rule_a, rule_b, pick_a, pick_b, macro_b = _dispatch_texts()
-    assert "gx" in rule_a and "S*=2" in rule_a and rule_a.endswith("constdim3grid(gx,S);")
-    assert rule_b == rule_a
-    assert pick_a.count("K(") == 16 and "hipLaunchKernelGGL" not in pick_a
-    assert pick_b == pick_a
-    assert re.findall(r"gemm_skinny_kernel<(\w+), R_, 4, U_, TAIL_, MB_, false, true>", macro_b) == ["BF16", "F16"]
-    assert len(re.findall(r"gemm_skinny_kernel<", macro_b)) == 2
-
-
-def _plan(lib, _lib, N, K, glu, layout, M, planes, ws_bytes, emit_norm=False):
-    buf = C.create_string_buffer(64 + 16)
-    base = (C.addressof(buf) + 15) & ~15
-    a = _lib.GemvArgs()
-    a.x = a.W = a.y = a.w_block_scale = base
-    a.M, a.N, a.K, a.glu = M, N, K, 1 if glu else 0
-    a.dtype, a.out_dtype, a.w_dtype = _lib.SX_F16, _lib.SX_F32, _lib.SX_FP4_E2M1
-    a.w_layout, a.x_layout, a.x_planes = (2 if layout == "t20" else 1), (1 if planes == 2 else 0), planes
-    if ws_bytes:
-        a.workspace, a.workspace_bytes = base, ws_bytes
-    if emit_norm:
-        a.x16_out = a.row_ssq_out = base
-    plan = (C.c_int32 * 6)()
-    st = lib.sx_gemv_fp4_plan(C.byref(a), plan)
-    assert st == 0, lib.sx_last_error().decode()
-    return list(plan)
-
-
-def _dispatch16(N, K, glu, layout, M, planes, ws_bytes, emit_norm=False):
-    """sx_gemv's 16-bit dispatch at its default tuning (g_skinny_var = {0, 0, 0, 1}), by hand: (gx, S, R, U, TAIL, MB)."""
-    tail20, planes2 = layout == "t20", planes == 2
-    r2 = not tail20 and (glu or N // 32 >= 256)
-    r4 = r2 and N % 64 == 0 and not emit_norm and N // 64 >= 200
-    gx = N // 20 if tail20 else N // 64 if r4 else N // 32 if r2 else N // 16
-    S = 1
-    if ws_bytes and not tail20:
-        if K >= 8192:
-            while S < 8 and gx * S < 1024 and (K // 64) // (2 * S * 4) >= 4:
-                S *= 2
-        mb = (64 if planes2 else 32) if M > 16 else (32 if planes2 else 16)
-        if S > 1 and (gx > 4096 or 16384 + S * mb * N * 4 > ws_bytes):
-            S = 1
-    big = M > 16
-    if big and planes2:
-        fam = (4, 1, 0, 4) if r4 else (2, 1, 1, 4) if tail20 else (2, 1, 0, 4) if r2 else (1, 2, 0, 4)
-    elif r4:
-        fam = (4, 1, 0, 2) if (big or planes2) else (4, 2, 0, 1)
-    elif big or planes2:
-        fam = (2, 2, 1, 2) if tail20 else (2, 2, 0, 2) if r2 else (1, 4, 0, 2)
-    else:
-        fam = (2, 4, 1, 1) if tail20 else (2, 4, 0, 1) if r2 else (1, 4, 0, 1)
-    return [gx, S, *fam]
+# ---- MXFP4 launches share sx_gemv's one dispatch plan ------------------------------------------------------------------------------
+def _case(N, K, glu, layout, M, planes, emit_norm=False, **kw):
+    return gv.case("", "f16", M=M, N=N, K=K, glu=glu, w_layout=2 if layout == "t20" else 1, x_layout=1 if planes == 2 else 0, planes=planes,
+                   out="f32", emit=emit_norm, **kw)
 
 
 def test_fp4_grid_rule_agrees_with_ssq_parts_and_the_16bit_dispatch():
-    """Through sx_gemv_fp4_plan (host only, nothing launched): on the seven shapes of the GPU tests and every (M, planes) they use, the
-    MXFP4 launch has the workgroup count sx_gemv_ssq_parts reports wherever the RMSNorm fold asks for it, and the grid, split factor and
-    kernel family of the 16-bit dispatch."""
+    """Through sx_gemv_plan (host only, nothing launched): on the seven shapes of the GPU tests and every (M, planes) they use, the
+    MXFP4 launch has the workgroup count sx_gemv_ssq_parts reports wherever the RMSNorm fold asks for it, and the 16-bit, FP8 and MXFP4
+    launches have one plan — path, grid, split factor and kernel family — which is the hand-written plan_of's."""
     from seedx_amd import _lib
     lib = _lib.load()
+    formats = (0, _lib.SX_FP8_E4M3, _lib.SX_FP4_E2M1)
+
+    def plan(c, ws):
+        """The one plan of the three weight formats (asserted equal to each other and to plan_of), without the format field."""
+        got = [gv.lib_plan(lib, gv.plan_args(c, ws, w_dtype=f)) for f in formats]
+        assert all(g is not None for g in got), lib.sx_last_error().decode()
+        assert [g[7] for g in got] == list(formats)
+        assert got[0][:7] == got[1][:7] == got[2][:7] == gv.plan_of(c, ws) and got[2][0] == 1, (c, ws, got, gv.plan_of(c, ws))
+        return list(got[2][1:7])
+
     seen = set()
     for N, K, glu, res, layout in SHAPES:
         ws = 16384 + 8 * 32 * N * 4
         for M, planes in [(1, 2), (11, 2), (16, 2), (21, 2), (32, 2), (8, 1), (24, 1)]:
-            got = _plan(lib, _lib, N, K, glu, layout, M, planes, ws)
-            assert got == _dispatch16(N, K, glu, layout, M, planes, ws), (N, K, glu, layout, M, planes, got)
+            got = plan(_case(N, K, glu, layout, M, planes), ws)
             seen.add(tuple(got[2:]))
             if not glu:           # the fold's producer form (x16_out): never 64-row workgroups, parts as the library reports them
-                fold = _plan(lib, _lib, N, K, glu, layout, M, planes, ws, emit_norm=True)
+                fold = plan(_case(N, K, glu, layout, M, planes, emit_norm=True), ws)
                 assert fold[0] == lib.sx_gemv_ssq_parts(N, 0, 2 if layout == "t20" else 1), (N, layout, fold)
-                assert fold == _dispatch16(N, K, glu, layout, M, planes, ws, emit_norm=True)
             elif got[2] != 4:
                 assert got[0] == lib.sx_gemv_ssq_parts(N, 1, 1)
-        assert _plan(lib, _lib, N, K, glu, layout, 16, 2, 0)[1] == 1                     # no workspace: never split
-    assert _plan(lib, _lib, 640, 13824, False, "t", 16, 2, 16384 + 8 * 32 * 640 * 4)[1] == 8     # the split-K shape splits
+        assert plan(_case(N, K, glu, layout, 16, 2), 0)[1] == 1                     # no workspace: never split
+    assert plan(_case(640, 13824, False, "t", 16, 2), 16384 + 8 * 32 * 640 * 4)[1] == 8     # the split-K shape splits
     assert len(seen) == 12, seen                        # every family of the default tuning (the other two are lab variants)
-    # refusals reach the plan query too: the 16-bit dtype, a missing scale, row-major W
-    a = _lib.GemvArgs()
-    plan = (C.c_int32 * 6)()
-    buf = C.create_string_buffer(64)
-    a.x = a.W = a.y = C.addressof(buf)
-    a.M, a.N, a.K, a.dtype, a.out_dtype, a.w_layout = 8, 64, 512, _lib.SX_F16, _lib.SX_F32, 1
-    assert lib.sx_gemv_fp4_plan(C.byref(a), plan) == 1 and "SX_FP4_E2M1" in lib.sx_last_error().decode()
+    # the query takes every format, and refusals reach it too: a 16-bit w_dtype without w_block_scale is accepted and reports format 0,
+    # SX_FP4_E2M1 without its block scales is refused
+    a = gv.plan_args(gv.case("", "f16", M=8, N=64, K=512, w_layout=1))
+    got = gv.lib_plan(lib, a)
+    assert got is not None and got[0] == 1 and got[7] == 0, lib.sx_last_error().decode()
     a.w_dtype = _lib.SX_FP4_E2M1
-    assert lib.sx_gemv_fp4_plan(C.byref(a), plan) == 1 and "w_block_scale" in lib.sx_last_error().decode()
+    assert gv.lib_plan(lib, a) is None and "w_block_scale" in lib.sx_last_error().decode()

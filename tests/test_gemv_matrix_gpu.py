@@ -1,5 +1,5 @@
 """sx_gemv and the decode attention against fp64: every instantiation of gemm_skinny_kernel and gemv_kernel that sx_gemv launches
-(csrc/decode.hip SX_SK_GO / SX_GEMV_GO), both 16-bit dtypes, 16-bit and FP8 weight tiles, at the k-slice lengths where the peeled rounds
+(csrc/decode.hip g_skinny_table / g_gemv_table), both 16-bit dtypes, 16-bit and FP8 weight tiles, at the k-slice lengths where the peeled rounds
 of the skinny kernel differ; and sx_attn_decode_b / sx_attn_decode_fused at the shapes where the split and the group combine differ.
 
 Each GEMV case drives sx_gemv through _lib.GemvArgs directly and checks
@@ -25,7 +25,8 @@ table against the sources.
 
 The hooks sx_gemv_tune / sx_gemv_force_valu are process-global: every launch that sets them restores (1, 0), (2, 0), (3, 1) and
 force_valu(0) on its way out, whatever happens in between (Hooks); test_hook_defaults_restored then asks the library itself, with
-launches that do not touch the hooks.
+launches and sx_gemv_plan queries that do not touch the hooks. kernel_of / plan_of restate sx_gemv's dispatch plan by hand and never
+ask the library; tests/test_cpu_suite.py holds sx_gemv_plan against them on the CPU, over the case table and a sweep.
 """
 import ctypes as C
 import math
@@ -47,7 +48,7 @@ DECODE_HIP = os.path.join(ROOT, "seed-x_amd", "csrc", "decode.hip")
 # ----------------------------------------------------------------------------------------------------------------------------
 # the case table
 # ----------------------------------------------------------------------------------------------------------------------------
-# (R, U, TAIL, MB) of gemm_skinny_kernel<TT, R, 4, U, TAIL, MB, W8>: the 14 instantiations of SX_SK_GO
+# (R, U, TAIL, MB) of gemm_skinny_kernel<TT, R, 4, U, TAIL, MB, W8, W4>: the 14 rows of g_skinny_table
 FAMILIES = ((1, 4, False, 1), (2, 4, False, 1), (2, 4, True, 1), (4, 2, False, 1),
             (1, 4, False, 2), (2, 2, False, 2), (2, 2, True, 2), (2, 4, False, 2), (2, 4, True, 2), (4, 1, False, 2),
             (1, 2, False, 4), (2, 1, False, 4), (2, 1, True, 4), (4, 1, False, 4))
@@ -55,6 +56,8 @@ VALU_MR = (1, 2, 4, 8)
 # K / 64 per U: the four waves' lengths cover 1..4 (U = 1), 1..9 (U = 2), 1..19 (U = 4)
 NKS = {1: (5, 13), 2: (5, 13, 21, 29, 33), 4: (5, 13, 21, 29, 37, 45, 53, 61, 69, 73)}
 FULL_CLASSES = ("0", "1", "2", "odd>=3", "even>=4")
+SSQ_DIM, SSQ_EPS = 4096, 1e-5                     # of every row_ssq_in
+_DUMMY = C.create_string_buffer(64 + 16)          # plan_args: where the pointers of a host-only query point
 
 
 def wave_rounds(nks, U, S=1):
@@ -85,19 +88,21 @@ def case(cid, dt, **kw):
 
 def n_blocks(c):
     """MB of the kernel a case runs on the MFMA path: x blocks per weight fragment."""
-    p2 = c["planes"] == 2
-    return 4 if (c["M"] > 16 and p2) else (2 if (c["M"] > 16 or p2) else 1)
+    return kernel_of(c)[4]
+
+
+def mfma_ok(c):
+    """The shapes the MFMA skinny kernel takes."""
+    return (c["M"] >= 2 or c["planes"] == 2) and c["K"] % 64 == 0 and c["K"] >= 256 and c["N"] % 32 == 0
 
 
 def kernel_of(c):
     """The kernel sx_gemv launches for a case — ('sk', R, U, TAIL, MB, W8) or ('valu', MR) — by the rules of its dispatch (mfma_ok,
-    tail20, r2, r4, M > 16, planes2, g_skinny_var[1], g_skinny_var[3]). RE-READ this function when the dispatch block changes
-    (tests/test_cpu_suite.py pins its CRC)."""
-    M, N, K = c["M"], c["N"], c["K"]
+    tail20, r2, r4, M > 16, planes2, g_skinny_var[1], g_skinny_var[3]). Written by hand and independent of the library:
+    tests/test_cpu_suite.py holds sx_gemv_plan against it."""
+    M, N = c["M"], c["N"]
     planes2 = c["planes"] == 2
-    y_tiled = c["out"] == "tiled"
-    mfma_ok = (M >= 2 or planes2) and K % 64 == 0 and K >= 256 and N % 32 == 0
-    if mfma_ok and (c["w_layout"] or c["x_layout"] or y_tiled or (c["fv"] != 1 and (M >= 5 or c["fv"] == 2))):
+    if mfma_ok(c) and (c["w_layout"] or c["x_layout"] or c["out"] == "tiled" or (c["fv"] != 1 and (M >= 5 or c["fv"] == 2))):
         tail20 = c["w_layout"] == 2
         r2 = not tail20 and (c["glu"] or N // 32 >= 256)
         r4 = r2 and c["var3"] > 0 and N % 64 == 0 and not c["emit"] and N // 64 >= (64 if c["var3"] == 2 else 200)
@@ -126,31 +131,77 @@ def kernel_of(c):
     return ("valu", 1 if M == 1 else (2 if M == 2 else (4 if M <= 4 else 8)))
 
 
-def split_factor(c):
-    """S the host uses: the forced factor unless the workspace is too small for it (then 1); automatic splits need K >= 8192, which
-    no case here has."""
-    return c["S"] if c["S"] > 1 and c["ws"] == "full" else 1
+def plan_of(c, ws_bytes):
+    """The launch of a case with `ws_bytes` of workspace under its hooks (var1, S = hook 2, var3, fv), as sx_gemv_plan reports it:
+    (path, gx, S, R | MR, U, TAIL, MB), or None where sx_gemv refuses the case. By hand, like kernel_of, with the automatic split
+    (K >= 8192, < 1024 workgroups, four double rounds left per wave, never on 20-row tiles) and the too-small-workspace fallback."""
+    M, N, K = c["M"], c["N"], c["K"]
+    tiles = c["w8"] or c.get("w4", False)
+    mfma_only = c["w_layout"] or c["x_layout"] or c["out"] == "tiled"
+    if ((c["glu"] and N % 32) or (c["planes"] == 2 and not c["x_layout"]) or (c["out_planes"] and not (c["out"] == "tiled" or c["emit"]))
+            or (c["emit"] and (c["out"] != "f32" or c["glu"] or N % 32)) or (c["gamma"] and not c["emit"])
+            or (c["w_layout"] == 2 and (c["glu"] or N % 20 or N % 32)) or ((mfma_only or tiles) and not mfma_ok(c)) or (tiles and not c["w_layout"])):
+        return None
+    if not (mfma_ok(c) and (mfma_only or (c["fv"] != 1 and (M >= 5 or c["fv"] == 2)))):
+        return None if (M > 8 or c["emit"] or c["ssq_in"]) else (0, ((N + 1) // 2 + 3) // 4, 1, kernel_of(c)[1], 0, 0, 0)
+    R, U, TAIL, MB = kernel_of(c)[1:5]
+    gx = N // 20 if TAIL else N // (16 * R)
+    S, forced = 1, c["S"]
+    if ws_bytes and not (TAIL and forced <= 0):
+        if forced > 0:
+            S = forced
+        elif forced == 0 and K >= 8192:
+            while S < 8 and gx * S < 1024 and (K // 64) // (4 * S * 2) >= 4:
+                S *= 2
+        if S > 1 and (gx > 4096 or 16384 + S * 16 * MB * N * 4 > ws_bytes):
+            S = 1
+    return (1, gx, S, R, U, int(TAIL), MB)
+
+
+def plan_args(c, ws_bytes=0, w_dtype=None):
+    """sx_gemv_args of a case with every pointer it needs set to one 16-B aligned dummy address: for host-only sx_gemv_plan queries, and
+    the scalar fields of a launch (which replaces the pointers). `w_dtype` overrides the case's weight format."""
+    from seedx_amd import _lib
+    a, base = _lib.GemvArgs(), (C.addressof(_DUMMY) + 15) & ~15
+    a.x = a.W = a.y = base
+    a.M, a.N, a.K = c["M"], c["N"], c["K"]
+    a.dtype = _lib.SX_F16 if c["dt"] == "f16" else _lib.SX_BF16
+    a.out_dtype = {"f32": _lib.SX_F32, "16": a.dtype, "tiled": a.dtype | _lib.SX_TILED16}[c["out"]]
+    a.act = {None: _lib.SX_ACT_NONE, "gelu": _lib.SX_ACT_GELU, "silu": _lib.SX_ACT_SILU}[c["act"]]
+    a.glu, a.w_layout, a.x_layout, a.x_planes, a.out_planes = int(c["glu"]), c["w_layout"], c["x_layout"], c["planes"], int(c["out_planes"])
+    a.w_dtype = (_lib.SX_FP8_E4M3 if c["w8"] else _lib.SX_FP4_E2M1 if c.get("w4") else 0) if w_dtype is None else w_dtype
+    if c["ssq_in"]:
+        a.ssq_in_parts, a.ssq_dim, a.ssq_eps = 64, SSQ_DIM, SSQ_EPS
+    for on, field in ((a.w_dtype == _lib.SX_FP8_E4M3, "w_scale"), (a.w_dtype == _lib.SX_FP4_E2M1, "w_block_scale"), (c["res"], "residual"),
+                      (c["gamma"], "x16_gamma"), (c["ssq_in"], "row_ssq_in"), (c["emit"], "x16_out"), (c["emit"], "row_ssq_out"),
+                      (ws_bytes, "workspace"), (ws_bytes, "workspace_bytes")):
+        if on:
+            setattr(a, field, ws_bytes if field == "workspace_bytes" else base)
+    return a
+
+
+def lib_plan(lib, a):
+    """sx_gemv_plan's answer for `a` as a tuple of its eight fields, or None where the library refuses the arguments."""
+    plan = (C.c_int32 * 8)()
+    return tuple(plan) if lib.sx_gemv_plan(C.byref(a), plan) == 0 else None
 
 
 def source_kernels():
-    """The instantiations in the sources: ({(R, U, TAIL, MB)}, {(TT, W8)} of SX_SK_GO, {MR}, {TT} of SX_GEMV_GO)."""
+    """The instantiations in the sources: ({(R, U, TAIL, MB)} of g_skinny_table, {(TT, W8, W4)} of its row macro, {MR}, {TT} of
+    g_gemv_table). Every gemm_skinny_kernel< / gemv_kernel< of the host section is one of them."""
     src = open(DECODE_HIP).read()
-    body = src[src.index("#define SX_SK_GO("):src.index("#undef SX_SK_GO")]
-    sk = {(int(r), int(u), t == "true", int(mb))
-          for r, u, t, mb in re.findall(r"gemm_skinny_kernel<TT, (\d), 4, (\d), (true|false), (\d), W8>", body)}
-    assert len(re.findall(r"gemm_skinny_kernel<", body)) == len(re.findall(r"gemm_skinny_kernel<TT, \d, 4, \d, (?:true|false), \d, W8>", body))
-    sk_tt = {(tt, w8 == "true") for tt, w8 in re.findall(r"SX_SK_GO\((BF16|F16), (true|false)\)", body)}
-    body = src[src.index("#define SX_GEMV_GO("):src.index("#undef SX_GEMV_GO")]
-    mr = {int(m) for m in re.findall(r"gemv_kernel<TT, (\d)>", body)}
-    tt = set(re.findall(r"SX_GEMV_GO\((BF16|F16)\)", body))
-    return sk, sk_tt, mr, tt
-
-
-def dispatch_crc():
-    """Whitespace-normalised CRC of sx_gemv's dispatch block (from `const bool tail20` to `#undef SX_SK_GO`)."""
-    src = open(DECODE_HIP).read()
-    body = src[src.index("const bool tail20"):src.index("#undef SX_SK_GO")]
-    return zlib.crc32(" ".join(body.split()).encode())
+    host = src[src.index("#define ST "):]
+    body = host[host.index("#define SX_SK_ROW("):host.index("#undef SX_SK_ROW")]
+    macro, table = body[:body.index("g_skinny_table")], body[body.index("g_skinny_table"):]
+    rows = re.findall(r"SX_SK_ROW\((\d), (\d), (true|false), (\d)\)", table)
+    sk = {(int(r), int(u), t == "true", int(mb)) for r, u, t, mb in rows}
+    assert len(rows) == len(sk) == table.count("SX_SK_ROW("), "a family is listed twice, or a row is not of the form (R, U, TAIL, MB)"
+    inst = re.findall(r"gemm_skinny_kernel<(BF16|F16), R, 4, U, TAIL, MB, (true|false), (true|false)>", macro)
+    assert len(host.split("gemm_skinny_kernel<")) - 1 == len(inst) == len(set(inst))
+    sk_tt = {(tt, w8 == "true", w4 == "true") for tt, w8, w4 in inst}
+    valu = re.findall(r"gemv_kernel<(BF16|F16), (\d)>", host)
+    assert len(host.split("gemv_kernel<")) - 1 == len(valu) == len(set(valu)) == len({t for t, _ in valu}) * len({m for _, m in valu})
+    return sk, sk_tt, {int(m) for _, m in valu}, {t for t, _ in valu}
 
 
 def _skinny(fam, i, nks, dt, w8, tag="", nonglu_wide=False, **kw):
@@ -395,7 +446,7 @@ def make_inputs(c, dev):
     if c["gamma"]:
         I["gamma"] = (1.0 + 0.5 * torch.randn(N, device=dev, generator=gen)).abs().clamp_min(0.2)
     if c["ssq_in"]:
-        I["ssq_dim"], I["ssq_eps"] = 4096, 1e-5
+        I["ssq_dim"], I["ssq_eps"] = SSQ_DIM, SSQ_EPS
         I["ssq"] = (torch.rand(16 * RB, 64, device=dev, generator=gen) * 1.5 + 0.25) * (I["ssq_dim"] / 64.0)
     return I
 
@@ -434,19 +485,14 @@ def launch(lib, c, I, dev, perm=None, w8=None, ws_S=None, hooks=True):
     w8 = c["w8"] if w8 is None else w8
     rows = (lambda t: t) if perm is None else (lambda t: t[perm].contiguous())
     keep = {}
-    a = _lib.GemvArgs()
+    a = plan_args(c, w_dtype=_lib.SX_FP8_E4M3 if w8 else 0)          # the scalar fields; every pointer is replaced below
     xs = [rows(xp) for xp in I["xs"]]
     keep["x"] = tile_rows(xs, M, K, dtype, dev) if c["x_layout"] else _nan_lead(xs[0])
     keep["W"] = weight_buffer(c, I, w8, dev)
     a.x, a.W = keep["x"].data_ptr(), keep["W"].data_ptr()
-    a.M, a.N, a.K = M, N, K
-    a.dtype = _lib.SX_F16 if dtype == F16 else _lib.SX_BF16
-    a.act = {None: _lib.SX_ACT_NONE, "gelu": _lib.SX_ACT_GELU, "silu": _lib.SX_ACT_SILU}[c["act"]]
-    a.glu, a.w_layout, a.x_layout, a.x_planes = int(c["glu"]), c["w_layout"], c["x_layout"], c["planes"]
-    a.out_planes = int(c["out_planes"])
     if w8:
         keep["scale"] = _nan_lead(I["scale"], 64)
-        a.w_dtype, a.w_scale = _lib.SX_FP8_E4M3, keep["scale"].data_ptr()
+        a.w_scale = keep["scale"].data_ptr()
     if c["res"]:
         keep["res"] = _nan_lead(rows(I["res"]))
         a.residual = keep["res"].data_ptr()
@@ -458,17 +504,14 @@ def launch(lib, c, I, dev, perm=None, w8=None, ws_S=None, hooks=True):
         if perm is not None:        # padding rows stay where they are
             ssq = torch.cat([ssq[:M][perm], ssq[M:]])
         keep["ssq_in"] = _nan_lead(ssq)
-        a.row_ssq_in, a.ssq_in_parts, a.ssq_dim, a.ssq_eps = keep["ssq_in"].data_ptr(), 64, I["ssq_dim"], I["ssq_eps"]
+        a.row_ssq_in = keep["ssq_in"].data_ptr()
     P_out = 2 if c["out_planes"] else 1
     R = dict(guards=[])
     if c["out"] == "tiled":
         yb = TiledOut(P_out, M, n_out, dtype, dev)
-        a.out_dtype = a.dtype | _lib.SX_TILED16
     else:
-        odt = torch.float32 if c["out"] == "f32" else dtype
-        yb = GBuf(M * n_out, odt, dev)
+        yb = GBuf(M * n_out, torch.float32 if c["out"] == "f32" else dtype, dev)
         yb.allow()[:] = True
-        a.out_dtype = _lib.SX_F32 if c["out"] == "f32" else a.dtype
     a.y = yb.ptr()
     R["guards"].append(("y", yb))
     if c["emit"]:
@@ -515,7 +558,7 @@ def check_guards(c, R, what):
         assert bool(torch.isfinite(R["x16"].float()).all()) and bool(torch.isfinite(R["ssq"][:c["M"]]).all()), f"{what}: non-finite x16_out / row_ssq_out"
     if "ws" in R:
         ws, nb = R["ws"], R["ws_bytes"]
-        S = split_factor(c)
+        S = plan_of(c, nb)[2]              # the forced factor unless the workspace is too small for it (no case splits by itself)
         ext = ws_extent(c, S) if S > 1 else 16384
         assert bool((ws[:256] == 0xA5).all()) and bool((ws[256 + nb:] == 0xA5).all()), f"{what}: written outside workspace_bytes"
         assert int(ws[256:256 + 16384].view(torch.int32).abs().sum()) == 0, f"{what}: arrival counters not left at zero"
@@ -746,6 +789,13 @@ def _probe_path(lib, dev, c, I):
     return launch(lib, c, I, dev, hooks=False)["y"]
 
 
+# where hooks 3 and 1 change the kernel family: 200 64-row workgroups (R = 4 by default, R = 2 with hook 3 at 0), 64 of them (R = 2 by
+# default, R = 4 with hook 3 at 2, as the matrix sets it), and 17 rows on 20-row tiles (U = 2 by default, U = 4 with hook 1 at 1 or 2)
+PROBE_R4 = case("defaults-r4", "f16", M=8, N=12800, K=256)
+PROBE_R2 = case("defaults-r2", "f16", M=8, N=4096, K=256, glu=True, act="silu")
+PROBE_U = case("defaults-u", "f16", M=17, N=640, K=256, w_layout=2)
+
+
 @stops_on_gpu_fault
 def test_hook_defaults_restored(dev):
     """After the matrix above (this test runs behind it) the library itself is asked, by launches that do NOT touch the hooks (every
@@ -754,14 +804,17 @@ def test_hook_defaults_restored(dev):
         (-1 and 1 would not);
       * sx_gemv_force_valu is 0: a row-major M = 3 launch gives the VALU kernel's bits (2 would give the MFMA kernel's), M = 5 the
         MFMA kernel's (1 would give the VALU kernel's).
-    The probes are then shown to see a leak: with (2, 8) resp. force_valu(1) / (2) set on purpose they answer the other way.
-    NOT verified here: hooks 1 and 3. They choose between kernels that give the same bits, the same partial-sum layout
-    ([S][16 MB][N]) and the same counters, so no launch can tell their state at a shape this suite affords (hook 3 changes the
-    automatic split factor only from N = 8192 at K = 8192), and the library has no getter. They are set and restored by the same
-    three lines as hook 2 (Hooks / restore_defaults), which is all that can be said for them."""
+      * sx_gemv_tune(3, .) is 1 and sx_gemv_tune(1, .) is 0. They choose between kernels that give the same bits, the same
+        partial-sum layout ([S][16 MB][N]) and the same counters, so no launch can tell their state at a shape this suite affords;
+        sx_gemv_plan can, without a launch: N = 12800 without GLU at M = 8 runs R = 4 (200 64-row workgroups; 0 would give R = 2),
+        GLU N = 4096 runs R = 2 (2 would give R = 4), 17 rows on 20-row tiles run U = 2 (hook 1 at 1 or 2 would give U = 4).
+    The probes are then shown to see a leak: with (2, 8) resp. force_valu(1) / (2), (3, 0), (3, 2), (1, 1) and (1, 2) set on purpose
+    they answer the other way."""
     from seedx_amd import _lib
     lib = _lib.load()
+    _probe_family = lambda c: lib_plan(lib, plan_args(c))[3:5]          # (R, U) by sx_gemv_plan: nothing launched, no hook touched
     # 1. the probes, before anything in this test sets a hook
+    family_r4, family_r2, family_u = (_probe_family(c) for c in (PROBE_R4, PROBE_R2, PROBE_U))
     leaked_split, auto_split = _probe_split(lib, dev, 320), _probe_split(lib, dev, 8192)
     paths = {}
     for M in (3, 5):
@@ -776,6 +829,9 @@ def test_hook_defaults_restored(dev):
     assert auto_split, "the automatic split-K is switched off: sx_gemv_tune(2, -1 or 1) leaked out of a test"
     assert same_bits(paths[3][2], forced[3][1]), "M = 3 does not run the VALU kernel: sx_gemv_force_valu(2) leaked out of a test"
     assert same_bits(paths[5][2], forced[5][2]), "M = 5 does not run the MFMA kernel: sx_gemv_force_valu(1) leaked out of a test"
+    assert family_r4 == (4, 2), f"N = 12800 at M = 8 does not run <4, 4, 2, F, 1> but (R, U) = {family_r4}: sx_gemv_tune(3, 0) leaked out of a test"
+    assert family_r2 == (2, 4), f"GLU N = 4096 at M = 8 does not run <2, 4, 4, F, 1> but (R, U) = {family_r2}: sx_gemv_tune(3, 2) leaked out of a test"
+    assert family_u == (2, 2), f"17 rows on 20-row tiles do not run <2, 4, 2, T, 2> but (R, U) = {family_u}: sx_gemv_tune(1, .) leaked out of a test"
     # 3. the probes do see a leak
     try:
         assert lib.sx_gemv_tune(2, 8) == 0
@@ -787,9 +843,18 @@ def test_hook_defaults_restored(dev):
             assert lib.sx_gemv_force_valu(fv) == 0
             c, I, _ = paths[M]
             assert same_bits(_probe_path(lib, dev, c, I), forced[M][fv]), f"the path probe does not see sx_gemv_force_valu({fv})"
+        assert lib.sx_gemv_force_valu(0) == 0 and lib.sx_gemv_tune(3, 0) == 0
+        assert _probe_family(PROBE_R4) == (2, 4), "the family probe does not see sx_gemv_tune(3, 0)"
+        assert lib.sx_gemv_tune(3, 2) == 0
+        assert _probe_family(PROBE_R2) == (4, 2), "the family probe does not see sx_gemv_tune(3, 2)"
+        assert lib.sx_gemv_tune(3, 1) == 0
+        for v in (1, 2):
+            assert lib.sx_gemv_tune(1, v) == 0
+            assert _probe_family(PROBE_U) == (2, 4), f"the family probe does not see sx_gemv_tune(1, {v})"
     finally:
         restore_defaults(lib)
     assert not _probe_split(lib, dev, 320) and _probe_split(lib, dev, 8192)
+    assert [_probe_family(c) for c in (PROBE_R4, PROBE_R2, PROBE_U)] == [(4, 2), (2, 4), (2, 2)]
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
