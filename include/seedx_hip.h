@@ -209,6 +209,14 @@ typedef struct sx_gemv_args {
                         * (v_cvt_scalef32_pk_{f16,bf16}_fp4, the block scale applied in the convert: every code * 2^e with e in [-13, 13] is
                         * a normal fp16 / bf16 number, so the operand is exact) in front of the same MFMAs, k-slices and epilogue as the
                         * 16-bit tiles: the result has the bits of the 16-bit kernel on the dequantised weights. No row scale. */
+  /* Pre-activation addend (MFMA path only — every w_dtype, w_layout 1 and 2, every x block count and split-K; SX_ERR_INVALID on the
+   * VALU path; all NULL / 0 = off, the launch is then exactly the one without these fields). The unmerged LoRA delta of sx_lora_expand:
+   * row m's summed accumulator gets addend[m][n] added AFTER the wave, split-K and plane sums, w_scale and rstd (row_ssq_in) and BEFORE
+   * activation, GLU and residual — y = epi(acc + addend). A row that does not take its addend keeps the bits of a launch without one,
+   * and nothing of addend is read for it. */
+  const float* addend;       /* fp32 [M][N], 16-B aligned, columns in the row order of W as passed (GLU-packed rows: packed order)         */
+  const int32_t* addend_sel; /* device int32 [M] or NULL. NULL: every row takes its addend; else row m iff addend_sel[m] in [0, addend_n) */
+  int32_t addend_n;          /* with addend_sel: the adapter count (>= 1), so that the rows sx_lora_expand left unwritten are skipped; else 0 */
 } sx_gemv_args;
 /* workgroups in x (= partial rows of row_ssq_out) sx_gemv launches for an M x N x K problem with / without GLU on the MFMA path */
 int sx_gemv_ssq_parts(int N, int glu, int w_layout);
@@ -497,6 +505,32 @@ int sx_split16(const float* x, int64_t ldx, void* out, int rows, int cols, int d
  * may be NULL) and / or the planes of y (out16, may be NULL). */
 int sx_rmsnorm_planes(const float* x, const float* gamma, float* y32, void* out16, int rows, int cols, float eps, int dtype,
                       void* stream);
+/* Per-request LoRA adapters, UNMERGED beside one resident base model (csrc/lora.hip; the rule in fp64: seedx_amd/lora.py). The reference
+ * trains LoRA r 32 / alpha 32 on q/k/v/o/gate/up/down with the three norms in modules_to_save (configs/clm_models/llm_seed_x_lora.yaml) and
+ * serves it through peft's Linear.forward (proj/peft/src/peft/tuners/lora.py:808-825): y = W x + s B (A x), s = alpha / r. Here the
+ * intermediate t = A x stays fp32. Every call reads the adapter index of a row from DEVICE memory (sel; graph-capturable); an index outside
+ * [0, n_adapters) makes the row a base row: nothing is read from the tables and nothing is written for it. Fixed reduction order; a row's
+ * result depends on the row, its adapter's tables and its sel only — not on the row count, the row's position or its neighbours.
+ *
+ * sx_lora_shrink: t[m][i] = sum_k A[sel[m]][i][k] * (hi[m][k] + lo[m][k]), i < SR = S * R — S projections that share the x operand (3 for
+ *   q|k|v, 2 for gate|up, 1 for o / down) times the rank table R. x: the planes of sx_split16 / sx_rmsnorm_planes* — dtype | SX_TILED16:
+ *   operand tiles [2][ceil(M / 16)][K/32][16][32] (M <= 32, K % 32 == 0: what sx_gemv reads with x_planes = 2); else rows [M][2K] =
+ *   [hi | lo] (any M <= 65535: prefill). A: 16-bit [n_adapters][SR][K] (an adapter of rank r < R is zero-padded: exact). t: fp32 [M][SR].
+ *   K % 8 == 0, SR % 4 == 0, 16-B aligned pointers. */
+int sx_lora_shrink(const void* x, const void* A, const int32_t* sel, float* t, int M, int K, int SR, int n_adapters, int dtype,
+                   void* stream);
+/* sx_lora_expand: delta[m][n] = scale[sel[m]] * sum_j B[sel[m]][n][j] * t[m][seg[n / 16] * R + j], j < R. B: 16-bit [n_adapters][N][R],
+ *   rows in the order of W AS PACKED (GLU-packed rows stay packed); seg: device int32 [N/16], the S-segment of t each 16-row group of W
+ *   reads (clamped into [0, S)); scale: fp32 [n_adapters] = lora_alpha / r. delta: fp32 [M][N] — sx_gemv_args.addend (with addend_sel =
+ *   sel, addend_n = n_adapters) or sx_gemm's bias2d with bias2d_rows = 1. Base rows of delta are NOT written.
+ *   N % 16 == 0, R % 8 == 0, S * R <= 512. */
+int sx_lora_expand(const float* t, const void* B, const int32_t* seg, const float* scale, const int32_t* sel, float* delta, int M, int N,
+                   int R, int S, int n_adapters, int dtype, void* stream);
+/* sx_rmsnorm_planes with one gamma per adapter (peft modules_to_save copies of input_layernorm / post_attention_layernorm / model.norm):
+ *   row m uses gamma_table[sel[m]] (fp32 [n_adapters][cols]) when sel[m] is in [0, n_adapters), else the base gamma. Every row has the bits
+ *   of sx_rmsnorm_planes called with the gamma it selected (one shared body). n_adapters = 0 (gamma_table may be NULL): all base rows. */
+int sx_rmsnorm_planes_sel(const float* x, const float* gamma, const float* gamma_table, const int32_t* sel, int n_adapters, float* y32,
+                          void* out16, int rows, int cols, float eps, int dtype, void* stream);
 /* sx_rope_kv_append_b on fp32 rows and fp32 caches (modeling_llama_xformer.py:141-149,215-220): qkv fp32 [G*T][3*H*D], q rotated in
  * place, rotated k and v appended to kcache / vcache fp32 [G][H][Tmax][D] at pos0[g] + t. The cos / sin tables are rounded to
  * table_dtype first (:128-131 casts them to the activation dtype); positions outside [0, Tmax) write nothing. */

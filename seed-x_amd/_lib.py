@@ -41,7 +41,8 @@ class GemvArgs(C.Structure):
                 ("w_layout", c_i32), ("x_layout", c_i32), ("workspace", c_vp), ("workspace_bytes", C.c_uint64),
                 ("x16_out", c_vp), ("row_ssq_out", c_vp), ("row_ssq_in", c_vp), ("ssq_in_parts", c_i32), ("ssq_dim", c_i32),
                 ("ssq_eps", c_f32), ("x_planes", c_i32), ("out_planes", c_i32), ("x16_gamma", c_vp),
-                ("w_dtype", c_i32), ("w_scale", c_vp), ("w_block_scale", c_vp)]
+                ("w_dtype", c_i32), ("w_scale", c_vp), ("w_block_scale", c_vp),
+                ("addend", c_vp), ("addend_sel", c_vp), ("addend_n", c_i32)]
 
 
 class AttnF32Args(C.Structure):
@@ -159,6 +160,9 @@ SIGNATURES = {
     "sx_split_bf16": [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp],
     "sx_split16": [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp],
     "sx_rmsnorm_planes": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_i32, c_vp],
+    "sx_lora_shrink": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
+    "sx_lora_expand": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
+    "sx_rmsnorm_planes_sel": [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_f32, c_i32, c_vp],
     "sx_rope_kv_append_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i32, c_vp],
     "sx_rope_kv_append_f32_v16": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i32, c_vp],
     "sx_rope_kv_append_f32_q8": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i32,

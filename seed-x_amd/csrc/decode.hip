@@ -31,6 +31,9 @@ struct GemvP {
   const float* x16_gamma;  // x16_out holds o * gamma[col] (the NEXT RMSNorm's gamma applied on the activation side: the weights stay exact)
   const float* w_scale;    // FP8 weight tiles (W8 kernels): fp32 [N], row n of W as passed is e4m3 code * w_scale[n]
   const unsigned char* w_bscale;   // MXFP4 weight tiles (W4 kernels): E8M0 bytes [N/16][K/64][16][2] (20-row tiles: [N/20][K/64][20][2])
+  const float* addend;     // MFMA path: fp32 [M][N] (rows of W as passed) added to row m's summed accumulator ahead of activation / GLU / residual
+  const int* addend_sel;   // int32 [M] or NULL: row m takes its addend iff NULL or addend_sel[m] in [0, addend_n) (the unmerged LoRA delta, csrc/lora.hip)
+  int addend_n;
 };
 
 template <typename TT, int MR>
@@ -497,6 +500,23 @@ __global__ __launch_bounds__(NWV * 64) void gemm_skinny_kernel(const GemvP p) {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
           if (b < RB) v[q][b][e] *= rstd_fold[b];
+  }
+  if (p.addend) {   // pre-activation addend: behind every sum and scale, ahead of activation / GLU / residual; a row that is switched off keeps its bits
+#pragma unroll
+    for (int b = 0; b < MB; ++b) {
+      if (b >= RB) break;
+      const int m = r + 16 * b;
+      bool on = mvalid[b];
+      if (on && p.addend_sel) {
+        const int a = p.addend_sel[m];
+        on = a >= 0 && a < p.addend_n;
+      }
+      if (on) {
+#pragma unroll
+        for (int q = 0; q < R; ++q)
+          if (!(TAIL && q == 1 && g != 0)) v[q][b] += *(const f32x4_t*)(p.addend + (size_t)m * p.N + n0 + q * 16 + 4 * g);
+      }
+    }
   }
   const int ncols = p.glu ? p.N / 2 : p.N;
   const size_t lo_off = (size_t)ncols * 16 * (size_t)((p.M + 15) >> 4);   // planes out: the lo plane follows the hi plane's row blocks
@@ -1488,6 +1508,11 @@ static int gemv_entry(const sx_gemv_args* a, void* stream, int32_t* plan) {
            "sx_gemv: SX_FP4_E2M1 weights need w_block_scale (16-B aligned E8M0 bytes)");
   SX_CHECK(w4 || !a->w_block_scale, "sx_gemv: w_block_scale belongs to SX_FP4_E2M1 weights");
   p.w_bscale = (const unsigned char*)a->w_block_scale;
+  // pre-activation addend (the LoRA delta of csrc/lora.hip): MFMA path only
+  SX_CHECK(a->addend || !a->addend_sel, "sx_gemv: addend_sel belongs to addend");
+  SX_CHECK(!a->addend || (((uintptr_t)a->addend & 15) == 0 && (a->addend_sel ? a->addend_n >= 1 : a->addend_n == 0)),
+           "sx_gemv: addend must be 16-B aligned fp32 [M][N]; addend_sel comes with addend_n >= 1 (rows with addend_sel[m] in [0, addend_n) take it)");
+  p.addend = a->addend; p.addend_sel = a->addend_sel; p.addend_n = a->addend_n;
   SX_CHECK(!a->w_layout || (mfma_ok && a->K % 64 == 0), "sx_gemv: the decode-tile layout needs M >= 2, K %% 64 == 0, K >= 256, N %% 32 == 0");
   SX_CHECK(!p.y_tiled || mfma_ok, "sx_gemv: a tiled output needs the MFMA path (M >= 2, K %% 64 == 0, K >= 256, N %% 32 == 0)");
   SX_CHECK(!a->x_layout || mfma_ok, "sx_gemv: tiled x needs the MFMA path (M >= 2, K %% 64 == 0, K >= 256, N %% 32 == 0)");
@@ -1496,6 +1521,7 @@ static int gemv_entry(const sx_gemv_args* a, void* stream, int32_t* plan) {
     SX_CHECK(a->M <= 8, "sx_gemv: M=%d > 8 needs K %% 64 == 0 and N %% 32 == 0 (MFMA path)", a->M);
     SX_CHECK(p.packed == 0, "sx_gemv: the VALU kernel reads row-major weights only");
     SX_CHECK(!a->x16_out && !a->row_ssq_in, "sx_gemv: the RMSNorm fold exists on the MFMA path only");
+    SX_CHECK(!a->addend, "sx_gemv: the pre-activation addend exists on the MFMA path only");
   }
   if (plan) {
     const int32_t out[8] = {pl.mfma, pl.gx, pl.S, pl.R, pl.U, pl.TAIL, pl.MB, a->w_dtype};

@@ -126,9 +126,18 @@ def _common_prefix(ids_a, sigs_a, ids_b, sigs_b, cap):
     return p
 
 
+def tag_signatures(sigs, adapter):
+    """Row signatures of a request that runs under the LoRA adapter ``adapter``: KV rows depend on the adapter that computed them, so every
+    row's signature carries its name — (signature, adapter). Records and prompts then agree on a row only under the same adapter, and a
+    prefix is kept or forked only among requests of one adapter. None (the base model) leaves the signatures as they are, so a queue
+    without adapters keeps its records; an untagged signature never equals a tagged one."""
+    return list(sigs) if adapter is None else [(s, adapter) for s in sigs]
+
+
 class PrefixIndex:
     """What the KV cache of each of ``n_slots`` slots holds: the token ids of its rows, one opaque hashable signature per row (the
-    engine: a fingerprint of the row's input embedding, so that image rows with equal ids and different features differ), the KV epoch
+    engine: a fingerprint of the row's input embedding, so that image rows with equal ids and different features differ — tagged with the
+    request's LoRA adapter, ``tag_signatures``), the KV epoch
     the record was made under and a last-use stamp from a clock that only moves forward (0: never used)."""
 
     def __init__(self, n_slots):
@@ -222,17 +231,22 @@ def plan_admission(index, free_slots, live_slots, requests, min_tokens, epoch=0)
     return [(c[1], c[0], c[2], c[3]) for c in placed], deferred
 
 
-def simulate_prefix(prompts, lengths, n_slots, max_admit=None, min_tokens=16, sigs=None, generated=None, index=None):
+def simulate_prefix(prompts, lengths, n_slots, max_admit=None, min_tokens=16, sigs=None, generated=None, index=None, adapters=None):
     """``simulate`` with prefix reuse: request i has the prompt ids ``prompts[i]`` (row signatures ``sigs[i]``; None: the ids themselves)
     and produces ``lengths[i]`` tokens by decode steps (a forced image chunk's tokens left out, as for ``simulate``). ``generated[i]``
     (optional) are ALL the ids it produced: a finished slot then holds its prompt and every produced id but the last, which later
     turns may match; without it only the prompt. ``index``: a PrefixIndex to start from and leave behind (None: empty). Returns
     ``simulate``'s dict — same decode_steps, live_slot_steps, parked_slot_steps and admissions: only the slots differ — with
     prefill_passes counting the rounds actually run, plus prefill_tokens (rows forwarded at admission), prefix_hit_tokens (rows not
-    forwarded), forked_tokens (those of them that were copied) and fork_launches (rounds with at least one copy)."""
+    forwarded), forked_tokens (those of them that were copied) and fork_launches (rounds with at least one copy).
+    ``adapters[i]`` (optional): the LoRA adapter request i runs under, or None — its rows' signatures, prompt rows and fed-back rows
+    alike, are tagged with it (``tag_signatures``) exactly as the engine tags them."""
     lengths = [int(n) for n in lengths]
     prompts = [list(p) for p in prompts]
     sigs = prompts if sigs is None else [list(s) for s in sigs]
+    adapters = [None] * len(prompts) if adapters is None else list(adapters)
+    assert len(adapters) == len(prompts)
+    sigs = [tag_signatures(s, a) for s, a in zip(sigs, adapters)]
     assert len(prompts) == len(lengths) == len(sigs) and all(n >= 1 for n in lengths)
     sch = SlotScheduler(n_slots, len(lengths), max_admit)
     index = PrefixIndex(n_slots) if index is None else index
@@ -244,7 +258,7 @@ def simulate_prefix(prompts, lengths, n_slots, max_admit=None, min_tokens=16, si
         r = sch.finish(g)
         stats["finish_order"].append(r)
         fed = list(generated[r])[:-1] if generated is not None else []
-        index.record(g, prompts[r] + fed, sigs[r] + fed, 0)
+        index.record(g, prompts[r] + fed, sigs[r] + tag_signatures(fed, adapters[r]), 0)
 
     while not sch.done:
         sch.new_pass()

@@ -62,6 +62,7 @@ import os
 import torch
 
 from . import ops
+from .lora import split_peft_state_dict
 from .parallel import Comm, llama_tp_shard
 
 
@@ -78,25 +79,7 @@ def merge_peft_lora(sd, lora_alpha=32, adapter="default"):
     norms): W' = W + (lora_B · lora_A) · lora_alpha / r, exactly peft's Linear.merge() / get_delta_weight()
     (proj/peft/src/peft/tuners/lora.py:779-806); `modules_to_save` copies replace the wrapped module's weight. The product is formed
     in fp32 and cast back to W's dtype. Keys without the `base_model.model.` prefix pass through unchanged."""
-    out, lora = {}, {}
-    pre = "base_model.model."
-    for k, v in sd.items():
-        k = k[len(pre):] if k.startswith(pre) else k
-        if ".lora_A." in k or ".lora_B." in k:
-            mod, rest = k.split(".lora_", 1)
-            which, ad = rest.split(".")[0], rest.split(".")[1]
-            if ad == adapter or rest.split(".")[1] == "weight":       # `X.lora_A.<adapter>.weight` (or, older peft, `X.lora_A.weight`)
-                lora.setdefault(mod, {})[which] = v
-            continue
-        if ".lora_dropout." in k or ".lora_embedding_" in k:
-            continue
-        if ".modules_to_save." in k:
-            mod, rest = k.split(".modules_to_save.", 1)
-            if rest.split(".")[0] == adapter:
-                out[mod + "." + rest.split(".", 1)[1]] = v
-            continue
-        k = k.replace(".original_module.", ".").replace(".base_layer.", ".")
-        out.setdefault(k, v)
+    out, lora, _, _ = split_peft_state_dict(sd, adapter)      # the parser shared with the unmerged serving path (lora.AdapterTables)
     for mod, ab in lora.items():
         if "A" not in ab or "B" not in ab:
             raise KeyError(f"merge_peft_lora: {mod} has only one of lora_A / lora_B")
@@ -165,6 +148,9 @@ class SlotState:
         self.force_id, self.eos_id = int(force_id), int(eos_id)
         self.logits = None
         self.sampling = SampleState(G, device) if sampling else None     # None: the greedy step (sx_greedy_next_slots)
+        # int32 [G] adapter table slot per slot, beside pos / ctx / step (the module's P["lora"]["sel"], which the adapter step reads):
+        # written at admission (LlamaForCausalLM.set_adapters), -1 for parked slots and slots without an adapter; None: max_adapters = 0
+        self.adapter = None
 
     def key(self):
         return tuple(t.data_ptr() for t in (self.live, self.n_new, self.max_new, self.force_at, self.status)) \
@@ -222,7 +208,7 @@ class LlamaForCausalLM:
     WEIGHT_RESIDENCIES = (None, "tiles")
 
     def __init__(self, config, max_cache_len=None, max_batch=1, comm=None, precise=None, kv_v16=None, weight_format=None, kv_format=None,
-                 weight_residency=None):
+                 weight_residency=None, max_adapters=0, lora_rank=32):
         self.config = config if not isinstance(config, dict) else LlamaConfigLite(**config)
         c = self.config
         self.H, self.nh, self.L = c.hidden_size, c.num_attention_heads, c.num_hidden_layers
@@ -320,6 +306,27 @@ class LlamaForCausalLM:
         # workgroups of 94 dependent iterations at 1.5k keys (BASELINE config 5: 4 of the token step's 11 ms). Below 512 workgroups the keys
         # of a head are spread over enough splits for ~1024 (+ a combine launch); from the GLOBAL head count, like decode_nsplit.
         self.decode_nsplit_f32 = 1 if self.G * self.nh >= 512 else min(16, max(1, -(-1024 // (self.G * self.nh))))
+        # unmerged per-request LoRA adapters (lora.py; opt-in: ``max_adapters`` > 0 preallocates that many table slots of rank
+        # ``lora_rank``): the base weights stay as they are — any weight_format / weight_residency / kv_format — and every row of a prefill
+        # pass or of the token step may use one of the resident adapters or none. 0: nothing is allocated, the feature is off. Never a
+        # fall-back: a configuration the adapter kernels do not cover is refused here
+        self.max_adapters, self.lora_rank = int(max_adapters), int(lora_rank)
+        if self.max_adapters < 0:
+            raise ValueError(f"LlamaForCausalLM: max_adapters={max_adapters} must be >= 0")
+        if self.max_adapters:
+            if tp > 1:
+                raise ValueError("LlamaForCausalLM: max_adapters needs a single rank (the o / down adapters of tensor-parallel ranks are not built)")
+            if not self.precise:
+                raise ValueError("LlamaForCausalLM: max_adapters needs the precise mode (the adapter kernels read the two-plane operands; the plain "
+                                 "16-bit flow has no adapter step)")
+            if not self._skinny_shapes_ok():
+                raise ValueError(f"LlamaForCausalLM: max_adapters needs the tiled precise decode path: hidden / head / FFN widths that are multiples "
+                                 f"of 64 and >= 256, output widths that are multiples of 32 (H {self.H}, FFN {self.I}): the pre-activation addend "
+                                 "exists on the MFMA skinny GEMM only")
+            if self.lora_rank < 8 or self.lora_rank % 8 or 3 * self.lora_rank > 512:
+                raise ValueError(f"LlamaForCausalLM: lora_rank={lora_rank} must be a multiple of 8 in 8 .. 168")
+        self._adapters = {}              # name -> table slot
+        self._sel_host = [-1] * self.G   # host mirror of P["lora"]["sel"]: the adapter slot of every sequence, -1 = none
         self.device, self.dtype = None, torch.float16
         self._sd, self._P = None, None
         self._drop_graphs()
@@ -363,6 +370,8 @@ class LlamaForCausalLM:
         """No captured token step: the lock-step one, the in-flight one (decode_step(..., slots=...): one per engine lifetime) and the
         sampled forms of the two (a greedy step and a sampled step never share a graph)."""
         self._graph = self._slot_graph = self._sample_graph = self._slot_sample_graph = None
+        # the adapter token step (_layers_single_precise(adapters=True)) has four graphs of its own: it never shares one with the steps above
+        self._graph_ad = self._slot_graph_ad = self._sample_graph_ad = self._slot_sample_graph_ad = None
 
     def memory_footprint(self):
         """Bytes this module will hold on its GPU once packed (per rank): 16-bit weights, their decode-tile copy (precise mode: always;
@@ -381,12 +390,20 @@ class LlamaForCausalLM:
         kv = self.L * self.G * self.nh_l * self.Tmax * self.hd * ((4 + (2 if self.kv_v16 else 4)) if self.precise else 4)
         if self.kv_format == "fp8_e4m3":        # one byte per k and per v value + the two fp32 row scales (the emulated twin: all fp32, above)
             kv = self.L * self.G * self.nh_l * self.Tmax * (2 * self.hd + 8)
+        # adapter tables (max_adapters slots): A and B of the seven projections in 16 bits, the three norms' gammas and the scale in fp32
+        ad = {"adapters": self.max_adapters * self._adapter_slot_bytes()} if self.max_adapters else {}
         if self.weight_residency == "tiles":
             # no row-major projection is held: embedding + lm_head + the one prefill scratch buffer (the largest per-rank projection)
             scratch = self._scratch_elems() * 2
             w = (self.V + self.V_l) * self.H * 2 + scratch
-            return {"weights": w, "prefill_scratch": scratch, "decode_tiles": tiles, "kv_cache": kv, "total": w + tiles + kv}
-        return {"weights": w, "decode_tiles": tiles, "kv_cache": kv, "total": w + tiles + kv}
+            return {"weights": w, "prefill_scratch": scratch, "decode_tiles": tiles, "kv_cache": kv, **ad,
+                    "total": w + tiles + kv + sum(ad.values())}
+        return {"weights": w, "decode_tiles": tiles, "kv_cache": kv, **ad, "total": w + tiles + kv + sum(ad.values())}
+
+    def _adapter_slot_bytes(self):
+        """Bytes of one adapter slot: R (K + N) 16-bit elements per projection (q, k, v, o: H x H; gate, up: I x H; down: H x I), the
+        2 L + 1 fp32 gammas and the fp32 scale. 0.25 GB at 13B dims with R = 32."""
+        return self.L * 2 * self.lora_rank * (8 * self.H + 3 * (self.H + self.I)) + (2 * self.L + 1) * self.H * 4 + 4
 
     def _scratch_elems(self):
         """Elements of the tiles residency's prefill scratch buffer: max over the four per-rank projections of N * K (gate|up at 13B)."""
@@ -659,10 +676,119 @@ class LlamaForCausalLM:
         P["attn_cnt"] = torch.zeros(G * self.nh_l, dtype=torch.int32, device=dev)   # arrival counters of the fused decode attention
         P["attn_f32_part"] = torch.empty((G, self.nh_l, self.decode_nsplit_f32, self.hd + 2), dtype=torch.float32, device=dev) \
             if (self.precise and self.decode_nsplit_f32 > 1) else None
+        if self.max_adapters:
+            from . import lora
+            nA, R, L, H, I = self.max_adapters, self.lora_rank, self.L, self.H, self.I
+            z16 = lambda *shape: torch.zeros(shape, dtype=dt, device=dev)
+            # [layer][adapter slot] tables; a free slot is all zero with the base gammas: it computes the base model
+            T = {"A": {"qkv": z16(L, nA, 3 * R, H), "o": z16(L, nA, R, H), "gu": z16(L, nA, 2 * R, H), "d": z16(L, nA, R, I)},
+                 "B": {"qkv": z16(L, nA, 3 * H, R), "o": z16(L, nA, H, R), "gu": z16(L, nA, 2 * I, R), "d": z16(L, nA, H, R)},
+                 "ln1": torch.stack([lw["ln1"] for lw in P["layers"]])[:, None].repeat(1, nA, 1).contiguous(),
+                 "ln2": torch.stack([lw["ln2"] for lw in P["layers"]])[:, None].repeat(1, nA, 1).contiguous(),
+                 "norm": P["norm"][None].repeat(nA, 1).contiguous(),
+                 "scale": torch.zeros(nA, dtype=torch.float32, device=dev),
+                 "seg": {k: v.to(dev) for k, v in lora.seg_tables(H, I).items()},
+                 "sel": torch.full((G,), -1, dtype=torch.int32, device=dev)}      # per-sequence adapter slot, beside pos / ctx / step
+            held = sum(t.numel() * t.element_size() for d in (T["A"], T["B"]) for t in d.values()) \
+                + sum(T[k].numel() * 4 for k in ("ln1", "ln2", "norm", "scale"))
+            assert held == fp["adapters"], (held, fp["adapters"])                 # memory_footprint() prices what is held
+            P["lora"] = T
+            self._sel_host = [-1] * G
         self._P = P
         self._sd = None
         self._drop_graphs()
         return P
+
+    # ---- unmerged LoRA adapters (lora.py) ---------------------------------------------------------------------------------
+    @property
+    def adapters(self):
+        """Names of the resident adapters."""
+        return sorted(self._adapters)
+
+    def _adapter_index(self, name):
+        """Table slot of a request's adapter: None → -1 (the base model); an unknown name is an error, never the base model."""
+        if name is None:
+            return -1
+        if not self.max_adapters:
+            raise ValueError(f"LlamaForCausalLM: adapter {name!r} requested but the model was built with max_adapters=0")
+        if name not in self._adapters:
+            raise ValueError(f"LlamaForCausalLM: unknown adapter {name!r} (resident: {self.adapters})")
+        return self._adapters[name]
+
+    def load_adapter(self, name, source, lora_alpha=None):
+        """Make a LoRA adapter resident under ``name``. ``source``: a PEFT directory (adapter_config.json + adapter_model.safetensors |
+        .bin) or a state dict with lora_A / lora_B / modules_to_save keys (the key forms merge_peft_lora parses). The tables were
+        allocated at pack time and are written IN PLACE: captured token steps stay valid and no other adapter is touched. Loading a
+        resident name again replaces it. ValueError (never a partial load or a fall-back) for what lora.AdapterTables refuses, a full
+        table, or a model built without ``max_adapters``."""
+        from . import lora
+        if not self.max_adapters:
+            raise ValueError("LlamaForCausalLM.load_adapter: the model was built with max_adapters=0")
+        if isinstance(source, (str, os.PathLike)):
+            import json
+            acfg = json.load(open(os.path.join(source, "adapter_config.json")))
+            if lora_alpha is None:
+                lora_alpha = acfg.get("lora_alpha", 32)
+            fs = os.path.join(source, "adapter_model.safetensors")
+            if os.path.exists(fs):
+                from safetensors.torch import load_file
+                source = load_file(fs)
+            else:
+                source = torch.load(os.path.join(source, "adapter_model.bin"), map_location="cpu")
+        tab = lora.AdapterTables(source, self.L, self.H, self.I, R=self.lora_rank, lora_alpha=32 if lora_alpha is None else lora_alpha,
+                                 dtype=self.dtype)
+        if name in self._adapters and self._adapters[name] in self._sel_host:
+            raise ValueError(f"LlamaForCausalLM.load_adapter: adapter {name!r} is in use by sequence(s) "
+                             f"{[g for g, v in enumerate(self._sel_host) if v == self._adapters[name]]}: its tables cannot be replaced under them")
+        if name not in self._adapters and len(self._adapters) >= self.max_adapters:
+            raise ValueError(f"LlamaForCausalLM.load_adapter: all {self.max_adapters} adapter slots are in use ({self.adapters})")
+        P = self._pack()
+        T = P["lora"]
+        a = self._adapters.get(name)
+        if a is None:
+            a = min(set(range(self.max_adapters)) - set(self._adapters.values()))
+        for li in range(self.L):
+            for k in ("qkv", "o", "gu", "d"):
+                T["A"][k][li, a].copy_(tab.A[k][li])
+                T["B"][k][li, a].copy_(tab.B[k][li])
+            T["ln1"][li, a].copy_(tab.ln1[li] if tab.ln1[li] is not None else P["layers"][li]["ln1"])
+            T["ln2"][li, a].copy_(tab.ln2[li] if tab.ln2[li] is not None else P["layers"][li]["ln2"])
+        T["norm"][a].copy_(tab.norm if tab.norm is not None else P["norm"])
+        T["scale"][a] = tab.scale
+        self._adapters[name] = a
+        return a
+
+    def unload_adapter(self, name):
+        """Free ``name``'s table slot: its tables go back to zero and its gammas to the base model's (a free slot computes the base
+        model), in place. No sequence may be using it."""
+        a = self._adapter_index(name)
+        if a < 0:
+            raise ValueError("LlamaForCausalLM.unload_adapter: no adapter named")
+        users = [g for g, v in enumerate(self._sel_host) if v == a]
+        if users:
+            raise ValueError(f"LlamaForCausalLM.unload_adapter: adapter {name!r} is in use by sequence(s) {users}")
+        P, T = self._pack(), self._P["lora"]
+        for k in ("qkv", "o", "gu", "d"):
+            T["A"][k][:, a].zero_()
+            T["B"][k][:, a].zero_()
+        for li in range(self.L):
+            T["ln1"][li, a].copy_(P["layers"][li]["ln1"])
+            T["ln2"][li, a].copy_(P["layers"][li]["ln2"])
+        T["norm"][a].copy_(P["norm"])
+        T["scale"][a] = 0.0
+        del self._adapters[name]
+
+    def set_adapters(self, seqs, names):
+        """Sequence seqs[i] decodes under adapter names[i] (None = the base model) from now on: one small host → device copy into the
+        per-sequence adapter index the token step reads (written at admission; a parked slot holds -1)."""
+        idx = [self._adapter_index(n) for n in names]
+        seqs = list(seqs)
+        if not self.max_adapters:
+            return
+        P = self._pack()
+        self._slot_write(P["lora"]["sel"], seqs, idx)
+        for g, a in zip(seqs, idx):
+            self._sel_host[g] = a
 
     # ---- core passes ---------------------------------------------------------------------------------------------------
     def reset(self, seq=None):
@@ -673,12 +799,17 @@ class LlamaForCausalLM:
         P["step"][s] = 0
         P["ctx"][s] = 1                 # invariant: ctx == pos + 1 (keys visible to the token at `pos`)
 
-    def _layers_multi(self, x, Ts, seqs):
+    def _layers_multi(self, x, Ts, seqs, adapters=None):
         """Ts[i] tokens appended to sequence seqs[i] at its cache position (prefill of several prompts, or the forced
         image-token chunk of several sequences, as ONE pass): every GEMM runs on all sum(Ts) rows at once — the weights
         stream once per pass instead of once per sequence — while RoPE / KV append / causal flash attention stay per
         sequence (batched into single launches when all sequences share T and position). x: fp32 [sum(Ts), H] residual
-        stream, rows ordered like seqs. Returns the final residual stream."""
+        stream, rows ordered like seqs. Returns the final residual stream.
+        ``adapters`` (table slots, one per sequence, -1 = none; None or all -1: the pass below is untouched): the rows of sequence i
+        run under adapter adapters[i] — its gammas in the norms (sx_rmsnorm_planes_sel) and, per projection, the fp32 delta of
+        sx_lora_shrink / sx_lora_expand on the row-major planes handed to the unchanged GEMM as ``bias2d`` (one row of it per output
+        row), which its epilogue adds before activation / GLU / residual. Rows without an adapter carry a zero delta; each projection
+        is one GEMM over all rows, so under weight_residency="tiles" it is dequantised once."""
         P, dt, H, nh, hd = self._P, self.dtype, self.H_l, self.nh_l, self.hd     # local heads under tensor parallelism
         comm, lead = self.comm, self.comm.rank == 0
         pr = self.precise
@@ -703,12 +834,32 @@ class LlamaForCausalLM:
         eps = self.config.rms_norm_eps
         scale = 1.0 / math.sqrt(hd)
         g0 = seqs[0]
+        lo = None
+        if adapters is not None and any(a >= 0 for a in adapters):
+            assert pr and self.max_adapters and len(adapters) == n
+            lo = P["lora"]
+            sel = torch.repeat_interleave(torch.tensor(list(adapters), dtype=torch.int32), torch.tensor(Ts)).to(x.device)   # [M] rows → slot
+            zbuf = {}
+
+            def norm(xx, li, k):
+                return ops.rmsnorm_planes_sel(xx, lw[k], lo[k][li], sel, eps, dt)[0]
+
+            def delta(hp, li, k):
+                """bias2d of projection k for the planes hp: zero for base rows (sx_lora_expand leaves them unwritten)."""
+                t = ops.lora_shrink(hp, lo["A"][k][li], sel)
+                N_ = lo["B"][k].shape[2]
+                if N_ not in zbuf:          # zeroed ONCE per pass and width: the base rows are never written, the adapter rows always
+                    zbuf[N_] = torch.zeros((M, N_), dtype=torch.float32, device=x.device)
+                return dict(bias2d=ops.lora_expand(t, lo["B"][k][li], lo["seg"][k], lo["scale"], sel, out=zbuf[N_]), bias2d_rows=1)
+        else:
+            norm = lambda xx, li, k: ops.rmsnorm_planes(xx, lw[k], eps, dt)[0]
+            delta = lambda hp, li, k: {}
         for li, lw in enumerate(P["layers"]):
             kc_l, vc_l = P["kc"][li], P["vc"][li]
             if pr:
                 # fp32-grade activations: operand planes into a_planes = 2 GEMMs with fp32 outputs, fp32 RoPE / cache / attention
-                h, _ = ops.rmsnorm_planes(x, lw["ln1"], eps, dt)
-                qkv = ops.gemm(h, wmat(lw, "wqkv"), a_planes=2, out_dtype=torch.float32)    # [M, 3H] fp32
+                h = norm(x, li, "ln1")
+                qkv = ops.gemm(h, wmat(lw, "wqkv"), a_planes=2, out_dtype=torch.float32, **delta(h, li, "qkv"))    # [M, 3H] fp32
                 # (kv_format: the append quantises; the emulated twin's attention is the plain fp32 call on its rounded rows)
                 if uniform:
                     kw = self._kv_kw(li, slice(g0, g0 + n))
@@ -725,10 +876,13 @@ class LlamaForCausalLM:
                                                hd, dt, **kw)
                         att[offs[i]:offs[i + 1]] = ops.attention_f32(rows, kc_l[g:g + 1], vc_l[g:g + 1], P["pos"][g:g + 1], 1, Ts[i],
                                                                      nh, hd, scale, dt, kv_scales=kw.get("kv_scales"))
-                x = comm.all_reduce(ops.gemm(att, wmat(lw, "wo"), a_planes=2, residual=x if lead else None, out_dtype=torch.float32))
-                h, _ = ops.rmsnorm_planes(x, lw["ln2"], eps, dt)
-                g_ = ops.split16(ops.gemm(h, wmat(lw, "wgu"), a_planes=2, act="silu", glu=True, out_dtype=torch.float32), dt)
-                x = comm.all_reduce(ops.gemm(g_, wmat(lw, "wd"), a_planes=2, residual=x if lead else None, out_dtype=torch.float32))
+                x = comm.all_reduce(ops.gemm(att, wmat(lw, "wo"), a_planes=2, residual=x if lead else None, out_dtype=torch.float32,
+                                             **delta(att, li, "o")))
+                h = norm(x, li, "ln2")
+                g_ = ops.split16(ops.gemm(h, wmat(lw, "wgu"), a_planes=2, act="silu", glu=True, out_dtype=torch.float32,
+                                          **delta(h, li, "gu")), dt)
+                x = comm.all_reduce(ops.gemm(g_, wmat(lw, "wd"), a_planes=2, residual=x if lead else None, out_dtype=torch.float32,
+                                             **delta(g_, li, "d")))
                 continue
             h = ops.rmsnorm(x, lw["ln1"], eps, dt)
             qkv = ops.gemm(h, lw["wqkv"])                                             # [M, 3H]
@@ -818,23 +972,41 @@ class LlamaForCausalLM:
             ops.add_i32(P["ctx"], 1)
         return x
 
-    def _layers_single_precise(self, x, slots=None):
+    def _layers_single_precise(self, x, slots=None, adapters=False):
         """_layers_single with fp32-grade activations: the x operand of every skinny GEMM is a two-block Tiled16 (hi plane, lo plane;
         sx_gemv x_planes = 2 — each weight fragment feeds two MFMAs, the weights stream once), its outputs are fp32; RoPE, the KV
         cache and attention are fp32 (sx_rope_kv_append_f32, sx_attention_f32 at T = 1). Shapes outside the skinny GEMM's MFMA path
-        (miniature test dims) take the a_planes = 2 GEMM instead. No host reads → graph-capturable."""
+        (miniature test dims) take the a_planes = 2 GEMM instead. No host reads → graph-capturable.
+        ``adapters``: the adapter token step — this body on its UNFOLDED arrangement (the branch SX_RMS_FOLD=0 selects) with the per-row
+        gammas (sx_rmsnorm_planes_sel) and, in front of each of the four skinny GEMMs, shrink + expand on the x operand it already
+        reads; the fp32 delta enters that GEMM's epilogue before activation / GLU / residual (sx_gemv_args.addend). The adapter slot of
+        every sequence is read from device memory (P["lora"]["sel"]); a row without an adapter has the bits of the unfolded base step."""
         P, dt, nh, hd, G = self._P, self.dtype, self.nh_l, self.hd, self.G
+        lo = P["lora"] if adapters else None
+        assert lo is None or (P["precise_tiled"] and P["decode_tiled"])
         comm, lead = self.comm, self.comm.rank == 0
         eps, scale = self.config.rms_norm_eps, 1.0 / math.sqrt(hd)
         tl, ws, f32 = P["precise_tiled"], P["gemv_ws"], torch.float32
         dtl = tl and P["decode_tiled"]                       # decode-tile weight copies (built for every G in precise mode)
+
+        def delta(xp, li, kk):
+            """the adapter step's addend of projection kk for the operand xp (nothing without adapters)"""
+            if lo is None:
+                return {}
+            t = ops.lora_shrink(xp, lo["A"][kk][li], lo["sel"])
+            return dict(addend=(ops.lora_expand(t, lo["B"][kk][li], lo["seg"][kk], lo["scale"], lo["sel"]), lo["sel"], self.max_adapters))
+
+        def norm(xx, li, k):
+            if lo is None:
+                return ops.rmsnorm_planes(xx, lw[k], eps, dt, tiled=tl)[0]
+            return ops.rmsnorm_planes_sel(xx, lw[k], lo[k][li], lo["sel"], eps, dt, tiled=tl)[0]
 
         def lin(xp, lw, k, **kw):
             if tl:
                 return ops.gemv(xp, lw[k], w_tiles=lw[k + "_t"] if dtl else None, workspace=ws if dtl else None,
                                 w_tiles20=lw.get(k + "_t20") if dtl else None, w_fp8=lw.get(k + "_f8"), w_fp4=lw.get(k + "_f4"), out_dtype=f32, **kw)
             return ops.gemm(xp, lw[k], a_planes=2, out_dtype=f32, **kw)
-        fold = P["rms_fold_precise"]
+        fold = P["rms_fold_precise"] and lo is None
         fuse_rope = hd == 128 and os.environ.get("SX_LLM_FUSE_ROPE", "1") != "0"
         x16 = ssq = None
         nl = len(P["layers"])
@@ -842,8 +1014,8 @@ class LlamaForCausalLM:
             if fold and li > 0:
                 qkv = lin(x16, lw, "wqkv", ssq_in=(ssq, self.H, eps))                 # x16 = planes of x * ln1 (written by the down GEMV)
             else:
-                h, _ = ops.rmsnorm_planes(x, lw["ln1"], eps, dt, tiled=tl)
-                qkv = lin(h, lw, "wqkv")                                              # [G, 3H] fp32
+                h = norm(x, li, "ln1")
+                qkv = lin(h, lw, "wqkv", **delta(h, li, "qkv"))                       # [G, 3H] fp32
             kw = self._kv_kw(li)    # kv_format: the row scales of the FP8 cache, or the emulate flag of its fp32 twin
             if fuse_rope:           # RoPE + KV append inside the attention launch (one graph node per layer instead of two)
                 att = ops.attention_f32(qkv, P["kc"][li], P["vc"][li], P["pos"], G, 1, nh, hd, scale, dt, tiled=tl,
@@ -862,21 +1034,25 @@ class LlamaForCausalLM:
                 else:                        # the final norm wants fp32 states: its own launch (rmsnorm_planes in _decode_step_body)
                     x = lin(g, lw, "wd", residual=x)
                 continue
-            x = comm.all_reduce(lin(att, lw, "wo", residual=x if lead else None))
-            h, _ = ops.rmsnorm_planes(x, lw["ln2"], eps, dt, tiled=tl)
+            x = comm.all_reduce(lin(att, lw, "wo", residual=x if lead else None, **delta(att, li, "o")))
+            h = norm(x, li, "ln2")
             if tl:                           # SiLU-GLU epilogue writes the two planes of its result itself (no sx_split16 launch)
                 g = ops.gemv(h, lw["wgu"], act="silu", glu=True, w_tiles=lw["wgu_t"] if dtl else None, w_fp8=lw.get("wgu_f8"), w_fp4=lw.get("wgu_f4"), y_tiled=True,
-                             planes_out=True)
+                             planes_out=True, **delta(h, li, "gu"))
             else:
                 g = ops.split16(lin(h, lw, "wgu", act="silu", glu=True), dt)
-            x = comm.all_reduce(lin(g, lw, "wd", residual=x if lead else None))
+            x = comm.all_reduce(lin(g, lw, "wd", residual=x if lead else None, **delta(g, li, "d")))
         if slots is None:
             ops.add_i32(P["pos"], 1)
             ops.add_i32(P["ctx"], 1)
         return x
 
-    def _final_norm(self, x):
-        """model.norm (modeling_llama_xformer.py:595) → fp32 hidden states."""
+    def _final_norm(self, x, sel=None):
+        """model.norm (modeling_llama_xformer.py:595) → fp32 hidden states. ``sel`` (int32 per row, device): the rows' adapter slots —
+        an adapter's modules_to_save copy of model.norm replaces gamma for its rows."""
+        if sel is not None:
+            return ops.rmsnorm_planes_sel(x.contiguous(), self._P["norm"], self._P["lora"]["norm"], sel, self.config.rms_norm_eps, self.dtype,
+                                          want_f32=True, want_planes=False)[1]
         if self.precise:
             return ops.rmsnorm_planes(x.contiguous(), self._P["norm"], self.config.rms_norm_eps, self.dtype, want_f32=True,
                                       want_planes=False)[1]
@@ -889,9 +1065,14 @@ class LlamaForCausalLM:
             return ops.linear_planes(hn_rows.contiguous(), P["lm_head"], w_tiles=P["lm_head_t"], out_dtype=torch.float32)
         return ops.linear(ops.cast(hn_rows.contiguous(), self.dtype), P["lm_head"], out_dtype=torch.float32)
 
-    def forward_embeds(self, inputs_embeds, need_logits=True, seq=0):
+    def forward_embeds(self, inputs_embeds, need_logits=True, seq=0, adapter=None):
         """inputs_embeds: fp32 [T, H] on the GPU, appended to sequence `seq` at its current cache position.
-        Returns (logits fp32 [Vpad] of the LAST position or None, final-norm hidden states fp32 [T, H])."""
+        Returns (logits fp32 [Vpad] of the LAST position or None, final-norm hidden states fp32 [T, H]).
+        ``adapter``: name of a resident LoRA adapter the rows run under (forward_embeds_batch)."""
+        if adapter is not None:
+            self.kv_epoch += 1          # a write outside generate_batch, as below
+            logits, hs = self.forward_embeds_batch([inputs_embeds], [seq], need_logits, adapters=[adapter])
+            return (None if logits is None else logits[0]), hs[0]
         P = self._pack()
         self.kv_epoch += 1              # a write outside generate_batch: cached-prefix records no longer describe the cache
         x = inputs_embeds.to(device=self.device, dtype=torch.float32).contiguous()
@@ -908,14 +1089,23 @@ class LlamaForCausalLM:
                 logits = self.comm.all_gather(logits).reshape(-1)                     # [tp, V/tp] → [Vpad], vocab order
         return logits, hn
 
-    def forward_embeds_batch(self, xs, seqs, need_logits=True):
+    def forward_embeds_batch(self, xs, seqs, need_logits=True, adapters=None):
         """xs[i]: fp32 [T_i, H] appended to sequence seqs[i]; all sequences in one pass (see _layers_multi).
-        Returns (logits fp32 [n, Vpad] of each sequence's LAST position or None, list of final-norm states [T_i, H])."""
+        Returns (logits fp32 [n, Vpad] of each sequence's LAST position or None, list of final-norm states [T_i, H]).
+        ``adapters``: per sequence the name of a resident LoRA adapter or None; the KV rows written depend on it. None, or no name at
+        all: exactly the pass without the argument."""
         P = self._pack()
         Ts = [int(x.shape[0]) for x in xs]
         x = torch.cat([x.to(device=self.device, dtype=torch.float32) for x in xs], dim=0).contiguous()   # plumbing
-        x = self._layers_multi(x, Ts, list(seqs))
-        hn = self._final_norm(x)
+        idx = [self._adapter_index(a) for a in adapters] if adapters is not None else None
+        if idx is not None and any(a >= 0 for a in idx):
+            assert len(idx) == len(Ts)
+            x = self._layers_multi(x, Ts, list(seqs), adapters=idx)
+            sel = torch.repeat_interleave(torch.tensor(idx, dtype=torch.int32), torch.tensor(Ts)).to(self.device)
+            hn = self._final_norm(x, sel)
+        else:
+            x = self._layers_multi(x, Ts, list(seqs))
+            hn = self._final_norm(x)
         ends = torch.tensor([sum(Ts[:i + 1]) - 1 for i in range(len(Ts))], device=self.device)
         logits = None
         if need_logits:
@@ -1005,6 +1195,8 @@ class LlamaForCausalLM:
             raise NotImplementedError("in-flight batching (slot states) is single-rank: tensor-parallel ranks are not supported")
         self._pack()
         st = SlotState(self.G, self.device, force_id, eos_id, sampling)
+        if self.max_adapters:
+            st.adapter = self._P["lora"]["sel"]
         self.park_slots(range(self.G), st)
         return st
 
@@ -1025,6 +1217,8 @@ class LlamaForCausalLM:
         self._slot_write(state.live, slots, 0)
         for k, v in SlotState.IDLE.items():
             self._slot_write(P[k], slots, v)
+        if self.max_adapters:
+            self.set_adapters(slots, [None] * len(slots))
 
     # ---- device-resident greedy decode step (all sequences in lock step) -----------------------------------------------
     def sample_state(self):
@@ -1035,7 +1229,7 @@ class LlamaForCausalLM:
             self._sample_state = SampleState(self.G, self.device)
         return self._sample_state
 
-    def _decode_step_body(self, img_ids_dev, out_ids, hid_buf, slots=None, sampling=None):
+    def _decode_step_body(self, img_ids_dev, out_ids, hid_buf, slots=None, sampling=None, adapters=False):
         """cur[G] → embedding → 40 layers → final norm → lm_head → logits rule + argmax → cur[G]. Records the post-norm
         hidden state of each INPUT token at hid_buf[g, step[g]] (what seed_x.py:196 collects) and the new id at
         out_ids[g, step[g]]; then step += 1. Everything stays on the device. ``slots`` (a SlotState): the tail is ONE
@@ -1043,8 +1237,13 @@ class LlamaForCausalLM:
         slots ride along through the GEMVs and write nothing."""
         P = self._P
         x = ops.embedding(P["cur"], P["embed"])                                        # [G, H] fp32
-        x = self._layers_single(x, slots)
-        if self.precise:
+        x = self._layers_single_precise(x, slots, adapters=True) if adapters else self._layers_single(x, slots)
+        if adapters:      # the adapter step: the final norm picks every row's gamma like the layers' norms; lm_head has no adapter
+            hp, hn = ops.rmsnorm_planes_sel(x, P["norm"], P["lora"]["norm"], P["lora"]["sel"], self.config.rms_norm_eps, self.dtype,
+                                            tiled=True, want_f32=True)
+            ops.scatter_rows_step(hn, P["step"], hid_buf)
+            logits = ops.gemv(hp, P["lm_head"], out_dtype=torch.float32, w_tiles=P["lm_head_t"])
+        elif self.precise:
             hp, hn = ops.rmsnorm_planes(x, P["norm"], self.config.rms_norm_eps, self.dtype, tiled=P["precise_tiled"], want_f32=True)
             ops.scatter_rows_step(hn, P["step"], hid_buf)
             if P["precise_tiled"]:
@@ -1072,13 +1271,20 @@ class LlamaForCausalLM:
         tail(logits, self.V, img_ids_dev, P["cur"], out_ids, P["step"], **sample)
         ops.add_i32(P["step"], 1)
 
-    def decode_step(self, img_ids_dev, out_ids, hid_buf, use_graph=True, slots=None, sampling=None):
+    def decode_step(self, img_ids_dev, out_ids, hid_buf, use_graph=True, slots=None, sampling=None, adapters=None):
         """out_ids: int32 [G, rows]; hid_buf: fp32 [G, rows, H]. ``slots``: a SlotState → the in-flight step (its captured graph is
         kept apart from the lock-step one, so one graph serves an engine's lifetime whatever else runs in between). ``sampling``: a
         SampleState → the lock-step step ends in sx_sample_next_b (token index = step[g]); a slot state brings its own
         (``slots.sampling``). The state's pointers are part of the graph key: a sampled step and a greedy step never share a graph,
-        and the parameters are read from device memory at replay."""
+        and the parameters are read from device memory at replay.
+        ``adapters``: None (default) → the adapter token step runs iff some sequence has an adapter (set_adapters); True / False force
+        it. The adapter step has captured graphs of its own; a step in which no sequence has an adapter runs the calls and graphs it
+        ran before adapters existed."""
         self._pack()
+        if adapters is None:
+            adapters = any(a >= 0 for a in self._sel_host)
+        if adapters and not self.max_adapters:
+            raise ValueError("LlamaForCausalLM.decode_step: the adapter step needs max_adapters > 0")
         assert out_ids.shape[0] == self.G and hid_buf.shape[0] == self.G and hid_buf.shape[1] == out_ids.shape[1]
         if slots is not None:
             if self.tp > 1:
@@ -1087,12 +1293,14 @@ class LlamaForCausalLM:
             assert sampling is None, "a slot state carries its own sampling state (slot_state(sampling=True))"
         assert sampling is None or sampling.G == self.G
         if not use_graph or not self.comm.graph_safe:
-            self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling)
+            self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling, adapters)
             return
         if slots is None:
             attr = "_graph" if sampling is None else "_sample_graph"
         else:
             attr = "_slot_graph" if slots.sampling is None else "_slot_sample_graph"
+        if adapters:
+            attr += "_ad"
         key = (img_ids_dev.data_ptr(), out_ids.data_ptr(), hid_buf.data_ptr(), tuple(out_ids.shape)) \
             + (slots.key() if slots is not None else ()) + (("sample",) + sampling.key() if sampling is not None else ())
         held = getattr(self, attr)
@@ -1106,14 +1314,14 @@ class LlamaForCausalLM:
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
-                self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling)
+                self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling, adapters)
             torch.cuda.current_stream().wait_stream(s)
             torch.cuda.synchronize()
             for t, v in snap.values():
                 t.copy_(v)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling)
+                self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling, adapters)
             for t, v in snap.values():
                 t.copy_(v)
             held = (key, g) + ((slots.logits,) if slots is not None else ())

@@ -392,7 +392,7 @@ def _mfma_shape(N, K):
 
 
 def gemv(x, w, residual=None, act=None, glu=False, out_dtype=None, w_tiles=None, y_tiled=False, workspace=None,
-         emit_norm=False, ssq_in=None, w_tiles20=None, planes_out=False, norm_gamma=None, w_fp8=None, w_fp4=None):
+         emit_norm=False, ssq_in=None, w_tiles20=None, planes_out=False, norm_gamma=None, w_fp8=None, w_fp4=None, addend=None):
     """w_tiles: the same weight in the decode layout (pack_decode_tiles); used instead of w when the MFMA path runs.
     x may be a Tiled16 (then w_tiles is required); y_tiled returns the 16-bit result as a Tiled16 for the next gemv.
     workspace: zero-initialised uint8 scratch enabling split-K over workgroups for shapes that need it (sx_gemv_args.workspace).
@@ -408,7 +408,11 @@ def gemv(x, w, residual=None, act=None, glu=False, out_dtype=None, w_tiles=None,
     dequantised 16-bit matrix) only gives shape and dtype. MFMA path only: any other shape is an error, never a fall-back.
     w_fp4 = (code_tiles, scale_tiles): the weight as MXFP4 decode tiles (pack_decode_tiles_fp4 / pack_decode_tiles20_fp4; the shape says
     which) with its E8M0 block-scale tiles (pack_block_scales_fp4 with the same rows); replaces w_tiles / w_tiles20 in the same way.
-    With w_fp8 / w_fp4, ``w`` may be a WeightShape: shape and dtype without storage (the tiles are the weight's only copy)."""
+    With w_fp8 / w_fp4, ``w`` may be a WeightShape: shape and dtype without storage (the tiles are the weight's only copy).
+    addend = delta or (delta, sel, n_adapters): fp32 [M, N] (columns in the row order of the weight as passed) added to the summed
+    accumulators BEFORE activation / GLU / residual (sx_gemv_args.addend: the unmerged LoRA delta of lora_expand); with sel (int32 [M] on
+    the device) only the rows whose sel is in [0, n_adapters) take it, every other row keeps the bits of a launch without an addend. MFMA
+    path only: an error on the VALU path, never a fall-back."""
     lib = _lib.load()
     xt = isinstance(x, Tiled16)
     assert not isinstance(w, WeightShape) or w_fp8 is not None or w_fp4 is not None, "gemv: a weight without storage needs its FP8 / MXFP4 tiles"
@@ -477,6 +481,13 @@ def gemv(x, w, residual=None, act=None, glu=False, out_dtype=None, w_tiles=None,
         t, dim, eps = ssq_in
         assert args.w_layout == 1 and t.dtype == torch.float32 and t.is_contiguous() and t.shape[0] == 16 * ((M + 15) // 16)
         args.row_ssq_in, args.ssq_in_parts, args.ssq_dim, args.ssq_eps = t.data_ptr(), t.shape[1], int(dim), float(eps)
+    if addend is not None:
+        d, asel, n_ad = addend if isinstance(addend, tuple) else (addend, None, 0)
+        assert d.dtype == torch.float32 and d.is_contiguous() and d.shape == (M, N) and d.device == dev
+        args.addend = d.data_ptr()
+        if asel is not None:
+            assert asel.dtype == torch.int32 and asel.is_contiguous() and asel.numel() >= M and asel.device == dev and n_ad >= 1
+            args.addend_sel, args.addend_n = asel.data_ptr(), int(n_ad)
     check(lib.sx_gemv(C.byref(args), _stream()), "sx_gemv")
     out = yt if y_tiled else y
     return (out, x16, ssq) if emit_norm else out
@@ -668,6 +679,68 @@ def rmsnorm_planes(x, gamma, eps, dtype, tiled=False, want_f32=False, want_plane
     check(_lib.load().sx_rmsnorm_planes(_p(x), _p(_f32c(gamma)), _p(y32), _p(buf), rows, cols, float(eps), code, _stream()),
           "sx_rmsnorm_planes")
     return ret, y32
+
+
+def rmsnorm_planes_sel(x, gamma, gamma_table, sel, eps, dtype, tiled=False, want_f32=False, want_planes=True):
+    """rmsnorm_planes with one gamma per adapter: row m uses gamma_table[sel[m]] (fp32 [n_adapters, cols]) when sel[m] (int32, device) is
+    in [0, n_adapters), else ``gamma`` — every row bit-identical to rmsnorm_planes with the gamma it selected (sx_rmsnorm_planes_sel)."""
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous()
+    rows, cols = x.shape
+    assert sel.dtype == torch.int32 and sel.is_contiguous() and sel.numel() >= rows and sel.device == x.device
+    n_ad = 0
+    if gamma_table is not None:
+        assert gamma_table.dtype == torch.float32 and gamma_table.is_contiguous() and gamma_table.dim() == 2 and gamma_table.shape[1] == cols
+        n_ad = gamma_table.shape[0]
+    ret = buf = None
+    code = _DT[dtype]
+    if want_planes:
+        ret, buf, code = _planes_out(rows, cols, dtype, x.device, tiled)
+    y32 = torch.empty_like(x) if want_f32 else None
+    check(_lib.load().sx_rmsnorm_planes_sel(_p(x), _p(_f32c(gamma)), _p(gamma_table), _p(sel), n_ad, _p(y32), _p(buf), rows, cols,
+                                            float(eps), code, _stream()), "sx_rmsnorm_planes_sel")
+    return ret, y32
+
+
+def lora_shrink(x, A, sel, out=None):
+    """t[m, i] = sum_k A[sel[m], i, k] * (hi + lo)[m, k] in fp32 (sx_lora_shrink; the rule: lora.lora_delta_ref). x: the planes of an
+    fp32-grade activation — a two-plane Tiled16 (the decode step's x operand, <= 32 rows) or rows [M, 2K] = [hi | lo] (prefill). A: 16-bit
+    [n_adapters, S*R, K]; sel: int32 [M] on the device. Rows whose index is outside [0, n_adapters) are base rows: their t is not written."""
+    xt = isinstance(x, Tiled16)
+    if xt:
+        assert x.planes == 2
+        M, K, xb, code = x.rows, x.cols, x.t, _DT[x.dtype] | _lib.SX_TILED16
+    else:
+        assert x.dim() == 2 and x.is_contiguous() and x.shape[1] % 2 == 0
+        M, K, xb, code = x.shape[0], x.shape[1] // 2, x, _DT[x.dtype]
+    assert A.dim() == 3 and A.is_contiguous() and A.dtype == xb.dtype and A.shape[2] == K and A.device == xb.device
+    assert sel.dtype == torch.int32 and sel.is_contiguous() and sel.numel() >= M and sel.device == xb.device
+    n_ad, SR = A.shape[0], A.shape[1]
+    if out is None:
+        out = torch.empty((M, SR), dtype=torch.float32, device=xb.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (M, SR)
+    check(_lib.load().sx_lora_shrink(_p(xb), _p(A), _p(sel), _p(out), M, K, SR, n_ad, code, _stream()), "sx_lora_shrink")
+    return out
+
+
+def lora_expand(t, B, seg, scale, sel, out=None):
+    """delta[m, n] = scale[sel[m]] * sum_j B[sel[m], n, j] * t[m, seg[n // 16] * R + j] in fp32 (sx_lora_expand). B: 16-bit
+    [n_adapters, N, R], rows in the order of the projection's weight AS PACKED; seg: int32 [N / 16]; scale: fp32 [n_adapters]. Base rows of
+    ``out`` (fp32 [M, N]; a fresh buffer is uninitialised) are not written: hand the result to gemv(addend=(delta, sel, n_adapters))."""
+    assert t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()
+    assert B.dim() == 3 and B.is_contiguous() and B.dtype in (torch.float16, torch.bfloat16) and B.device == t.device
+    n_ad, N, R = B.shape
+    M = t.shape[0]
+    assert t.shape[1] % R == 0
+    S = t.shape[1] // R
+    assert seg.dtype == torch.int32 and seg.is_contiguous() and seg.numel() == N // 16 and seg.device == t.device
+    assert scale.dtype == torch.float32 and scale.is_contiguous() and scale.numel() == n_ad and scale.device == t.device
+    assert sel.dtype == torch.int32 and sel.is_contiguous() and sel.numel() >= M and sel.device == t.device
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=t.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == (M, N)
+    check(_lib.load().sx_lora_expand(_p(t), _p(B), _p(seg), _p(scale), _p(sel), _p(out), M, N, R, S, n_ad, _DT[B.dtype], _stream()),
+          "sx_lora_expand")
+    return out
 
 
 def _kv_scales_ok(kv_scales, kcache, vcache):

@@ -12,15 +12,31 @@ inside the captured step and is refilled from the queue before the next one (inf
 ``agent.prefix_cache = True`` an admitted request keeps, or gets copied from another slot by one sx_kv_fork launch, the cache rows of the
 longest prompt prefix some slot already holds, and prefills only the rest.
 """
+import functools
+
 import torch
 
 from . import ops
-from .inflight import PrefixIndex, SlotScheduler, plan_admission
+from .inflight import PrefixIndex, SlotScheduler, plan_admission, tag_signatures
 from .sampling import SamplingParams
 
 BOI_TOKEN = '<img>'
 EOI_TOKEN = '</img>'
 IMG_TOKEN = '<img_{:05d}>'
+
+
+def _clears_adapters(fn):
+    """A serving call leaves no sequence on an adapter, also when it raises midway: the per-sequence adapter index goes back to -1, so a
+    later token step without adapters runs the base step and its graph."""
+    @functools.wraps(fn)
+    def wrapped(self, *args, **kw):
+        try:
+            return fn(self, *args, **kw)
+        finally:
+            llm = self.llm
+            if getattr(llm, "max_adapters", 0) and llm._P is not None:
+                llm.set_adapters(range(llm.G), [None] * llm.G)
+    return wrapped
 
 
 class ContinuousLVLM:
@@ -41,7 +57,7 @@ class ContinuousLVLM:
         self.chunk_forced_image_tokens = True
         self.prefix_cache = False        # generate_inflight: reuse the cache rows of a prompt prefix some slot already holds (opt-in)
         self.prefix_min_tokens = self.PREFIX_MIN_TOKENS   # shortest prefix worth a slot-to-slot copy, or worth waiting one round for
-        self._conv = {}                  # sequence → (token ids, row fingerprints, LLM cache epoch) held by its KV cache
+        self._conv = {}                  # sequence → (token ids, row fingerprints, LLM cache epoch, adapter name) held by its KV cache
         self._sig_w = {}
         self.last_prefill_tokens = []
         self.last_inflight_stats = None
@@ -124,19 +140,22 @@ class ContinuousLVLM:
             self._sig_w[(x.shape[1], x.device)] = w
         return torch.stack([(bits * w[:, 0]).sum(dim=1), (bits * w[:, 1]).sum(dim=1)], dim=1)
 
-    def _reuse_prefix(self, prompts):
+    def _reuse_prefix(self, prompts, adapters=None):
         """Cross-turn KV reuse (no reference counterpart: seed_x.py:184-189 re-prefills the whole conversation every turn).
         For sequence g the cache still holds the previous call's prompt + the generated tokens that were fed back. The new
         prompt's longest prefix whose token ids AND embedding rows (image features included) are identical to what produced
-        those cache entries is kept; only the rest is prefilled. Returns the prefix length per sequence."""
+        those cache entries is kept; only the rest is prefilled. Returns the prefix length per sequence. KV rows depend on the LoRA
+        adapter they were computed under: a sequence whose adapter changed keeps nothing and is prefilled from row 0."""
         starts = []
         for g, (ids, x) in enumerate(prompts):
             prev = self._conv.get(g)
             p = 0
             if prev is not None and prev[2] != self.llm.kv_epoch:
                 prev = None                      # the cache was reset / written behind our back (llm.reset, llm.forward, ...)
+            if prev is not None and prev[3] != (adapters[g] if adapters is not None else None):
+                prev = None                      # the rows were written under another adapter
             if prev is not None:
-                old_ids, old_sig, _ = prev
+                old_ids, old_sig = prev[:2]
                 m = min(len(old_ids), len(ids) - 1)                                   # >= 1 token must be forwarded
                 while p < m and old_ids[p] == ids[p]:
                     p += 1
@@ -146,7 +165,7 @@ class ContinuousLVLM:
             starts.append(p)
         return starts
 
-    def _remember(self, g, prompt, gen_ids_fed):
+    def _remember(self, g, prompt, gen_ids_fed, adapter=None):
         """Records what sequence g's KV cache now holds: the prompt rows and the generated tokens that were fed back."""
         ids, x = prompt
         sig = self._row_sig(x)
@@ -154,8 +173,9 @@ class ContinuousLVLM:
             P = self.llm._P
             e = ops.embedding(torch.tensor(gen_ids_fed, dtype=torch.int32, device=x.device), P["embed"])
             sig = torch.cat([sig, self._row_sig(e)])
-        self._conv[g] = (list(ids) + list(gen_ids_fed), sig, self.llm.kv_epoch)
+        self._conv[g] = (list(ids) + list(gen_ids_fed), sig, self.llm.kv_epoch, adapter)
 
+    @_clears_adapters
     @torch.no_grad()
     def generate_batch(self, tokenizer, requests, num_img_gen_tokens=64, max_new_tokens=120, eos_token_id="auto",
                        force_image_at=None, reuse_cache=False):
@@ -167,9 +187,16 @@ class ContinuousLVLM:
         without a sampling request the call runs the greedy path unchanged. Tensor-parallel ranks (each its own process) must be
         given the same explicit ``seed``: ``seed=None`` is refused there (ValueError), since each rank would draw its own.
         ``reuse_cache``: keep each sequence's KV cache across calls and prefill only the part of the new prompt that is not
-        already in it (multi-turn conversations; results are identical to a full re-prefill)."""
+        already in it (multi-turn conversations; results are identical to a full re-prefill).
+        A request may carry ``"adapter": name`` — a LoRA adapter resident on the LLM (``llm.load_adapter``; ValueError for an unknown
+        name or an LLM built without ``max_adapters``): its prompt, its forced image chunks and its token steps run under that adapter,
+        unmerged, beside requests under other adapters or none; every result carries ``'adapter'``. Without such a request the call
+        runs the calls and captured graphs it always ran. ``reuse_cache`` re-prefills a sequence whose adapter changed."""
         llm = self.llm
         params = [SamplingParams.from_request(req, world=llm.comm.world) for req in requests]     # refuses seed=None on tp > 1 ranks
+        names = [req.get("adapter") for req in requests]
+        for n in names:
+            llm._adapter_index(n)                       # unknown name / feature off: ValueError before anything is touched
         dev, H, G = llm.device, llm.H, len(requests)
         P = llm._pack()
         assert G == llm.G, f"the LLM was built for max_batch={llm.G} lock-step sequences, got {G} requests"
@@ -188,7 +215,7 @@ class ContinuousLVLM:
             ss.set_rows(range(G), params)
         if self._inflight is not None:
             self._inflight["prefix"] = None             # generate_inflight's slot records: this call rewrites the slots
-        starts = self._reuse_prefix(prompts) if reuse_cache else [0] * G
+        starts = self._reuse_prefix(prompts, names) if reuse_cache else [0] * G
         if not reuse_cache:
             llm.reset()
             self._conv = {}
@@ -200,8 +227,11 @@ class ContinuousLVLM:
             xs.append(x[starts[g]:])
             last_ids.append(input_ids[-1])
         P["step"].zero_()
-        logits, _ = llm.forward_embeds_batch(xs, list(range(G)))
+        named = any(n is not None for n in names)
+        logits, _ = llm.forward_embeds_batch(xs, list(range(G)), **(dict(adapters=names) if named else {}))
         logits = logits.contiguous()
+        if llm.max_adapters:
+            llm.set_adapters(range(G), names)           # the per-sequence adapter index the token step reads (-1: none)
         self.last_prefill_tokens = [int(x.shape[0]) for x in xs]
         P["cur"].copy_(torch.tensor(last_ids, dtype=torch.int32))
         if ss is not None:
@@ -233,7 +263,7 @@ class ContinuousLVLM:
             hit = [g for g in range(G) if not done[g] and self.chunk_forced_image_tokens and cur[g] == boi_id
                    and n_new[g] + nchunk <= max_new_tokens]
             if hit:
-                self._forced_image_chunk(hit, n_new, img_ids, hid, out_ids)
+                self._forced_image_chunk(hit, n_new, img_ids, hid, out_ids, [names[g] for g in hit] if named else None)
                 for g in hit:
                     n_new[g] += nchunk
                     P["step"][g] = n_new[g]
@@ -259,10 +289,11 @@ class ContinuousLVLM:
             n = final_n[g]
             generate_ids = out_ids[g, :n].cpu().long()
             if reuse_cache:
-                self._remember(g, prompts[g], generate_ids[:n - 1].tolist())          # the last new token was never fed
+                self._remember(g, prompts[g], generate_ids[:n - 1].tolist(), names[g])   # the last new token was never fed
             results.append(self._result(tokenizer, generate_ids, hid[g, 1:n], boi_id, eoi_id, num_img_gen_tokens))
             if params[g] is not None:
                 results[-1]['seed'] = params[g].seed
+            results[-1]['adapter'] = names[g]
         return results
 
     @staticmethod
@@ -275,13 +306,13 @@ class ContinuousLVLM:
             eos_token_id = getattr(tokenizer, "eos_token_id", None)
         return img_ids, img_ids[0], img_ids[-1], eos_token_id
 
-    def _forced_image_chunk(self, hit, n_new, img_ids, hid, out_ids):
+    def _forced_image_chunk(self, hit, n_new, img_ids, hid, out_ids, adapters=None):
         """The forced image block of the sequences ``hit`` (their current token is <img>): inputs [<img>, <img_0> … <img_63>] as one
         causal chunk per sequence, all of them in ONE pass; the outputs are forced (generation.py:23-26). Sequence g's hidden states
         and ids [<img_0> …, </img>] go to rows n_new[g] … of ``hid`` / ``out_ids``; the caller advances its counters."""
         llm, dev = self.llm, self.llm.device
         xe = ops.embedding(torch.tensor(img_ids[:-1], dtype=torch.int32, device=dev), llm._P["embed"])
-        _, hns = llm.forward_embeds_batch([xe] * len(hit), hit, need_logits=False)
+        _, hns = llm.forward_embeds_batch([xe] * len(hit), hit, need_logits=False, **(dict(adapters=adapters) if adapters else {}))
         forced = torch.tensor(img_ids[1:], dtype=torch.int32, device=dev)
         for g, hn in zip(hit, hns):
             hid[g, n_new[g]:n_new[g] + len(img_ids) - 1] = hn                                # plumbing copy
@@ -304,6 +335,7 @@ class ContinuousLVLM:
         return {'text': text, 'has_img_output': len(eoi_indices) > 0, 'img_gen_feat': img_gen_feat,
                 'num_gen_imgs': len(eoi_indices), 'generate_ids': generate_ids, 'last_hidden_states': last_hidden}
 
+    @_clears_adapters
     @torch.no_grad()
     def generate_inflight(self, tokenizer, requests, num_img_gen_tokens=64, max_new_tokens=120, eos_token_id="auto",
                           max_admit=None, on_result=None):
@@ -318,6 +350,11 @@ class ContinuousLVLM:
         one such request runs the sampled token step (sx_sample_next_slots: same stop rule, the parameters are read per slot from
         device memory, greedy requests keep the arg-max); a queue without one runs the greedy step as before. A request's ids depend
         on its own logits, parameters, seed and token indices only — never on its slot or its neighbours.
+        A request may carry ``"adapter": name`` as in generate_batch (ValueError for an unknown name): the slot's adapter index
+        (``SlotState.adapter``) is written at its admission and goes back to -1 when the slot parks, its prefill, forced chunks and
+        token steps run under the adapter, and a queue may mix adapters and none; a step in which no live slot has an adapter is the
+        step of a queue without adapters. With ``prefix_cache`` the adapter rides in every row's signature (inflight.tag_signatures):
+        prefixes are kept and forked only among requests of the same adapter. Results carry ``'adapter'``.
         Forced image blocks stay host-driven chunks as in generate_batch (the other slots wait). Slots are reused without zeroing:
         keys at or above ``pos`` are never visible. generate_batch's cross-turn records (``reuse_cache``) are cleared by this call.
         Prefix reuse is switched on the engine, like ``use_graph``: ``agent.prefix_cache = True`` (off by default: the call then takes
@@ -350,6 +387,10 @@ class ContinuousLVLM:
         budget = [int(req.get("max_new_tokens") or max_new_tokens) for req in requests]
         force_at = [-1 if req.get("force_image_at") is None else int(req["force_image_at"]) for req in requests]
         params = [SamplingParams.from_request(req) for req in requests]
+        names = [req.get("adapter") for req in requests]
+        for nm in names:
+            llm._adapter_index(nm)                      # unknown name / feature off: ValueError before anything is touched
+        named = any(nm is not None for nm in names)
         sampled = any(p is not None for p in params)
         assert all(b >= 1 for b in budget)
         rows = max(budget) + 8
@@ -391,8 +432,9 @@ class ContinuousLVLM:
         self.last_prefill_tokens = []
         prompts, held = {}, {}                           # prefix_cache: request -> (ids, x, row signatures); slot -> (ids, signatures)
 
-        def sigs_of(x):
-            return [tuple(s) for s in self._row_sig(x).tolist()]
+        def sigs_of(x, adapter=None):
+            # KV rows depend on the adapter that computed them: its name rides in every row's signature (inflight.tag_signatures)
+            return tag_signatures([tuple(s) for s in self._row_sig(x).tolist()], adapter)
 
         def harvest(g, n):
             r = sched.finish(g)
@@ -401,12 +443,13 @@ class ContinuousLVLM:
                 ids, sig = held.pop(g)
                 fed = generate_ids[:n - 1].tolist()
                 if fed:
-                    sig = sig + sigs_of(ops.embedding(torch.tensor(fed, dtype=torch.int32, device=dev), P["embed"]))
+                    sig = sig + sigs_of(ops.embedding(torch.tensor(fed, dtype=torch.int32, device=dev), P["embed"]), names[r])
                 index.record(g, ids + fed, sig, llm.kv_epoch)
             last_hidden = hid[g, 1:n].clone()                                                # the slot's rows are reused
             results[r] = self._result(tokenizer, generate_ids, last_hidden, boi_id, eoi_id, num_img_gen_tokens)
             if params[r] is not None:
                 results[r]['seed'] = params[r].seed
+            results[r]['adapter'] = names[r]
             if on_result is not None:
                 on_result(r, results[r])
 
@@ -425,7 +468,10 @@ class ContinuousLVLM:
                 last_ids.append(ids[-1])
             llm._slot_write(P["pos"], slots, 0 if starts is None else list(starts))
             llm._slot_write(P["ctx"], slots, 1 if starts is None else [s + 1 for s in starts])
-            logits, _ = llm.forward_embeds_batch(xs, slots)
+            adn = [names[r] for _, r in adm]
+            logits, _ = llm.forward_embeds_batch(xs, slots, **(dict(adapters=adn) if any(nm is not None for nm in adn) else {}))
+            if llm.max_adapters:
+                llm.set_adapters(slots, adn)             # admission: the slot's adapter index (SlotState.adapter), -1 = none
             if starts is not None:                       # the slots hold their prompts now
                 for g in slots:
                     index.record(g, held[g][0], held[g][1], llm.kv_epoch)
@@ -463,7 +509,7 @@ class ContinuousLVLM:
             for r in cand:
                 if r not in prompts:                     # (a deferred request keeps its embeddings for the next round)
                     ids, x = self._prompt_embeds(tokenizer, requests[r])
-                    prompts[r] = (ids, x, sigs_of(x))
+                    prompts[r] = (ids, x, sigs_of(x, names[r]))
             plan, _ = plan_admission(index, sched.free_slots(), sched.live_slots(), [(r, prompts[r][0], prompts[r][2]) for r in cand],
                                      prefix_min_tokens, llm.kv_epoch)
             forks = [(d, g, start) for g, _, start, d in plan if d is not None]
@@ -494,7 +540,8 @@ class ContinuousLVLM:
             hit = [g for g in live if self.chunk_forced_image_tokens and cur[g] == boi_id
                    and n_new[g] + nchunk <= budget[sched.slot_req[g]]]
             if hit:
-                self._forced_image_chunk(hit, n_new, img_ids, hid, out_ids)                  # the other slots wait, as in generate_batch
+                self._forced_image_chunk(hit, n_new, img_ids, hid, out_ids,                 # the other slots wait, as in generate_batch
+                                         [names[sched.slot_req[g]] for g in hit] if named else None)
                 for g in hit:
                     n_new[g] += nchunk
                     cur[g] = eoi_id
@@ -515,10 +562,14 @@ class ContinuousLVLM:
             stats["decode_steps"] += 1
             stats["live_slot_steps"] += len(live)
             stats["parked_slot_steps"] += G - len(live)
+            gone = []
             for g in live:
                 cur[g], alive, n_new[g], fin_n = status[g]
                 if not alive:
                     harvest(g, fin_n)
+                    gone.append(g)
+            if gone and named:
+                llm.set_adapters(gone, [None] * len(gone))   # the device parked the slot itself: its adapter index goes back to -1
         owned(llm.reset)                                 # pos / ctx / step leave their idle values
         self.last_inflight_stats = stats
         return results
@@ -527,13 +578,14 @@ class ContinuousLVLM:
     def generate(self, tokenizer, prompt=None, input_ids=None, image_embeds=None, embeds_cmp_mask=None,
                  ids_cmp_mask=None, logits_processor=None, num_img_gen_tokens=64, temperature=0.7, num_beams=1,
                  max_new_tokens=120, top_p=0.5, dtype=torch.float16, device='cuda', patch_positions=None,
-                 eos_token_id="auto", force_image_at=None, reuse_cache=False, do_sample=False, top_k=50, seed=None):
+                 eos_token_id="auto", force_image_at=None, reuse_cache=False, do_sample=False, top_k=50, seed=None, adapter=None):
         """Reference signature (seed_x.py:130-145). Greedy by default (do_sample=False, num_beams=1 — temperature/top_p are inert
         in the reference too, :175-189). ``do_sample=True`` makes ``temperature`` / ``top_p`` live (defaults: the reference's 0.7 /
         0.5) together with ``top_k`` (50, transformers' generation default) and ``seed`` (None: 64 bits from os.urandom): the seeded
         device-side rule of seedx_amd.sampling; the result then carries ``'seed'``. ``eos_token_id``: "auto" →
         tokenizer.eos_token_id; None disables the EOS stop. On tensor-parallel ranks ``do_sample=True`` needs an explicit ``seed``, the
-        same on every rank (ValueError otherwise)."""
+        same on every rank (ValueError otherwise). ``adapter``: name of a LoRA adapter resident on the LLM (``llm.load_adapter``) the
+        request runs under, unmerged; the result carries ``'adapter'``."""
         assert logits_processor is None, "the AutoImageTokenGenerationProcessor rule is fused on the device"
         assert num_beams == 1
         assert self.llm.G == 1, "this LLM was built for lock-step batches: use generate_batch()"
@@ -541,5 +593,7 @@ class ContinuousLVLM:
                    ids_cmp_mask=ids_cmp_mask, patch_positions=patch_positions)
         if do_sample:
             req.update(do_sample=True, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
+        if adapter is not None:
+            req["adapter"] = adapter
         return self.generate_batch(tokenizer, [req], num_img_gen_tokens, max_new_tokens, eos_token_id, force_image_at,
                                    reuse_cache)[0]
