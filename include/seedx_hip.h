@@ -439,6 +439,58 @@ int sx_sample_next_b(float* logits, int ld_logits, int vocab, const int32_t* img
 /* sx_greedy_next_slots (parking, force_at after the draw, stop rule, counters, status — all unchanged) with the id by the rule above. */
 int sx_sample_next_slots(const sx_slot_step_args* args, const sx_sample_args* sample, void* stream);
 
+/* Speculative decoding (lossless): the token step carries T = K + 1 rows per slot — row g*T is the slot's current token, rows g*T + 1 ..
+ * g*T + n_draft[g] K drafted continuations — and sx_greedy_next_b / sx_sample_next_b over the G*T rows (previous id = the row's input,
+ * token index = step[g] + t) give every row its candidate id. sx_spec_accept keeps, per LIVE slot, the longest run the model itself
+ * would have produced one token at a time (seedx_amd.spec.accept states the rule): for t = 0, 1, ...
+ *   id = cand[g*T + t], replaced by force_id if n_new[g] + t == force_at[g] (after the rule, as in sx_greedy_next_slots);
+ *   id goes to out_ids[g][step[g] + t] (inside the row capacity ld_out) and to hist[g][pos[g] + 1 + t] (inside Tmax): the cache position
+ *     at which it will be fed;
+ *   the walk continues to t + 1 only if t < n_draft[g], id == rows_in[g*T + t + 1] (the draft row t + 1 was fed), id != eos_id,
+ *     id != img_ids_dev[0] (<img>: the host-driven image chunk takes over; NULL = no such id) and n_new[g] + t + 1 < max_new[g].
+ * pos, ctx, step and n_new advance by the emitted count (>= 1), cur[g] = rows_in[g*T] = the last emitted id (row 0 of the next step:
+ * a caller that drafts by itself only fills rows 1 .. and n_draft); the stop rule (EOS or budget), the parking
+ * values and status[g] = { last id, live, n_new, n_new at the finish or -1 } are sx_greedy_next_slots'. With n_draft = 0 the launch IS
+ * that entry's slot advance. A parked slot reads and writes nothing. A rejected draft leaves cache rows at or above the new pos, which
+ * no kernel reads before the next steps overwrite them. T <= 8, G*T <= 32; all arrays int32 in device memory. */
+typedef struct sx_spec_accept_args {
+  const int32_t* cand;          /* [G*T] candidate ids                                                                             */
+  int32_t* rows_in;             /* [G*T] the ids the rows were fed; row g*T is rewritten with the last emitted id                  */
+  const int32_t* n_draft;       /* [G] drafted rows per slot, 0 .. T - 1                                                           */
+  int32_t* cur;
+  int32_t* live;
+  int32_t* n_new;
+  const int32_t* max_new;
+  const int32_t* force_at;
+  int32_t* pos;
+  int32_t* ctx;
+  int32_t* step;
+  int32_t* out_ids;             /* [G][ld_out] or NULL                                                                             */
+  int32_t* status;              /* [G][4]                                                                                          */
+  int32_t* hist;                /* [G][Tmax] ids by cache position, or NULL                                                        */
+  const int32_t* img_ids_dev;   /* sx_slot_step_args' list (only <img>, its first entry, is read), or NULL                         */
+  int32_t G, T, ld_out, Tmax, force_id, eos_id;
+} sx_spec_accept_args;
+int sx_spec_accept(const sx_spec_accept_args* args, void* stream);
+/* The drafter that needs no second model: prompt-lookup n-grams (seedx_amd.spec.propose_ngram states the rule). Per slot g with
+ * L = pos[g] + 1 known ids hist[g][0 .. L) (cur[g] is the last): for n = ngram_max down to ngram_min take the LARGEST start i with
+ * hist[i .. i+n) == hist[L-n .. L) and i + n <= L - 1; the first n that matches proposes hist[i+n .. min(i+n+K, L)), K = T - 1.
+ * Writes the next step's row inputs rows_out[g*T ..]: row 0 = cur[g], rows 1 .. n_draft[g] the draft, the rest cur[g]; no match, a
+ * parked slot (pos < 0) or L > Tmax give n_draft[g] = 0. One workgroup per slot. */
+typedef struct sx_spec_draft_args {
+  const int32_t* hist;          /* [G][Tmax]                                                                                       */
+  const int32_t* pos;           /* [G]                                                                                             */
+  const int32_t* cur;           /* [G]                                                                                             */
+  int32_t* rows_out;            /* [G*T]                                                                                           */
+  int32_t* n_draft;             /* [G]                                                                                             */
+  int32_t G, T, Tmax, ngram_max, ngram_min, reserved;
+} sx_spec_draft_args;
+int sx_spec_draft_ngram(const sx_spec_draft_args* args, void* stream);
+/* the hidden-state log of a verify step: dst[(g*seq_rows + step[g] + t)][:] = src[g*T + t][:] fp32 (rows of parked slots, step < 0, and
+ * rows past seq_rows are dropped); tok_index (optional, int32 [G*T]) receives max(step[g], 0) + t, the candidates' token indices */
+int sx_scatter_rows_spec(const float* src, const int32_t* step_dev, float* dst, int32_t* tok_index, int G, int T, int dim,
+                         int seq_rows, void* stream);
+
 /* KV-cache prefix fork (prefix reuse of in-flight batching, inflight.py): copies the first rows of one slot's cache to other slots,
  * every layer and head in ONE launch. The cache is addressed as bytes, so one entry serves every cache tensor and format: the fp32 K
  * cache (row_bytes 512 at head_dim 128), the 16-bit caches (256), the FP8 codes (128) and their fp32 row scales (row_bytes 4).
@@ -575,7 +627,13 @@ typedef struct sx_attn_f32_args {
   /* T == 1, causal, D == 128 only — RoPE + KV append fused into the step (modeling_llama_xformer.py:141-149,204-244 in ONE launch
    * per layer): rope_cos != NULL means q is the UNROTATED row, k_new / v_new are the new token's rows (row stride q_row_stride: the
    * qkv buffer's + H*D and + 2*H*D), and the launch appends the rotated k and v (rounded when v16) to kcache / vcache at pos0[g] —
-   * the two cache pointers are written through in this form. NULL (default) = sx_rope_kv_append_f32* ran before. */
+   * the two cache pointers are written through in this form. NULL (default) = sx_rope_kv_append_f32* ran before.
+   * 2 <= T <= 8 with rope_cos is the VERIFY form of speculative decoding (G*T <= 32, kv_fp8 = 0, nsplit >= 1, scratch fp32
+   * [G*T][H][nsplit][D + 2] always): q / k_new / v_new are rows g*T + t, row t sits at position pos0[g] + t. The launch equals, bit
+   * for bit, T successive T = 1 calls of this form with the same nsplit, v16 and dtype (call t on row t at position pos0[g] + t) in
+   * the context planes, the k rows and the v rows of every row whose position lies in [0, Tmax); every K / V row of a (head,
+   * sequence, split) is loaded once for the T query rows. pos0[g] < 0 idles all T rows of the slot; a row at or past Tmax writes no
+   * cache row; both stay finite. */
   const float* rope_cos;    /* [Tmax][D/2] fp32 (rounded to the planes' dtype inside, like sx_rope_kv_append_f32)                    */
   const float* rope_sin;
   const float* k_new;

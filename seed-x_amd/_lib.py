@@ -79,6 +79,18 @@ class SampleArgs(C.Structure):
                 ("token_index", c_vp), ("n_kept", c_vp), ("p_chosen", c_vp)]
 
 
+class SpecAcceptArgs(C.Structure):
+    _fields_ = [("cand", c_vp), ("rows_in", c_vp), ("n_draft", c_vp), ("cur", c_vp), ("live", c_vp), ("n_new", c_vp), ("max_new", c_vp),
+                ("force_at", c_vp), ("pos", c_vp), ("ctx", c_vp), ("step", c_vp), ("out_ids", c_vp), ("status", c_vp), ("hist", c_vp),
+                ("img_ids_dev", c_vp), ("G", c_i32), ("T", c_i32), ("ld_out", c_i32), ("Tmax", c_i32), ("force_id", c_i32),
+                ("eos_id", c_i32)]
+
+
+class SpecDraftArgs(C.Structure):
+    _fields_ = [("hist", c_vp), ("pos", c_vp), ("cur", c_vp), ("rows_out", c_vp), ("n_draft", c_vp),
+                ("G", c_i32), ("T", c_i32), ("Tmax", c_i32), ("ngram_max", c_i32), ("ngram_min", c_i32), ("reserved", c_i32)]
+
+
 class KvForkArgs(C.Structure):
     _fields_ = [("cache", c_vp), ("src", c_vp), ("dst", c_vp), ("n_rows", c_vp),
                 ("outer_stride", c_i64), ("slot_stride", c_i64), ("inner_stride", c_i64),
@@ -149,6 +161,9 @@ SIGNATURES = {
     "sx_greedy_next_slots": [C.POINTER(SlotStepArgs), c_vp],
     "sx_sample_next_b": [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, C.POINTER(SampleArgs), c_vp],
     "sx_sample_next_slots": [C.POINTER(SlotStepArgs), C.POINTER(SampleArgs), c_vp],
+    "sx_spec_accept": [C.POINTER(SpecAcceptArgs), c_vp],
+    "sx_spec_draft_ngram": [C.POINTER(SpecDraftArgs), c_vp],
+    "sx_scatter_rows_spec": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp],
     "sx_kv_fork": [C.POINTER(KvForkArgs), c_vp],
     "sx_dequant_tiles": [C.POINTER(DequantTilesArgs), c_vp],
     "sx_scatter_rows_step": [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp],

@@ -1713,6 +1713,138 @@ extern "C" int sx_sample_next_slots(const sx_slot_step_args* a, const sx_sample_
   return launch_next_token("sx_sample_next_slots", slot_tail(a), true, sample, true, stream);
 }
 
+// ---- speculative decoding: the accept rule and the prompt-lookup drafter (include/seedx_hip.h: sx_spec_accept, sx_spec_draft_ngram) ---
+// seedx_amd.spec states both rules in Python (accept, propose_ngram); the kernels equal them exactly.
+// Accept: thread g walks slot g's T candidates. Everything it does for an emitted id is slot_advance's work for that id (force_at after
+// the rule, the id log, the counters, the stop rule, parking, the status row), plus the id history at the cache position where the id
+// will be fed; the walk goes on only while the id just emitted is the draft the next row was fed.
+__global__ __launch_bounds__(64) void spec_accept_kernel(const sx_spec_accept_args a) {
+  const int g = blockIdx.x * 64 + threadIdx.x;
+  if (g >= a.G || a.live[g] == 0) return;             // parked: reads and writes nothing
+  const int T = a.T, nd = min(max(a.n_draft[g], 0), T - 1);
+  const int fa = a.force_at[g], mx = a.max_new[g];
+  int n = a.n_new[g], st = a.step[g], ps = a.pos[g], cx = a.ctx[g];
+  const int img_id = a.img_ids_dev ? a.img_ids_dev[0] : -1;
+  int id = 0;
+  bool stop = false;
+  for (int t = 0; t < T; ++t) {
+    id = a.cand[g * T + t];
+    if (fa >= 0 && n == fa) id = a.force_id;
+    if (a.out_ids && st >= 0 && st < a.ld_out) a.out_ids[(size_t)g * a.ld_out + st] = id;
+    n += 1;
+    st += 1;
+    ps += 1;
+    cx += 1;
+    if (a.hist && ps >= 0 && ps < a.Tmax) a.hist[(size_t)g * a.Tmax + ps] = id;
+    stop = (a.eos_id >= 0 && id == a.eos_id) || n >= mx;
+    if (stop || t >= nd || id != a.rows_in[g * T + t + 1] || id == img_id) break;
+  }
+  a.cur[g] = id;
+  a.rows_in[g * T] = id;                               // row 0 of the next verify step (a drafter rewrites the rows anyway)
+  a.n_new[g] = n;
+  if (stop) {
+    a.live[g] = 0;
+    a.step[g] = -1;
+    a.pos[g] = -1;
+    a.ctx[g] = 0;
+  } else {
+    a.step[g] = st;
+    a.pos[g] = ps;
+    a.ctx[g] = cx;
+  }
+  int* q = a.status + 4 * g;
+  q[0] = id;
+  q[1] = stop ? 0 : 1;
+  q[2] = n;
+  q[3] = stop ? n : -1;
+}
+
+// Draft: one workgroup per slot. L = pos + 1 known ids (hist[g][0 .. L), cur the last). For n = ngram_max .. ngram_min the threads
+// stride over the starts i <= L - 1 - n and keep the largest one whose n ids equal the last n; the first n with a match wins and
+// proposes hist[i + n .. min(i + n + K, L)). Rows: row 0 = cur, rows 1 .. n_draft = the draft, the rest cur (any valid id).
+__global__ __launch_bounds__(256) void spec_draft_ngram_kernel(const sx_spec_draft_args a) {
+  __shared__ int best;
+  const int g = blockIdx.x, T = a.T;
+  const int L = a.pos[g] + 1;
+  int* rows = a.rows_out + (size_t)g * T;
+  if (L <= 0 || L > a.Tmax) {                         // parked, or no room in the history: no draft; the row inputs stay valid ids
+    if (threadIdx.x == 0) {
+      a.n_draft[g] = 0;
+      if (L > 0) for (int t = 0; t < T; ++t) rows[t] = a.cur[g];
+    }
+    return;
+  }
+  const int* h = a.hist + (size_t)g * a.Tmax;
+  int found_n = 0, found_i = -1;
+  for (int n = a.ngram_max; n >= a.ngram_min; --n) {  // uniform over the workgroup
+    if (threadIdx.x == 0) best = -1;
+    __syncthreads();
+    int mine = -1;
+    for (int i = threadIdx.x; i + n <= L - 1; i += 256) {
+      bool eq = true;
+      for (int e = 0; e < n; ++e) eq = eq && (h[i + e] == h[L - n + e]);
+      if (eq) mine = i;                               // ascending i: the last match of the thread is its largest
+    }
+    if (mine >= 0) atomicMax(&best, mine);
+    __syncthreads();
+    const int b = best;
+    __syncthreads();                                  // everyone has read best before the next n resets it
+    if (b >= 0) { found_n = n; found_i = b; break; }
+  }
+  if (threadIdx.x != 0) return;
+  const int cur = a.cur[g];
+  int nd = 0;
+  if (found_i >= 0) nd = min(T - 1, L - (found_i + found_n));
+  rows[0] = cur;
+  for (int t = 1; t < T; ++t) rows[t] = t <= nd ? h[found_i + found_n + t - 1] : cur;
+  a.n_draft[g] = nd;
+}
+
+// dst[g][step[g] + t][:] = src[g*T + t][:] (the hidden-state log of a verify step: row t of slot g is the state at the input token that
+// would be the slot's (step + t)-th), and tok[g*T + t] = max(step[g], 0) + t, the token index its candidate is drawn with
+__global__ void scatter_rows_spec_kernel(const float* src, const int* step, float* dst, int* tok, int G, int T, int dim, int seq_rows) {
+  const int64_t total = (int64_t)G * T * dim;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int r = (int)(i / dim), d = (int)(i % dim);
+    const int g = r / T, t = r - g * T;
+    const int st = step[g];
+    if (tok && d == 0) tok[r] = (st < 0 ? 0 : st) + t;
+    if (st < 0 || st + t >= seq_rows) continue;      // parked, or past the log: drop the row instead of corrupting HBM
+    dst[((size_t)g * seq_rows + st + t) * dim + d] = src[i];
+  }
+}
+
+extern "C" int sx_scatter_rows_spec(const float* src, const int32_t* step_dev, float* dst, int32_t* tok_index, int G, int T, int dim,
+                                    int seq_rows, void* stream) {
+  SX_CHECK(src && step_dev && dst && G >= 1 && T >= 1 && dim >= 1 && seq_rows >= 1, "sx_scatter_rows_spec: bad args");
+  hipLaunchKernelGGL(scatter_rows_spec_kernel, gs_grid((int64_t)G * T * dim), dim3(256), 0, ST, src, step_dev, dst, tok_index, G, T, dim,
+                     seq_rows);
+  SX_HIP_LAUNCH_CHECK();
+  return SX_OK;
+}
+
+extern "C" int sx_spec_accept(const sx_spec_accept_args* a, void* stream) {
+  SX_CHECK(a && a->cand && a->rows_in && a->n_draft && a->cur && a->live && a->n_new && a->max_new && a->force_at && a->pos && a->ctx &&
+           a->step && a->status, "sx_spec_accept: null pointer");
+  SX_CHECK(a->G >= 1 && a->T >= 1 && a->T <= 8 && (int64_t)a->G * a->T <= 32, "sx_spec_accept: G=%d T=%d (T <= 8, G*T <= 32)", a->G, a->T);
+  SX_CHECK(!a->out_ids || a->ld_out >= 1, "sx_spec_accept: out_ids needs ld_out >= 1 (the row capacity)");
+  SX_CHECK(!a->hist || a->Tmax >= 1, "sx_spec_accept: hist needs Tmax >= 1");
+  hipLaunchKernelGGL(spec_accept_kernel, dim3((a->G + 63) / 64), dim3(64), 0, ST, *a);
+  SX_HIP_LAUNCH_CHECK();
+  return SX_OK;
+}
+
+extern "C" int sx_spec_draft_ngram(const sx_spec_draft_args* a, void* stream) {
+  SX_CHECK(a && a->hist && a->pos && a->cur && a->rows_out && a->n_draft, "sx_spec_draft_ngram: null pointer");
+  SX_CHECK(a->G >= 1 && a->T >= 2 && a->T <= 8 && (int64_t)a->G * a->T <= 32 && a->Tmax >= 1, "sx_spec_draft_ngram: G=%d T=%d Tmax=%d (2 <= T <= 8, G*T <= 32)",
+           a->G, a->T, a->Tmax);
+  SX_CHECK(a->ngram_min >= 1 && a->ngram_max >= a->ngram_min && a->ngram_max <= 16, "sx_spec_draft_ngram: ngram_max=%d ngram_min=%d (1 <= min <= max <= 16)",
+           a->ngram_max, a->ngram_min);
+  hipLaunchKernelGGL(spec_draft_ngram_kernel, dim3(a->G), dim3(256), 0, ST, *a);
+  SX_HIP_LAUNCH_CHECK();
+  return SX_OK;
+}
+
 extern "C" int sx_scatter_rows_step(const float* src, const int32_t* step_dev, float* dst, int G, int dim, int seq_rows,
                                     void* stream) {
   SX_CHECK(src && step_dev && dst && G >= 1, "sx_scatter_rows_step: bad args");

@@ -207,6 +207,97 @@ __global__ __launch_bounds__(256) void rope_kv_q8_kernel(float* qkv, void* kc_, 
   }
 }
 
+// ---- device code shared by attn_f32_kernel and attn_f32_verify_kernel: the verify form must give the bits of T successive fused T = 1
+// launches, so the rotation expression, the score, the per-key update and the group / wave merges exist once ---------------------------
+// x1 c - x2 s (sg = -1, first half of the head) or x2 c + x1 s (sg = +1): xp is the rotation partner's value
+__device__ __forceinline__ float rope_rot(float x, float xp, float c, float s, float sg) { return x * c + sg * (xp * s); }
+
+// rope_rot as attn_f32_kernel<.., QB = 1, DC = 1, ..> compiles it, spelled out: the compiler contracts the expression differently at its two
+// uses there, the same way in all its T = 1 instantiations (their gfx950 code: q is v_pk_mul (x c), v_pk_mul (xp s), v_pk_fma (sg, xp s,
+// x c); k is v_pk_mul (xp s), v_pk_mul (sg, ·), v_pk_fma (x, c, ·)). A new instantiation is free to contract otherwise, so the verify
+// kernel, which owes the T = 1 launch's bits, uses these two.
+__device__ __forceinline__ float rope_rot_q_t1(float x, float xp, float c, float s, float sg) { return __builtin_fmaf(sg, xp * s, x * c); }
+__device__ __forceinline__ float rope_rot_k_t1(float x, float xp, float c, float s, float sg) { return __builtin_fmaf(x, c, sg * (xp * s)); }
+
+// q · k of one key row: the lane's DW dims in one fma chain, then the 16 lanes of the group by four xor butterflies
+template <int DW>
+__device__ __forceinline__ float attn_score(const float (&kf)[DW], const float (&qv)[DW]) {
+  float s = 0.f;
+#pragma unroll
+  for (int e = 0; e < DW; ++e) s = fmaf(kf[e], qv[e], s);
+  s += __shfl_xor(s, 1, 64);
+  s += __shfl_xor(s, 2, 64);
+  s += __shfl_xor(s, 4, 64);
+  s += __shfl_xor(s, 8, 64);
+  return s;
+}
+
+// online softmax: one key with score s and value row vf joins the running (max, sum, weighted values) of a query row
+template <int DW>
+__device__ __forceinline__ void attn_key_update(float s, const float (&vf)[DW], float& m_run, float& l_run, float (&o)[DW]) {
+  const float m_new = fmaxf(m_run, s);
+  const float alpha = __expf(m_run - m_new);   // exp(-inf) = 0 on the first key
+  const float pr = __expf(s - m_new);
+  l_run = l_run * alpha + pr;
+#pragma unroll
+  for (int e = 0; e < DW; ++e) o[e] = fmaf(pr, vf[e], o[e] * alpha);
+  m_run = m_new;
+}
+
+// the four 16-lane groups of a wave (xor-16 / xor-32 butterflies: the same order in every lane) into red[wave][row]: the values at
+// [0, DMAX), the wave's max at [DMAX], its sum at [DMAX + 1]
+template <int QB, int DC>
+__device__ __forceinline__ void attn_merge_groups(float (&o)[QB][8 * DC], const float (&m_run)[QB], const float (&l_run)[QB],
+                                                  float (&red)[4][QB][128 * DC + 4], const bool (&dvalid)[DC], int lane, int wave, int dl) {
+  constexpr int DW = 8 * DC, DMAX = 128 * DC;
+#pragma unroll
+  for (int i = 0; i < QB; ++i) {
+    float mw = fmaxf(m_run[i], __shfl_xor(m_run[i], 16, 64));
+    mw = fmaxf(mw, __shfl_xor(mw, 32, 64));
+    const float sc = (m_run[i] == -INFINITY) ? 0.f : __expf(m_run[i] - mw);
+    float lw = l_run[i] * sc;
+    lw += __shfl_xor(lw, 16, 64);
+    lw += __shfl_xor(lw, 32, 64);
+#pragma unroll
+    for (int e = 0; e < DW; ++e) {
+      float t = o[i][e] * sc;
+      t += __shfl_xor(t, 16, 64);
+      t += __shfl_xor(t, 32, 64);
+      o[i][e] = t;
+    }
+    if ((lane >> 4) == 0) {
+#pragma unroll
+      for (int c = 0; c < DC; ++c) {
+        if (dvalid[c]) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) red[wave][i][c * 128 + dl * 8 + e] = o[i][8 * c + e];
+        }
+      }
+      if (dl == 0) {
+        red[wave][i][DMAX] = mw;
+        red[wave][i][DMAX + 1] = lw;
+      }
+    }
+  }
+}
+
+// the four waves of the workgroup in wave order, for output (row i, dim d): max, weighted value, weighted sum
+template <int QB, int DMAX>
+__device__ __forceinline__ void attn_merge_waves(const float (&red)[4][QB][DMAX + 4], int i, int d, float& mg, float& acc, float& lsum) {
+  mg = -INFINITY;
+#pragma unroll
+  for (int gg = 0; gg < 4; ++gg) mg = fmaxf(mg, red[gg][i][DMAX]);
+  acc = 0.f;
+  lsum = 0.f;
+#pragma unroll
+  for (int gg = 0; gg < 4; ++gg) {
+    const float mgk = red[gg][i][DMAX];
+    const float w = (mgk == -INFINITY) ? 0.f : __expf(mgk - mg);
+    acc = fmaf(w, red[gg][i][d], acc);
+    lsum = fmaf(w, red[gg][i][DMAX + 1], lsum);
+  }
+}
+
 // Causal attention over the fp32 cache, fp32 FMA arithmetic (modeling_llama_xformer.py:204-239: prefill is causal, a q_len == 1 step
 // sees the whole cache — both are "row t of the chunk sees keys 0 .. pos0 + t"). Workgroup = (QB query rows of the chunk, head,
 // sequence), 16 groups of 16 lanes: a group owns keys grp, grp + 16, ...; a lane owns 8 of the D <= 128 head dims; every key row is
@@ -323,8 +414,8 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnF32P p) {
       const float sg = (dl < 8) ? -1.0f : 1.0f;       // first half: x1 c - x2 s; second half: x2 c + x1 s
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        qv[0][e] = (qo[e] * cs[e] + sg * (qp[e] * sn[e])) * p.scale;
-        knew[e] = ko[e] * cs[e] + sg * (kp[e] * sn[e]);
+        qv[0][e] = rope_rot(qo[e], qp[e], cs[e], sn[e], sg) * p.scale;
+        knew[e] = rope_rot(ko[e], kp[e], cs[e], sn[e], sg);
         vnew[e] = V16 ? TT::to_f32(TT::from_f32(vo[e])) : vo[e];
       }
       u32x2_t kcod, vcod;
@@ -401,90 +492,26 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnF32P p) {
     }
 #pragma unroll
     for (int i = 0; i < QB; ++i) {
-      float s = 0.f;
-#pragma unroll
-      for (int e = 0; e < DW; ++e) s = fmaf(kf[e], qv[i][e], s);
-      s += __shfl_xor(s, 1, 64);
-      s += __shfl_xor(s, 2, 64);
-      s += __shfl_xor(s, 4, 64);
-      s += __shfl_xor(s, 8, 64);
+      float s = attn_score<DW>(kf, qv[i]);
       if constexpr (KV8 == 1) s *= ksc;
-      if (i < nq && t <= pos0 + q0 + i) {               // uniform over the 16-lane group
-        const float m_new = fmaxf(m_run[i], s);
-        const float alpha = __expf(m_run[i] - m_new);   // exp(-inf) = 0 on the first key
-        const float pr = __expf(s - m_new);
-        l_run[i] = l_run[i] * alpha + pr;
-#pragma unroll
-        for (int e = 0; e < DW; ++e) o[i][e] = fmaf(pr, vf[e], o[i][e] * alpha);
-        m_run[i] = m_new;
-      }
+      if (i < nq && t <= pos0 + q0 + i) attn_key_update<DW>(s, vf, m_run[i], l_run[i], o[i]);   // uniform over the 16-lane group
     }
   }
   if constexpr (QB == 1 && DC == 1) {
     if (own_new && grp == 0) {                        // the new token's own key / value, straight from the registers
-      float s = 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s = fmaf(knew[e], qv[0][e], s);
-      s += __shfl_xor(s, 1, 64);
-      s += __shfl_xor(s, 2, 64);
-      s += __shfl_xor(s, 4, 64);
-      s += __shfl_xor(s, 8, 64);
-      const float m_new = fmaxf(m_run[0], s);
-      const float alpha = __expf(m_run[0] - m_new);
-      const float pr = __expf(s - m_new);
-      l_run[0] = l_run[0] * alpha + pr;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[0][e] = fmaf(pr, vnew[e], o[0][e] * alpha);
-      m_run[0] = m_new;
+      attn_key_update<8>(attn_score<8>(knew, qv[0]), vnew, m_run[0], l_run[0], o[0]);
     }
   }
   // the four 16-lane groups of a wave first (xor-16 / xor-32 butterflies: the same order in every lane), then the four waves through LDS
   // in wave order: deterministic
-#pragma unroll
-  for (int i = 0; i < QB; ++i) {
-    float mw = fmaxf(m_run[i], __shfl_xor(m_run[i], 16, 64));
-    mw = fmaxf(mw, __shfl_xor(mw, 32, 64));
-    const float sc = (m_run[i] == -INFINITY) ? 0.f : __expf(m_run[i] - mw);
-    float lw = l_run[i] * sc;
-    lw += __shfl_xor(lw, 16, 64);
-    lw += __shfl_xor(lw, 32, 64);
-#pragma unroll
-    for (int e = 0; e < DW; ++e) {
-      float t = o[i][e] * sc;
-      t += __shfl_xor(t, 16, 64);
-      t += __shfl_xor(t, 32, 64);
-      o[i][e] = t;
-    }
-    if ((lane >> 4) == 0) {
-#pragma unroll
-      for (int c = 0; c < DC; ++c) {
-        if (dvalid[c]) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) red[wave][i][c * 128 + dl * 8 + e] = o[i][8 * c + e];
-        }
-      }
-      if (dl == 0) {
-        red[wave][i][DMAX] = mw;
-        red[wave][i][DMAX + 1] = lw;
-      }
-    }
-  }
+  attn_merge_groups<QB, DC>(o, m_run, l_run, red, dvalid, lane, wave, dl);
   __syncthreads();
   // thread → (row i, dim d): 256 threads cover QB * DMAX outputs in QB * DMAX / 256 passes
   for (int idx = threadIdx.x; idx < QB * DMAX; idx += 256) {
     const int i = idx / DMAX, d = idx - i * DMAX;
     if (i >= nq || d >= D) continue;
-    float mg = -INFINITY;
-#pragma unroll
-    for (int gg = 0; gg < 4; ++gg) mg = fmaxf(mg, red[gg][i][DMAX]);
-    float acc = 0.f, lsum = 0.f;
-#pragma unroll
-    for (int gg = 0; gg < 4; ++gg) {
-      const float mgk = red[gg][i][DMAX];
-      const float w = (mgk == -INFINITY) ? 0.f : __expf(mgk - mg);
-      acc = fmaf(w, red[gg][i][d], acc);
-      lsum = fmaf(w, red[gg][i][DMAX + 1], lsum);
-    }
+    float mg, acc, lsum;
+    attn_merge_waves<QB, DMAX>(red, i, d, mg, acc, lsum);
     if constexpr (SPLIT) {
       float* pr = p.part + ((size_t)((size_t)g * p.H + h) * p.nsplit + blockIdx.x) * (D + 2);
       pr[d] = acc;
@@ -535,6 +562,182 @@ __global__ __launch_bounds__(128) void attn_f32_combine_kernel(const AttnF32P p)
     unsigned short* b = p.out + (size_t)g * 2 * cols + col;
     b[0] = hi;
     b[cols] = lo;
+  }
+}
+
+// ---- the VERIFY form of the fused-RoPE decode attention (speculative decoding: T = K + 1 rows per sequence, 2 <= T <= 8, D = 128) ------
+// Row t of sequence g (qkv row g*T + t) sits at position pos0[g] + t. The launch gives, bit for bit, what T successive fused T = 1 SPLIT
+// launches give (call t on row t at position pos0 + t, same nsplit): context partials, appended k rows, appended v rows. Workgroup =
+// (key split, head, sequence) as in the T = 1 launch, but it serves all T query rows: every cache key row of the (head, sequence, split)
+// is loaded ONCE for the T rows. What each row keeps of its own T = 1 launch:
+//   * its own chunk ((kend_t + nsplit - 1) / nsplit + 15) & ~15 with kend_t from pos0 + t + 1, hence its own key range per split — the
+//     ranges of two rows differ when the context crosses a multiple of 16 nsplit inside the launch; the key loop walks the union and a
+//     row takes a key only inside its own range;
+//   * keys go to 16-lane groups by key % 16 (every range starts at a multiple of 16), in ascending order per group: cache keys below
+//     pos0 first, then the earlier draft rows' keys pos0 + j (j < t) by group (pos0 + j) % 16, which the T = 1 launches would have
+//     found in the cache — here they come from LDS, where group t parked row t's rotated q, k and (rounded under V16) v — and last the
+//     row's own key by group 0;
+//   * the arithmetic: rope_rot (its two T = 1 contractions), attn_score, attn_key_update, attn_merge_groups, attn_merge_waves above, shared with attn_f32_kernel.
+// A parked slot (pos0 < 0) idles ALL its rows like the T = 1 launch idles its one (they read key row 0 of the slot's own cache, write
+// no cache row, stay finite); a row at or past Tmax writes no cache row. The partials go to part[G*T][H][nsplit][D + 2]; the combine is
+// attn_f32_combine_kernel over G*T rows.
+template <typename TT, int TQ, bool V16>
+__global__ __launch_bounds__(256) void attn_f32_verify_kernel(const AttnF32P p) {
+  constexpr int D = 128;
+  __shared__ float red[4][TQ][D + 4];
+  __shared__ float qs[TQ][D], kn[TQ][D], vn[TQ][D];
+  const int sp = blockIdx.x, h = blockIdx.y, g = blockIdx.z, T = p.T;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int grp = wave * 4 + (lane >> 4), dl = lane & 15;
+  const bool dvalid[1] = {true};
+  const int praw0 = p.pos0_dev[g];
+  const bool parked = praw0 < 0;
+  const int pos0 = parked ? 0 : praw0;
+  const int climit = parked ? 1 : min(pos0, p.Tmax);    // cache rows this launch may read: those below pos0 (parked: key row 0)
+  const float* kh = p.kc + (size_t)g * p.seq_stride + (size_t)h * p.head_stride;
+  const size_t vbase = (size_t)g * p.seq_stride + (size_t)h * p.head_stride;
+  float qv[TQ][8], o[TQ][8], m_run[TQ], l_run[TQ];
+  int kb[TQ], ke[TQ];                                   // the row's key range in this split, its own key excluded
+  bool own[TQ];                                         // this split attends to the row's own key and appends it
+  int lo = p.Tmax, hi = 0;                              // union of the rows' cache ranges
+  const int jb = (dl & 7) * 8;
+  const float sg = (dl < 8) ? -1.0f : 1.0f;             // first half: x1 c - x2 s; second half: x2 c + x1 s
+#pragma unroll
+  for (int i = 0; i < TQ; ++i) {
+    m_run[i] = -INFINITY;
+    l_run[i] = 0.f;
+    kb[i] = 0;
+    ke[i] = 0;
+    own[i] = false;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { qv[i][e] = 0.f; o[i][e] = 0.f; }
+    if (i < T) {                                        // uniform over the workgroup
+      const int pr = pos0 + i;
+      const bool pos_ok = !parked && pr < p.Tmax;
+      const int kend = parked ? 1 : min(p.Tmax, pr + 1);
+      const int chunk = ((kend + p.nsplit - 1) / p.nsplit + 15) & ~15;
+      kb[i] = sp * chunk;
+      ke[i] = min(kend, kb[i] + chunk);
+      own[i] = pos_ok && (pr / chunk == sp);
+      if (pos_ok) ke[i] = min(ke[i], pr);
+      const int ce = min(ke[i], climit);
+      if (kb[i] < ce) { lo = min(lo, kb[i]); hi = max(hi, ce); }
+    }
+    if (i < T && grp == i) {                            // group i rotates row i, parks its q / k / v in LDS and, in the owning split, appends k / v
+      const int pr = pos0 + i;
+      const int pt = (!parked && pr < p.Tmax) ? pr : 0;
+      float cs[8], sn[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {                     // tables rounded to the model dtype like the reference's cast (rope_kv_f32_kernel)
+        cs[e] = TT::to_f32(TT::from_f32(p.cos_t[(size_t)pt * 64 + jb + e]));
+        sn[e] = TT::to_f32(TT::from_f32(p.sin_t[(size_t)pt * 64 + jb + e]));
+      }
+      const size_t rbase = (size_t)((size_t)g * T + i) * p.q_stride + (size_t)h * D;
+      const float* qo = p.q + rbase + dl * 8;
+      const float* qp = p.q + rbase + (dl ^ 8) * 8;
+      const float* ko = p.knew + rbase + dl * 8;
+      const float* kp = p.knew + rbase + (dl ^ 8) * 8;
+      const float* vo = p.vnew + rbase + dl * 8;
+      float kr[8], vr[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        qs[i][dl * 8 + e] = rope_rot_q_t1(qo[e], qp[e], cs[e], sn[e], sg) * p.scale;
+        kr[e] = rope_rot_k_t1(ko[e], kp[e], cs[e], sn[e], sg);
+        vr[e] = V16 ? TT::to_f32(TT::from_f32(vo[e])) : vo[e];
+      }
+      {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { kn[i][dl * 8 + e] = kr[e]; vn[i][dl * 8 + e] = vr[e]; }
+        if (own[i]) {
+          float* kd = const_cast<float*>(kh) + (size_t)pr * p.row_stride + dl * 8;
+          const size_t vo_c = vbase + (size_t)pr * p.row_stride + dl * 8;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) kd[e] = kr[e];
+          if constexpr (V16) {
+            unsigned short* vd = (unsigned short*)const_cast<void*>(p.vc) + vo_c;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) vd[e] = TT::from_f32(vo[e]);
+          } else {
+            float* vd = (float*)const_cast<void*>(p.vc) + vo_c;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) vd[e] = vo[e];
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < TQ; ++i) {
+    if (i < T) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) qv[i][e] = qs[i][dl * 8 + e];
+    }
+  }
+  // ---- cache keys below pos0: one load per key row for all T query rows ----
+  for (int t = lo + grp; t < hi; t += 16) {             // lo is a multiple of 16; hi <= climit <= Tmax
+    float kf[8], vf[8];
+    const float* kr = kh + (size_t)t * p.row_stride + dl * 8;
+    const size_t vo = vbase + (size_t)t * p.row_stride + dl * 8;
+    const f32x4_t k0 = *(const f32x4_t*)kr, k1 = *(const f32x4_t*)(kr + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { kf[e] = k0[e]; kf[4 + e] = k1[e]; }
+    if constexpr (V16) {
+      const u32x4_t w = *(const u32x4_t*)((const unsigned short*)p.vc + vo);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        vf[2 * e] = TT::to_f32((unsigned short)(w[e] & 0xffffu));
+        vf[2 * e + 1] = TT::to_f32((unsigned short)(w[e] >> 16));
+      }
+    } else {
+      const float* vr = (const float*)p.vc + vo;
+      const f32x4_t v0 = *(const f32x4_t*)vr, v1 = *(const f32x4_t*)(vr + 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { vf[e] = v0[e]; vf[4 + e] = v1[e]; }
+    }
+#pragma unroll
+    for (int i = 0; i < TQ; ++i) {
+      const float s = attn_score<8>(kf, qv[i]);
+      if (t >= kb[i] && t < min(ke[i], climit)) attn_key_update<8>(s, vf, m_run[i], l_run[i], o[i]);   // uniform over the 16-lane group
+    }
+  }
+  // ---- the earlier draft rows' keys pos0 + j, ascending, by the group the cache walk would have given them ----
+#pragma unroll
+  for (int j = 0; j < TQ - 1; ++j) {
+    const int key = pos0 + j;
+    if (j < T - 1 && !parked && key < p.Tmax && (key & 15) == grp) {
+      float kf[8], vf[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { kf[e] = kn[j][dl * 8 + e]; vf[e] = vn[j][dl * 8 + e]; }
+#pragma unroll
+      for (int i = j + 1; i < TQ; ++i) {
+        const float s = attn_score<8>(kf, qv[i]);
+        if (key >= kb[i] && key < ke[i]) attn_key_update<8>(s, vf, m_run[i], l_run[i], o[i]);
+      }
+    }
+  }
+  // ---- every row's own key, last, by group 0 ----
+  if (grp == 0) {
+#pragma unroll
+    for (int i = 0; i < TQ; ++i) {
+      if (own[i]) {
+        float kf[8], vf[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { kf[e] = kn[i][dl * 8 + e]; vf[e] = vn[i][dl * 8 + e]; }
+        attn_key_update<8>(attn_score<8>(kf, qv[i]), vf, m_run[i], l_run[i], o[i]);
+      }
+    }
+  }
+  attn_merge_groups<TQ, 1>(o, m_run, l_run, red, dvalid, lane, wave, dl);
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < TQ * D; idx += 256) {
+    const int i = idx / D, d = idx - i * D;
+    if (i >= T) continue;
+    float mg, acc, lsum;
+    attn_merge_waves<TQ, D>(red, i, d, mg, acc, lsum);
+    float* pr = p.part + ((size_t)((size_t)((size_t)g * T + i) * p.H + h) * p.nsplit + sp) * (D + 2);
+    pr[d] = acc;
+    if (d == 0) { pr[D] = mg; pr[D + 1] = lsum; }
   }
 }
 
@@ -836,9 +1039,30 @@ extern "C" int sx_attention_f32(const sx_attn_f32_args* a, void* stream) {
     SX_CHECK(p.seq_stride % 16 == 0, "sx_attention_f32: kv_fp8 = 1 needs cache_seq_stride %% 16 == 0 (16-B aligned code rows)");
   }
   if (a->rope_cos) {
-    SX_CHECK(a->T == 1 && a->causal && a->D == 128 && a->rope_sin && a->k_new && a->v_new && a->kv_row_stride <= 0 + (int64_t)a->D,
-             "sx_attention_f32: the fused RoPE form is the T = 1 causal step at head_dim 128 over the cache layout (rope_sin, k_new, v_new set)");
+    SX_CHECK(a->T >= 1 && a->T <= 8 && a->causal && a->D == 128 && a->rope_sin && a->k_new && a->v_new && a->kv_row_stride <= 0 + (int64_t)a->D,
+             "sx_attention_f32: the fused RoPE form is the causal step of T <= 8 rows per sequence at head_dim 128 over the cache layout (rope_sin, k_new, v_new set)");
     SX_CHECK((((uintptr_t)a->k_new) & 15) == 0 && (((uintptr_t)a->v_new) & 15) == 0, "sx_attention_f32: k_new / v_new alignment");
+  }
+  if (a->rope_cos && a->T > 1) {
+    // the verify form: T = K + 1 rows per sequence, key splits + combine over G*T rows (nsplit = 1 included: one split per row)
+    SX_CHECK(a->kv_fp8 == 0, "sx_attention_f32: the verify form (rope_cos with T > 1) has no FP8 KV cache");
+    SX_CHECK((int64_t)a->G * a->T <= 32, "sx_attention_f32: the verify form carries G*T <= 32 rows, not %lld", (long long)a->G * a->T);
+    SX_CHECK(a->scratch && a->nsplit >= 1 && a->nsplit <= 64, "sx_attention_f32: the verify form needs nsplit in 1..64 and scratch [G*T][H][nsplit][D + 2] floats");
+    SX_CHECK(a->kv_head_stride <= 0 || a->kv_head_stride >= (int64_t)a->Tmax * p.row_stride, "sx_attention_f32: kv_head_stride");
+    SX_CHECK(!a->v16 || (a->v16 == 1 && p.row_stride % 8 == 0 && p.head_stride % 8 == 0 && p.seq_stride % 8 == 0),
+             "sx_attention_f32: a 16-bit V cache needs 16-B aligned rows");
+    const dim3 grid(a->nsplit, a->H, a->G);
+#define SX_VERIFY_GO(TT, TQ, V16) hipLaunchKernelGGL((attn_f32_verify_kernel<TT, TQ, V16>), grid, dim3(256), 0, ST, p)
+#define SX_VERIFY_TQ(TT, V16) do { if (a->T <= 4) SX_VERIFY_GO(TT, 4, V16); else SX_VERIFY_GO(TT, 8, V16); } while (0)
+    if (dt == SX_BF16) { if (a->v16) SX_VERIFY_TQ(BF16, true); else SX_VERIFY_TQ(BF16, false); }
+    else { if (a->v16) SX_VERIFY_TQ(F16, true); else SX_VERIFY_TQ(F16, false); }
+#undef SX_VERIFY_TQ
+#undef SX_VERIFY_GO
+    SX_HIP_LAUNCH_CHECK();
+    if (dt == SX_BF16) hipLaunchKernelGGL(attn_f32_combine_kernel<BF16>, dim3(a->H, a->G * a->T), dim3(128), 0, ST, p);
+    else hipLaunchKernelGGL(attn_f32_combine_kernel<F16>, dim3(a->H, a->G * a->T), dim3(128), 0, ST, p);
+    SX_HIP_LAUNCH_CHECK();
+    return SX_OK;
   }
   if (a->T == 1 && a->nsplit > 1) {
     // the decode step of few sequences: key splits + combine (two launches)

@@ -363,7 +363,7 @@ class _DenoiseLoop:
                 torch.cuda.current_stream().wait_stream(side)
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
+                with ops.graph_capture(g):
                     step_body()
                 for k, v in snap.items():
                     S[k].copy_(v)

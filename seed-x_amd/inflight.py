@@ -110,6 +110,46 @@ def simulate(lengths, n_slots, max_admit=None):
     return stats
 
 
+def simulate_spec(lengths, n_slots, emitted, max_admit=None):
+    """``simulate`` for the verify step of speculative decoding (agent.speculative): the k-th decode step request i is live in emits
+    ``emitted[i][k]`` tokens (>= 1; what the accept rule kept) instead of one; a count that overshoots the request's length is cut there.
+    Returns simulate's dict plus emitted_tokens (tokens produced by decode steps)."""
+    lengths = [int(n) for n in lengths]
+    assert all(n >= 1 for n in lengths) and len(emitted) == len(lengths)
+    sch = SlotScheduler(n_slots, len(lengths), max_admit)
+    made, k = {}, {}
+    stats = dict(decode_steps=0, live_slot_steps=0, parked_slot_steps=0, admissions=0, prefill_passes=0, finish_order=[], emitted_tokens=0)
+    while not sch.done:
+        sch.new_pass()
+        while True:
+            adm = sch.admit()
+            if not adm:
+                break
+            stats["admissions"] += len(adm)
+            stats["prefill_passes"] += 1
+            for g, r in adm:
+                made[g], k[g] = 1, 0                          # token 1 comes from the admission prefill
+                if made[g] >= lengths[r]:
+                    stats["finish_order"].append(sch.finish(g))
+        live = sch.live_slots()
+        if not live:
+            continue
+        stats["decode_steps"] += 1
+        stats["live_slot_steps"] += len(live)
+        stats["parked_slot_steps"] += n_slots - len(live)
+        for g in live:
+            r = sch.slot_req[g]
+            e = int(emitted[r][k[g]])
+            assert e >= 1
+            e = min(e, lengths[r] - made[g])
+            made[g] += e
+            k[g] += 1
+            stats["emitted_tokens"] += e
+            if made[g] >= lengths[r]:
+                stats["finish_order"].append(sch.finish(g))
+    return stats
+
+
 def lockstep_wave_steps(lengths, n_slots):
     """Decode steps of the lock-step alternative: FIFO waves of ``n_slots`` requests, every wave as long as its longest member."""
     lengths = [int(n) for n in lengths]

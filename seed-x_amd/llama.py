@@ -172,10 +172,13 @@ class SampleState:
         self.seed = torch.zeros((G, 2), dtype=torch.int32, device=device)
         self.n_kept = torch.full((G,), -1, dtype=torch.int32, device=device)
         self.p_chosen = torch.ones(G, dtype=torch.float32, device=device)
+        # speculative decoding: (a SampleState of G*T rows, T) that holds slot g's parameters in its rows g*T .. g*T + T - 1 — what
+        # the candidates of a verify step are drawn with; set_rows keeps it in step. None: no verify step
+        self.rows = None
 
     def key(self):
         return tuple(t.data_ptr() for t in (self.do_sample, self.temperature, self.top_k, self.top_p, self.seed, self.n_kept,
-                                            self.p_chosen))
+                                            self.p_chosen)) + (self.rows[0].key() if self.rows is not None else ())
 
     def set_rows(self, rows, params):
         """rows[i] takes params[i] (a sampling.SamplingParams, or None = greedy): five small host → device copies."""
@@ -192,6 +195,9 @@ class SampleState:
         self.top_k.index_copy_(0, idx, i32([p.top_k if o else 0 for p, o in zip(params, on)]))
         self.top_p.index_copy_(0, idx, f32([p.top_p if o else 1.0 for p, o in zip(params, on)]))
         self.seed.index_copy_(0, idx, i32([[s32(p.seed & 0xffffffff), s32(p.seed >> 32)] if o else [0, 0] for p, o in zip(params, on)]))
+        if self.rows is not None:
+            st, T = self.rows
+            st.set_rows([g * T + t for g in rows for t in range(T)], [p for p in params for _ in range(T)])
 
     def gather(self, rows):
         """A state of len(rows) rows holding copies of the given rows' parameters (the first token of admitted requests)."""
@@ -208,7 +214,7 @@ class LlamaForCausalLM:
     WEIGHT_RESIDENCIES = (None, "tiles")
 
     def __init__(self, config, max_cache_len=None, max_batch=1, comm=None, precise=None, kv_v16=None, weight_format=None, kv_format=None,
-                 weight_residency=None, max_adapters=0, lora_rank=32):
+                 weight_residency=None, max_adapters=0, lora_rank=32, spec_tokens=0):
         self.config = config if not isinstance(config, dict) else LlamaConfigLite(**config)
         c = self.config
         self.H, self.nh, self.L = c.hidden_size, c.num_attention_heads, c.num_hidden_layers
@@ -325,6 +331,34 @@ class LlamaForCausalLM:
                                  "exists on the MFMA skinny GEMM only")
             if self.lora_rank < 8 or self.lora_rank % 8 or 3 * self.lora_rank > 512:
                 raise ValueError(f"LlamaForCausalLM: lora_rank={lora_rank} must be a multiple of 8 in 8 .. 168")
+        # lossless speculative decoding (spec.py; opt-in: ``spec_tokens=K`` drafted tokens per sequence and step): the verify step
+        # (``decode_step(..., slots=st, spec=True)``) carries K + 1 rows per slot through the skinny GEMMs — the weights stream once
+        # whatever the row count — and keeps the longest prefix the model itself would have produced (sx_spec_accept). 0: nothing is
+        # allocated, nothing changes. Never a fall-back: what the verify kernels do not cover is refused here
+        self.spec_tokens = int(spec_tokens)
+        self.spec_ngram = (3, 1)         # (longest, shortest) n-gram of the prompt-lookup drafter (sx_spec_draft_ngram)
+        if self.spec_tokens:
+            K = self.spec_tokens
+            if not 1 <= K <= 7:
+                raise ValueError(f"LlamaForCausalLM: spec_tokens={spec_tokens} must be 0 (off) or 1 .. 7 (the verify attention holds 8 rows per sequence)")
+            if not self.precise:
+                raise ValueError("LlamaForCausalLM: spec_tokens needs the precise mode (the verify form exists for the fp32 decode attention only)")
+            if not self._skinny_shapes_ok():
+                raise ValueError(f"LlamaForCausalLM: spec_tokens needs the tiled precise decode path: hidden / head / FFN widths that are multiples "
+                                 f"of 64 and >= 256, output widths that are multiples of 32 (H {self.H}, heads x dim {self.H_l}, FFN {self.I_l}, "
+                                 f"vocab rows {self.V_l}): the K + 1 rows per sequence ride on the MFMA skinny GEMM")
+            if self.hd != 128:
+                raise ValueError(f"LlamaForCausalLM: spec_tokens needs head_dim 128, not {self.hd} (the verify attention is the fused-RoPE form)")
+            if tp > 1:
+                raise ValueError("LlamaForCausalLM: spec_tokens needs a single rank (tensor-parallel ranks are not supported)")
+            if self.G * (K + 1) > 32:
+                raise ValueError(f"LlamaForCausalLM: max_batch {self.G} x (spec_tokens {K} + 1) = {self.G * (K + 1)} rows exceed the 32 rows of "
+                                 "the skinny GEMM's operand tiles")
+            if kv_format is not None:
+                raise ValueError(f"LlamaForCausalLM: spec_tokens and kv_format={kv_format!r} exclude each other (the verify attention has no FP8 "
+                                 "KV cache form)")
+            if self.max_adapters:
+                raise ValueError("LlamaForCausalLM: spec_tokens and max_adapters > 0 exclude each other (the adapter token step has no verify form)")
         self._adapters = {}              # name -> table slot
         self._sel_host = [-1] * self.G   # host mirror of P["lora"]["sel"]: the adapter slot of every sequence, -1 = none
         self.device, self.dtype = None, torch.float16
@@ -372,6 +406,8 @@ class LlamaForCausalLM:
         self._graph = self._slot_graph = self._sample_graph = self._slot_sample_graph = None
         # the adapter token step (_layers_single_precise(adapters=True)) has four graphs of its own: it never shares one with the steps above
         self._graph_ad = self._slot_graph_ad = self._sample_graph_ad = self._slot_sample_graph_ad = None
+        # the verify step of speculative decoding (decode_step(..., spec=True)): graphs of its own, greedy and sampled
+        self._spec_graph = self._spec_sample_graph = None
 
     def memory_footprint(self):
         """Bytes this module will hold on its GPU once packed (per rank): 16-bit weights, their decode-tile copy (precise mode: always;
@@ -392,6 +428,8 @@ class LlamaForCausalLM:
             kv = self.L * self.G * self.nh_l * self.Tmax * (2 * self.hd + 8)
         # adapter tables (max_adapters slots): A and B of the seven projections in 16 bits, the three norms' gammas and the scale in fp32
         ad = {"adapters": self.max_adapters * self._adapter_slot_bytes()} if self.max_adapters else {}
+        if self.spec_tokens:                    # the verify step's own buffers (_pack: P["spec"])
+            ad["spec_decode"] = self._spec_bytes()
         if self.weight_residency == "tiles":
             # no row-major projection is held: embedding + lm_head + the one prefill scratch buffer (the largest per-rank projection)
             scratch = self._scratch_elems() * 2
@@ -404,6 +442,17 @@ class LlamaForCausalLM:
         """Bytes of one adapter slot: R (K + N) 16-bit elements per projection (q, k, v, o: H x H; gate, up: I x H; down: H x I), the
         2 L + 1 fp32 gammas and the fp32 scale. 0.25 GB at 13B dims with R = 32."""
         return self.L * 2 * self.lora_rank * (8 * self.H + 3 * (self.H + self.I)) + (2 * self.L + 1) * self.H * 4 + 4
+
+    def _spec_bytes(self):
+        """Bytes of the verify step's own buffers: the id history, the row inputs / candidates / token indices, n_draft, the split-K
+        workspace of G (K + 1) rows and the verify attention's partials."""
+        R = self.G * (self.spec_tokens + 1)
+        return (self.G * self.Tmax + 3 * R + self.G) * 4 + self._gemv_ws_bytes(R) + R * self.nh_l * self.decode_nsplit_f32 * (self.hd + 2) * 4
+
+    def _gemv_ws_bytes(self, rows):
+        """split-K scratch of the skinny GEMM for ``rows`` rows: counters + 8 partial [16, H] blocks per operand block
+        (include/seedx_hip.h: sx_gemv_args.workspace)"""
+        return 16384 + 8 * 16 * ((2 if self.precise else 1) * ((rows + 15) // 16)) * self.H * 4
 
     def _scratch_elems(self):
         """Elements of the tiles residency's prefill scratch buffer: max over the four per-rank projections of N * K (gate|up at 13B)."""
@@ -640,8 +689,7 @@ class LlamaForCausalLM:
         assert P["rms_fold"] or not fold or not any(lw["wgu_t"] is not None for lw in P["layers"]), \
             "folded decode tiles without the tiled decode path"
         # split-K scratch of the skinny GEMM: counters + 8 partial [16, H] blocks (include/seedx_hip.h: sx_gemv_args.workspace)
-        P["gemv_ws"] = torch.zeros(16384 + 8 * 16 * ((2 if self.precise else 1) * ((self.G + 15) // 16)) * self.H * 4, dtype=torch.uint8,
-                                   device=dev) if P["decode_tiled"] else None
+        P["gemv_ws"] = torch.zeros(self._gemv_ws_bytes(self.G), dtype=torch.uint8, device=dev) if P["decode_tiled"] else None
         # precise decode step on the skinny GEMM (operand tiles, two planes): every projection shape must satisfy its MFMA path
         P["precise_tiled"] = self._precise_tiled_ok()
         # RMSNorm fold of the precise decode step (single rank, decode tiles, a multiple of 64 workgroups in the o / down launches —
@@ -694,6 +742,22 @@ class LlamaForCausalLM:
             assert held == fp["adapters"], (held, fp["adapters"])                 # memory_footprint() prices what is held
             P["lora"] = T
             self._sel_host = [-1] * G
+        if self.spec_tokens:
+            # the verify step's own buffers; the plain step keeps its workspace, scratch and graphs untouched
+            R = G * (self.spec_tokens + 1)
+            zi = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+            S = {"hist": zi(G, self.Tmax),                 # ids by cache position (prompt ids at admission, emitted ids by sx_spec_accept)
+                 "rows": zi(R),                            # the step's row inputs: row g*T = cur, rows g*T + 1 .. = the draft
+                 "cand": zi(R), "tok": zi(R),              # candidate id and token index (step[g] + t) of every row
+                 "n_draft": zi(G),
+                 "gemv_ws": torch.zeros(self._gemv_ws_bytes(R), dtype=torch.uint8, device=dev),
+                 "attn_part": torch.empty((R, self.nh_l, self.decode_nsplit_f32, self.hd + 2), dtype=torch.float32, device=dev)}
+            held = sum(t.numel() * t.element_size() for t in S.values())
+            assert held == fp["spec_decode"], (held, fp["spec_decode"])           # memory_footprint() prices what is held
+            if not (P["precise_tiled"] and P["decode_tiled"]):
+                raise ValueError("LlamaForCausalLM: spec_tokens needs the tiled precise decode path")
+            S["sample"] = None                             # SampleState of R rows, made with the first sampled slot state
+            P["spec"] = S
         self._P = P
         self._sd = None
         self._drop_graphs()
@@ -972,7 +1036,7 @@ class LlamaForCausalLM:
             ops.add_i32(P["ctx"], 1)
         return x
 
-    def _layers_single_precise(self, x, slots=None, adapters=False):
+    def _layers_single_precise(self, x, slots=None, adapters=False, spec=False):
         """_layers_single with fp32-grade activations: the x operand of every skinny GEMM is a two-block Tiled16 (hi plane, lo plane;
         sx_gemv x_planes = 2 — each weight fragment feeds two MFMAs, the weights stream once), its outputs are fp32; RoPE, the KV
         cache and attention are fp32 (sx_rope_kv_append_f32, sx_attention_f32 at T = 1). Shapes outside the skinny GEMM's MFMA path
@@ -980,13 +1044,21 @@ class LlamaForCausalLM:
         ``adapters``: the adapter token step — this body on its UNFOLDED arrangement (the branch SX_RMS_FOLD=0 selects) with the per-row
         gammas (sx_rmsnorm_planes_sel) and, in front of each of the four skinny GEMMs, shrink + expand on the x operand it already
         reads; the fp32 delta enters that GEMM's epilogue before activation / GLU / residual (sx_gemv_args.addend). The adapter slot of
-        every sequence is read from device memory (P["lora"]["sel"]); a row without an adapter has the bits of the unfolded base step."""
+        every sequence is read from device memory (P["lora"]["sel"]); a row without an adapter has the bits of the unfolded base step.
+        ``spec``: the verify step of speculative decoding — x holds T = spec_tokens + 1 rows per sequence (row g*T + t at position
+        pos[g] + t), the attention is the verify form of the fused-RoPE launch, and the split-K workspace and attention partials are
+        the ones sized for G*T rows (P["spec"]). Everything else is the same calls on more rows."""
         P, dt, nh, hd, G = self._P, self.dtype, self.nh_l, self.hd, self.G
+        T = self.spec_tokens + 1 if spec else 1
+        assert not (spec and adapters) and x.shape[0] == G * T
         lo = P["lora"] if adapters else None
         assert lo is None or (P["precise_tiled"] and P["decode_tiled"])
         comm, lead = self.comm, self.comm.rank == 0
         eps, scale = self.config.rms_norm_eps, 1.0 / math.sqrt(hd)
         tl, ws, f32 = P["precise_tiled"], P["gemv_ws"], torch.float32
+        part = P["attn_f32_part"]
+        if spec:
+            ws, part = P["spec"]["gemv_ws"], P["spec"]["attn_part"]
         dtl = tl and P["decode_tiled"]                       # decode-tile weight copies (built for every G in precise mode)
 
         def delta(xp, li, kk):
@@ -1007,7 +1079,7 @@ class LlamaForCausalLM:
                                 w_tiles20=lw.get(k + "_t20") if dtl else None, w_fp8=lw.get(k + "_f8"), w_fp4=lw.get(k + "_f4"), out_dtype=f32, **kw)
             return ops.gemm(xp, lw[k], a_planes=2, out_dtype=f32, **kw)
         fold = P["rms_fold_precise"] and lo is None
-        fuse_rope = hd == 128 and os.environ.get("SX_LLM_FUSE_ROPE", "1") != "0"
+        fuse_rope = hd == 128 and (spec or os.environ.get("SX_LLM_FUSE_ROPE", "1") != "0")   # (the verify form IS the fused form)
         x16 = ssq = None
         nl = len(P["layers"])
         for li, lw in enumerate(P["layers"]):
@@ -1018,8 +1090,8 @@ class LlamaForCausalLM:
                 qkv = lin(h, lw, "wqkv", **delta(h, li, "qkv"))                       # [G, 3H] fp32
             kw = self._kv_kw(li)    # kv_format: the row scales of the FP8 cache, or the emulate flag of its fp32 twin
             if fuse_rope:           # RoPE + KV append inside the attention launch (one graph node per layer instead of two)
-                att = ops.attention_f32(qkv, P["kc"][li], P["vc"][li], P["pos"], G, 1, nh, hd, scale, dt, tiled=tl,
-                                        nsplit=self.decode_nsplit_f32, scratch=P["attn_f32_part"], rope=(P["cos"], P["sin"]), **kw)
+                att = ops.attention_f32(qkv, P["kc"][li], P["vc"][li], P["pos"], G, T, nh, hd, scale, dt, tiled=tl,
+                                        nsplit=self.decode_nsplit_f32, scratch=part, rope=(P["cos"], P["sin"]), **kw)
             else:
                 ops.rope_kv_append_f32(qkv, P["kc"][li], P["vc"][li], P["cos"], P["sin"], P["pos"], G, 1, nh, hd, dt, **kw)
                 att = ops.attention_f32(qkv, P["kc"][li], P["vc"][li], P["pos"], G, 1, nh, hd, scale, dt, tiled=tl,
@@ -1195,6 +1267,9 @@ class LlamaForCausalLM:
             raise NotImplementedError("in-flight batching (slot states) is single-rank: tensor-parallel ranks are not supported")
         self._pack()
         st = SlotState(self.G, self.device, force_id, eos_id, sampling)
+        if sampling and self.spec_tokens:
+            T = self.spec_tokens + 1
+            st.sampling.rows = (SampleState(self.G * T, self.device), T)
         if self.max_adapters:
             st.adapter = self._P["lora"]["sel"]
         self.park_slots(range(self.G), st)
@@ -1271,7 +1346,36 @@ class LlamaForCausalLM:
         tail(logits, self.V, img_ids_dev, P["cur"], out_ids, P["step"], **sample)
         ops.add_i32(P["step"], 1)
 
-    def decode_step(self, img_ids_dev, out_ids, hid_buf, use_graph=True, slots=None, sampling=None, adapters=None):
+    def _spec_step_body(self, img_ids_dev, out_ids, hid_buf, slots, draft):
+        """The verify step of speculative decoding, the slot step over G*T rows (T = spec_tokens + 1): [n-gram draft →] embedding of the
+        row inputs → the layers with the verify attention → final norm → hidden state of row (g, t) at hid_buf[g, step[g] + t] →
+        lm_head → every row's candidate id (the plain step's rule or sampler: previous id = the row's input, token index step[g] + t)
+        → sx_spec_accept: the emitted ids to out_ids[g, step[g] ...] and to the id history, the counters advanced by the emitted
+        count, stop rule, parking and status as in the plain slot step. No host reads."""
+        P, S = self._P, self._P["spec"]
+        if draft == "ngram":
+            ops.spec_draft_ngram(S["hist"], P["pos"], P["cur"], S["rows"], S["n_draft"], self.spec_ngram)
+        x = ops.embedding(S["rows"], P["embed"])                                       # [G*T, H] fp32
+        x = self._layers_single_precise(x, slots, spec=True)
+        hp, hn = ops.rmsnorm_planes(x, P["norm"], self.config.rms_norm_eps, self.dtype, tiled=True, want_f32=True)
+        ops.scatter_rows_spec(hn, P["step"], hid_buf, S["tok"])
+        logits = ops.gemv(hp, P["lm_head"], out_dtype=torch.float32, w_tiles=P["lm_head_t"])
+        ss = slots.sampling
+        ops.spec_candidates(logits, self.V, img_ids_dev, S["rows"], S["cand"], S["tok"], sample=None if ss is None else ss.rows[0])
+        ops.spec_accept(S["cand"], S["rows"], S["n_draft"], P["cur"], slots.live, slots.n_new, slots.max_new, slots.force_at, P["pos"],
+                        P["ctx"], P["step"], out_ids, slots.status, hist=S["hist"], force_id=slots.force_id, eos_id=slots.eos_id,
+                        img_ids_dev=img_ids_dev)
+        slots.logits = logits
+
+    def spec_write_history(self, slot, start, ids):
+        """hist[slot, start : start + len(ids)] = ids: the ids fed (or about to be fed) at those cache positions, for the n-gram drafter.
+        Admission writes the prompt's ids (placeholders for image rows) and the first token; a host-driven chunk its block."""
+        S = self._pack()["spec"]
+        ids = [int(i) for i in ids][:max(0, self.Tmax - int(start))]
+        if ids:
+            S["hist"][slot, start:start + len(ids)] = torch.tensor(ids, dtype=torch.int32, device=self.device)
+
+    def decode_step(self, img_ids_dev, out_ids, hid_buf, use_graph=True, slots=None, sampling=None, adapters=None, spec=False, draft="ngram"):
         """out_ids: int32 [G, rows]; hid_buf: fp32 [G, rows, H]. ``slots``: a SlotState → the in-flight step (its captured graph is
         kept apart from the lock-step one, so one graph serves an engine's lifetime whatever else runs in between). ``sampling``: a
         SampleState → the lock-step step ends in sx_sample_next_b (token index = step[g]); a slot state brings its own
@@ -1281,6 +1385,46 @@ class LlamaForCausalLM:
         it. The adapter step has captured graphs of its own; a step in which no sequence has an adapter runs the calls and graphs it
         ran before adapters existed."""
         self._pack()
+        if spec:
+            # the verify step of speculative decoding (spec_tokens > 0, a slot state): graphs of its own, greedy and sampled; without
+            # ``spec`` a model built with spec_tokens runs the plain steps and graphs below. ``draft``: "ngram" → the step starts with
+            # sx_spec_draft_ngram over the id history (``self.spec_ngram`` = (longest, shortest) n-gram); "given" → the caller wrote
+            # rows 1 .. of P["spec"]["rows"] and P["spec"]["n_draft"] itself (row 0 is kept by sx_spec_accept)
+            if not self.spec_tokens or slots is None:
+                raise ValueError("LlamaForCausalLM.decode_step(spec=True) needs spec_tokens > 0 and a slot state")
+            if draft not in ("ngram", "given"):
+                raise ValueError(f"LlamaForCausalLM.decode_step: draft must be 'ngram' or 'given', not {draft!r}")
+            assert sampling is None and not adapters and slots.G == self.G and out_ids.is_contiguous() and hid_buf.is_contiguous()
+            assert out_ids.shape[0] == self.G and hid_buf.shape[0] == self.G and hid_buf.shape[1] == out_ids.shape[1]
+            assert slots.sampling is None or slots.sampling.rows is not None, "a sampled slot state made by slot_state() of this model"
+            if not use_graph or not self.comm.graph_safe:
+                self._spec_step_body(img_ids_dev, out_ids, hid_buf, slots, draft)
+                return
+            attr = "_spec_graph" if slots.sampling is None else "_spec_sample_graph"
+            key = (img_ids_dev.data_ptr(), out_ids.data_ptr(), hid_buf.data_ptr(), tuple(out_ids.shape), draft, tuple(self.spec_ngram)) + slots.key()
+            held = getattr(self, attr)
+            if held is None or held[0] != key:
+                P, S = self._P, self._P["spec"]
+                snap = [(P[k], P[k].clone()) for k in ("pos", "ctx", "step", "cur")] + [(S[k], S[k].clone()) for k in ("rows", "n_draft")] \
+                    + [(getattr(slots, k), getattr(slots, k).clone()) for k in ("live", "n_new", "status")]
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):             # the warm-up really runs a step: everything it advances is put back
+                    self._spec_step_body(img_ids_dev, out_ids, hid_buf, slots, draft)
+                torch.cuda.current_stream().wait_stream(s)
+                torch.cuda.synchronize()
+                for t, v in snap:
+                    t.copy_(v)
+                g = torch.cuda.CUDAGraph()
+                with ops.graph_capture(g):
+                    self._spec_step_body(img_ids_dev, out_ids, hid_buf, slots, draft)
+                for t, v in snap:
+                    t.copy_(v)
+                held = (key, g, slots.logits)
+                setattr(self, attr, held)
+            slots.logits = held[2]
+            held[1].replay()
+            return
         if adapters is None:
             adapters = any(a >= 0 for a in self._sel_host)
         if adapters and not self.max_adapters:
@@ -1320,7 +1464,7 @@ class LlamaForCausalLM:
             for t, v in snap.values():
                 t.copy_(v)
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with ops.graph_capture(g):
                 self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling, adapters)
             for t, v in snap.values():
                 t.copy_(v)

@@ -4,7 +4,9 @@ PyTorch is used only for device memory and the current HIP stream: every wrapper
 ``torch.cuda.current_stream().cuda_stream`` to libseedx_hip.so. There is no eager/CPU fallback — a missing
 library or a non-CUDA tensor raises.
 """
+import contextlib
 import ctypes as C
+import gc
 import math
 
 import os
@@ -34,6 +36,23 @@ def _p(t):
     if not t.is_cuda:
         raise RuntimeError("seedx_amd.ops: tensors must live on the GPU (no CPU fallback)")
     return C.c_void_p(t.data_ptr())
+
+
+@contextlib.contextmanager
+def graph_capture(g):
+    """``with torch.cuda.graph(g)`` with Python's cyclic garbage collector out of the way: torch no longer collects when a capture starts,
+    and a collection that fires INSIDE one may finalise a dead object that owns GPU resources (an earlier model's captured graph or
+    side stream, kept by a reference cycle) — destroying those is not allowed while a stream captures and aborts the process. Collect
+    first, keep the collector off until the capture has ended."""
+    gc.collect()
+    was = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(g):
+            yield
+    finally:
+        if was:
+            gc.enable()
 
 
 def _f32c(t):
@@ -783,6 +802,8 @@ def attention_f32(qkv, kcache, vcache, pos_dev, G, T, H, D, scale, dtype, tiled=
     head rows at the front of qkv's rows. Returns the planes of the context [G*T, H*D] (see split16).
     rope=(cos, sin) (T == 1, D == 128): qkv holds the UNROTATED q | k | v rows of the new token; the launch rotates q and k, appends k / v
     to the caches at pos[g] and attends — rope_kv_append_f32 + attention_f32 in one launch per layer.
+    rope with 2 <= T <= 8 (G*T <= 32) is the VERIFY form of speculative decoding: rows g*T + t at positions pos[g] + t, bit for bit what T
+    successive T = 1 calls with the same nsplit give (planes, k rows, v rows); pos[g] < 0 idles the whole slot. No FP8 cache.
     kv_scales=(kscale, vscale): the FP8 cache (uint8 codes + row scales, see rope_kv_append_f32) — the same bits as this call on a cache
     holding the dequantised values. kv_emulate (with rope): fp32 caches, the new token's rows quantised and dequantised on append."""
     assert qkv.dtype == torch.float32 and qkv.is_contiguous() and qkv.shape[0] == G * T and qkv.shape[1] >= H * D
@@ -800,13 +821,14 @@ def attention_f32(qkv, kcache, vcache, pos_dev, G, T, H, D, scale, dtype, tiled=
     a.q_row_stride, a.cache_seq_stride = qkv.stride(0), kcache.stride(0)
     a.G, a.T, a.H, a.D, a.Tmax, a.dtype, a.scale, a.causal = G, T, H, D, kcache.shape[2], code, float(scale), 1
     a.v16 = 0 if vcache.dtype in (torch.float32, torch.uint8) else 1
-    if nsplit > 1 and T == 1:         # decode step of few sequences: key splits (scratch: fp32 [G, H, nsplit, D + 2])
+    verify = rope is not None and T > 1   # speculative decoding: T = K + 1 rows per sequence, always split + combine (nsplit >= 1)
+    if (nsplit > 1 and T == 1) or verify:  # decode step of few sequences: key splits (scratch: fp32 [G*T, H, nsplit, D + 2])
         if scratch is None:
-            scratch = torch.empty((G, H, nsplit, D + 2), dtype=torch.float32, device=qkv.device)
-        assert scratch.dtype == torch.float32 and scratch.numel() >= G * H * nsplit * (D + 2)
+            scratch = torch.empty((G * T, H, nsplit, D + 2), dtype=torch.float32, device=qkv.device)
+        assert scratch.dtype == torch.float32 and scratch.numel() >= G * T * H * nsplit * (D + 2)
         a.nsplit, a.scratch = nsplit, _p(scratch)
     if rope is not None:
-        assert T == 1 and D == 128 and qkv.shape[1] == 3 * H * D
+        assert 1 <= T <= 8 and D == 128 and qkv.shape[1] == 3 * H * D
         cos, sin = rope
         a.rope_cos, a.rope_sin = _p(cos), _p(sin)
         a.k_new, a.v_new = qkv.data_ptr() + 4 * H * D, qkv.data_ptr() + 8 * H * D
@@ -1119,6 +1141,78 @@ def sample_next_slots(logits, vocab, img_ids_dev, cur, live, n_new, max_new, for
                         status, force_id, eos_id)
     s = _sample_args(sample, logits.shape[0], None, n_kept, p_chosen)
     check(_lib.load().sx_sample_next_slots(C.byref(a), C.byref(s), _stream()), "sx_sample_next_slots")
+
+
+def _i32s(who, *ts):
+    for t in ts:
+        assert t.dtype == torch.int32 and t.is_contiguous(), f"{who}: contiguous int32 tensors"
+        _p(t)                                   # (GPU tensors only: no CPU fallback)
+
+
+def scatter_rows_spec(src, step_dev, dst, tok_index=None):
+    """dst [G, rows, dim] fp32; dst[g, step[g] + t] = src[g*T + t] for the T = src.shape[0] // G rows of every slot (sx_scatter_rows_spec);
+    ``tok_index`` int32 [G*T] receives step[g] + t."""
+    G, rows, dim = dst.shape
+    T = src.shape[0] // G
+    assert src.shape == (G * T, dim) and src.is_contiguous() and dst.is_contiguous() and src.dtype == dst.dtype == torch.float32
+    assert step_dev.dtype == torch.int32 and step_dev.numel() == G
+    assert tok_index is None or (tok_index.dtype == torch.int32 and tok_index.is_contiguous() and tok_index.numel() == G * T)
+    check(_lib.load().sx_scatter_rows_spec(_p(src), _p(step_dev), _p(dst), _p(tok_index), G, T, dim, rows, _stream()), "sx_scatter_rows_spec")
+
+
+def spec_candidates(logits, vocab, img_ids_dev, rows_in, cand, token_index, sample=None):
+    """Candidate ids of the G*T rows of a verify step: sx_greedy_next_b, or sx_sample_next_b with ``sample`` (a sampling state whose
+    tensors hold one entry per ROW), over logits fp32 [G*T, ld]. Previous id = the row's input ``rows_in``; ``token_index`` int32 [G*T]
+    = step[g] + t; ``cand`` int32 [G*T] receives the ids. Nothing else is written (the image columns of the logits rows are zeroed in place)."""
+    lib = _lib.load()
+    R = logits.shape[0]
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1
+    _i32s("spec_candidates", img_ids_dev, rows_in, cand, token_index)
+    assert rows_in.numel() == R and cand.numel() == R and token_index.numel() == R
+    args = (_p(logits), logits.stride(0), vocab, _p(img_ids_dev), img_ids_dev.numel(), _p(rows_in), _p(cand), None, 0, _p(token_index), R)
+    if sample is None:
+        check(lib.sx_greedy_next_b(*args, _stream()), "sx_greedy_next_b")
+    else:
+        check(lib.sx_sample_next_b(*args, C.byref(_sample_args(sample, R, token_index)), _stream()), "sx_sample_next_b")
+
+
+def spec_accept(cand, rows_in, n_draft, cur, live, n_new, max_new, force_at, pos, ctx, step, out_ids, status, hist=None, force_id=-1,
+                eos_id=-1, img_ids_dev=None):
+    """The accept rule of speculative decoding on the device (sx_spec_accept; seedx_amd.spec.accept states it): per live slot the longest
+    run of candidates ``cand`` [G*T] the model itself would have produced given the drafts fed as ``rows_in`` [G*T] (``n_draft`` [G] of
+    them per slot), with greedy_next_slots' force_at, id log, counters, stop rule, parking and status; ``hist`` int32 [G, Tmax] receives
+    the emitted ids at the cache positions where they will be fed; ``img_ids_dev`` (the token step's list): its first id, <img>, ends a
+    run. Row 0 of every live slot in ``rows_in`` becomes the new current token. Parked slots are not touched."""
+    G = cur.numel()
+    T = cand.numel() // G
+    who = "spec_accept"
+    _i32s(who, cand, rows_in, n_draft, cur, live, n_new, max_new, force_at, pos, ctx, step, status)
+    _i32s(who, *[t for t in (out_ids, hist, img_ids_dev) if t is not None])
+    assert cand.numel() == G * T and rows_in.numel() == G * T and status.numel() == 4 * G
+    for t in (n_draft, live, n_new, max_new, force_at, pos, ctx, step):
+        assert t.numel() == G
+    assert (out_ids is None or out_ids.shape[0] == G) and (hist is None or (hist.dim() == 2 and hist.shape[0] == G))
+    a = _lib.SpecAcceptArgs(
+        cand=cand.data_ptr(), rows_in=rows_in.data_ptr(), n_draft=n_draft.data_ptr(), cur=cur.data_ptr(), live=live.data_ptr(),
+        n_new=n_new.data_ptr(), max_new=max_new.data_ptr(), force_at=force_at.data_ptr(), pos=pos.data_ptr(), ctx=ctx.data_ptr(),
+        step=step.data_ptr(), out_ids=out_ids.data_ptr() if out_ids is not None else None, status=status.data_ptr(),
+        hist=hist.data_ptr() if hist is not None else None, G=G, T=T, ld_out=out_ids.shape[1] if out_ids is not None else 0,
+        img_ids_dev=img_ids_dev.data_ptr() if img_ids_dev is not None else None,
+        Tmax=hist.shape[1] if hist is not None else 0, force_id=int(force_id), eos_id=int(eos_id))
+    check(_lib.load().sx_spec_accept(C.byref(a), _stream()), "sx_spec_accept")
+
+
+def spec_draft_ngram(hist, pos, cur, rows_out, n_draft, ngram=(3, 1)):
+    """The prompt-lookup drafter on the device (sx_spec_draft_ngram; seedx_amd.spec.propose_ngram states the rule): ``hist`` int32
+    [G, Tmax] holds the ids by cache position, ``pos`` [G] the position of ``cur`` [G]; writes the next verify step's row inputs
+    ``rows_out`` [G*T] (row 0 = cur, then the draft) and ``n_draft`` [G]. ``ngram`` = (longest, shortest) n-gram tried."""
+    G, Tmax = hist.shape
+    T = rows_out.numel() // G
+    _i32s("spec_draft_ngram", hist, pos, cur, rows_out, n_draft)
+    assert pos.numel() == G and cur.numel() == G and n_draft.numel() == G and rows_out.numel() == G * T
+    a = _lib.SpecDraftArgs(hist=hist.data_ptr(), pos=pos.data_ptr(), cur=cur.data_ptr(), rows_out=rows_out.data_ptr(),
+                           n_draft=n_draft.data_ptr(), G=G, T=T, Tmax=Tmax, ngram_max=int(ngram[0]), ngram_min=int(ngram[1]), reserved=0)
+    check(_lib.load().sx_spec_draft_ngram(C.byref(a), _stream()), "sx_spec_draft_ngram")
 
 
 def scatter_rows_step(src, step_dev, dst):

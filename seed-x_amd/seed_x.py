@@ -57,6 +57,8 @@ class ContinuousLVLM:
         self.chunk_forced_image_tokens = True
         self.prefix_cache = False        # generate_inflight: reuse the cache rows of a prompt prefix some slot already holds (opt-in)
         self.prefix_min_tokens = self.PREFIX_MIN_TOKENS   # shortest prefix worth a slot-to-slot copy, or worth waiting one round for
+        self.speculative = False         # generate_inflight: lossless speculative decoding on an LLM built with spec_tokens > 0 (opt-in)
+        self.spec_ngram = (3, 1)         # (longest, shortest) n-gram of its prompt-lookup drafter
         self._conv = {}                  # sequence → (token ids, row fingerprints, LLM cache epoch, adapter name) held by its KV cache
         self._sig_w = {}
         self.last_prefill_tokens = []
@@ -371,11 +373,20 @@ class ContinuousLVLM:
         admits does not change, so the step counts stay inflight.simulate's; ``last_prefill_tokens`` lists the suffix lengths and
         ``last_inflight_stats`` also counts prefix_hit_tokens, forked_tokens and fork_launches (inflight.simulate_prefix predicts them).
         Reused rows are the rows an earlier pass wrote: results agree with the uncached call like generate_batch's ``reuse_cache``
-        (identical ids, states within the prefill-shape rounding)."""
+        (identical ids, states within the prefill-shape rounding).
+        Speculative decoding is switched on the engine too: ``agent.speculative = True`` (off by default) with an LLM built with
+        ``spec_tokens=K`` runs the verify step (``llm.decode_step(..., spec=True)``) instead of the plain slot step: every live slot
+        feeds its current token and up to K ids drafted from its own history by prompt lookup (``agent.spec_ngram``) and keeps the
+        longest prefix the model itself would have produced (spec.py), so a step emits 1 .. K + 1 tokens per slot and the ids are those
+        of the call without the switch, for greedy and for sampled requests. The engine writes the prompt's ids (and a forced image
+        block's) to the LLM's id history at admission and still reads one [G, 4] status per step; ``last_inflight_stats`` gains
+        spec_steps and spec_emitted_tokens (inflight.simulate_spec predicts the step count from the per-step emitted counts)."""
         llm = self.llm
         if llm.comm.world > 1:
             raise NotImplementedError("generate_inflight is single-rank: tensor-parallel ranks are not supported")
         prefix_cache, prefix_min_tokens = bool(self.prefix_cache), int(self.prefix_min_tokens)
+        spec = bool(self.speculative) and llm.spec_tokens > 0
+        K = llm.spec_tokens if spec else 0            # extra rows a verify step may write past a slot's last token
         requests = list(requests)
         N = len(requests)
         assert N >= 1, "generate_inflight needs at least one request"
@@ -393,7 +404,7 @@ class ContinuousLVLM:
         named = any(nm is not None for nm in names)
         sampled = any(p is not None for p in params)
         assert all(b >= 1 for b in budget)
-        rows = max(budget) + 8
+        rows = max(budget) + 8 + K
         keep = self._inflight
         if keep is None or keep["key"] != (tuple(img_ids), eos, G, id(P)) or keep["out_ids"].shape[1] < rows:
             keep = self._inflight = dict(
@@ -426,7 +437,12 @@ class ContinuousLVLM:
         sched = SlotScheduler(G, N, max_admit)
         results = [None] * N
         n_new, cur = [0] * G, [0] * G                    # host mirrors of the live slots' state
+        plen = [0] * G                                   # speculative: prompt rows of the slot's request (cur sits at plen + n_new - 1)
         stats = dict(decode_steps=0, live_slot_steps=0, parked_slot_steps=0, admissions=0, prefill_passes=0, prefill_tokens=0)
+        if spec:
+            stats.update(spec_steps=0, spec_emitted_tokens=0)
+            llm.spec_ngram = (int(self.spec_ngram[0]), int(self.spec_ngram[1]))
+            self.last_spec_emitted = [[] for _ in range(N)]      # per request: tokens emitted by each verify step it was live in
         if prefix_cache:
             stats.update(prefix_hit_tokens=0, forked_tokens=0, fork_launches=0)
         self.last_prefill_tokens = []
@@ -463,9 +479,12 @@ class ContinuousLVLM:
             xs, last_ids = [], []
             for i, (g, r) in enumerate(adm):
                 ids, x = prompts.pop(r)[:2] if starts is not None else self._prompt_embeds(tokenizer, requests[r])
-                assert len(ids) + budget[r] <= llm.Tmax, "KV cache too small for prompt + max_new_tokens"
+                assert len(ids) + budget[r] + K <= llm.Tmax, "KV cache too small for prompt + max_new_tokens (+ spec_tokens draft rows)"
                 xs.append(x if starts is None else x[starts[i]:])
                 last_ids.append(ids[-1])
+                if spec:                                 # the drafter's history: the prompt's ids by cache position (image rows: placeholders)
+                    plen[g] = len(ids)
+                    llm.spec_write_history(g, 0, ids)
             llm._slot_write(P["pos"], slots, 0 if starts is None else list(starts))
             llm._slot_write(P["ctx"], slots, 1 if starts is None else [s + 1 for s in starts])
             adn = [names[r] for _, r in adm]
@@ -493,6 +512,9 @@ class ContinuousLVLM:
                 n_new[g] = 1
             out_ids[torch.tensor(slots, device=dev), 0] = torch.tensor([cur[g] for g in slots], dtype=torch.int32, device=dev)
             llm._slot_write(P["cur"], slots, [cur[g] for g in slots])
+            if spec:
+                for g in slots:
+                    llm.spec_write_history(g, plen[g], [cur[g]])
             llm._slot_write(P["step"], slots, 1)
             llm._slot_write(st.n_new, slots, 1)
             llm._slot_write(st.max_new, slots, [budget[r] for _, r in adm])
@@ -543,8 +565,12 @@ class ContinuousLVLM:
                 self._forced_image_chunk(hit, n_new, img_ids, hid, out_ids,                 # the other slots wait, as in generate_batch
                                          [names[sched.slot_req[g]] for g in hit] if named else None)
                 for g in hit:
+                    if spec:                             # the block's ids at the positions they were fed (</img> is the new current token)
+                        llm.spec_write_history(g, plen[g] + n_new[g] - 1, img_ids)
                     n_new[g] += nchunk
                     cur[g] = eoi_id
+                if spec:
+                    llm._slot_write(P["spec"]["n_draft"], hit, 0)
                 llm._slot_write(st.n_new, hit, [n_new[g] for g in hit])
                 llm._slot_write(P["step"], hit, [n_new[g] for g in hit])
                 llm._slot_write(P["cur"], hit, eoi_id)
@@ -556,13 +582,21 @@ class ContinuousLVLM:
                 live = sched.live_slots()
             if not live:
                 continue
-            llm.decode_step(img_ids_dev, out_ids, hid, use_graph=self.use_graph, slots=st)   # one token for every live slot
+            if spec:                                     # 1 .. K + 1 tokens for every live slot
+                llm.decode_step(img_ids_dev, out_ids, hid, use_graph=self.use_graph, slots=st, spec=True, draft="ngram")
+            else:
+                llm.decode_step(img_ids_dev, out_ids, hid, use_graph=self.use_graph, slots=st)   # one token for every live slot
             status = st.status.tolist()                                                      # the only read-back per step
             llm.comm.check()
             stats["decode_steps"] += 1
             stats["live_slot_steps"] += len(live)
             stats["parked_slot_steps"] += G - len(live)
             gone = []
+            if spec:
+                stats["spec_steps"] += 1
+                for g in live:
+                    stats["spec_emitted_tokens"] += status[g][2] - n_new[g]
+                    self.last_spec_emitted[sched.slot_req[g]].append(status[g][2] - n_new[g])
             for g in live:
                 cur[g], alive, n_new[g], fin_n = status[g]
                 if not alive:
