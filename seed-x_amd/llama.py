@@ -64,13 +64,7 @@ import torch
 from . import ops
 from .lora import split_peft_state_dict
 from .parallel import Comm, llama_tp_shard
-
-
-def glu_pack_rows(lin, gate):
-    """[I,K] linear rows and [I,K] gate rows → [2I,K] in 32-row groups [16 linear | 16 gate] (sx_gemm glu contract)."""
-    I, K = lin.shape
-    assert I % 16 == 0
-    return torch.cat([lin.view(I // 16, 16, K), gate.view(I // 16, 16, K)], dim=1).reshape(2 * I, K).contiguous()
+from .projection import Projection, glu_pack_rows  # noqa: F401  (glu_pack_rows: imported from here by tests and tools)
 
 
 def merge_peft_lora(sd, lora_alpha=32, adapter="default"):
@@ -268,10 +262,7 @@ class LlamaForCausalLM:
             if not self.precise:
                 raise ValueError(f"LlamaForCausalLM: weight_format={weight_format!r} needs the precise mode (the plain 16-bit flow folds the RMSNorm "
                                  "gamma into its decode tiles: those are not the checkpoint's matrices and would be quantised a second, different time)")
-            if not self._skinny_shapes_ok():
-                raise ValueError(f"LlamaForCausalLM: weight_format={weight_format!r} needs the tiled precise decode path: hidden / per-rank head and FFN "
-                                 f"widths that are multiples of 64 and >= 256, output widths that are multiples of 32 (H {self.H}, "
-                                 f"heads x dim {self.H_l}, FFN {self.I_l}, vocab rows {self.V_l}): FP8 / MXFP4 tiles exist for the MFMA skinny GEMM only")
+            self._need_tiled_precise(f"weight_format={weight_format!r}", "FP8 / MXFP4 tiles exist for the MFMA skinny GEMM only")
         # residency of the quantised projections (module docstring; opt-in: ``weight_residency="tiles"`` or SX_LLM_WEIGHT_RESIDENCY=tiles):
         # None keeps the row-major 16-bit copy of the dequantised values for prefill, "tiles" holds the decode tiles alone
         if weight_residency is None:
@@ -325,10 +316,7 @@ class LlamaForCausalLM:
             if not self.precise:
                 raise ValueError("LlamaForCausalLM: max_adapters needs the precise mode (the adapter kernels read the two-plane operands; the plain "
                                  "16-bit flow has no adapter step)")
-            if not self._skinny_shapes_ok():
-                raise ValueError(f"LlamaForCausalLM: max_adapters needs the tiled precise decode path: hidden / head / FFN widths that are multiples "
-                                 f"of 64 and >= 256, output widths that are multiples of 32 (H {self.H}, FFN {self.I}): the pre-activation addend "
-                                 "exists on the MFMA skinny GEMM only")
+            self._need_tiled_precise("max_adapters", "the pre-activation addend exists on the MFMA skinny GEMM only")
             if self.lora_rank < 8 or self.lora_rank % 8 or 3 * self.lora_rank > 512:
                 raise ValueError(f"LlamaForCausalLM: lora_rank={lora_rank} must be a multiple of 8 in 8 .. 168")
         # lossless speculative decoding (spec.py; opt-in: ``spec_tokens=K`` drafted tokens per sequence and step): the verify step
@@ -343,10 +331,7 @@ class LlamaForCausalLM:
                 raise ValueError(f"LlamaForCausalLM: spec_tokens={spec_tokens} must be 0 (off) or 1 .. 7 (the verify attention holds 8 rows per sequence)")
             if not self.precise:
                 raise ValueError("LlamaForCausalLM: spec_tokens needs the precise mode (the verify form exists for the fp32 decode attention only)")
-            if not self._skinny_shapes_ok():
-                raise ValueError(f"LlamaForCausalLM: spec_tokens needs the tiled precise decode path: hidden / head / FFN widths that are multiples "
-                                 f"of 64 and >= 256, output widths that are multiples of 32 (H {self.H}, heads x dim {self.H_l}, FFN {self.I_l}, "
-                                 f"vocab rows {self.V_l}): the K + 1 rows per sequence ride on the MFMA skinny GEMM")
+            self._need_tiled_precise("spec_tokens", "the K + 1 rows per sequence ride on the MFMA skinny GEMM")
             if self.hd != 128:
                 raise ValueError(f"LlamaForCausalLM: spec_tokens needs head_dim 128, not {self.hd} (the verify attention is the fused-RoPE form)")
             if tp > 1:
@@ -394,6 +379,25 @@ class LlamaForCausalLM:
     def _skinny_shapes_ok(self):
         """precise_tiled and decode_tiled of _pack, from the dims alone (the attention output travels as operand tiles too)."""
         return self._precise_tiled_ok() and self.H_l % 32 == 0
+
+    def _need_tiled_precise(self, what, why):
+        """The one refusal of a feature that exists on the MFMA skinny GEMM only (weight_format, max_adapters, spec_tokens)."""
+        if not self._skinny_shapes_ok():
+            raise ValueError(f"LlamaForCausalLM: {what} needs the tiled precise decode path: hidden / per-rank head and FFN widths that are "
+                             f"multiples of 64 and >= 256, output widths that are multiples of 32 (H {self.H}, heads x dim {self.H_l}, "
+                             f"FFN {self.I_l}, vocab rows {self.V_l}): {why}")
+
+    def _proj_shapes(self):
+        """(N, K) of this rank's four projections."""
+        return {"wqkv": (3 * self.H_l, self.H), "wo": (self.H, self.H_l), "wgu": (2 * self.I_l, self.H), "wd": (self.H, self.I_l)}
+
+    def _has_tiles(self, N, K):
+        """A weight of this shape gets decode tiles: the batch runs the MFMA skinny GEMM (G >= 5; precise mode: always) and the shape fits it."""
+        return (self.G >= 5 or self.precise) and ops._mfma_shape(N, K)
+
+    def _decode_tiled(self):
+        """Every decode GEMV has its decode tiles, so its 16-bit inputs travel as operand tiles too (_pack's P["decode_tiled"])."""
+        return all(self._has_tiles(N, K) for N, K in self._proj_shapes().values()) and self.H_l % 32 == 0
 
     def _bal20(self, n_rows):
         """o / down projections run from 20-row decode tiles where that gives 256 equal workgroups (N = 5120): the one rule for the
@@ -570,17 +574,14 @@ class LlamaForCausalLM:
         if v1 > v0:
             lm[:v1 - v0] = sd["lm_head.weight"][v0:v1].detach().to(dev, dt)
         P["lm_head"] = lm
-
-        def tiles(w):
-            """Second copy of a weight in the decode-tile layout for the lock-step batched decode (G >= 5 rows take the MFMA
-            skinny GEMM, whose wave-wide loads then cover whole contiguous kilobytes: 2.85 → 4.2 TB/s per layer in situ,
-            tools/bench_gemv_layout.py). Costs the weights' size again (25.7 GB of 288 GB at 13B); prefill keeps row-major."""
-            N, K = w.shape
-            # (precise mode: every lock-step batch size runs the MFMA skinny GEMM — the lo plane is its second operand block — so the
-            # tiles exist from G = 1: 15.1 → 8 ms per token step at G = 4, BASELINE config 5)
-            return ops.pack_decode_tiles(w) if ((self.G >= 5 or self.precise) and N % 32 == 0 and K % 64 == 0 and K >= 256) else None
-        P["lm_head_t"] = tiles(lm)
-        # RMSNorm folded into the batched decode step (single rank, G >= 5; sx_gemv_args.x16_out / row_ssq_*): the decode-tile copies
+        # Second copy of a weight in the decode-tile layout for the lock-step batched decode (G >= 5 rows take the MFMA skinny GEMM, whose
+        # wave-wide loads then cover whole contiguous kilobytes: 2.85 → 4.2 TB/s per layer in situ, tools/bench_gemv_layout.py). Costs
+        # the weights' size again (25.7 GB of 288 GB at 13B); prefill keeps row-major. (precise mode: every lock-step batch size runs
+        # the MFMA skinny GEMM, so the tiles exist from G = 1: 15.1 → 8 ms per token step at G = 4, BASELINE config 5)
+        P["lm_head_t"] = ops.pack_decode_tiles(lm) if self._has_tiles(*lm.shape) else None
+        P["decode_tiled"] = self._decode_tiled()        # every decode GEMV has its tiles → its 16-bit inputs travel as operand tiles too
+        P["precise_tiled"] = self._precise_tiled_ok()   # precise step on the skinny GEMM (operand tiles, two planes): every shape fits its MFMA path
+        # RMSNorm folded into the batched decode step (single rank, G >= 5; sx_gemv_args.x16_out / row_ssq_*): the decode tiles
         # of the projections that FOLLOW a norm carry that norm's gamma (W' = W · diag(gamma), product rounded once to 16 bits) —
         # wgu of every layer (post_attention_layernorm) and wqkv of layers >= 1 (input_layernorm; layer 0's input comes from the
         # embedding, not from a GEMV). Prefill keeps the row-major, unfolded weights and the norm kernel.
@@ -589,116 +590,68 @@ class LlamaForCausalLM:
         # (asked from the library, not re-derived here: sx_gemv's own workgroup count for an N = H launch in that weight layout)
         from . import _lib
         parts = _lib.load().sx_gemv_ssq_parts(self.H, 0, 2 if self._bal20(self.H) else 1)
-        fold = self.G >= 5 and tp == 1 and parts % 64 == 0 and os.environ.get("SX_RMS_FOLD", "1") != "0" \
-            and not self.precise      # (SX_RMS_FOLD=0: A/B switch, tools/; the precise mode norms in fp32 with its own kernel)
-        fp8 = self.weight_format is not None         # a quantised weight format: FP8 row codes or MXFP4 block codes
-        fp4 = self.weight_format == "mxfp4"
-        fkey = "_f4" if fp4 else "_f8"
-        if fp8:
+        fold_ok = tp == 1 and parts % 64 == 0 and self.H % 32 == 0 and P["decode_tiled"] and os.environ.get("SX_RMS_FOLD", "1") != "0"
+        P["rms_fold"] = fold_ok and self.G >= 5 and not self.precise       # (the precise mode norms in fp32 and folds in its own way:)
+        # RMSNorm fold of the precise decode step (the plain fold's conditions): the residual GEMV writes the two planes of
+        # x * gamma_next and the rows' sums of squares, the projection behind the norm scales by rstd. gamma sits on the ACTIVATION
+        # here: the checkpoint's weights stay exact.
+        P["rms_fold_precise"] = fold_ok and self.precise and P["precise_tiled"] and self.I_l % 32 == 0
+        # tiled_step: the token step reads decode tiles (``tl`` of _layers_single / _layers_single_precise). Each projection is held in
+        # exactly ONE tile layout: N = 5120 output rows are 320 16-row groups on 256 CUs; as 256 groups of 20 rows every CU streams the
+        # same bytes (sx_gemv w_layout 2) — o and down at 13B dims where the step is tiled, 16-row tiles elsewhere, none where unread
+        fmt, tiled_step = self.weight_format, P["decode_tiled"] and (P["precise_tiled"] or not self.precise)
+        if fmt is not None:
             from . import quant
             qerr = {n.split(".")[1]: torch.zeros(2, dtype=torch.float64, device=dev) for n in quant.LLAMA_PROJECTIONS}   # [|W - Wq|^2, |W|^2]
         for i in range(self.L):
             p = f"model.layers.{i}."
-            if fp8:
+            src, codes, scales = sd, None, None
+            if fmt is not None:
                 # the FULL matrices are quantised (after the LoRA merge, before the tensor-parallel slicing): every rank holds slices of
                 # one quantised model. From here on "the weights" are the dequantised values; codes and scales are sliced the same way
-                ql = quant.quantize_llama_layer(sd, p, dt, dev, weight_format=self.weight_format)
+                ql = quant.quantize_llama_layer(sd, p, dt, dev, weight_format=fmt)
                 for k, (_, _, wq) in ql.items():
                     w0 = sd[k].detach().to(dev, dt).double()
                     qerr[k[len(p):].split(".")[1]] += torch.stack([(w0 - wq.double()).square().sum(), w0.square().sum()])
-                if fp4:     # packed codes and block scales: o / down are sliced along K in both
-                    sh8, sc8 = quant.llama_tp_shard_mxfp4({k: v[0] for k, v in ql.items()}, {k: v[1] for k, v in ql.items()}, p, r, tp,
-                                                          self.nh, self.hd)
+                cq, sq, src = ({k: v[j] for k, v in ql.items()} for j in range(3))
+                if fmt == "mxfp4":     # packed codes and block scales: o / down are sliced along K in both
+                    codes, scales = quant.llama_tp_shard_mxfp4(cq, sq, p, r, tp, self.nh, self.hd)
                 else:
-                    sh8 = llama_tp_shard({k: v[0] for k, v in ql.items()}, p, r, tp, self.nh, self.hd)
-                    sc8 = quant.llama_tp_shard_scales({k: v[1] for k, v in ql.items()}, p, r, tp, self.nh, self.hd)
-                lsd = {k: v[2] for k, v in ql.items()}
-                del ql
-            sh = llama_tp_shard(lsd if fp8 else sd, p, r, tp, self.nh, self.hd)
-            qkv = torch.cat([sh["q"].detach(), sh["k"].detach(), sh["v"].detach()], dim=0)
-            gu = glu_pack_rows(sh["up"].detach().to(dev, dt), sh["gate"].detach().to(dev, dt))
-            P["layers"].append(dict(
-                ln1=f32(sd[p + "input_layernorm.weight"]), ln2=f32(sd[p + "post_attention_layernorm.weight"]),
-                wqkv=w16(qkv), wo=w16(sh["o"]), wgu=gu, wd=w16(sh["down"])))
-            lw = P["layers"][-1]
-            if fp8:
-                # decode tiles = the codes (one layout per projection: 20-row tiles where o / down use them, else 16-row) + row scales;
-                # GLU row packing moves the codes and the scales alike. No 16-bit tile copy at all.
-                c8 = {"wqkv": torch.cat([sh8["q"], sh8["k"], sh8["v"]], dim=0), "wo": sh8["o"], "wd": sh8["down"],
-                      "wgu": glu_pack_rows(sh8["up"], sh8["gate"])}
-                if fp4:     # block scales [rows, K/32]: the GLU packing moves whole rows of them
-                    s8 = {"wqkv": torch.cat([sc8["q"], sc8["k"], sc8["v"]], dim=0), "wo": sc8["o"], "wd": sc8["down"],
-                          "wgu": glu_pack_rows(sc8["up"], sc8["gate"])}
-                else:
-                    s8 = {"wqkv": torch.cat([sc8["q"], sc8["k"], sc8["v"]]), "wo": sc8["o"], "wd": sc8["down"],
-                          "wgu": glu_pack_rows(sc8["up"][:, None], sc8["gate"][:, None]).reshape(-1)}
-                for k in ("wqkv", "wo", "wgu", "wd"):
-                    lw[k + "_t"] = lw[k + "_t20"] = None
-                    t20 = k in ("wo", "wd") and self._bal20(c8[k].shape[0])
-                    if fp4:
-                        lw[k + "_f4"] = ((ops.pack_decode_tiles20_fp4 if t20 else ops.pack_decode_tiles_fp4)(c8[k].contiguous()),
-                                         ops.pack_block_scales_fp4(s8[k].contiguous(), rows=20 if t20 else 16))
-                        continue
-                    lw[k + "_f8"] = ((ops.pack_decode_tiles20_fp8 if t20 else ops.pack_decode_tiles_fp8)(c8[k].contiguous()),
-                                     s8[k].contiguous().clone())
-                del sh8, sc8, c8, s8, lsd
-                if self.weight_residency == "tiles":
-                    # the tiles are the only copy: this layer's row-major matrices existed while the tiles were built and go now (peak
-                    # load-time memory is one layer); what stays is the shape / dtype handle ops.gemv asks for
-                    del sh, qkv, gu
-                    for k in ("wqkv", "wo", "wgu", "wd"):
-                        lw[k] = ops.WeightShape(lw[k].shape, dt)
-                continue
-            for k in ("wqkv", "wo", "wgu", "wd"):
-                lw[k + "_t"] = tiles(lw[k])
-            # N = 5120 output rows are 320 16-row groups on 256 CUs; as 256 groups of 20 rows every CU streams the same bytes
-            # (sx_gemv w_layout 2) — the o and down projections of the 13B geometry
-            for k in ("wo", "wd"):
-                lw[k + "_t20"] = None
-                if lw[k + "_t"] is not None and self._bal20(lw[k].shape[0]):
-                    lw[k + "_t20"] = ops.pack_decode_tiles20(lw[k])
-            if fold and lw["wgu_t"] is not None and lw["wqkv_t"] is not None:
-                g2 = lw["ln2"][None, :]
-                lw["wgu_t"] = tiles(glu_pack_rows((sh["up"].detach().to(dev, torch.float32) * g2).to(dt),
-                                                  (sh["gate"].detach().to(dev, torch.float32) * g2).to(dt)))
-                if i > 0:
-                    lw["wqkv_t"] = tiles((qkv.to(dev, torch.float32) * lw["ln1"][None, :]).to(dt).contiguous())
-        # every decode GEMV has the decode-tile weight copy → its 16-bit inputs travel as operand tiles too (_layers_single)
-        P["decode_tiled"] = all((lw.get(k + fkey) if fp8 else lw[k + "_t"]) is not None for lw in P["layers"] for k in ("wqkv", "wo", "wgu", "wd")) \
-            and (self.nh_l * self.hd) % 32 == 0
-        if fp8:
-            held = sum(t.numel() * t.element_size() for lw in P["layers"] for k in ("wqkv", "wo", "wgu", "wd") for t in lw[k + fkey]) \
-                + P["lm_head_t"].numel() * P["lm_head_t"].element_size()
-            assert held == fp["decode_tiles"], (held, fp["decode_tiles"])      # memory_footprint() prices what is held, nothing else
+                    codes, scales = llama_tp_shard(cq, p, r, tp, self.nh, self.hd), quant.llama_tp_shard_scales(sq, p, r, tp, self.nh, self.hd)
+                del ql, cq, sq
+            sh = llama_tp_shard(src, p, r, tp, self.nh, self.hd)
+            lw = dict(ln1=f32(sd[p + "input_layernorm.weight"]), ln2=f32(sd[p + "post_attention_layernorm.weight"]))
+            for k, names in (("wqkv", ("q", "k", "v")), ("wo", ("o",)), ("wgu", ("up", "gate")), ("wd", ("down",))):
+                N, K = self._proj_shapes()[k]
+                pick = lambda d: None if d is None else [d[n] for n in names]
+                gamma = {"wgu": lw["ln2"], "wqkv": lw["ln1"] if i > 0 else None}.get(k) if P["rms_fold"] else None
+                lw[k] = Projection.build(pick(sh), dt, dev, glu=k == "wgu", format=fmt, codes=pick(codes), scales=pick(scales),
+                                         tile_rows=20 if tiled_step and k in ("wo", "wd") and self._bal20(N) else 16,
+                                         tiled=self._has_tiles(N, K) and (P["precise_tiled"] or not self.precise), tile_gamma=gamma,
+                                         keep_matrix=self.weight_residency != "tiles")
+            P["layers"].append(lw)
+            del sh, src, codes, scales
+        projections = [lw[k] for lw in P["layers"] for k in ("wqkv", "wo", "wgu", "wd")]
+        held = sum(pj.nbytes_tiles for pj in projections) + (0 if P["lm_head_t"] is None else 2 * P["lm_head_t"].numel())
+        # memory_footprint() prices what is held, nothing else, in every format (where the step is not tiled it prices the tiled one)
+        assert held == fp["decode_tiles"] or not tiled_step, (held, fp["decode_tiles"])
+        if fmt is not None:
             err = {k: math.sqrt(float(v[0] / v[1])) if float(v[1]) > 0 else 0.0 for k, v in qerr.items()}
-            tiles16 = sum(2 * lw[k].numel() for lw in P["layers"] for k in ("wqkv", "wo", "wgu", "wd")) + 2 * P["lm_head_t"].numel()
-            self.weight_quant_report = {"weight_format": self.weight_format, "decode_tile_bytes": held, "decode_tile_bytes_16bit": tiles16,
+            tiles16 = sum(2 * pj.shape.numel() for pj in projections) + 2 * P["lm_head_t"].numel()
+            self.weight_quant_report = {"weight_format": fmt, "decode_tile_bytes": held, "decode_tile_bytes_16bit": tiles16,
                                         "rel_frobenius_error": err, "weight_residency": self.weight_residency}
             if self.weight_residency == "tiles":
                 # ONE buffer for all four projections of every layer. Prefill runs on one stream: the GEMM on projection k finishes
                 # before the dequantisation of projection k + 1 overwrites the buffer (_layers_multi). The decode step never reads it.
                 P["w_scratch"] = torch.empty(self._scratch_elems(), dtype=dt, device=dev)
-                rowmajor = P["embed"].numel() * 2 + P["lm_head"].numel() * 2 + P["w_scratch"].numel() * 2 \
-                    + sum(lw[k].numel() * 2 for lw in P["layers"] for k in ("wqkv", "wo", "wgu", "wd") if torch.is_tensor(lw[k]))
+                rowmajor = P["embed"].numel() * 2 + P["lm_head"].numel() * 2 + P["w_scratch"].numel() * 2 + sum(pj.nbytes_rowmajor for pj in projections)
                 assert rowmajor == fp["weights"] and P["w_scratch"].numel() * 2 == fp["prefill_scratch"], (rowmajor, fp)
             logging.getLogger("seedx_amd").info(
                 "LlamaForCausalLM._pack: %s weight tiles, %.2f GB of decode tiles (16-bit: %.2f GB); relative Frobenius error of the "
-                "quantisation against the %s checkpoint: %s", "MXFP4" if fp4 else "FP8 e4m3", held / 1e9, self.weight_quant_report["decode_tile_bytes_16bit"] / 1e9,
+                "quantisation against the %s checkpoint: %s", "MXFP4" if fmt == "mxfp4" else "FP8 e4m3", held / 1e9, tiles16 / 1e9,
                 str(dt).replace("torch.", ""), ", ".join(f"{k} {v:.4f}" for k, v in err.items()))
-        P["rms_fold"] = fold and P["decode_tiled"] and self.H % 32 == 0
-        assert P["rms_fold"] or not fold or not any(lw["wgu_t"] is not None for lw in P["layers"]), \
-            "folded decode tiles without the tiled decode path"
         # split-K scratch of the skinny GEMM: counters + 8 partial [16, H] blocks (include/seedx_hip.h: sx_gemv_args.workspace)
         P["gemv_ws"] = torch.zeros(self._gemv_ws_bytes(self.G), dtype=torch.uint8, device=dev) if P["decode_tiled"] else None
-        # precise decode step on the skinny GEMM (operand tiles, two planes): every projection shape must satisfy its MFMA path
-        P["precise_tiled"] = self._precise_tiled_ok()
-        # RMSNorm fold of the precise decode step (single rank, decode tiles, a multiple of 64 workgroups in the o / down launches —
-        # the plain fold's conditions): the residual GEMV writes the two planes of x * gamma_next and the rows' sums of squares, the
-        # projection behind the norm scales by rstd. gamma sits on the ACTIVATION here: the checkpoint's weights stay exact.
-        P["rms_fold_precise"] = self.precise and P["precise_tiled"] and P["decode_tiled"] and tp == 1 and parts % 64 == 0 \
-            and self.H % 32 == 0 and self.I_l % 32 == 0 and os.environ.get("SX_RMS_FOLD", "1") != "0"
-        if fp8 and not (P["precise_tiled"] and P["decode_tiled"]):
-            raise ValueError(f"LlamaForCausalLM: weight_format={self.weight_format!r} needs the tiled precise decode path (FP8 / MXFP4 tiles exist for the MFMA skinny GEMM only)")
         inv = 1.0 / (self.config.rope_base ** (torch.arange(0, self.hd, 2).float() / self.hd))
         fr = torch.outer(torch.arange(self.Tmax).float(), inv)           # [Tmax, hd/2] fp32 (:97-113)
         P["cos"], P["sin"] = fr.cos().to(dev).contiguous(), fr.sin().to(dev).contiguous()
@@ -754,8 +707,6 @@ class LlamaForCausalLM:
                  "attn_part": torch.empty((R, self.nh_l, self.decode_nsplit_f32, self.hd + 2), dtype=torch.float32, device=dev)}
             held = sum(t.numel() * t.element_size() for t in S.values())
             assert held == fp["spec_decode"], (held, fp["spec_decode"])           # memory_footprint() prices what is held
-            if not (P["precise_tiled"] and P["decode_tiled"]):
-                raise ValueError("LlamaForCausalLM: spec_tokens needs the tiled precise decode path")
             S["sample"] = None                             # SampleState of R rows, made with the first sampled slot state
             P["spec"] = S
         self._P = P
@@ -878,14 +829,10 @@ class LlamaForCausalLM:
         comm, lead = self.comm, self.comm.rank == 0
         pr = self.precise
         n = len(seqs)
-        if self.weight_residency == "tiles":
-            # the tiles are the only copy of a projection: rebuild it (exactly: sx_dequant_tiles) into the shared scratch buffer right in
-            # front of its GEMM. Everything here runs on ONE stream, so the GEMM on projection k has finished before the dequantisation
-            # of projection k + 1 overwrites the buffer; nothing else reads it (the decode step runs from the tiles).
-            fkey = "_f4" if self.weight_format == "mxfp4" else "_f8"
-            wmat = lambda lw, k: ops.dequant_tiles(dtype=dt, out=P["w_scratch"], **{"w_fp4" if fkey == "_f4" else "w_fp8": lw[k + fkey]})
-        else:
-            wmat = lambda lw, k: lw[k]
+        # tiles residency: the tiles are the only copy of a projection: rebuild it (exactly: sx_dequant_tiles) into the shared scratch buffer
+        # right in front of its GEMM. Everything here runs on ONE stream, so the GEMM on projection k has finished before the
+        # dequantisation of projection k + 1 overwrites the buffer; nothing else reads it (the decode step runs from the tiles).
+        wmat = lambda lw, k: lw[k].matrix(P.get("w_scratch"))
         pos_all = P["pos"].tolist()                                              # one host read per pass
         pos0 = [pos_all[g] for g in seqs]
         for T, p0 in zip(Ts, pos0):
@@ -949,7 +896,7 @@ class LlamaForCausalLM:
                                              **delta(g_, li, "d")))
                 continue
             h = ops.rmsnorm(x, lw["ln1"], eps, dt)
-            qkv = ops.gemm(h, lw["wqkv"])                                             # [M, 3H]
+            qkv = ops.gemm(h, lw["wqkv"].w)                                           # [M, 3H]
             if uniform:
                 T, Tk = Ts[0], pos0[0] + Ts[0]
                 ops.rope_kv_append_b(qkv, kc_l[g0:g0 + n], vc_l[g0:g0 + n], P["cos"], P["sin"], P["pos"][g0:g0 + n], n, T,
@@ -968,10 +915,10 @@ class LlamaForCausalLM:
                     k4 = kc_l[g][:, :Tk].permute(1, 0, 2).unsqueeze(0)                # [1, Tk, nh, hd] view of the cache
                     v4 = vc_l[g][:, :Tk].permute(1, 0, 2).unsqueeze(0)
                     ops.attention(q4, k4, v4, scale, causal=True, out=att[offs[i]:offs[i + 1]].view(1, T, H))
-            x = comm.all_reduce(ops.gemm(att, lw["wo"], residual=x if lead else None, out_dtype=torch.float32))
+            x = comm.all_reduce(ops.gemm(att, lw["wo"].w, residual=x if lead else None, out_dtype=torch.float32))
             h = ops.rmsnorm(x, lw["ln2"], eps, dt)
-            g_ = ops.gemm(h, lw["wgu"], act="silu", glu=True)                         # silu(gate) * up, [M, I/tp]
-            x = comm.all_reduce(ops.gemm(g_, lw["wd"], residual=x if lead else None, out_dtype=torch.float32))
+            g_ = ops.gemm(h, lw["wgu"].w, act="silu", glu=True)                       # silu(gate) * up, [M, I/tp]
+            x = comm.all_reduce(ops.gemm(g_, lw["wd"].w, residual=x if lead else None, out_dtype=torch.float32))
         if uniform:
             ops.add_i32(P["pos"][g0:g0 + n], Ts[0])
             ops.add_i32(P["ctx"][g0:g0 + n], Ts[0])
@@ -1002,10 +949,10 @@ class LlamaForCausalLM:
         nl = len(P["layers"])
         for li, lw in enumerate(P["layers"]):
             if fold and li > 0:
-                qkv = ops.gemv(x16, lw["wqkv"], w_tiles=lw["wqkv_t"], ssq_in=(ssq, self.H, eps))
+                qkv = lw["wqkv"].gemv(x16, ssq_in=(ssq, self.H, eps))
             else:
                 h = ops.rmsnorm(x, lw["ln1"], eps, dt, tiled=tl)
-                qkv = ops.gemv(h, lw["wqkv"], w_tiles=lw["wqkv_t"])                   # [G, 3H]
+                qkv = lw["wqkv"].gemv(h)                                             # [G, 3H]
             if self.fused_decode_attention and hd % 16 == 0:
                 # RoPE + KV append + split-KV attention + combine as one launch (bit-identical to the three-kernel form below)
                 att = ops.attn_decode_fused(qkv, P["kc"][li], P["vc"][li], P["pos"], P["cos"], P["sin"], scale, nh, hd,
@@ -1015,22 +962,17 @@ class LlamaForCausalLM:
                 q = qkv[:, :H].unflatten(1, (nh, hd))                                # strided view into qkv: no copy
                 att = ops.attn_decode_b(q, P["kc"][li], P["vc"][li], P["ctx"], scale, nsplit=self.decode_nsplit, out_tiled=tl)
             if fold:
-                x, x16, ssq = ops.gemv(att, lw["wo"], residual=x, out_dtype=torch.float32, w_tiles=lw["wo_t"], workspace=ws,
-                                       emit_norm=True, w_tiles20=lw["wo_t20"])
-                g = ops.gemv(x16, lw["wgu"], act="silu", glu=True, w_tiles=lw["wgu_t"], y_tiled=True, ssq_in=(ssq, self.H, eps))
+                x, x16, ssq = lw["wo"].gemv(att, ws, residual=x, out_dtype=torch.float32, emit_norm=True)
+                g = lw["wgu"].gemv(x16, act="silu", glu=True, y_tiled=True, ssq_in=(ssq, self.H, eps))
                 if li + 1 < nl:
-                    x, x16, ssq = ops.gemv(g, lw["wd"], residual=x, out_dtype=torch.float32, w_tiles=lw["wd_t"], workspace=ws,
-                                           emit_norm=True, w_tiles20=lw["wd_t20"])
+                    x, x16, ssq = lw["wd"].gemv(g, ws, residual=x, out_dtype=torch.float32, emit_norm=True)
                 else:                        # the final norm needs fp32 states (hidden-state output): its own launch
-                    x = ops.gemv(g, lw["wd"], residual=x, out_dtype=torch.float32, w_tiles=lw["wd_t"], workspace=ws,
-                                 w_tiles20=lw["wd_t20"])
+                    x = lw["wd"].gemv(g, ws, residual=x, out_dtype=torch.float32)
                 continue
-            x = comm.all_reduce(ops.gemv(att, lw["wo"], residual=x if lead else None, out_dtype=torch.float32,
-                                         w_tiles=lw["wo_t"], workspace=ws, w_tiles20=lw["wo_t20"] if tl else None))
+            x = comm.all_reduce(lw["wo"].gemv(att, ws, residual=x if lead else None, out_dtype=torch.float32))
             h = ops.rmsnorm(x, lw["ln2"], eps, dt, tiled=tl)
-            g = ops.gemv(h, lw["wgu"], act="silu", glu=True, w_tiles=lw["wgu_t"], y_tiled=tl)
-            x = comm.all_reduce(ops.gemv(g, lw["wd"], residual=x if lead else None, out_dtype=torch.float32,
-                                         w_tiles=lw["wd_t"], workspace=ws, w_tiles20=lw["wd_t20"] if tl else None))
+            g = lw["wgu"].gemv(h, act="silu", glu=True, y_tiled=tl)
+            x = comm.all_reduce(lw["wd"].gemv(g, ws, residual=x if lead else None, out_dtype=torch.float32))
         if slots is None:
             ops.add_i32(P["pos"], 1)
             ops.add_i32(P["ctx"], 1)
@@ -1059,7 +1001,6 @@ class LlamaForCausalLM:
         part = P["attn_f32_part"]
         if spec:
             ws, part = P["spec"]["gemv_ws"], P["spec"]["attn_part"]
-        dtl = tl and P["decode_tiled"]                       # decode-tile weight copies (built for every G in precise mode)
 
         def delta(xp, li, kk):
             """the adapter step's addend of projection kk for the operand xp (nothing without adapters)"""
@@ -1075,9 +1016,8 @@ class LlamaForCausalLM:
 
         def lin(xp, lw, k, **kw):
             if tl:
-                return ops.gemv(xp, lw[k], w_tiles=lw[k + "_t"] if dtl else None, workspace=ws if dtl else None,
-                                w_tiles20=lw.get(k + "_t20") if dtl else None, w_fp8=lw.get(k + "_f8"), w_fp4=lw.get(k + "_f4"), out_dtype=f32, **kw)
-            return ops.gemm(xp, lw[k], a_planes=2, out_dtype=f32, **kw)
+                return lw[k].gemv(xp, ws, out_dtype=f32, **kw)      # (tl: every projection has its decode tiles, built for every G)
+            return ops.gemm(xp, lw[k].w, a_planes=2, out_dtype=f32, **kw)
         fold = P["rms_fold_precise"] and lo is None
         fuse_rope = hd == 128 and (spec or os.environ.get("SX_LLM_FUSE_ROPE", "1") != "0")   # (the verify form IS the fused form)
         x16 = ssq = None
@@ -1099,8 +1039,7 @@ class LlamaForCausalLM:
             if fold:
                 # residual GEMV: fp32 x, the planes of x * gamma of the NEXT norm, the rows' sums of squares; GLU epilogue: planes directly
                 x, x16, ssq = lin(att, lw, "wo", residual=x, emit_norm=True, planes_out=True, norm_gamma=lw["ln2"])
-                g = ops.gemv(x16, lw["wgu"], act="silu", glu=True, w_tiles=lw["wgu_t"], w_fp8=lw.get("wgu_f8"), w_fp4=lw.get("wgu_f4"), y_tiled=True, planes_out=True,
-                             ssq_in=(ssq, self.H, eps))
+                g = lw["wgu"].gemv(x16, act="silu", glu=True, y_tiled=True, planes_out=True, ssq_in=(ssq, self.H, eps))
                 if li + 1 < nl:
                     x, x16, ssq = lin(g, lw, "wd", residual=x, emit_norm=True, planes_out=True, norm_gamma=P["layers"][li + 1]["ln1"])
                 else:                        # the final norm wants fp32 states: its own launch (rmsnorm_planes in _decode_step_body)
@@ -1109,8 +1048,7 @@ class LlamaForCausalLM:
             x = comm.all_reduce(lin(att, lw, "wo", residual=x if lead else None, **delta(att, li, "o")))
             h = norm(x, li, "ln2")
             if tl:                           # SiLU-GLU epilogue writes the two planes of its result itself (no sx_split16 launch)
-                g = ops.gemv(h, lw["wgu"], act="silu", glu=True, w_tiles=lw["wgu_t"] if dtl else None, w_fp8=lw.get("wgu_f8"), w_fp4=lw.get("wgu_f4"), y_tiled=True,
-                             planes_out=True, **delta(h, li, "gu"))
+                g = lw["wgu"].gemv(h, act="silu", glu=True, y_tiled=True, planes_out=True, **delta(h, li, "gu"))
             else:
                 g = ops.split16(lin(h, lw, "wgu", act="silu", glu=True), dt)
             x = comm.all_reduce(lin(g, lw, "wd", residual=x if lead else None, **delta(g, li, "d")))
@@ -1304,6 +1242,53 @@ class LlamaForCausalLM:
             self._sample_state = SampleState(self.G, self.device)
         return self._sample_state
 
+    def _step_tail(self, x, hid_buf, sel=None, tok=None):
+        """The end of every token step: final norm → the post-norm fp32 rows into hid_buf (row g at step[g]; verify step: row (g, t) at
+        step[g] + t, ``tok`` takes the token indices) → lm_head logits fp32 [rows, Vpad / tp]. ``sel``: the adapter step — the final
+        norm picks every row's gamma like the layers' norms; lm_head has no adapter."""
+        P, eps, dt, f32 = self._P, self.config.rms_norm_eps, self.dtype, torch.float32
+        tl = P["precise_tiled"]
+        if not self.precise:
+            hn = ops.rmsnorm(x, P["norm"], eps, f32)
+        elif sel is not None:
+            hp, hn = ops.rmsnorm_planes_sel(x, P["norm"], P["lora"]["norm"], sel, eps, dt, tiled=tl, want_f32=True)
+        else:
+            hp, hn = ops.rmsnorm_planes(x, P["norm"], eps, dt, tiled=tl, want_f32=True)
+        if tok is None:
+            ops.scatter_rows_step(hn, P["step"], hid_buf)
+        else:
+            ops.scatter_rows_spec(hn, P["step"], hid_buf, tok)
+        if self.precise and not tl:              # shapes outside the skinny GEMM's MFMA path (miniature test dims)
+            return ops.gemm(hp, P["lm_head"], a_planes=2, out_dtype=f32)
+        return ops.gemv(hp if self.precise else ops.cast(hn, dt), P["lm_head"], out_dtype=f32, w_tiles=P["lm_head_t"])
+
+    def _replay(self, attr, key, body, snap, slots=None):
+        """Replay the token step ``body`` (a callable without arguments) from the graph held in ``self.<attr>`` = (key, graph[, the
+        slot step's logits]); captured first where none is held under ``key``: warm-up on a side stream (allocator / lazy module
+        load), then capture of one step. Both really run the step: everything it advances — pos / ctx / step / cur and the tensors
+        ``snap``; in slot mode it may even finish a slot — is put back after each."""
+        held = getattr(self, attr)
+        if held is None or held[0] != key:
+            saved = [(t, t.clone()) for t in [self._P[k] for k in ("pos", "ctx", "step", "cur")] + snap]
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                body()
+            torch.cuda.current_stream().wait_stream(s)
+            torch.cuda.synchronize()
+            for t, v in saved:
+                t.copy_(v)
+            g = torch.cuda.CUDAGraph()
+            with ops.graph_capture(g):
+                body()
+            for t, v in saved:
+                t.copy_(v)
+            held = (key, g) + ((slots.logits,) if slots is not None else ())
+            setattr(self, attr, held)
+        if slots is not None:
+            slots.logits = held[2]
+        held[1].replay()
+
     def _decode_step_body(self, img_ids_dev, out_ids, hid_buf, slots=None, sampling=None, adapters=False):
         """cur[G] → embedding → 40 layers → final norm → lm_head → logits rule + argmax → cur[G]. Records the post-norm
         hidden state of each INPUT token at hid_buf[g, step[g]] (what seed_x.py:196 collects) and the new id at
@@ -1313,23 +1298,7 @@ class LlamaForCausalLM:
         P = self._P
         x = ops.embedding(P["cur"], P["embed"])                                        # [G, H] fp32
         x = self._layers_single_precise(x, slots, adapters=True) if adapters else self._layers_single(x, slots)
-        if adapters:      # the adapter step: the final norm picks every row's gamma like the layers' norms; lm_head has no adapter
-            hp, hn = ops.rmsnorm_planes_sel(x, P["norm"], P["lora"]["norm"], P["lora"]["sel"], self.config.rms_norm_eps, self.dtype,
-                                            tiled=True, want_f32=True)
-            ops.scatter_rows_step(hn, P["step"], hid_buf)
-            logits = ops.gemv(hp, P["lm_head"], out_dtype=torch.float32, w_tiles=P["lm_head_t"])
-        elif self.precise:
-            hp, hn = ops.rmsnorm_planes(x, P["norm"], self.config.rms_norm_eps, self.dtype, tiled=P["precise_tiled"], want_f32=True)
-            ops.scatter_rows_step(hn, P["step"], hid_buf)
-            if P["precise_tiled"]:
-                logits = ops.gemv(hp, P["lm_head"], out_dtype=torch.float32, w_tiles=P["lm_head_t"])
-            else:
-                logits = ops.gemm(hp, P["lm_head"], a_planes=2, out_dtype=torch.float32)
-        else:
-            hn = ops.rmsnorm(x, P["norm"], self.config.rms_norm_eps, torch.float32)
-            ops.scatter_rows_step(hn, P["step"], hid_buf)
-            logits = ops.gemv(ops.cast(hn, self.dtype), P["lm_head"], out_dtype=torch.float32,
-                              w_tiles=P["lm_head_t"])                                  # [G, Vpad / tp]
+        logits = self._step_tail(x, hid_buf, sel=P["lora"]["sel"] if adapters else None)
         if self.tp > 1:
             logits = self.comm.all_gather(logits).permute(1, 0, 2).reshape(self.G, self.Vpad).contiguous()
         # sampled step: same tail, the id by the seeded rule (token index = step[g]); on tensor-parallel ranks every rank draws from the
@@ -1357,9 +1326,7 @@ class LlamaForCausalLM:
             ops.spec_draft_ngram(S["hist"], P["pos"], P["cur"], S["rows"], S["n_draft"], self.spec_ngram)
         x = ops.embedding(S["rows"], P["embed"])                                       # [G*T, H] fp32
         x = self._layers_single_precise(x, slots, spec=True)
-        hp, hn = ops.rmsnorm_planes(x, P["norm"], self.config.rms_norm_eps, self.dtype, tiled=True, want_f32=True)
-        ops.scatter_rows_spec(hn, P["step"], hid_buf, S["tok"])
-        logits = ops.gemv(hp, P["lm_head"], out_dtype=torch.float32, w_tiles=P["lm_head_t"])
+        logits = self._step_tail(x, hid_buf, tok=S["tok"])
         ss = slots.sampling
         ops.spec_candidates(logits, self.V, img_ids_dev, S["rows"], S["cand"], S["tok"], sample=None if ss is None else ss.rows[0])
         ops.spec_accept(S["cand"], S["rows"], S["n_draft"], P["cur"], slots.live, slots.n_new, slots.max_new, slots.force_at, P["pos"],
@@ -1384,7 +1351,7 @@ class LlamaForCausalLM:
         ``adapters``: None (default) → the adapter token step runs iff some sequence has an adapter (set_adapters); True / False force
         it. The adapter step has captured graphs of its own; a step in which no sequence has an adapter runs the calls and graphs it
         ran before adapters existed."""
-        self._pack()
+        P = self._pack()
         if spec:
             # the verify step of speculative decoding (spec_tokens > 0, a slot state): graphs of its own, greedy and sampled; without
             # ``spec`` a model built with spec_tokens runs the plain steps and graphs below. ``draft``: "ngram" → the step starts with
@@ -1397,34 +1364,12 @@ class LlamaForCausalLM:
             assert sampling is None and not adapters and slots.G == self.G and out_ids.is_contiguous() and hid_buf.is_contiguous()
             assert out_ids.shape[0] == self.G and hid_buf.shape[0] == self.G and hid_buf.shape[1] == out_ids.shape[1]
             assert slots.sampling is None or slots.sampling.rows is not None, "a sampled slot state made by slot_state() of this model"
+            body = lambda: self._spec_step_body(img_ids_dev, out_ids, hid_buf, slots, draft)
             if not use_graph or not self.comm.graph_safe:
-                self._spec_step_body(img_ids_dev, out_ids, hid_buf, slots, draft)
-                return
-            attr = "_spec_graph" if slots.sampling is None else "_spec_sample_graph"
+                return body()
             key = (img_ids_dev.data_ptr(), out_ids.data_ptr(), hid_buf.data_ptr(), tuple(out_ids.shape), draft, tuple(self.spec_ngram)) + slots.key()
-            held = getattr(self, attr)
-            if held is None or held[0] != key:
-                P, S = self._P, self._P["spec"]
-                snap = [(P[k], P[k].clone()) for k in ("pos", "ctx", "step", "cur")] + [(S[k], S[k].clone()) for k in ("rows", "n_draft")] \
-                    + [(getattr(slots, k), getattr(slots, k).clone()) for k in ("live", "n_new", "status")]
-                s = torch.cuda.Stream()
-                s.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(s):             # the warm-up really runs a step: everything it advances is put back
-                    self._spec_step_body(img_ids_dev, out_ids, hid_buf, slots, draft)
-                torch.cuda.current_stream().wait_stream(s)
-                torch.cuda.synchronize()
-                for t, v in snap:
-                    t.copy_(v)
-                g = torch.cuda.CUDAGraph()
-                with ops.graph_capture(g):
-                    self._spec_step_body(img_ids_dev, out_ids, hid_buf, slots, draft)
-                for t, v in snap:
-                    t.copy_(v)
-                held = (key, g, slots.logits)
-                setattr(self, attr, held)
-            slots.logits = held[2]
-            held[1].replay()
-            return
+            return self._replay("_spec_graph" if slots.sampling is None else "_spec_sample_graph", key, body,
+                                [P["spec"]["rows"], P["spec"]["n_draft"], slots.live, slots.n_new, slots.status], slots)
         if adapters is None:
             adapters = any(a >= 0 for a in self._sel_host)
         if adapters and not self.max_adapters:
@@ -1436,40 +1381,13 @@ class LlamaForCausalLM:
             assert out_ids.is_contiguous() and slots.G == self.G
             assert sampling is None, "a slot state carries its own sampling state (slot_state(sampling=True))"
         assert sampling is None or sampling.G == self.G
+        body = lambda: self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling, adapters)
         if not use_graph or not self.comm.graph_safe:
-            self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling, adapters)
-            return
+            return body()
         if slots is None:
             attr = "_graph" if sampling is None else "_sample_graph"
         else:
             attr = "_slot_graph" if slots.sampling is None else "_slot_sample_graph"
-        if adapters:
-            attr += "_ad"
         key = (img_ids_dev.data_ptr(), out_ids.data_ptr(), hid_buf.data_ptr(), tuple(out_ids.shape)) \
             + (slots.key() if slots is not None else ()) + (("sample",) + sampling.key() if sampling is not None else ())
-        held = getattr(self, attr)
-        if held is None or held[0] != key:
-            # warm-up on a side stream (allocator / lazy module load), then capture one token step. The warm-up really runs a
-            # step: everything it advances is put back (in slot mode it may even finish a slot: live / n_new / status too)
-            P = self._P
-            snap = {k: (P[k], P[k].clone()) for k in ("pos", "ctx", "step", "cur")}
-            if slots is not None:
-                snap.update({k: (getattr(slots, k), getattr(slots, k).clone()) for k in ("live", "n_new", "status")})
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling, adapters)
-            torch.cuda.current_stream().wait_stream(s)
-            torch.cuda.synchronize()
-            for t, v in snap.values():
-                t.copy_(v)
-            g = torch.cuda.CUDAGraph()
-            with ops.graph_capture(g):
-                self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling, adapters)
-            for t, v in snap.values():
-                t.copy_(v)
-            held = (key, g) + ((slots.logits,) if slots is not None else ())
-            setattr(self, attr, held)
-        if slots is not None:
-            slots.logits = held[2]
-        held[1].replay()
+        self._replay(attr + ("_ad" if adapters else ""), key, body, [slots.live, slots.n_new, slots.status] if slots is not None else [], slots)

@@ -281,9 +281,12 @@ def test_fp4_model_equals_the_default_model_on_dequantised_weights(dev, dt):
     P = A._pack()
     assert A.precise and P["rms_fold_precise"] and P["decode_tiled"] and P["precise_tiled"]
     lw = P["layers"][0]
-    assert all(lw[k + "_t"] is None and lw[k + "_t20"] is None and "wqkv_f8" not in lw for k in ("wqkv", "wo", "wgu", "wd"))   # no 16-bit tiles
-    assert all(lw[k + "_f4"][0].dtype == lw[k + "_f4"][1].dtype == torch.uint8 and lw[k + "_f4"][0].shape[2] == 16 for k in ("wqkv", "wo", "wgu", "wd"))
-    held = sum(t.numel() for l in P["layers"] for k in ("wqkv", "wo", "wgu", "wd") for t in l[k + "_f4"]) + P["lm_head_t"].numel() * 2
+    # one handle per projection: MXFP4 codes + E8M0 scale tiles, no 16-bit and no FP8 tiles (the step is handed w_fp4 and nothing else)
+    assert all(lw[k].format == "mxfp4" and {"w_tiles", "w_tiles20", "w_fp8", "w_fp4"} & set(lw[k].gemv_kwargs()) == {"w_fp4"}
+               for k in ("wqkv", "wo", "wgu", "wd"))
+    assert all(lw[k].tiles.dtype == lw[k].scales.dtype == torch.uint8 and lw[k].tiles.shape[2] == lw[k].tile_rows == 16 for k in ("wqkv", "wo", "wgu", "wd"))
+    held = sum(t.numel() for l in P["layers"] for k in ("wqkv", "wo", "wgu", "wd") for t in (l[k].tiles, l[k].scales)) + P["lm_head_t"].numel() * 2
+    assert held == sum(l[k].nbytes_tiles for l in P["layers"] for k in ("wqkv", "wo", "wgu", "wd")) + P["lm_head_t"].numel() * 2
     nk = 3 * H * H + H * H + 2 * I * H + H * I
     assert held == L * (nk // 2 + nk // 32) + A.V_l * H * 2
     assert A.memory_footprint()["decode_tiles"] == held and A.weight_quant_report["decode_tile_bytes"] == held
@@ -291,7 +294,7 @@ def test_fp4_model_equals_the_default_model_on_dequantised_weights(dev, dt):
     # round-to-nearest e2m1 with the block maximum in [4, 8): 0.114 on Gaussian rows (tests/test_fp4_weights_cpu.py holds it in [0.10, 0.13])
     assert rep["weight_format"] == "mxfp4" and all(0.10 < v < 0.13 for v in rep["rel_frobenius_error"].values()), rep
     for k, name in (("wo", "self_attn.o_proj"), ("wd", "mlp.down_proj")):      # the row-major weights ARE the dequantised model
-        assert torch.equal(lw[k].float().cpu(), sd_q[f"model.layers.0.{name}.weight"])
+        assert torch.equal(lw[k].w.float().cpu(), sd_q[f"model.layers.0.{name}.weight"])
     a_log, a_ids, a_hid = _prefill_and_decode(A, dev, xs, cur0, img_ids, STEPS, use_graph=False)
     g_log, g_ids, g_hid = _prefill_and_decode(A, dev, xs, cur0, img_ids, STEPS, use_graph=True)
     assert torch.equal(g_log, a_log) and torch.equal(g_ids, a_ids) and torch.equal(g_hid, a_hid)          # graph replay == eager
@@ -299,7 +302,7 @@ def test_fp4_model_equals_the_default_model_on_dequantised_weights(dev, dt):
     torch.cuda.empty_cache()
     B = build(sd_q)
     PB = B._pack()
-    assert B.weight_format is None and PB["rms_fold_precise"] and PB["layers"][0]["wqkv_t"] is not None and "wqkv_f4" not in PB["layers"][0]
+    assert B.weight_format is None and PB["rms_fold_precise"] and PB["layers"][0]["wqkv"].format is None and "w_tiles" in PB["layers"][0]["wqkv"].gemv_kwargs()
     b_log, b_ids, b_hid = _prefill_and_decode(B, dev, xs, cur0, img_ids, STEPS, use_graph=False)
     del B, PB
     torch.cuda.empty_cache()
@@ -349,7 +352,7 @@ def test_fp4_serving_paths_agree(dev):
         inflight = agent.generate_inflight(tok, reqs, **kw)
         batch = agent.generate_batch(tok, [strip(r) for r in reqs[:4]], max_new_tokens=8, **kw)
         lw = llm._pack()["layers"][0]
-        assert llm.weight_format == fmt and llm.kv_format == "fp8_e4m3" and (("wqkv_f4" in lw) == (fmt == "mxfp4"))
+        assert llm.weight_format == fmt and llm.kv_format == "fp8_e4m3" and lw["wqkv"].format == fmt and (("w_fp4" in lw["wqkv"].gemv_kwargs()) == (fmt == "mxfp4"))
         out[name] = ([x["generate_ids"].tolist() for x in inflight], [x["generate_ids"].tolist() for x in batch])
         del agent, llm, lw
         torch.cuda.empty_cache()

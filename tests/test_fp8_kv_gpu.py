@@ -566,7 +566,7 @@ def test_fp8_kv_serving_paths_agree(dev, weight_format):
     got = agent.generate_inflight(tok, reqs, **kw)
     P = llm._pack()
     assert llm.kv_format == "fp8_e4m3" and P["kc"].dtype == torch.uint8 and llm.weight_format == weight_format
-    assert ("wqkv_f8" in P["layers"][0]) == (weight_format is not None)
+    assert P["layers"][0]["wqkv"].format == weight_format and ("w_fp8" in P["layers"][0]["wqkv"].gemv_kwargs()) == (weight_format is not None)
     assert [len(x["generate_ids"]) for x in got] == budgets
     strip = lambda q: {k: v for k, v in q.items() if k != "max_new_tokens"}
     for wave in ([0, 1, 2, 3], [4, 5, 0, 1]):

@@ -267,9 +267,13 @@ def test_fp8_model_equals_the_default_model_on_dequantised_weights(dev, dt, H, n
     P = A._pack()
     assert A.precise and P["rms_fold_precise"] and P["decode_tiled"] and P["precise_tiled"]
     lw = P["layers"][0]
-    assert all(lw[k + "_t"] is None and lw[k + "_f8"][0].dtype == torch.uint8 for k in ("wqkv", "wo", "wgu", "wd"))
-    assert [lw[k + "_f8"][0].shape[2] for k in ("wqkv", "wo", "wgu", "wd")] == ([16, 20, 16, 20] if H == 5120 else [16] * 4)
-    held = sum(t.numel() * t.element_size() for l in P["layers"] for k in ("wqkv", "wo", "wgu", "wd") for t in l[k + "_f8"]) \
+    # one handle per projection: FP8 codes + fp32 row scales, no 16-bit tiles (the step is handed w_fp8 and nothing else)
+    assert all(lw[k].format == "fp8_e4m3" and lw[k].tiles.dtype == torch.uint8 and lw[k].scales.dtype == torch.float32
+               and {"w_tiles", "w_tiles20", "w_fp8", "w_fp4"} & set(lw[k].gemv_kwargs()) == {"w_fp8"} for k in ("wqkv", "wo", "wgu", "wd"))
+    rows = [16, 20, 16, 20] if H == 5120 else [16] * 4
+    assert [lw[k].tile_rows for k in ("wqkv", "wo", "wgu", "wd")] == rows == [lw[k].tiles.shape[2] for k in ("wqkv", "wo", "wgu", "wd")]
+    held = sum(l[k].nbytes_tiles for l in P["layers"] for k in ("wqkv", "wo", "wgu", "wd")) + P["lm_head_t"].numel() * 2
+    assert held == sum(t.numel() * t.element_size() for l in P["layers"] for k in ("wqkv", "wo", "wgu", "wd") for t in (l[k].tiles, l[k].scales)) \
         + P["lm_head_t"].numel() * 2
     assert A.memory_footprint()["decode_tiles"] == held and A.weight_quant_report["decode_tile_bytes"] == held
     # e4m3 rounds a normal value by at most 2^-4 of itself; the subnormal tail (|w| < amax / 2^13) adds < 1e-3 of the row norm
@@ -277,7 +281,7 @@ def test_fp8_model_equals_the_default_model_on_dequantised_weights(dev, dt, H, n
     for k in ("wqkv", "wo", "wd"):                                   # the row-major weights ARE the dequantised model
         name = {"wo": "self_attn.o_proj", "wd": "mlp.down_proj"}.get(k)
         if name:
-            assert torch.equal(lw[k].float().cpu(), sd_q[f"model.layers.0.{name}.weight"])
+            assert torch.equal(lw[k].w.float().cpu(), sd_q[f"model.layers.0.{name}.weight"])
     a_log, a_ids, a_hid = _prefill_and_decode(A, dev, xs[:G], cur0[:G], img_ids, STEPS, use_graph=False)
     g_log, g_ids, g_hid = _prefill_and_decode(A, dev, xs[:G], cur0[:G], img_ids, STEPS, use_graph=True)
     assert torch.equal(g_log, a_log) and torch.equal(g_ids, a_ids) and torch.equal(g_hid, a_hid)          # graph replay == eager
@@ -285,7 +289,7 @@ def test_fp8_model_equals_the_default_model_on_dequantised_weights(dev, dt, H, n
     torch.cuda.empty_cache()
     B = build(sd_q, G)
     PB = B._pack()
-    assert B.weight_format is None and PB["rms_fold_precise"] and PB["layers"][0]["wqkv_t"] is not None and "wqkv_f8" not in PB["layers"][0]
+    assert B.weight_format is None and PB["rms_fold_precise"] and PB["layers"][0]["wqkv"].format is None and "w_tiles" in PB["layers"][0]["wqkv"].gemv_kwargs()
     b_log, b_ids, b_hid = _prefill_and_decode(B, dev, xs[:G], cur0[:G], img_ids, STEPS, use_graph=False)
     del B, PB
     torch.cuda.empty_cache()
@@ -339,7 +343,7 @@ def test_fp8_serving_paths_agree(dev):
     for r, s in ((1, 21), (2, 22), (5, 23)):
         reqs[r].update(do_sample=True, temperature=1.0, top_k=50, top_p=0.9, seed=s)
     got = agent.generate_inflight(tok, reqs, **kw)
-    assert llm.weight_format == "fp8_e4m3" and llm._pack()["layers"][0]["wqkv_f8"][0].dtype == torch.uint8
+    assert llm.weight_format == "fp8_e4m3" and llm._pack()["layers"][0]["wqkv"].format == "fp8_e4m3" and llm._pack()["layers"][0]["wqkv"].tiles.dtype == torch.uint8
     assert [len(x["generate_ids"]) for x in got] == budgets
     strip = lambda q: {k: v for k, v in q.items() if k != "max_new_tokens"}
     for wave in ([0, 1, 2, 3], [4, 5, 0, 1]):

@@ -48,8 +48,13 @@ def test_rmsnorm_fold_model_level(dev, dt, H, nh, I, L, precise, monkeypatch):
         P = llm._pack()
         assert bool(P["rms_fold_precise" if precise else "rms_fold"]) == (fold == "1") and P["decode_tiled"], (fold, P["rms_fold"])
         assert not (precise and P["rms_fold"]) and not (not precise and P["rms_fold_precise"])
-        if H == 5120:
-            assert P["layers"][0]["wo_t20"] is not None                  # the 20-row tiles feed the fold's 256 partial sums
+        pj = [lw[k] for lw in P["layers"] for k in ("wqkv", "wo", "wgu", "wd")]
+        if H == 5120:                                                    # the 20-row tiles feed the fold's 256 partial sums
+            assert [p.tile_rows for p in pj[:4]] == [16, 20, 16, 20]
+            assert [k for p in pj[:4] for k in p.gemv_kwargs() if k.startswith("w_")] == ["w_tiles", "w_tiles20", "w_tiles", "w_tiles20"]
+        # one 16-bit tile layout per projection, and memory_footprint() prices exactly what is held
+        assert sum(p.nbytes_tiles for p in pj) + P["lm_head_t"].numel() * 2 == llm.memory_footprint()["decode_tiles"]
+        assert all(p.nbytes_tiles == 2 * p.shape.numel() == p.tiles.numel() * p.tiles.element_size() for p in pj)
         llm.forward_embeds_batch([x.to(dev) for x in xs], list(range(G)))
         P["cur"].copy_(cur0.to(dev))
         P["step"].zero_()

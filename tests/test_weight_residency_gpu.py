@@ -223,8 +223,11 @@ def _held(P, keys=("wqkv", "wo", "wgu", "wd")):
     """Bytes by memory_footprint()'s categories, from the tensors the packed model holds."""
     nb = lambda t: t.numel() * t.element_size()
     w = nb(P["embed"]) + nb(P["lm_head"]) + (nb(P["w_scratch"]) if "w_scratch" in P else 0) \
-        + sum(nb(lw[k]) for lw in P["layers"] for k in keys if torch.is_tensor(lw[k]))
-    tiles = nb(P["lm_head_t"]) + sum(nb(t) for lw in P["layers"] for k in keys for f in ("_f4", "_f8") for t in lw.get(k + f, ()))
+        + sum(nb(lw[k].w) for lw in P["layers"] for k in keys if lw[k].w is not None)
+    tiles = nb(P["lm_head_t"]) + sum(nb(t) for lw in P["layers"] for k in keys for t in (lw[k].tiles, lw[k].scales))
+    assert w - nb(P["embed"]) - nb(P["lm_head"]) - (nb(P["w_scratch"]) if "w_scratch" in P else 0) \
+        == sum(lw[k].nbytes_rowmajor for lw in P["layers"] for k in keys)
+    assert tiles - nb(P["lm_head_t"]) == sum(lw[k].nbytes_tiles for lw in P["layers"] for k in keys)
     return {"weights": w, "decode_tiles": tiles, "kv_cache": nb(P["kc"]) + nb(P["vc"])}
 
 
@@ -249,7 +252,6 @@ def test_tiles_residency_equals_the_default_residency(dev, dt, fmt):
     cur0 = torch.arange(20, 20 + G, dtype=torch.int32)
     img_ids = torch.arange(400, 466, dtype=torch.int32, device=dev)
     keys = ("wqkv", "wo", "wgu", "wd")
-    fkey = "_f4" if fmt == "mxfp4" else "_f8"
     per_layer = (3 * H * H + H * H + 2 * I * H + H * I) * 2
     scratch = 2 * I * H * 2
 
@@ -267,9 +269,11 @@ def test_tiles_residency_equals_the_default_residency(dev, dt, fmt):
     assert A.weight_residency == "tiles" and A.precise and P["rms_fold_precise"] and P["decode_tiled"] and P["precise_tiled"]
     for lw in P["layers"]:
         for k in keys:
-            h = lw[k]
-            assert isinstance(h, ops.WeightShape) and not torch.is_tensor(h) and h.data_ptr() == 0 and h.dtype == dt
-            assert lw[k + "_t"] is None and lw[k + "_t20"] is None and lw[k + fkey][0].dtype == torch.uint8
+            h = lw[k].gemv_kwargs()["w"]                             # what the token step hands ops.gemv as ``w``: no storage
+            assert lw[k].w is None and lw[k].nbytes_rowmajor == 0
+            assert isinstance(h, ops.WeightShape) and not torch.is_tensor(h) and h.data_ptr() == 0 and h.dtype == dt == lw[k].dtype
+            assert lw[k].format == fmt and lw[k].tiles.dtype == torch.uint8             # quantised tiles only: no 16-bit ones
+            assert {"w_tiles", "w_tiles20", "w_fp8", "w_fp4"} & set(lw[k].gemv_kwargs()) == {"w_fp4" if fmt == "mxfp4" else "w_fp8"}
     assert tuple(P["layers"][0]["wgu"].shape) == (2 * I, H) and tuple(P["layers"][0]["wd"].shape) == (H, I)
     assert P["w_scratch"].numel() * 2 == scratch and P["w_scratch"].dtype == dt
     fa, held_a = A.memory_footprint(), _held(P)
@@ -281,7 +285,7 @@ def test_tiles_residency_equals_the_default_residency(dev, dt, fmt):
     assert torch.equal(g_log, a_log) and torch.equal(g_ids, a_ids) and torch.equal(g_hid, a_hid)          # graph replay == eager
     del A, P, lw, h
     B, PB, bytes_b = build()
-    assert B.weight_residency is None and "w_scratch" not in PB and all(torch.is_tensor(PB["layers"][0][k]) for k in keys)
+    assert B.weight_residency is None and "w_scratch" not in PB and all(torch.is_tensor(PB["layers"][0][k].w) and PB["layers"][0][k].gemv_kwargs()["w"] is PB["layers"][0][k].w for k in keys)
     fb, held_b = B.memory_footprint(), _held(PB)
     assert "prefill_scratch" not in fb and all(held_b[k] == fb[k] for k in held_b), (held_b, fb)
     assert B.weight_quant_report["weight_residency"] is None
@@ -329,7 +333,7 @@ def test_serving_paths_agree_with_the_default_residency(dev):
         agent.prefix_cache = False
         batch = agent.generate_batch(tok, [strip(r) for r in reqs[:4]], max_new_tokens=8, **kw)
         lw = llm._pack()["layers"][0]
-        assert llm.weight_residency == res and torch.is_tensor(lw["wqkv"]) == (res is None) and "wqkv_f4" in lw
+        assert llm.weight_residency == res and torch.is_tensor(lw["wqkv"].w) == (res is None) and lw["wqkv"].format == "mxfp4"
         ids = lambda rs: [x["generate_ids"].tolist() for x in rs]
         out[res] = (ids(inflight), ids(first), ids(cached), ids(batch), stats["prefix_hit_tokens"] + stats["forked_tokens"])
         del agent, llm, lw
@@ -361,7 +365,7 @@ def test_tensor_parallel_tiles_residency(dev):
         out = llm(inputs_embeds=xe.to(dev))
         torch.cuda.synchronize()
         P = llm._P
-        assert isinstance(P["layers"][0]["wd"], ops.WeightShape) == (res == "tiles")
+        assert isinstance(P["layers"][0]["wd"].gemv_kwargs()["w"], ops.WeightShape) == (res == "tiles") == (P["layers"][0]["wd"].w is None)
         if res == "tiles":       # per-rank slices: gate|up [2 I / 2, H] is the largest
             assert P["w_scratch"].numel() == 2 * (cfg["intermediate_size"] // 2) * cfg["hidden_size"]
             assert tuple(P["layers"][0]["wd"].shape) == (cfg["hidden_size"], cfg["intermediate_size"] // 2)
