@@ -594,6 +594,13 @@ int sx_rope_kv_append_f32(float* qkv, float* kcache, float* vcache, const float*
 int sx_rope_kv_append_f32_v16(float* qkv, float* kcache, void* vcache16, const float* cos_tab, const float* sin_tab,
                               const int32_t* pos0_dev, int G, int T, int H, int D, int Tmax, int64_t cache_seq_stride,
                               int table_dtype, void* stream);
+/* the same two with the paged cache (sx_attn_f32_args.page_table states the layout): kpool / vpool are [n_pages + 1][H][page size][D]
+ * (v16 = 1: vpool is 16-bit in table_dtype), pages page_stride elements apart; the row of position pos0[g] + t goes to page
+ * page_table[g][pos >> page_shift] (int32 [G][ceil(Tmax / page size)], clamped to [0, n_pages]) at row pos & (page size - 1). A row whose
+ * entry is 0 (the null page) and a position outside [0, Tmax) write nothing; q is rotated either way. head_dim 128, page_shift 5..7. */
+int sx_rope_kv_append_f32_paged(float* qkv, float* kpool, void* vpool, int v16, const float* cos_tab, const float* sin_tab,
+                                const int32_t* pos0_dev, const int32_t* page_table, int G, int T, int H, int D, int Tmax,
+                                int page_shift, int n_pages, int64_t page_stride, int table_dtype, void* stream);
 /* the same with the FP8 KV cache (LlamaForCausalLM(kv_format="fp8_e4m3"), head_dim 128 only): the rotated k row and the v row of every
  * (token, head) are quantised to OCP e4m3fn codes with ONE power-of-two scale per row — s = clamp(ceil(log2(amax / 448)), -64, 64), 0 for a
  * zero row, code = e4m3fn(rne(clamp(x * 2^-s, +-448))), never a NaN code (seedx_amd.quant.quantize_kv_rows states the rule on the host, bit
@@ -648,6 +655,19 @@ typedef struct sx_attn_f32_args {
   const float* k_scale;
   const float* v_scale;
   int64_t scale_seq_stride;
+  /* Paged cache (LlamaForCausalLM(kv_pages=N); head_dim 128, causal, kv_fp8 = 0, not the verify form — each refused with a message).
+   * NULL (default, also a zero-initialised struct): the contiguous addressing above, the very launches of a build without paging.
+   * Else kcache / vcache are page POOLS [n_pages + 1][H][page size][D] (page size = 1 << page_shift = 32, 64 or 128 rows; pages
+   * page_stride elements apart; v16 as above) and page_table is device int32 [G][ceil(Tmax / page size)]: key row t of sequence g lives
+   * in page page_table[g][t >> page_shift] at row t & (page size - 1). cache_seq_stride and the K / V strides are unused. Page 0 is the
+   * NULL page — all zeros, never handed out, never written: an entry without a reservation names it, so whatever the contiguous kernels
+   * read from rows nobody owns (a parked slot's key row 0, the MFMA tile's rows past the last visible key) reads finite zeros, and the
+   * fused append of a row whose entry is 0 writes nothing. Entries are clamped to [0, n_pages]: a wrong table gives wrong numbers, never
+   * a wild address. The table is read at launch (at replay under a captured graph); one lookup per page (VALU kernels) or per 32-key
+   * tile (MFMA kernel). Every launch has the bits of the contiguous call on a cache holding the same rows. */
+  const int32_t* page_table;
+  int32_t page_shift, n_pages;
+  int64_t page_stride;
 } sx_attn_f32_args;
 int sx_attention_f32(const sx_attn_f32_args* args, void* stream);
 /* tuning / test hook: 1 (default) = causal chunks above 8 tokens at head_dim 128 run on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32)

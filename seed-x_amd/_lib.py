@@ -51,7 +51,8 @@ class AttnF32Args(C.Structure):
                 ("G", c_i32), ("T", c_i32), ("H", c_i32), ("D", c_i32), ("Tmax", c_i32), ("dtype", c_i32),
                 ("scale", c_f32), ("causal", c_i32), ("v16", c_i32), ("nsplit", c_i32), ("scratch", c_vp),
                 ("rope_cos", c_vp), ("rope_sin", c_vp), ("k_new", c_vp), ("v_new", c_vp),
-                ("kv_fp8", c_i32), ("k_scale", c_vp), ("v_scale", c_vp), ("scale_seq_stride", c_i64)]
+                ("kv_fp8", c_i32), ("k_scale", c_vp), ("v_scale", c_vp), ("scale_seq_stride", c_i64),
+                ("page_table", c_vp), ("page_shift", c_i32), ("n_pages", c_i32), ("page_stride", c_i64)]
 
 
 class OneshotArgs(C.Structure):
@@ -180,6 +181,8 @@ SIGNATURES = {
     "sx_rmsnorm_planes_sel": [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_f32, c_i32, c_vp],
     "sx_rope_kv_append_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i32, c_vp],
     "sx_rope_kv_append_f32_v16": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i32, c_vp],
+    "sx_rope_kv_append_f32_paged": [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64,
+                                    c_i32, c_vp],
     "sx_rope_kv_append_f32_q8": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i32,
                                  c_i32, c_vp],
     "sx_attention_f32": [C.POINTER(AttnF32Args), c_vp],

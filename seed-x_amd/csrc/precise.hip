@@ -86,6 +86,54 @@ __global__ void rope_kv_f32_kernel(float* qkv, float* kc, void* vc_, const float
   }
 }
 
+// rope_kv_f32_kernel on the paged cache (LlamaForCausalLM(kv_pages=N)) — a kernel of its own, its statements copied, so that the contiguous
+// kernel above keeps its signature and its code to the instruction: kc / vc are page pools [n_pages + 1][H][page size][D], page_stride
+// elements between pages, and ptab int32 [G][ptw] names the page that holds key rows [i << pshift, (i + 1) << pshift) of sequence g. Page 0 is
+// the null page: a row whose entry is 0 is not appended (q is still rotated). The entry is clamped to [0, npages]: a wrong table never gives
+// a wild address.
+template <typename TT, bool V16>
+__global__ void rope_kv_f32_paged_kernel(float* qkv, float* kc, void* vc_, const float* cos_t, const float* sin_t, const int* pos0_dev, int T,
+                                         int H, int D, int Tmax, int G, long long page_stride, const int* ptab, int pshift, int npages,
+                                         int ptw) {
+  const int half = D / 2;
+  const int64_t total = (int64_t)G * T * H * half;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int j = (int)(i % half);
+    const int h = (int)((i / half) % H);
+    const int r = (int)(i / ((int64_t)half * H));
+    const int g = r / T, t = r - g * T;
+    int pos = pos0_dev[g] + t;
+    const bool pos_ok = pos >= 0 && pos < Tmax;
+    if (!pos_ok) pos = 0;
+    const float c = TT::to_f32(TT::from_f32(cos_t[(size_t)pos * half + j]));
+    const float s = TT::to_f32(TT::from_f32(sin_t[(size_t)pos * half + j]));
+    float* row = qkv + (size_t)r * 3 * H * D;
+    float* qh = row + (size_t)h * D;
+    const float* kh = row + (size_t)(H + h) * D;
+    const float* vh = row + (size_t)(2 * H + h) * D;
+    const float q1 = qh[j], q2 = qh[j + half];
+    qh[j] = q1 * c - q2 * s;
+    qh[j + half] = q2 * c + q1 * s;
+    if (!pos_ok) continue;                  // a device-resident position past the cache never writes outside it
+    const int pg = min(max(ptab[(size_t)g * ptw + (pos >> pshift)], 0), npages);
+    if (pg == 0) continue;                  // no reservation behind this row: nothing is written
+    const size_t vo = (size_t)pg * page_stride + (((size_t)h << pshift) + (pos & ((1 << pshift) - 1))) * D;   // the row's place in its page
+    const float k1 = kh[j], k2 = kh[j + half];
+    float* kd = kc + vo;
+    kd[j] = k1 * c - k2 * s;
+    kd[j + half] = k2 * c + k1 * s;
+    if constexpr (V16) {
+      unsigned short* vd = (unsigned short*)vc_ + vo;
+      vd[j] = TT::from_f32(vh[j]);
+      vd[j + half] = TT::from_f32(vh[j + half]);
+    } else {
+      float* vd = (float*)vc_ + vo;
+      vd[j] = vh[j];
+      vd[j + half] = vh[j + half];
+    }
+  }
+}
+
 // ---- FP8 (e4m3fn) KV cache: LlamaForCausalLM(kv_format="fp8_e4m3") -----------------------------------------------------------------
 // The ONE quantiser of every append path (quant.py quantize_kv_rows is its host statement). A 16-lane group owns a row of D = 128 values,
 // lane dl the dims 8 dl .. 8 dl + 7 (the mapping of attn_f32_kernel's fused RoPE block). Row amax by four xor shuffles; s = ceil(log2(amax
@@ -328,7 +376,67 @@ struct AttnF32P {
   const float* ks;
   const float* vs;
   long long sc_seq_stride;
+  // paged cache (PAGED kernels, D = 128): kc / vc are page pools [npages + 1][H][page size][D] — seq_stride is the element stride between
+  // PAGES, head_stride = page size * row_stride — and ptab int32 [G][ptw] names the page of key rows [i << pshift, (i + 1) << pshift) of
+  // sequence g. Page 0 is the null page (all zeros, never written): what a contiguous kernel reads from rows nobody owns comes from there.
+  const int* ptab;
+  int pshift, npages, ptw;
 };
+
+// element offset of the page behind table entry pi of sequence g; entry and index are clamped, so a wrong table gives wrong numbers, never
+// a wild address. Uniform over the workgroup (g, pi are): the lookup is scalar loads and SGPR arithmetic
+__device__ __forceinline__ size_t attn_page_off(const AttnF32P& p, int g, int pi) {
+  const int pg = p.ptab[(size_t)g * p.ptw + min(max(pi, 0), p.ptw - 1)];
+  return (size_t)min(max(pg, 0), p.npages) * (size_t)p.seq_stride;
+}
+
+// one key row t of attn_f32_kernel's walk, as text: the contiguous loop below is, token for token, the loop it always was (its code does
+// not move when the paged loop changes), and the paged loop runs the same statements on a page. KH_ / VBASE_: where row 0 sits in k / in
+// the v cache's elements; VIS_ + i: the last row query i may see
+#define SX_ATTN_F32_KEY_ROW(KH_, VBASE_, VIS_)                                                                                  \
+    float kf[DW], vf[DW];                                                                                                       \
+    float ksc = 1.f;                                                                                                            \
+    _Pragma("unroll")                                                                                                           \
+    for (int e = 0; e < DW; ++e) { kf[e] = 0.f; vf[e] = 0.f; }                                                                  \
+    if constexpr (KV8 == 1) {                                                                                                   \
+      const u32x2_t kw = *(const u32x2_t*)(kc8 + (size_t)t * p.row_stride + dl * 8);                                            \
+      const u32x2_t vw = *(const u32x2_t*)(vc8 + (size_t)t * p.row_stride + dl * 8);                                            \
+      ksc = p.ks[sbase + t];                                                                                                    \
+      const float vsc = p.vs[sbase + t];                                                                                        \
+      decode8(kw, kf);                                                                                                          \
+      decode8(vw, vf);                                                                                                          \
+    _Pragma("unroll")                                                                                                           \
+      for (int e = 0; e < 8; ++e) vf[e] *= vsc;                                                                                 \
+    }                                                                                                                           \
+    _Pragma("unroll")                                                                                                           \
+    for (int c = 0; c < DC; ++c) {                                                                                              \
+      if (KV8 != 1 && dvalid[c]) {                                                                                              \
+        const float* kr = (KH_) + (size_t)t * p.row_stride + c * 128 + dl * 8;                                                  \
+        const size_t vo = (VBASE_) + (size_t)t * p.row_stride + c * 128 + dl * 8;                                               \
+        const f32x4_t k0 = *(const f32x4_t*)kr, k1 = *(const f32x4_t*)(kr + 4);                                                 \
+    _Pragma("unroll")                                                                                                           \
+        for (int e = 0; e < 4; ++e) { kf[8 * c + e] = k0[e]; kf[8 * c + 4 + e] = k1[e]; }                                       \
+        if constexpr (V16) {                                                                                                    \
+          const u32x4_t w = *(const u32x4_t*)((const unsigned short*)p.vc + vo);                                                \
+    _Pragma("unroll")                                                                                                           \
+          for (int e = 0; e < 4; ++e) {                                                                                         \
+            vf[8 * c + 2 * e] = TT::to_f32((unsigned short)(w[e] & 0xffffu));                                                   \
+            vf[8 * c + 2 * e + 1] = TT::to_f32((unsigned short)(w[e] >> 16));                                                   \
+          }                                                                                                                     \
+        } else {                                                                                                                \
+          const float* vr = (const float*)p.vc + vo;                                                                            \
+          const f32x4_t v0 = *(const f32x4_t*)vr, v1 = *(const f32x4_t*)(vr + 4);                                               \
+    _Pragma("unroll")                                                                                                           \
+          for (int e = 0; e < 4; ++e) { vf[8 * c + e] = v0[e]; vf[8 * c + 4 + e] = v1[e]; }                                     \
+        }                                                                                                                       \
+      }                                                                                                                         \
+    }                                                                                                                           \
+    _Pragma("unroll")                                                                                                           \
+    for (int i = 0; i < QB; ++i) {                                                                                              \
+      float s = attn_score<DW>(kf, qv[i]);                                                                                      \
+      if constexpr (KV8 == 1) s *= ksc;                                                                                         \
+      if (i < nq && t <= (VIS_) + i) attn_key_update<DW>(s, vf, m_run[i], l_run[i], o[i]);                                      \
+    }
 
 // QB query rows per workgroup: 4 for the decode step and short chunks, 8 for prefill (every key row is loaded once per QB rows: the
 // K / V re-reads from L2 halve — 1.5k-token prompts, BASELINE config 5). DC = 8-dim chunks per lane: 1 covers D <= 128 (16 lanes x 8),
@@ -344,9 +452,14 @@ struct AttnF32P {
 // bit for bit, the KV8 = 0 kernel's on a cache holding the dequantised values. 2 = the bit-reference twin of the fused RoPE form: fp32
 // caches, the new token's k / v quantised and dequantised on append. In both, the new token's own key / value (attended to from
 // registers) are the dequantised values — the reason vnew is rounded under V16.
-template <typename TT, int QB, int DC, bool V16 = false, bool SPLIT = false, int KV8 = 0>
+// PAGED (the paged cache, D = 128, KV8 = 0): the key walk goes page by page — ONE table lookup per page, uniform over the workgroup — and
+// inside a page a group walks its keys grp + 16 i as before (splits start at multiples of 16, pages at multiples of 32: every group sees
+// its keys in the same ascending order, so the bits are the contiguous kernel's). The fused append goes through the table too and writes
+// nothing where the entry is 0.
+template <typename TT, int QB, int DC, bool V16 = false, bool SPLIT = false, int KV8 = 0, bool PAGED = false>
 __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnF32P p) {
   constexpr int DW = 8 * DC, DMAX = 128 * DC;
+  static_assert(!PAGED || (DC == 1 && KV8 == 0), "the paged cache: head_dim 128, fp32 k");
   static_assert(!SPLIT || (QB == 1 && DC == 1), "key splits: the single-row decode form");
   static_assert(KV8 == 0 || (DC == 1 && !V16), "the FP8 cache: head_dim 128, no 16-bit v");
   static_assert(KV8 != 2 || QB == 1, "KV8 = 2 only differs in the fused RoPE form");
@@ -377,8 +490,9 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnF32P p) {
       }
     }
   }
-  const float* kh = p.kc + (size_t)g * p.seq_stride + (size_t)h * p.head_stride;       // (KV8 = 1: unused, see kc8)
-  const size_t vbase = (size_t)g * p.seq_stride + (size_t)h * p.head_stride;
+  // (KV8 = 1: kh is unused, see kc8; PAGED: the head's offset inside a page, the page's own comes from the table)
+  const float* kh = PAGED ? p.kc + (size_t)h * p.head_stride : p.kc + (size_t)g * p.seq_stride + (size_t)h * p.head_stride;
+  const size_t vbase = PAGED ? (size_t)h * p.head_stride : (size_t)g * p.seq_stride + (size_t)h * p.head_stride;
   const unsigned char* kc8 = (const unsigned char*)p.kc + vbase;                        // KV8 = 1: codes, same element strides
   const unsigned char* vc8 = (const unsigned char*)p.vc + vbase;
   const size_t sbase = (size_t)g * p.sc_seq_stride + (size_t)h * p.Tmax;                // KV8 = 1: the row scales of this (sequence, head)
@@ -425,8 +539,15 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnF32P p) {
         quant_dequant_row8(vnew, vcod, vsc);
       }
       own_new = pos_ok && (SPLIT ? (praw / chunk == (int)blockIdx.x) : true);
-      if (own_new && grp == 0) {                      // append: one 16-lane group covers the 128 dims
-        const size_t vo_c = vbase + (size_t)praw * p.row_stride + dl * 8;
+      size_t ao = (size_t)praw * p.row_stride;        // the appended row's offset from (kh, vbase)
+      bool held = true;                               // PAGED: a page is reserved behind the row (entry != 0)
+      if constexpr (PAGED) {
+        const size_t po = attn_page_off(p, g, pt >> p.pshift);
+        held = po != 0;
+        ao = po + (size_t)(pt & ((1 << p.pshift) - 1)) * p.row_stride;
+      }
+      if (own_new && grp == 0 && held) {              // append: one 16-lane group covers the 128 dims
+        const size_t vo_c = vbase + ao + dl * 8;
         if constexpr (KV8 == 1) {                     // codes: one 8-byte store per lane, one lane stores the two scales
           *(u32x2_t*)(const_cast<unsigned char*>(kc8) + (size_t)praw * p.row_stride + dl * 8) = kcod;
           *(u32x2_t*)(const_cast<unsigned char*>(vc8) + (size_t)praw * p.row_stride + dl * 8) = vcod;
@@ -435,7 +556,7 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnF32P p) {
             const_cast<float*>(p.vs)[sbase + praw] = vsc;
           }
         } else {
-          float* kd = const_cast<float*>(kh) + (size_t)praw * p.row_stride + dl * 8;
+          float* kd = const_cast<float*>(kh) + ao + dl * 8;
 #pragma unroll
           for (int e = 0; e < 8; ++e) kd[e] = knew[e];
           if constexpr (V16) {
@@ -452,50 +573,19 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnF32P p) {
       if (pos_ok) kend = min(kend, praw);             // the cache rows below pos; the new key comes from registers
     }
   }
-  for (int t = kbeg + grp; t < kend; t += 16) {
-    float kf[DW], vf[DW];
-    float ksc = 1.f;
-#pragma unroll
-    for (int e = 0; e < DW; ++e) { kf[e] = 0.f; vf[e] = 0.f; }
-    if constexpr (KV8 == 1) {
-      const u32x2_t kw = *(const u32x2_t*)(kc8 + (size_t)t * p.row_stride + dl * 8);
-      const u32x2_t vw = *(const u32x2_t*)(vc8 + (size_t)t * p.row_stride + dl * 8);
-      ksc = p.ks[sbase + t];
-      const float vsc = p.vs[sbase + t];
-      decode8(kw, kf);
-      decode8(vw, vf);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) vf[e] *= vsc;
-    }
-#pragma unroll
-    for (int c = 0; c < DC; ++c) {
-      if (KV8 != 1 && dvalid[c]) {
-        const float* kr = kh + (size_t)t * p.row_stride + c * 128 + dl * 8;
-        const size_t vo = vbase + (size_t)t * p.row_stride + c * 128 + dl * 8;
-        const f32x4_t k0 = *(const f32x4_t*)kr, k1 = *(const f32x4_t*)(kr + 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { kf[8 * c + e] = k0[e]; kf[8 * c + 4 + e] = k1[e]; }
-        if constexpr (V16) {
-          const u32x4_t w = *(const u32x4_t*)((const unsigned short*)p.vc + vo);        // 8 values in one 16-byte load
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            vf[8 * c + 2 * e] = TT::to_f32((unsigned short)(w[e] & 0xffffu));
-            vf[8 * c + 2 * e + 1] = TT::to_f32((unsigned short)(w[e] >> 16));
-          }
-        } else {
-          const float* vr = (const float*)p.vc + vo;
-          const f32x4_t v0 = *(const f32x4_t*)vr, v1 = *(const f32x4_t*)(vr + 4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { vf[8 * c + e] = v0[e]; vf[8 * c + 4 + e] = v1[e]; }
-        }
+  if constexpr (PAGED) {                              // one trip, and ONE table lookup, per page the key range touches
+    for (int pi = kbeg >> p.pshift; pi < ((kend + (1 << p.pshift) - 1) >> p.pshift); ++pi) {
+      const int pb = pi << p.pshift;                  // the page's first key row; t counts from it
+      const size_t po = attn_page_off(p, g, pi);
+      const int te = min(kend, pb + (1 << p.pshift)) - pb;
+      for (int t = max(kbeg, pb) - pb + grp; t < te; t += 16) {
+        SX_ATTN_F32_KEY_ROW(kh + po, vbase + po, pos0 + q0 - pb)
       }
     }
-#pragma unroll
-    for (int i = 0; i < QB; ++i) {
-      float s = attn_score<DW>(kf, qv[i]);
-      if constexpr (KV8 == 1) s *= ksc;
-      if (i < nq && t <= pos0 + q0 + i) attn_key_update<DW>(s, vf, m_run[i], l_run[i], o[i]);   // uniform over the 16-lane group
-    }
+  } else {
+  for (int t = kbeg + grp; t < kend; t += 16) {
+    SX_ATTN_F32_KEY_ROW(kh, vbase, pos0 + q0)
+  }
   }
   if constexpr (QB == 1 && DC == 1) {
     if (own_new && grp == 0) {                        // the new token's own key / value, straight from the registers
@@ -534,6 +624,8 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnF32P p) {
     }
   }
 }
+
+#undef SX_ATTN_F32_KEY_ROW
 
 // merge of the key splits of one (head, sequence): thread d adds the partials in split order
 template <typename TT>
@@ -761,8 +853,11 @@ typedef float f32x16v_t __attribute__((ext_vector_type(16)));
 // KV8 (the FP8 cache): the K tile is 64 code bytes of the lane's half row (four 16-byte loads), a V step 4 code bytes; the k scale
 // multiplies the key's score row, the v scale the decoded operand (exact, see attn_f32_kernel) — the same bits as the fp32 kernel on the
 // dequantised cache.
-template <typename TT, bool V16, bool KV8 = false>
+// PAGED (the paged cache): k0 is a multiple of 32 and a page holds a multiple of 32 rows, so a tile lies in ONE page: one uniform table
+// lookup per tile; rows past kend (cancelled by P = 0) come from the tile's own page or the null page, finite either way.
+template <typename TT, bool V16, bool KV8 = false, bool PAGED = false>
 __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const AttnF32P p) {
+  static_assert(!(PAGED && KV8), "the paged cache has no FP8 form");
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int D = 128;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -785,8 +880,8 @@ __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const AttnF32P p) {
       qv[4 * e] = a[0] * p.scale; qv[4 * e + 1] = a[1] * p.scale; qv[4 * e + 2] = a[2] * p.scale; qv[4 * e + 3] = a[3] * p.scale;
     }
   }
-  const float* kh = p.kc + (size_t)g * p.seq_stride + (size_t)h * p.head_stride;
-  const size_t vbase = (size_t)g * p.seq_stride + (size_t)h * p.head_stride;
+  const float* kh = PAGED ? p.kc + (size_t)h * p.head_stride : p.kc + (size_t)g * p.seq_stride + (size_t)h * p.head_stride;
+  const size_t vbase = PAGED ? (size_t)h * p.head_stride : (size_t)g * p.seq_stride + (size_t)h * p.head_stride;
   const unsigned char* kc8 = (const unsigned char*)p.kc + vbase;                        // KV8: codes, same element strides
   const unsigned char* vc8 = (const unsigned char*)p.vc + vbase;
   const size_t sbase = (size_t)g * p.sc_seq_stride + (size_t)h * p.Tmax;                // KV8: the row scales of this (sequence, head)
@@ -801,8 +896,14 @@ __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const AttnF32P p) {
   const int vis = pos0 + qi;                                    // last key this lane's row may see
   for (int k0 = 0; k0 < kend; k0 += 32) {
     // ---- S^T tile = K[k0 .. k0+31] · Q^T ----
-    const int kr_ = min(k0 + l32, p.Tmax - 1);
-    const float* kr = kh + (size_t)kr_ * p.row_stride + half * 64;
+    size_t po = 0;                                               // PAGED: the tile's page (uniform); its rows are (k0 + ..) & pm inside it
+    int pm = -1;
+    if constexpr (PAGED) {
+      po = attn_page_off(p, g, k0 >> p.pshift);
+      pm = (1 << p.pshift) - 1;
+    }
+    const int kr_ = PAGED ? ((k0 + l32) & pm) : min(k0 + l32, p.Tmax - 1);
+    const float* kr = kh + po + (size_t)kr_ * p.row_stride + half * 64;
     f32x16v_t sacc;
 #pragma unroll
     for (int j = 0; j < 16; ++j) sacc[j] = 0.f;
@@ -861,8 +962,8 @@ __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const AttnF32P p) {
     // ---- O^T += V^T · P^T ----
 #pragma unroll
     for (int t = 0; t < 16; ++t) {
-      const int key = min(k0 + (t >> 2) * 8 + half * 4 + (t & 3), p.Tmax - 1);
-      const size_t vo = vbase + (size_t)key * p.row_stride + 4 * l32;
+      const int key = PAGED ? ((k0 + (t >> 2) * 8 + half * 4 + (t & 3)) & pm) : min(k0 + (t >> 2) * 8 + half * 4 + (t & 3), p.Tmax - 1);
+      const size_t vo = vbase + po + (size_t)key * p.row_stride + 4 * l32;
       float vv[4];
       if constexpr (KV8) {
         const unsigned w = *(const unsigned*)(vc8 + (size_t)key * p.row_stride + 4 * l32);
@@ -944,21 +1045,44 @@ extern "C" int sx_rmsnorm_planes(const float* x, const float* gamma, float* y32,
   return SX_OK;
 }
 
+// (page_table == NULL: the contiguous caches, cache_seq_stride between sequences; else the page pools, cache_seq_stride between pages)
 static int rope_kv_f32_impl(float* qkv, float* kcache, void* vcache, int v16, const float* cos_tab, const float* sin_tab,
                             const int32_t* pos0_dev, int G, int T, int H, int D, int Tmax, int64_t cache_seq_stride, int table_dtype,
-                            void* stream) {
+                            void* stream, const int32_t* page_table = nullptr, int page_shift = 0, int n_pages = 0) {
   SX_CHECK(qkv && kcache && vcache && cos_tab && sin_tab && pos0_dev, "sx_rope_kv_append_f32: null pointer");
   SX_CHECK(D % 2 == 0 && G >= 1 && T >= 1 && H >= 1, "sx_rope_kv_append_f32: D/G/T/H");
   SX_CHECK(table_dtype == SX_F16 || table_dtype == SX_BF16, "sx_rope_kv_append_f32: table_dtype");
   const int64_t n = (int64_t)G * T * H * (D / 2);
+  const int ptw = page_table ? (Tmax + (1 << page_shift) - 1) >> page_shift : 0;
 #define SX_ROPE_GO(TT, V16)                                                                                                            \
   hipLaunchKernelGGL((rope_kv_f32_kernel<TT, V16>), gs_grid(n), dim3(256), 0, ST, qkv, kcache, vcache, cos_tab, sin_tab, pos0_dev, T, H, D, \
                      Tmax, G, (long long)cache_seq_stride)
+#define SX_ROPE_PAGED_GO(TT, V16)                                                                                                      \
+  hipLaunchKernelGGL((rope_kv_f32_paged_kernel<TT, V16>), gs_grid(n), dim3(256), 0, ST, qkv, kcache, vcache, cos_tab, sin_tab, pos0_dev, T, \
+                     H, D, Tmax, G, (long long)cache_seq_stride, page_table, page_shift, n_pages, ptw)
+  if (page_table) {
+    if (table_dtype == SX_BF16) { if (v16) SX_ROPE_PAGED_GO(BF16, true); else SX_ROPE_PAGED_GO(BF16, false); }
+    else { if (v16) SX_ROPE_PAGED_GO(F16, true); else SX_ROPE_PAGED_GO(F16, false); }
+  } else
   if (table_dtype == SX_BF16) { if (v16) SX_ROPE_GO(BF16, true); else SX_ROPE_GO(BF16, false); }
   else { if (v16) SX_ROPE_GO(F16, true); else SX_ROPE_GO(F16, false); }
 #undef SX_ROPE_GO
+#undef SX_ROPE_PAGED_GO
   SX_HIP_LAUNCH_CHECK();
   return SX_OK;
+}
+
+extern "C" int sx_rope_kv_append_f32_paged(float* qkv, float* kpool, void* vpool, int v16, const float* cos_tab, const float* sin_tab,
+                                           const int32_t* pos0_dev, const int32_t* page_table, int G, int T, int H, int D, int Tmax,
+                                           int page_shift, int n_pages, int64_t page_stride, int table_dtype, void* stream) {
+  SX_CHECK(page_table, "sx_rope_kv_append_f32_paged: page_table is NULL (the contiguous cache is sx_rope_kv_append_f32 / _v16)");
+  SX_CHECK(page_shift >= 5 && page_shift <= 7, "sx_rope_kv_append_f32_paged: page_shift %d (pages hold 32, 64 or 128 rows)", page_shift);
+  SX_CHECK(D == 128, "sx_rope_kv_append_f32_paged: head_dim %d (the paged cache exists for head_dim 128 only)", D);
+  SX_CHECK(n_pages >= 1 && Tmax >= 1 && page_stride >= ((int64_t)H << page_shift) * D, "sx_rope_kv_append_f32_paged: n_pages=%d Tmax=%d page_stride=%lld "
+           "(pools are [n_pages + 1][H][page size][D])", n_pages, Tmax, (long long)page_stride);
+  SX_CHECK(v16 == 0 || v16 == 1, "sx_rope_kv_append_f32_paged: v16");
+  return rope_kv_f32_impl(qkv, kpool, vpool, v16, cos_tab, sin_tab, pos0_dev, G, T, H, D, Tmax, page_stride, table_dtype, stream, page_table,
+                          page_shift, n_pages);
 }
 
 extern "C" int sx_rope_kv_append_f32(float* qkv, float* kcache, float* vcache, const float* cos_tab, const float* sin_tab,
@@ -997,6 +1121,16 @@ extern "C" int sx_rope_kv_append_f32_q8(float* qkv, void* kcodes, void* vcodes, 
   return SX_OK;
 }
 
+// the paged launches of sx_attention_f32: the D = 128 forms of the fp32 / mixed cache, one instantiation each beside the contiguous one
+template <typename TT, bool V16>
+static void attn_f32_paged_launch(const sx_attn_f32_args* a, const AttnF32P& p, bool mfma, void* stream) {
+  if (a->T == 1 && a->nsplit > 1) hipLaunchKernelGGL((attn_f32_kernel<TT, 1, 1, V16, true, 0, true>), dim3(a->nsplit, a->H, a->G), dim3(256), 0, ST, p);
+  else if (mfma) hipLaunchKernelGGL((attn_f32_mfma_kernel<TT, V16, false, true>), dim3((a->T + 127) / 128, a->H, a->G), dim3(256), 0, ST, p);
+  else if (a->T > 8) hipLaunchKernelGGL((attn_f32_kernel<TT, 8, 1, V16, false, 0, true>), dim3((a->T + 7) / 8, a->H, a->G), dim3(256), 0, ST, p);
+  else if (a->T == 1) hipLaunchKernelGGL((attn_f32_kernel<TT, 1, 1, V16, false, 0, true>), dim3(1, a->H, a->G), dim3(256), 0, ST, p);
+  else hipLaunchKernelGGL((attn_f32_kernel<TT, 4, 1, V16, false, 0, true>), dim3((a->T + 3) / 4, a->H, a->G), dim3(256), 0, ST, p);
+}
+
 static int g_attn_f32_mfma = 1;    // 0: chunks above 8 tokens keep the VALU kernel (A/B and the bit-reference of the tests)
 extern "C" int sx_attention_f32_variant(int v) {
   SX_CHECK(v == 0 || v == 1, "sx_attention_f32_variant: 0 (VALU kernels only) or 1 (fp32 MFMA kernel for chunks above 8 tokens)");
@@ -1024,6 +1158,21 @@ extern "C" int sx_attention_f32(const sx_attn_f32_args* a, void* stream) {
   p.part = a->scratch; p.nsplit = a->nsplit;
   p.cos_t = a->rope_cos; p.sin_t = a->rope_sin; p.knew = a->k_new; p.vnew = a->v_new;
   p.ks = a->k_scale; p.vs = a->v_scale; p.sc_seq_stride = a->scale_seq_stride;
+  p.ptab = a->page_table; p.pshift = a->page_shift; p.npages = a->n_pages; p.ptw = 0;
+  if (a->page_table) {
+    // the paged cache: kcache / vcache are the page pools; only the D = 128 forms of the fp32 / mixed cache read a table
+    SX_CHECK(a->D == 128, "sx_attention_f32: a page table needs head_dim 128, not %d (the paged cache has no other form)", a->D);
+    SX_CHECK(a->kv_fp8 == 0, "sx_attention_f32: a page table and kv_fp8 exclude each other (paged row scales are not built)");
+    SX_CHECK(!(a->rope_cos && a->T > 1), "sx_attention_f32: a page table and the verify form (rope_cos with T > 1) exclude each other (the verify "
+             "kernel reads the contiguous cache only)");
+    SX_CHECK(a->causal && a->kv_row_stride <= 0 && a->kv_head_stride <= 0, "sx_attention_f32: a page table is the causal form over the pool layout (no K / V strides)");
+    SX_CHECK(a->page_shift >= 5 && a->page_shift <= 7, "sx_attention_f32: page_shift %d (pages hold 32, 64 or 128 rows)", a->page_shift);
+    SX_CHECK(a->n_pages >= 1 && a->page_stride >= ((int64_t)a->H << a->page_shift) * a->D && a->page_stride % 8 == 0,
+             "sx_attention_f32: n_pages=%d page_stride=%lld (pools are [n_pages + 1][H][page size][D], 16-B aligned pages)", a->n_pages, (long long)a->page_stride);
+    p.seq_stride = a->page_stride;
+    p.head_stride = ((int64_t)1 << a->page_shift) * p.row_stride;
+    p.ptw = (a->Tmax + (1 << a->page_shift) - 1) >> a->page_shift;
+  }
   // the FP8 KV cache: 1 = codes + row scales, 2 = fp32 caches with quantise-dequantise on append (only the fused RoPE form appends:
   // without it 2 IS the fp32 call, on a cache that already holds dequantised values)
   SX_CHECK(a->kv_fp8 >= 0 && a->kv_fp8 <= 2, "sx_attention_f32: kv_fp8 must be 0 (off), 1 (e4m3 codes + row scales) or 2 (fp32 caches, quantise-dequantise on append)");
@@ -1042,6 +1191,24 @@ extern "C" int sx_attention_f32(const sx_attn_f32_args* a, void* stream) {
     SX_CHECK(a->T >= 1 && a->T <= 8 && a->causal && a->D == 128 && a->rope_sin && a->k_new && a->v_new && a->kv_row_stride <= 0 + (int64_t)a->D,
              "sx_attention_f32: the fused RoPE form is the causal step of T <= 8 rows per sequence at head_dim 128 over the cache layout (rope_sin, k_new, v_new set)");
     SX_CHECK((((uintptr_t)a->k_new) & 15) == 0 && (((uintptr_t)a->v_new) & 15) == 0, "sx_attention_f32: k_new / v_new alignment");
+  }
+  if (a->page_table) {
+    // split + combine for the T = 1 step of few sequences, else the one launch the contiguous cache would get
+    // (in front of the contiguous dispatch below: none of its branches reads a table)
+    const bool split = a->T == 1 && a->nsplit > 1;
+    const bool mfma = g_attn_f32_mfma && a->T > 8 && !tiled && (((uintptr_t)a->out) & 7) == 0 && a->q_row_stride % 4 == 0;   // (causal, D = 128: checked above)
+    SX_CHECK(!a->v16 || (p.row_stride % 8 == 0 && p.seq_stride % 8 == 0), "sx_attention_f32: a 16-bit V pool needs 16-B aligned rows");
+    SX_CHECK(!split || (a->scratch && a->nsplit <= 64), "sx_attention_f32: key splits need scratch [G][H][nsplit][D + 2] floats and nsplit <= 64");
+    SX_CHECK(a->v16 == 0 || a->v16 == 1, "sx_attention_f32: v16");
+    if (dt == SX_BF16) { if (a->v16) attn_f32_paged_launch<BF16, true>(a, p, mfma, stream); else attn_f32_paged_launch<BF16, false>(a, p, mfma, stream); }
+    else { if (a->v16) attn_f32_paged_launch<F16, true>(a, p, mfma, stream); else attn_f32_paged_launch<F16, false>(a, p, mfma, stream); }
+    SX_HIP_LAUNCH_CHECK();
+    if (split) {
+      if (dt == SX_BF16) hipLaunchKernelGGL(attn_f32_combine_kernel<BF16>, dim3(a->H, a->G), dim3(128), 0, ST, p);
+      else hipLaunchKernelGGL(attn_f32_combine_kernel<F16>, dim3(a->H, a->G), dim3(128), 0, ST, p);
+      SX_HIP_LAUNCH_CHECK();
+    }
+    return SX_OK;
   }
   if (a->rope_cos && a->T > 1) {
     // the verify form: T = K + 1 rows per sequence, key splits + combine over G*T rows (nsplit = 1 included: one split per row)

@@ -15,6 +15,9 @@ choose the slots of a round: a request whose prompt starts like a slot's record 
 gets them copied from the donor slot by one sx_kv_fork launch, and prefills only the rest. The requests admitted per pass, hence the
 decode-step counts, are those of the plain schedule; ``simulate_prefix`` is ``simulate``'s counterpart with the token counts.
 
+On a paged KV cache (``LlamaForCausalLM(kv_pages=N)``) a request is admitted only when the pages for its prompt and budget are free:
+``SlotScheduler.admit(fits)`` stops a round at a queue head that does not fit, and ``simulate_paged`` is ``simulate`` with that gate.
+
 ``SlotScheduler`` turns finish events into admissions; ``simulate`` drives it with known lengths and counts steps, which is what
 the tests compare the engine's ``last_inflight_stats`` with and what tools/bench_inflight.py prints next to its wall clocks. A forced
 image block is a host-driven chunk that takes no decode step: give ``simulate`` a request's length minus its chunk tokens.
@@ -35,13 +38,17 @@ class SlotScheduler:
         """Start an admission pass: resets the pass's quota."""
         self.quota = self.n_slots if self.max_admit is None else int(self.max_admit)
 
-    def admit(self):
-        """One round of the current pass: [(slot, request)] for the free slots, lowest slot first, queue head first."""
+    def admit(self, fits=None):
+        """One round of the current pass: [(slot, request)] for the free slots, lowest slot first, queue head first.
+        ``fits(slot, request)`` (the paged KV cache: it reserves the request's pages for the slot, or returns False): a queue head that
+        does not fit WAITS — the round ends there and nothing overtakes it, so admission stays first in, first out."""
         out = []
         for g in range(self.n_slots):
             if not self.queue or self.quota <= 0:
                 break
             if self.slot_req[g] is None:
+                if fits is not None and not fits(g, self.queue[0]):
+                    break
                 self.slot_req[g] = self.queue.popleft()
                 self.quota -= 1
                 out.append((g, self.slot_req[g]))
@@ -107,6 +114,62 @@ def simulate(lengths, n_slots, max_admit=None):
             made[g] += 1
             if made[g] >= lengths[sch.slot_req[g]]:
                 stats["finish_order"].append(sch.finish(g))
+    return stats
+
+
+def simulate_paged(prompt_lens, lengths, n_slots, n_pages, page_size, max_admit=None, budgets=None):
+    """``simulate`` on a paged KV cache of ``n_pages`` pages of ``page_size`` rows (paging.PagePool): request i is admitted only when
+    the pages for its ``prompt_lens[i]`` prompt rows plus its budget are free, and holds them until it finishes; a queue head that does
+    not fit waits for a finishing request's pages and nothing overtakes it. ``budgets[i]``: the rows reserved beyond the prompt (the
+    request's ``max_new_tokens``); None: ``lengths[i]`` — the two differ for a request that stops early (EOS) or whose ``lengths``
+    entry leaves out a forced image chunk's tokens, as for ``simulate``. Returns simulate's dict plus page_waits (admission rounds
+    that ended at a queue head that did not fit while a slot was free) and peak_pages (most pages held at once). With an ample pool the
+    counts are simulate's. ValueError for a request that can never fit."""
+    from .paging import PagePool, pages_for
+    lengths = [int(n) for n in lengths]
+    budgets = lengths if budgets is None else [int(b) for b in budgets]
+    rows = [int(p) + b for p, b in zip(prompt_lens, budgets)]
+    assert len(rows) == len(lengths) and all(n >= 1 for n in lengths)
+    for i, n in enumerate(rows):
+        if pages_for(n, page_size) > n_pages:
+            raise ValueError(f"simulate_paged: request {i} needs {pages_for(n, page_size)} pages of {page_size} rows for {n} rows, "
+                             f"the pool holds {n_pages}")
+    pool = PagePool(n_pages, page_size, n_slots, max(rows))
+    sch = SlotScheduler(n_slots, len(lengths), max_admit)
+    made = {}
+    stats = dict(decode_steps=0, live_slot_steps=0, parked_slot_steps=0, admissions=0, prefill_passes=0, finish_order=[], page_waits=0,
+                 peak_pages=0)
+
+    def finish(g):
+        stats["finish_order"].append(sch.finish(g))
+        pool.release(g)
+
+    while not sch.done:
+        sch.new_pass()
+        before = stats["admissions"]
+        while True:
+            adm = sch.admit(lambda g, r: pool.reserve(g, rows[r]))
+            if not adm:
+                stats["page_waits"] += bool(sch.queue and sch.quota > 0 and sch.free_slots())
+                break
+            stats["admissions"] += len(adm)
+            stats["prefill_passes"] += 1
+            for g, r in adm:
+                made[g] = 1                                   # token 1 comes from the admission prefill
+                if made[g] >= lengths[r]:
+                    finish(g)
+        live = sch.live_slots()
+        assert live or sch.done or stats["admissions"] > before, "a request that fits an empty pool is always admitted"
+        if not live:
+            continue
+        stats["decode_steps"] += 1
+        stats["live_slot_steps"] += len(live)
+        stats["parked_slot_steps"] += n_slots - len(live)
+        for g in live:
+            made[g] += 1
+            if made[g] >= lengths[sch.slot_req[g]]:
+                finish(g)
+    stats["peak_pages"] = pool.peak
     return stats
 
 

@@ -50,6 +50,21 @@ logits, past_key_values, hidden_states with the LAST entry = post-final-norm sta
     weights per prefill pass (0.53 / 1.03 B read + 2 B written per weight). Measured at 13B dims (profiles/weight_residency.md): 25.1 GB
     less held; + 4.3 .. 8.2 ms per pass, which is + 5 % of a 2048-row prefill (150 ms) but + 31 .. 35 % of the 8-row suffix prefills
     (14.5 ms) that in-flight batching with prefix reuse lives on; the token step is unchanged.
+  * ``kv_pages=N`` (opt-in, exact; ``kv_page_size`` 32 / 64 / 128 rows, default 64; precise mode, head_dim 128, single rank): the paged KV
+    cache — per layer ONE pool of N pages [N + 1][heads][page size][128] (k fp32, v fp32 or 16-bit under ``kv_v16``) shared by every
+    slot, instead of ``max_cache_len`` rows per slot, and one int32 page table [max_batch][ceil(max_cache_len / page size)] for all
+    layers (the same page index names a slot's rows in every layer's pool). ``max_cache_len`` stays the per-slot ceiling (table width,
+    RoPE tables, split arithmetic); it no longer sizes the cache. Page 0 is the NULL page: all zeros, never handed out, never written;
+    a table entry without a reservation names it, so reads of rows nobody owns hit finite zeros and an append there writes nothing.
+    ``kv_reserve(seq, n_rows)`` extends a sequence's pages (paging.PagePool: LIFO free list, deterministic), ``kv_release(seq)``,
+    ``reset`` and ``park_slots`` give them back; the host writes table rows only OUTSIDE captured graphs, and the captured token step
+    reads the table from device memory at replay. Only the ADDRESS of a key row changes: a paged model computes, bit for bit, what
+    the contiguous model computes (tests/test_kv_paged_gpu.py: torch.equal). Prefill and chunk passes reserve what they append;
+    whoever drives ``decode_step`` directly reserves the rows its steps will write (the generate* engines reserve prompt +
+    ``max_new_tokens`` up front). ``past_key_values`` are gathered copies. Follow-ups, refused with a ValueError today: the paged FP8
+    cache (``kv_format``: paged row scales), the verify step of speculative decoding (``spec_tokens``: the verify kernel reads the
+    contiguous cache), prefix reuse (``agent.prefix_cache``: sharing pages by reference in place of sx_kv_fork copies),
+    tensor-parallel ranks, and preemption or swapping of a live request. Cost and the choice of 64 rows: profiles/kv_paged.md
   * ``comm`` with world > 1: Megatron tensor parallelism (parallel.py) — this rank owns nh/tp heads (their q/k/v rows, KV
     cache and o_proj columns), I/tp FFN rows (gate/up rows, down_proj columns) and Vpad/tp lm_head rows; the fp32
     residual stream is all-reduced after o_proj and down_proj (rank 0's GEMM epilogue adds the residual), the logits are
@@ -208,7 +223,7 @@ class LlamaForCausalLM:
     WEIGHT_RESIDENCIES = (None, "tiles")
 
     def __init__(self, config, max_cache_len=None, max_batch=1, comm=None, precise=None, kv_v16=None, weight_format=None, kv_format=None,
-                 weight_residency=None, max_adapters=0, lora_rank=32, spec_tokens=0):
+                 weight_residency=None, max_adapters=0, lora_rank=32, spec_tokens=0, kv_pages=0, kv_page_size=64):
         self.config = config if not isinstance(config, dict) else LlamaConfigLite(**config)
         c = self.config
         self.H, self.nh, self.L = c.hidden_size, c.num_attention_heads, c.num_hidden_layers
@@ -344,6 +359,30 @@ class LlamaForCausalLM:
                                  "KV cache form)")
             if self.max_adapters:
                 raise ValueError("LlamaForCausalLM: spec_tokens and max_adapters > 0 exclude each other (the adapter token step has no verify form)")
+        # paged KV cache (module docstring; opt-in: ``kv_pages=N`` pages of ``kv_page_size`` rows shared by every slot). 0: nothing is
+        # allocated and nothing is launched differently. Never a fall-back: what the paged kernels do not cover is refused here
+        self.kv_pages, self.kv_page_size = int(kv_pages), int(kv_page_size)
+        self._pool = None                # paging.PagePool, made by _pack
+        if self.kv_pages < 0:
+            raise ValueError(f"LlamaForCausalLM: kv_pages={kv_pages} must be >= 0 (0: the contiguous cache)")
+        if self.kv_pages:
+            from .paging import PAGE_SIZES
+            if self.kv_page_size not in PAGE_SIZES:
+                raise ValueError(f"LlamaForCausalLM: kv_page_size must be 32, 64 or 128 (powers of two and multiples of the MFMA prefill "
+                                 f"kernel's 32-key tile, so no tile straddles a page), not {kv_page_size!r}")
+            if not self.precise:
+                raise ValueError("LlamaForCausalLM: kv_pages needs the precise mode (only the fp32 cache kernels read a page table; the plain "
+                                 "16-bit flow's cache has no paged form)")
+            if self.hd != 128:
+                raise ValueError(f"LlamaForCausalLM: kv_pages needs head_dim 128, not {self.hd} (the paged kernels are the head_dim 128 forms)")
+            if tp > 1:
+                raise ValueError("LlamaForCausalLM: kv_pages needs a single rank (tensor-parallel ranks are a follow-up)")
+            if kv_format is not None:
+                raise ValueError(f"LlamaForCausalLM: kv_pages and kv_format={kv_format!r} exclude each other for now (follow-up: paged row "
+                                 "scales for the FP8 cache)")
+            if self.spec_tokens:
+                raise ValueError("LlamaForCausalLM: kv_pages and spec_tokens > 0 exclude each other for now (follow-up: a page table in the "
+                                 "verify kernel)")
         self._adapters = {}              # name -> table slot
         self._sel_host = [-1] * self.G   # host mirror of P["lora"]["sel"]: the adapter slot of every sequence, -1 = none
         self.device, self.dtype = None, torch.float16
@@ -360,11 +399,14 @@ class LlamaForCausalLM:
             return "FP8 e4m3 codes + fp32 row scales"
         if self.kv_format == "fp8_e4m3_emulated":
             return "fp32 holding FP8-e4m3-rounded rows (the reference twin)"
-        return "k fp32 + v 16-bit" if self.kv_v16 else "fp32"
+        return ("k fp32 + v 16-bit" if self.kv_v16 else "fp32") + \
+            (f", paged: {self.kv_pages} pages of {self.kv_page_size} rows" if self.kv_pages else "")
 
     def _kv_kw(self, li, s=slice(None)):
         """What ops.rope_kv_append_f32 / attention_f32 take beyond the caches under ``kv_format``: layer li's row scales of the sequences
-        ``s``, or the emulate flag."""
+        ``s``, or the emulate flag. Paged cache: the page table rows of the sequences ``s`` (and the per-slot ceiling)."""
+        if self.kv_pages:
+            return {"paged": (self._P["ptab"][s], self.Tmax)}
         if self.kv_format == "fp8_e4m3":
             return {"kv_scales": (self._P["ks"][li][s], self._P["vs"][li][s])}
         if self.kv_format == "fp8_e4m3_emulated":
@@ -428,6 +470,8 @@ class LlamaForCausalLM:
             # half a byte per weight + one E8M0 byte per 32 weights, one layout per projection; lm_head's tiles stay 16-bit
             tiles = self.L * (per_layer // 4 + per_layer // 64) + self.V_l * self.H * 2
         kv = self.L * self.G * self.nh_l * self.Tmax * self.hd * ((4 + (2 if self.kv_v16 else 4)) if self.precise else 4)
+        if self.kv_pages:                       # the pool (null page included), whatever max_batch x max_cache_len would come to
+            kv = self.L * (self.kv_pages + 1) * self.nh_l * self.kv_page_size * self.hd * (4 + (2 if self.kv_v16 else 4))
         if self.kv_format == "fp8_e4m3":        # one byte per k and per v value + the two fp32 row scales (the emulated twin: all fp32, above)
             kv = self.L * self.G * self.nh_l * self.Tmax * (2 * self.hd + 8)
         # adapter tables (max_adapters slots): A and B of the seven projections in 16 bits, the three norms' gammas and the scale in fp32
@@ -665,6 +709,16 @@ class LlamaForCausalLM:
             P["vs"] = torch.zeros_like(P["ks"])
             held = sum(P[k].numel() * P[k].element_size() for k in ("kc", "vc", "ks", "vs"))
             assert held == fp["kv_cache"], (held, fp["kv_cache"])          # memory_footprint() prices what is held
+        elif self.kv_pages:
+            # the page pools, all zeros (page 0 stays so: the null page), and ONE page table for all layers; the table's pointer never
+            # changes, its rows are written by kv_reserve / kv_release outside captured graphs
+            from .paging import PagePool
+            P["kc"] = torch.zeros((self.L, self.kv_pages + 1, self.nh_l, self.kv_page_size, self.hd), dtype=torch.float32, device=dev)
+            P["vc"] = torch.zeros_like(P["kc"], dtype=dt) if self.kv_v16 else torch.zeros_like(P["kc"])
+            self._pool = PagePool(self.kv_pages, self.kv_page_size, G, self.Tmax)
+            P["ptab"] = torch.zeros((G, self._pool.width), dtype=torch.int32, device=dev)
+            held = sum(P[k].numel() * P[k].element_size() for k in ("kc", "vc"))
+            assert held == fp["kv_cache"], (held, fp["kv_cache"])          # memory_footprint() prices what is held
         else:
             P["kc"] = torch.zeros((self.L, G, self.nh_l, self.Tmax, self.hd), dtype=torch.float32 if self.precise else dt,
                                   device=dev)                                                      # this rank's heads
@@ -805,10 +859,62 @@ class LlamaForCausalLM:
         for g, a in zip(seqs, idx):
             self._sel_host[g] = a
 
+    # ---- paged KV cache (paging.py) -----------------------------------------------------------------------------------------
+    @property
+    def kv_pages_free(self):
+        """Pages of the pool nobody holds (``kv_pages`` on a model that holds no sequence)."""
+        if not self.kv_pages:
+            raise ValueError("LlamaForCausalLM.kv_pages_free: the model was built with kv_pages=0 (the contiguous cache)")
+        self._pack()
+        return self._pool.free
+
+    def kv_reserve(self, seq, n_rows):
+        """Sequence ``seq`` may hold ``n_rows`` cache rows from now on: its page list is EXTENDED to cover them (idempotent; pages already
+        held stay where they are) and its row of the device page table is rewritten — one small host → device copy, never inside a
+        captured graph. False: the free pages do not cover it (or n_rows exceeds ``max_cache_len``) and nothing changed."""
+        if not self.kv_pages:
+            raise ValueError("LlamaForCausalLM.kv_reserve: the model was built with kv_pages=0 (the contiguous cache)")
+        P = self._pack()
+        had = len(self._pool.pages(seq))
+        if not self._pool.reserve(seq, n_rows):
+            return False
+        if len(self._pool.pages(seq)) != had:
+            P["ptab"][seq].copy_(torch.tensor(self._pool.table_row(seq), dtype=torch.int32))
+        return True
+
+    def kv_release(self, seq=None):
+        """Gives the pages of sequence ``seq`` (None: of every sequence) back to the pool; its table row names the null page again."""
+        if not self.kv_pages:
+            raise ValueError("LlamaForCausalLM.kv_release: the model was built with kv_pages=0 (the contiguous cache)")
+        P = self._pack()
+        for g in (range(self.G) if seq is None else [seq]):
+            if self._pool.release(g):
+                P["ptab"][g].zero_()
+
+    def _kv_need(self, seq, n_rows, what):
+        """kv_reserve or a RuntimeError that names the shortfall."""
+        if not self.kv_reserve(seq, n_rows):
+            pool = self._pool
+            raise RuntimeError(f"LlamaForCausalLM: {what}: sequence {seq} needs {n_rows} cache rows = {pool.need(seq, n_rows)} more pages of "
+                               f"{pool.page_size} rows, but {pool.free} of the pool's {pool.n_pages} pages are free (per-slot ceiling "
+                               f"max_cache_len = {self.Tmax} rows): build the model with more kv_pages or release a sequence")
+
+    def _kv_gather(self, li, seq, n_rows):
+        """Contiguous copies [heads, n_rows, hd] of layer li's k and v rows of sequence ``seq`` (plumbing: past_key_values, tests)."""
+        P = self._P
+        idx = torch.tensor(self._pool.table_row(seq), dtype=torch.int64, device=self.device)
+        out = []
+        for c in (P["kc"][li], P["vc"][li]):
+            rows = c[idx].permute(1, 0, 2, 3).reshape(self.nh_l, -1, self.hd)      # [heads, width * page size, hd]
+            out.append(rows[:, :n_rows].contiguous())
+        return tuple(out)
+
     # ---- core passes ---------------------------------------------------------------------------------------------------
     def reset(self, seq=None):
         P = self._pack()
         self.kv_epoch += 1              # invalidates ContinuousLVLM's cross-turn prefix bookkeeping
+        if self.kv_pages:
+            self.kv_release(seq)
         s = slice(None) if seq is None else slice(seq, seq + 1)
         P["pos"][s] = 0
         P["step"][s] = 0
@@ -837,6 +943,9 @@ class LlamaForCausalLM:
         pos0 = [pos_all[g] for g in seqs]
         for T, p0 in zip(Ts, pos0):
             assert p0 + T <= self.Tmax, f"sequence {p0 + T} exceeds the KV cache ({self.Tmax})"
+        if self.kv_pages:               # paged cache: the pass holds pages for every row it appends (a no-op where the caller reserved more)
+            for g, T, p0 in zip(seqs, Ts, pos0):
+                self._kv_need(g, p0 + T, f"a pass of {T} rows at position {p0}")
         uniform = n > 1 and len(set(Ts)) == 1 and len(set(pos0)) == 1 and list(seqs) == list(range(seqs[0], seqs[0] + n))
         offs = [0]
         for T in Ts:
@@ -872,21 +981,24 @@ class LlamaForCausalLM:
                 h = norm(x, li, "ln1")
                 qkv = ops.gemm(h, wmat(lw, "wqkv"), a_planes=2, out_dtype=torch.float32, **delta(h, li, "qkv"))    # [M, 3H] fp32
                 # (kv_format: the append quantises; the emulated twin's attention is the plain fp32 call on its rounded rows)
+                # paged cache: the caches are the layer's whole pools and the sequences' table rows ride in kw["paged"]
+                cs = (lambda c, a, b: c) if self.kv_pages else (lambda c, a, b: c[a:b])
+                akw = lambda kw: {k: kw[k] for k in ("kv_scales", "paged") if k in kw}   # (attention: the emulated twin is the plain call)
                 if uniform:
                     kw = self._kv_kw(li, slice(g0, g0 + n))
-                    ops.rope_kv_append_f32(qkv, kc_l[g0:g0 + n], vc_l[g0:g0 + n], P["cos"], P["sin"], P["pos"][g0:g0 + n], n, Ts[0],
+                    ops.rope_kv_append_f32(qkv, cs(kc_l, g0, g0 + n), cs(vc_l, g0, g0 + n), P["cos"], P["sin"], P["pos"][g0:g0 + n], n, Ts[0],
                                            nh, hd, dt, **kw)
-                    att = ops.attention_f32(qkv, kc_l[g0:g0 + n], vc_l[g0:g0 + n], P["pos"][g0:g0 + n], n, Ts[0], nh, hd, scale, dt,
-                                            kv_scales=kw.get("kv_scales"))
+                    att = ops.attention_f32(qkv, cs(kc_l, g0, g0 + n), cs(vc_l, g0, g0 + n), P["pos"][g0:g0 + n], n, Ts[0], nh, hd, scale, dt,
+                                            **akw(kw))
                 else:
                     att = torch.empty((M, 2 * H), dtype=dt, device=x.device)
                     for i, g in enumerate(seqs):
                         rows = qkv[offs[i]:offs[i + 1]]
                         kw = self._kv_kw(li, slice(g, g + 1))
-                        ops.rope_kv_append_f32(rows, kc_l[g:g + 1], vc_l[g:g + 1], P["cos"], P["sin"], P["pos"][g:g + 1], 1, Ts[i], nh,
+                        ops.rope_kv_append_f32(rows, cs(kc_l, g, g + 1), cs(vc_l, g, g + 1), P["cos"], P["sin"], P["pos"][g:g + 1], 1, Ts[i], nh,
                                                hd, dt, **kw)
-                        att[offs[i]:offs[i + 1]] = ops.attention_f32(rows, kc_l[g:g + 1], vc_l[g:g + 1], P["pos"][g:g + 1], 1, Ts[i],
-                                                                     nh, hd, scale, dt, kv_scales=kw.get("kv_scales"))
+                        att[offs[i]:offs[i + 1]] = ops.attention_f32(rows, cs(kc_l, g, g + 1), cs(vc_l, g, g + 1), P["pos"][g:g + 1], 1, Ts[i],
+                                                                     nh, hd, scale, dt, **akw(kw))
                 x = comm.all_reduce(ops.gemm(att, wmat(lw, "wo"), a_planes=2, residual=x if lead else None, out_dtype=torch.float32,
                                              **delta(att, li, "o")))
                 h = norm(x, li, "ln2")
@@ -1028,14 +1140,15 @@ class LlamaForCausalLM:
             else:
                 h = norm(x, li, "ln1")
                 qkv = lin(h, lw, "wqkv", **delta(h, li, "qkv"))                       # [G, 3H] fp32
-            kw = self._kv_kw(li)    # kv_format: the row scales of the FP8 cache, or the emulate flag of its fp32 twin
+            kw = self._kv_kw(li)    # kv_format: the row scales of the FP8 cache, or the emulate flag of its fp32 twin; kv_pages: the page table
             if fuse_rope:           # RoPE + KV append inside the attention launch (one graph node per layer instead of two)
                 att = ops.attention_f32(qkv, P["kc"][li], P["vc"][li], P["pos"], G, T, nh, hd, scale, dt, tiled=tl,
                                         nsplit=self.decode_nsplit_f32, scratch=part, rope=(P["cos"], P["sin"]), **kw)
             else:
                 ops.rope_kv_append_f32(qkv, P["kc"][li], P["vc"][li], P["cos"], P["sin"], P["pos"], G, 1, nh, hd, dt, **kw)
                 att = ops.attention_f32(qkv, P["kc"][li], P["vc"][li], P["pos"], G, 1, nh, hd, scale, dt, tiled=tl,
-                                        nsplit=self.decode_nsplit_f32, scratch=P["attn_f32_part"], kv_scales=kw.get("kv_scales"))
+                                        nsplit=self.decode_nsplit_f32, scratch=P["attn_f32_part"],
+                                        **{k: kw[k] for k in ("kv_scales", "paged") if k in kw})
             if fold:
                 # residual GEMV: fp32 x, the planes of x * gamma of the NEXT norm, the rows' sums of squares; GLU epilogue: planes directly
                 x, x16, ssq = lin(att, lw, "wo", residual=x, emit_norm=True, planes_out=True, norm_gamma=lw["ln2"])
@@ -1088,6 +1201,8 @@ class LlamaForCausalLM:
         x = inputs_embeds.to(device=self.device, dtype=torch.float32).contiguous()
         T = x.shape[0]
         if T == 1 and self.G == 1:
+            if self.kv_pages:           # (the multi-row pass reserves for itself; this one runs the token step's layers)
+                self._kv_need(seq, int(P["pos"][seq].item()) + 1, "a one-token pass")
             x = self._layers_single(x)
         else:
             x = self._layers_multi(x, [T], [seq])
@@ -1187,6 +1302,9 @@ class LlamaForCausalLM:
             tab = quant.decode_table(self.device)
             deq = lambda c, sc: (tab[c[0][:, :Tk].long()] * sc[0][:, :Tk, None]).unsqueeze(0)
             pkv = tuple((deq(P["kc"][li], P["ks"][li]), deq(P["vc"][li], P["vs"][li])) for li in range(self.L))
+        elif use_cache and self.kv_pages:
+            # gathered COPIES of sequence 0's pages (plumbing, like the FP8 cache's dequantised copies)
+            pkv = tuple(tuple(t.unsqueeze(0) for t in self._kv_gather(li, 0, Tk)) for li in range(self.L))
         else:
             pkv = tuple((P["kc"][li][0][:, :Tk].unsqueeze(0), P["vc"][li][0][:, :Tk].unsqueeze(0)) for li in range(self.L)) \
                 if use_cache else None
@@ -1230,6 +1348,9 @@ class LlamaForCausalLM:
         self._slot_write(state.live, slots, 0)
         for k, v in SlotState.IDLE.items():
             self._slot_write(P[k], slots, v)
+        if self.kv_pages:
+            for g in slots:
+                self.kv_release(g)
         if self.max_adapters:
             self.set_adapters(slots, [None] * len(slots))
 

@@ -771,13 +771,36 @@ def _kv_scales_ok(kv_scales, kcache, vcache):
     return ks, vs
 
 
-def rope_kv_append_f32(qkv, kcache, vcache, cos_tab, sin_tab, pos_dev, G, T, H, D, table_dtype, kv_scales=None, kv_emulate=False):
+def _paged_ok(paged, kcache, vcache, G, H, D):
+    """The paged cache's tensors: pools [n_pages + 1, H, page size, 128] (k fp32; v fp32 or 16-bit) and ``paged`` = (page table int32
+    [G, ceil(Tmax / page size)] on the device, Tmax). Returns (table, Tmax, page shift, n_pages)."""
+    table, Tmax = paged
+    ps = kcache.shape[2]
+    assert kcache.dim() == 4 and kcache.is_contiguous() and vcache.is_contiguous() and vcache.shape == kcache.shape
+    assert kcache.shape[0] >= 2 and kcache.shape[1] == H and kcache.shape[3] == D and ps in (32, 64, 128), "pools are [n_pages + 1, H, 32 | 64 | 128, D]"
+    assert table.dtype == torch.int32 and table.is_contiguous() and table.device == kcache.device and table.dim() == 2
+    assert table.shape[0] >= G and table.shape[1] == (int(Tmax) + ps - 1) // ps, "page table: int32 [G, ceil(Tmax / page size)]"
+    return table, int(Tmax), ps.bit_length() - 1, kcache.shape[0] - 1
+
+
+def rope_kv_append_f32(qkv, kcache, vcache, cos_tab, sin_tab, pos_dev, G, T, H, D, table_dtype, kv_scales=None, kv_emulate=False,
+                       paged=None):
     """qkv fp32 [G*T, 3HD] (q rotated in place); caches [G, H, Tmax, D]: k fp32, v fp32 or — the mixed cache — the model's 16-bit dtype
     (= table_dtype); pos_dev int32 [G].
+    paged=(page table, Tmax): the paged cache — kcache / vcache are the page pools [n_pages + 1, H, page size, D] and the row of position
+    p of sequence g goes to page table[g, p // page size] (entry 0: nothing is written). Row g of the table belongs to pos_dev[g].
     kv_scales=(kscale, vscale) fp32 [G, H, Tmax]: the FP8 cache — kcache / vcache are uint8 e4m3 codes, every appended row is quantised
     with one power-of-two scale (quant.quantize_kv_rows' rule). kv_emulate: fp32 caches receive the dequantised values instead (the
     bit-reference twin of the FP8 cache)."""
     assert qkv.dtype == torch.float32 and qkv.is_contiguous() and qkv.shape == (G * T, 3 * H * D)
+    if paged is not None:
+        assert kv_scales is None and not kv_emulate, "the paged cache has no FP8 form"
+        table, Tmax, shift, n_pages = _paged_ok(paged, kcache, vcache, G, H, D)
+        assert kcache.dtype == torch.float32 and vcache.dtype in (torch.float32, table_dtype)
+        check(_lib.load().sx_rope_kv_append_f32_paged(_p(qkv), _p(kcache), _p(vcache), 0 if vcache.dtype == torch.float32 else 1, _p(cos_tab),
+                                                      _p(sin_tab), _p(pos_dev), _p(table), G, T, H, D, Tmax, shift, n_pages, kcache.stride(0),
+                                                      _DT[table_dtype], _stream()), "sx_rope_kv_append_f32_paged")
+        return
     assert kcache.dim() == 4 and kcache.shape[0] == G and kcache[0].is_contiguous() and vcache.stride() == kcache.stride()
     if kv_scales is not None or kv_emulate:
         assert not (kv_scales is not None and kv_emulate)
@@ -797,7 +820,7 @@ def rope_kv_append_f32(qkv, kcache, vcache, cos_tab, sin_tab, pos_dev, G, T, H, 
 
 
 def attention_f32(qkv, kcache, vcache, pos_dev, G, T, H, D, scale, dtype, tiled=False, nsplit=1, scratch=None, rope=None, kv_scales=None,
-                  kv_emulate=False):
+                  kv_emulate=False, paged=None):
     """Causal fp32 attention of a T-token chunk per sequence over the fp32 cache (row t sees keys 0 .. pos[g] + t); q = the rotated
     head rows at the front of qkv's rows. Returns the planes of the context [G*T, H*D] (see split16).
     rope=(cos, sin) (T == 1, D == 128): qkv holds the UNROTATED q | k | v rows of the new token; the launch rotates q and k, appends k / v
@@ -805,11 +828,19 @@ def attention_f32(qkv, kcache, vcache, pos_dev, G, T, H, D, scale, dtype, tiled=
     rope with 2 <= T <= 8 (G*T <= 32) is the VERIFY form of speculative decoding: rows g*T + t at positions pos[g] + t, bit for bit what T
     successive T = 1 calls with the same nsplit give (planes, k rows, v rows); pos[g] < 0 idles the whole slot. No FP8 cache.
     kv_scales=(kscale, vscale): the FP8 cache (uint8 codes + row scales, see rope_kv_append_f32) — the same bits as this call on a cache
-    holding the dequantised values. kv_emulate (with rope): fp32 caches, the new token's rows quantised and dequantised on append."""
+    holding the dequantised values. kv_emulate (with rope): fp32 caches, the new token's rows quantised and dequantised on append.
+    paged=(page table, Tmax): the paged cache (see rope_kv_append_f32) — the same bits as this call on contiguous caches holding the same
+    rows. The library refuses the forms that read no table (D != 128, the FP8 cache, the verify form)."""
     assert qkv.dtype == torch.float32 and qkv.is_contiguous() and qkv.shape[0] == G * T and qkv.shape[1] >= H * D
-    assert kcache.shape[0] == G and kcache.shape[1] == H and kcache.shape[3] == D and vcache.stride() == kcache.stride()
-    ret, buf, code = _planes_out(G * T, H * D, dtype, qkv.device, tiled)
     a = _lib.AttnF32Args()
+    Tmax = kcache.shape[2]
+    if paged is not None:
+        table, Tmax, a.page_shift, a.n_pages = _paged_ok(paged, kcache, vcache, G, H, D)
+        a.page_table, a.page_stride = _p(table), kcache.stride(0)
+    else:
+        assert kcache.shape[0] == G
+    assert kcache.shape[1] == H and kcache.shape[3] == D and vcache.stride() == kcache.stride()
+    ret, buf, code = _planes_out(G * T, H * D, dtype, qkv.device, tiled)
     if kv_scales is not None:
         assert not kv_emulate
         ks, vs = _kv_scales_ok(kv_scales, kcache, vcache)
@@ -819,7 +850,7 @@ def attention_f32(qkv, kcache, vcache, pos_dev, G, T, H, D, scale, dtype, tiled=
         a.kv_fp8 = 2 if kv_emulate else 0
     a.q, a.kcache, a.vcache, a.out, a.pos0_dev = _p(qkv), _p(kcache), _p(vcache), _p(buf), _p(pos_dev)
     a.q_row_stride, a.cache_seq_stride = qkv.stride(0), kcache.stride(0)
-    a.G, a.T, a.H, a.D, a.Tmax, a.dtype, a.scale, a.causal = G, T, H, D, kcache.shape[2], code, float(scale), 1
+    a.G, a.T, a.H, a.D, a.Tmax, a.dtype, a.scale, a.causal = G, T, H, D, Tmax, code, float(scale), 1
     a.v16 = 0 if vcache.dtype in (torch.float32, torch.uint8) else 1
     verify = rope is not None and T > 1   # speculative decoding: T = K + 1 rows per sequence, always split + combine (nsplit >= 1)
     if (nsplit > 1 and T == 1) or verify:  # decode step of few sequences: key splits (scratch: fp32 [G*T, H, nsplit, D + 2])

@@ -97,17 +97,21 @@ class ContinuousLVLM:
         return self
 
     # ------------------------------------------------------------------------------------------------------------
-    def _prompt_embeds(self, tokenizer, req):
-        """embed_tokens + input resampler + patch-position term + scatter (seed_x.py:154-173) for ONE request."""
-        llm = self.llm
-        dev, H = llm.device, llm.H
+    @staticmethod
+    def _prompt_ids(tokenizer, req):
+        """The request's prompt as a list of token ids (host only: what a paged admission sizes its reservation from)."""
         input_ids = req.get("input_ids")
         if req.get("prompt") is not None:
             input_ids = tokenizer(req["prompt"], return_tensors="pt").input_ids
         if isinstance(input_ids, torch.Tensor):
-            input_ids = input_ids.reshape(-1).tolist()
-        else:
-            input_ids = list(input_ids[0]) if len(input_ids) and isinstance(input_ids[0], (list, tuple)) else list(input_ids)
+            return input_ids.reshape(-1).tolist()
+        return list(input_ids[0]) if len(input_ids) and isinstance(input_ids[0], (list, tuple)) else list(input_ids)
+
+    def _prompt_embeds(self, tokenizer, req):
+        """embed_tokens + input resampler + patch-position term + scatter (seed_x.py:154-173) for ONE request."""
+        llm = self.llm
+        dev, H = llm.device, llm.H
+        input_ids = self._prompt_ids(tokenizer, req)
         ids_dev = torch.tensor(input_ids, dtype=torch.int32, device=dev)
         x = ops.embedding(ids_dev, llm._pack()["embed"])                                    # [T, H] fp32 (:158)
         image_embeds = req.get("image_embeds")
@@ -193,7 +197,9 @@ class ContinuousLVLM:
         A request may carry ``"adapter": name`` — a LoRA adapter resident on the LLM (``llm.load_adapter``; ValueError for an unknown
         name or an LLM built without ``max_adapters``): its prompt, its forced image chunks and its token steps run under that adapter,
         unmerged, beside requests under other adapters or none; every result carries ``'adapter'``. Without such a request the call
-        runs the calls and captured graphs it always ran. ``reuse_cache`` re-prefills a sequence whose adapter changed."""
+        runs the calls and captured graphs it always ran. ``reuse_cache`` re-prefills a sequence whose adapter changed.
+        On a paged KV cache (``LlamaForCausalLM(kv_pages=N)``) every sequence reserves prompt + ``max_new_tokens`` rows up front and a
+        ``reuse_cache`` turn extends its reservation; RuntimeError naming the shortfall if the pool is too small."""
         llm = self.llm
         params = [SamplingParams.from_request(req, world=llm.comm.world) for req in requests]     # refuses seed=None on tp > 1 ranks
         names = [req.get("adapter") for req in requests]
@@ -224,6 +230,11 @@ class ContinuousLVLM:
         xs, last_ids = [], []
         for g, (input_ids, x) in enumerate(prompts):
             assert len(input_ids) + rows <= llm.Tmax, "KV cache too small for prompt + max_new_tokens"
+            if llm.kv_pages:
+                # paged cache: prompt + max_new_tokens rows per sequence, up front (the token steps are captured graphs: they reserve
+                # nothing); a reuse_cache turn extends what the sequence holds. A sequence that has finished keeps stepping beside the
+                # others past its reservation: those appends find no page and write nothing
+                llm._kv_need(g, len(input_ids) + max_new_tokens, f"generate_batch, a prompt of {len(input_ids)} rows + max_new_tokens {max_new_tokens}")
             if reuse_cache:
                 llm.set_position(g, starts[g])
             xs.append(x[starts[g]:])
@@ -380,11 +391,21 @@ class ContinuousLVLM:
         longest prefix the model itself would have produced (spec.py), so a step emits 1 .. K + 1 tokens per slot and the ids are those
         of the call without the switch, for greedy and for sampled requests. The engine writes the prompt's ids (and a forced image
         block's) to the LLM's id history at admission and still reads one [G, 4] status per step; ``last_inflight_stats`` gains
-        spec_steps and spec_emitted_tokens (inflight.simulate_spec predicts the step count from the per-step emitted counts)."""
+        spec_steps and spec_emitted_tokens (inflight.simulate_spec predicts the step count from the per-step emitted counts).
+        On a paged KV cache (``LlamaForCausalLM(kv_pages=N)``) a request is admitted only if the pages for its prompt + budget are free
+        and holds them until it finishes; otherwise the queue head waits for a finishing slot's pages and nothing overtakes it, so
+        admission stays deterministic (with an ample pool it is exactly the admission above). A request that can never fit — more pages
+        than the pool has, or more rows than ``max_cache_len`` — raises ValueError before anything is touched.
+        ``last_inflight_stats`` gains page_waits and peak_pages (inflight.simulate_paged predicts them and the step counts).
+        ``prefix_cache`` raises ValueError there: prefix reuse on pages means sharing pages by reference, a follow-up."""
         llm = self.llm
         if llm.comm.world > 1:
             raise NotImplementedError("generate_inflight is single-rank: tensor-parallel ranks are not supported")
         prefix_cache, prefix_min_tokens = bool(self.prefix_cache), int(self.prefix_min_tokens)
+        paged = bool(llm.kv_pages)
+        if paged and prefix_cache:
+            raise ValueError("generate_inflight: agent.prefix_cache and a paged KV cache (kv_pages) exclude each other for now (follow-up: "
+                             "prefix reuse by sharing pages by reference in place of sx_kv_fork copies)")
         spec = bool(self.speculative) and llm.spec_tokens > 0
         K = llm.spec_tokens if spec else 0            # extra rows a verify step may write past a slot's last token
         requests = list(requests)
@@ -404,6 +425,16 @@ class ContinuousLVLM:
         named = any(nm is not None for nm in names)
         sampled = any(p is not None for p in params)
         assert all(b >= 1 for b in budget)
+        need = None
+        if paged:
+            # rows each request reserves at admission: prompt + budget. Sized from the token ids alone, before anything is touched
+            from .paging import pages_for
+            need = [len(self._prompt_ids(tokenizer, req)) + b for req, b in zip(requests, budget)]
+            for r, n in enumerate(need):
+                if n > llm.Tmax or pages_for(n, llm.kv_page_size) > llm.kv_pages:
+                    raise ValueError(f"generate_inflight: request {r} needs {n} cache rows (prompt + max_new_tokens) = "
+                                     f"{pages_for(n, llm.kv_page_size)} pages of {llm.kv_page_size} rows; the pool holds {llm.kv_pages} pages and "
+                                     f"a slot at most max_cache_len = {llm.Tmax} rows: it can never be admitted")
         rows = max(budget) + 8 + K
         keep = self._inflight
         if keep is None or keep["key"] != (tuple(img_ids), eos, G, id(P)) or keep["out_ids"].shape[1] < rows:
@@ -445,6 +476,10 @@ class ContinuousLVLM:
             self.last_spec_emitted = [[] for _ in range(N)]      # per request: tokens emitted by each verify step it was live in
         if prefix_cache:
             stats.update(prefix_hit_tokens=0, forked_tokens=0, fork_launches=0)
+        if paged:
+            stats.update(page_waits=0, peak_pages=0)
+            llm._pool.peak = llm._pool.used             # (0: the reset above released every sequence)
+        fits = (lambda g, r: llm.kv_reserve(g, need[r])) if paged else None
         self.last_prefill_tokens = []
         prompts, held = {}, {}                           # prefix_cache: request -> (ids, x, row signatures); slot -> (ids, signatures)
 
@@ -454,6 +489,8 @@ class ContinuousLVLM:
 
         def harvest(g, n):
             r = sched.finish(g)
+            if paged:                                    # the request's pages go back to the pool (a slot the host parked gave them back already)
+                llm.kv_release(g)
             generate_ids = out_ids[g, :n].cpu().long()
             if index is not None:                        # the slot now holds its prompt and the generated ids that were fed back
                 ids, sig = held.pop(g)
@@ -551,8 +588,10 @@ class ContinuousLVLM:
         while not sched.done:
             sched.new_pass()
             while True:
-                adm = sched.candidates() if prefix_cache else sched.admit()
+                adm = sched.candidates() if prefix_cache else sched.admit(fits)
                 if not adm:
+                    if paged:                            # the queue head waits for pages although a slot is free
+                        stats["page_waits"] += bool(sched.queue and sched.quota > 0 and sched.free_slots())
                     break
                 if prefix_cache:
                     admit_round_prefix(adm)
@@ -604,6 +643,8 @@ class ContinuousLVLM:
                     gone.append(g)
             if gone and named:
                 llm.set_adapters(gone, [None] * len(gone))   # the device parked the slot itself: its adapter index goes back to -1
+        if paged:
+            stats["peak_pages"] = llm._pool.peak
         owned(llm.reset)                                 # pos / ctx / step leave their idle values
         self.last_inflight_stats = stats
         return results
