@@ -438,6 +438,37 @@ int sx_sample_next_b(float* logits, int ld_logits, int vocab, const int32_t* img
                      const int32_t* step_dev, int G, const sx_sample_args* sample, void* stream);
 /* sx_greedy_next_slots (parking, force_at after the draw, stop rule, counters, status — all unchanged) with the id by the rule above. */
 int sx_sample_next_slots(const sx_slot_step_args* args, const sx_sample_args* sample, void* stream);
+/* Token log-probabilities (seedx_amd.sampling.token_logprobs states the rule in fp64). For an fp32 logits row x[0..vocab) as lm_head
+ * produced it — before the processor rule's in-place zeroing, temperature, top-k and top-p —
+ *   lp(v) = (x[v] − m) − log Σ exp(x − m),  m = max x,
+ * and the n_top (0 .. 8) largest columns by successive first-maximal-index selection (ties: lowest index first; past the end of the
+ * row: id −1, value −inf). One workgroup per row, fp32 ACCUMULATION in a layout fixed by vocab alone: thread t of 1024 adds the columns
+ * t, t + 1024, ... in ascending order, the lanes of a wave combine in a xor butterfly, the 16 wave sums in a pairwise tree (42 additions
+ * deep at vocab <= 32768); the maximum is exact. The bits of a record are a function of (row values, vocab) only — not of the slot,
+ * the neighbours, G, the launch or graph replay — and the same in all three entry points below, which share one non-inlined device
+ * function. x[v] = −inf gives −inf; a row holding NaN (or +inf, or nothing but −inf) gives NaN values and ids −1.
+ * sx_token_logprobs: teacher-forced rows (scoring). logits [rows][ld], vocab >= 1 of any size (columns >= vocab are never read),
+ * targets int32 [rows] (outside [0, vocab): NaN); chosen fp32 [rows]; top_ids int32 / top fp32 [rows][n_top], both NULL iff n_top = 0. */
+int sx_token_logprobs(const float* logits, int64_t ld, int vocab, const int32_t* targets, float* chosen, int32_t* top_ids, float* top,
+                      int n_top, int rows, void* stream);
+/* The LP form of the decode tail: sx_sample_next_b / sx_sample_next_slots (sample == NULL: sx_greedy_next_b / sx_greedy_next_slots) that
+ * also record, per row g with want[g] != 0, the log-probability of the id the row EMITS (after force_at replacement) and the top
+ * list, at chosen[g][step[g]] and top_ids / top[g][step[g]][0..n_top) under out_ids' guard 0 <= step[g] < ld_out (out_ids itself may be
+ * NULL; ld_out >= 1 and step are required). The statistics are taken from the raw row before the rule edits it. A row whose previous id
+ * lies inside the image chain records NaN and ids −1: the rule forces its id, the model did not choose. Parked slots and rows with
+ * want[g] == 0 record nothing. Everything else — ids, the zeroed columns, counters, stop rule, status, n_kept / p_chosen — is bit for
+ * bit the call without the record. vocab <= 32768. */
+typedef struct sx_logprob_args {
+  const int32_t* want;          /* [G]: 0 = the row records nothing                                                                */
+  float* chosen;                /* [G][ld_out]                                                                                     */
+  int32_t* top_ids;             /* [G][ld_out][n_top]; NULL iff n_top == 0                                                         */
+  float* top;                   /* [G][ld_out][n_top]; NULL iff n_top == 0                                                         */
+  int32_t n_top, reserved;
+} sx_logprob_args;
+int sx_sample_next_b_lp(float* logits, int ld_logits, int vocab, const int32_t* img_ids_dev, int n_img,
+                        const int32_t* prev_id_dev, int32_t* next_id_dev, int32_t* out_ids, int ld_out,
+                        const int32_t* step_dev, int G, const sx_sample_args* sample, const sx_logprob_args* lp, void* stream);
+int sx_sample_next_slots_lp(const sx_slot_step_args* args, const sx_sample_args* sample, const sx_logprob_args* lp, void* stream);
 
 /* Speculative decoding (lossless): the token step carries T = K + 1 rows per slot — row g*T is the slot's current token, rows g*T + 1 ..
  * g*T + n_draft[g] K drafted continuations — and sx_greedy_next_b / sx_sample_next_b over the G*T rows (previous id = the row's input,

@@ -80,6 +80,10 @@ class SampleArgs(C.Structure):
                 ("token_index", c_vp), ("n_kept", c_vp), ("p_chosen", c_vp)]
 
 
+class LogprobArgs(C.Structure):
+    _fields_ = [("want", c_vp), ("chosen", c_vp), ("top_ids", c_vp), ("top", c_vp), ("n_top", c_i32), ("reserved", c_i32)]
+
+
 class SpecAcceptArgs(C.Structure):
     _fields_ = [("cand", c_vp), ("rows_in", c_vp), ("n_draft", c_vp), ("cur", c_vp), ("live", c_vp), ("n_new", c_vp), ("max_new", c_vp),
                 ("force_at", c_vp), ("pos", c_vp), ("ctx", c_vp), ("step", c_vp), ("out_ids", c_vp), ("status", c_vp), ("hist", c_vp),
@@ -162,6 +166,10 @@ SIGNATURES = {
     "sx_greedy_next_slots": [C.POINTER(SlotStepArgs), c_vp],
     "sx_sample_next_b": [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, C.POINTER(SampleArgs), c_vp],
     "sx_sample_next_slots": [C.POINTER(SlotStepArgs), C.POINTER(SampleArgs), c_vp],
+    "sx_token_logprobs": [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp],
+    "sx_sample_next_b_lp": [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, C.POINTER(SampleArgs),
+                            C.POINTER(LogprobArgs), c_vp],
+    "sx_sample_next_slots_lp": [C.POINTER(SlotStepArgs), C.POINTER(SampleArgs), C.POINTER(LogprobArgs), c_vp],
     "sx_spec_accept": [C.POINTER(SpecAcceptArgs), c_vp],
     "sx_spec_draft_ngram": [C.POINTER(SpecDraftArgs), c_vp],
     "sx_scatter_rows_spec": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp],

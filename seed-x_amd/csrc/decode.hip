@@ -1340,14 +1340,178 @@ __device__ __forceinline__ void slot_advance(const TailP& p, int g, int result) 
 
 struct NoSampleP {};
 
+// ---- token log-probabilities: lp(v) = x[v] - logsumexp(x) of the RAW row, and the n_top largest (sx_token_logprobs, the LP tail) ------
+// seedx_amd.sampling.token_logprobs states the rule in fp64. One workgroup of 1024 threads per row, fp32 throughout, in a layout that
+// depends on nothing but vocab: thread t owns the columns t, t + 1024, t + 2048, ...
+//   m      = the row maximum (exact), found together with its first index: that pair is also entry 0 of the top list;
+//   S      = sum of expf(x - m): every thread adds its columns in ascending order (32 terms at vocab <= 32768), the 64 lanes of a wave
+//            combine in a 6-step xor butterfly (both partners add the same two numbers, so every lane holds the same bits), the 16 wave
+//            sums combine in a fixed 4-level pairwise tree: 42 additions deep at vocab <= 32768, 32 more per further 32768 columns;
+//   lp(v)  = (x[v] - m) - logf(S);
+//   top j  = the first maximal index among the columns after entry j - 1 in the order (value descending, index ascending). Every
+//            thread keeps the best of its own columns; only the owner of a selected column looks for its next one.
+// Reassociation is switched off for this function and it is never inlined: the standalone kernel and the LP tail run the same
+// instructions, so the record's bits are a function of (row values, vocab) alone, whatever the slot, G, the launch or graph replay.
+// NaN anywhere in the row (or +inf, or a row of -inf only) makes S NaN: the record is NaN with ids -1.
+constexpr int LP_MAX_TOP = 8;
+constexpr int LP_REG_COLS = 32;             // columns a thread keeps in registers: rows of up to 32768 columns
+struct LpScratch {
+  float rv[2][16];
+  int ri[2][16];
+  float ps[16];
+  float topv[LP_MAX_TOP];
+  int topi[LP_MAX_TOP];
+  float m, log_s, raw;
+};
+
+__device__ __forceinline__ bool lp_before(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+
+// After it returns (behind a barrier) every thread may read s->m, s->log_s and s->topv / s->topi [0, n_top): the raw values and indices
+// of the n_top largest columns, index -1 and value -inf past the end of the row.
+// (A template, like token_logprobs_kernel below, only for its place in the code object: templates are emitted where they are first used,
+// behind the kernels the library already had, which keep their order and their offsets within .text — profiles/logprobs.md compares them.)
+template <int UNUSED = 0>
+__device__ __noinline__ void row_logprob_stats(const float* row, int vocab, int n_top, LpScratch* s) {
+#pragma clang fp reassociate(off)
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  float pv = INFINITY, m = -INFINITY;       // the entry selected last; nothing yet
+  int pi = -1;
+  float bv = -INFINITY;                     // this thread's best column after (pv, pi); bi = INT_MAX: none left
+  int bi = 0x7fffffff;
+  bool scan = true;
+  const int passes = n_top > 1 ? n_top : 1;
+  // rows of up to 32768 columns are read from memory ONCE: the thread's columns stay in registers for every pass (same values, same
+  // order of operations as the loops over memory that longer rows take)
+  const bool reg = vocab <= LP_REG_COLS * 1024;
+  const int cnt = vocab > t ? (vocab - t + 1023) >> 10 : 0;
+  float loc[LP_REG_COLS];
+  if (reg) {
+#pragma unroll
+    for (int j = 0; j < LP_REG_COLS; ++j) loc[j] = j < cnt ? row[t + 1024 * j] : 0.f;
+  }
+  for (int k = 0; k < passes; ++k) {
+    if (scan) {
+      bv = -INFINITY;
+      bi = 0x7fffffff;
+      auto consider = [&](float v, int i) {
+        if ((k == 0 || lp_before(pv, pi, v, i)) && lp_before(v, i, bv, bi)) { bv = v; bi = i; }
+      };
+      if (reg) {
+#pragma unroll
+        for (int j = 0; j < LP_REG_COLS; ++j)
+          if (j < cnt) consider(loc[j], t + 1024 * j);
+      } else {
+        for (int i = t; i < vocab; i += 1024) consider(row[i], i);
+      }
+    }
+    float rv = bv;
+    int ri = bi;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(rv, o, 64);
+      const int oi = __shfl_xor(ri, o, 64);
+      if (lp_before(ov, oi, rv, ri)) { rv = ov; ri = oi; }
+    }
+    if (lane == 0) { s->rv[k & 1][wv] = rv; s->ri[k & 1][wv] = ri; }
+    __syncthreads();                        // (the buffers alternate: pass k + 2 writes this one again behind pass k + 1's barrier)
+    rv = s->rv[k & 1][0];
+    ri = s->ri[k & 1][0];
+#pragma unroll
+    for (int w = 1; w < 16; ++w)
+      if (lp_before(s->rv[k & 1][w], s->ri[k & 1][w], rv, ri)) { rv = s->rv[k & 1][w]; ri = s->ri[k & 1][w]; }
+    if (k == 0) m = rv;
+    const bool none = ri == 0x7fffffff;
+    if (t == 0 && k < n_top) { s->topv[k] = none ? -INFINITY : rv; s->topi[k] = none ? -1 : ri; }
+    scan = !none && (ri & 1023) == t;       // the owner of the selected column finds its next one
+    pv = rv;
+    pi = ri;
+  }
+  float acc = 0.f;
+  if (reg) {
+#pragma unroll
+    for (int j = 0; j < LP_REG_COLS; ++j)
+      if (j < cnt) acc += expf(loc[j] - m);
+  } else {
+    for (int i = t; i < vocab; i += 1024) acc += expf(row[i] - m);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if (lane == 0) s->ps[wv] = acc;
+  __syncthreads();
+  if (t == 0) {
+    const float* q = s->ps;
+    const float a0 = (q[0] + q[1]) + (q[2] + q[3]), a1 = (q[4] + q[5]) + (q[6] + q[7]);
+    const float a2 = (q[8] + q[9]) + (q[10] + q[11]), a3 = (q[12] + q[13]) + (q[14] + q[15]);
+    s->m = m;
+    s->log_s = logf((a0 + a1) + (a2 + a3));
+  }
+  __syncthreads();
+}
+
+// One record: raw = x[id] of the raw row. Thread 0 stores the chosen value, threads [0, n_top) the top list. ``none``: the model did
+// not choose (a row inside the image chain): NaN and ids -1, as for a row that holds NaN.
+__device__ __forceinline__ void lp_store(const LpScratch* s, float raw, bool none, float* chosen, int* top_ids, float* top, int n_top) {
+#pragma clang fp reassociate(off)
+  const float ls = s->log_s, m = s->m;
+  const bool bad = none || ls != ls;
+  const int t = threadIdx.x;
+  if (t == 0 && chosen) *chosen = bad ? NAN : (raw - m) - ls;
+  if (t < n_top) {
+    if (top_ids) top_ids[t] = bad ? -1 : s->topi[t];
+    if (top) top[t] = bad ? NAN : (s->topv[t] - m) - ls;
+  }
+}
+
+struct LogprobP {
+  const int* want;
+  float* chosen;
+  int* top_ids;
+  float* top;
+  int n_top;
+};
+struct NoLogprobP {};
+
+template <int UNUSED = 0>
+__global__ __launch_bounds__(1024) void token_logprobs_kernel(const float* logits, int64_t ld, int vocab, const int* targets, float* chosen,
+                                                              int* top_ids, float* top, int n_top) {
+  __shared__ LpScratch scr;
+  const int r = blockIdx.x;
+  const float* row = logits + (size_t)r * ld;
+  row_logprob_stats(row, vocab, n_top, &scr);
+  const int id = targets[r];
+  const bool in = id >= 0 && id < vocab;    // a target outside the row: NaN, nothing is read
+  lp_store(&scr, in ? row[id] : NAN, false, chosen + r, top_ids ? top_ids + (size_t)r * n_top : nullptr,
+           top ? top + (size_t)r * n_top : nullptr, n_top);
+}
+
 // SAMPLE: the id by the seeded rule (token index: token_index[g] in the lock-step form, step[g] in the in-flight form), else the
-// greedy id; the greedy instantiation holds nothing of the sampler.
-template <bool SAMPLE>
-__global__ __launch_bounds__(1024) void next_token_kernel(const TailP p, const std::conditional_t<SAMPLE, SampleP, NoSampleP> s) {
+// greedy id; the greedy instantiation holds nothing of the sampler. LP: rows with want[g] != 0 also record the log-probability of the
+// id they emit and the n_top largest of the row, at [g][step[g]] under out_ids' guard. The statistics are taken from the raw row BEFORE
+// the rule zeroes its image columns, whose raw values the threads that zero them keep; nothing else of the tail changes.
+template <bool SAMPLE, bool LP = false>
+__global__ __launch_bounds__(1024) void next_token_kernel(const TailP p, const std::conditional_t<SAMPLE, SampleP, NoSampleP> s,
+                                                          const std::conditional_t<LP, LogprobP, NoLogprobP> lp) {
   const int g = blockIdx.x;
   const bool slots = p.live != nullptr;
   if (slots && p.live[g] == 0) return;              // parked (uniform over the workgroup: no barrier is skipped by a part of it)
   float* row = p.logits + (size_t)g * p.ld_logits;
+  [[maybe_unused]] bool rec = false;
+  [[maybe_unused]] float raw_img = 0.f;
+  [[maybe_unused]] int lp_prev = 0, lp_step = 0, lp_forced = -1;
+  [[maybe_unused]] LpScratch* scr = nullptr;
+  if constexpr (LP) {
+    __shared__ LpScratch lp_scr;
+    scr = &lp_scr;
+    rec = lp.want[g] != 0;                          // (uniform over the workgroup)
+    if (rec) {
+      // everything thread 0 rewrites after the id is known, read by every thread before the barriers of the statistics
+      lp_prev = p.prev[g];
+      lp_step = p.step[g];
+      if (slots && p.force_at[g] >= 0 && p.n_new[g] == p.force_at[g]) lp_forced = p.force_id;
+      row_logprob_stats(row, p.vocab, lp.n_top, scr);
+      if ((int)threadIdx.x < p.n_img - 1) raw_img = row[p.img_ids[1 + threadIdx.x]];
+    }
+  }
   // every thread reads prev[g] and the token index before the first barrier of the id functions; thread 0 stores to next[g] (which
   // may be prev[g]) and step[g] after the last one
   int result;
@@ -1355,6 +1519,20 @@ __global__ __launch_bounds__(1024) void next_token_kernel(const TailP p, const s
     result = sample_next_id(row, p.vocab, p.img_ids, p.n_img, p.prev[g], s, g, slots ? p.step[g] : s.token_index[g]);
   else
     result = greedy_next_id(row, p.vocab, p.img_ids, p.n_img, p.prev[g]);
+  if constexpr (LP) {
+    if (rec) {
+      const int id = lp_forced >= 0 ? lp_forced : result;        // the id slot_advance emits
+      if (threadIdx.x == 0) scr->raw = id >= 0 && id < p.vocab ? row[id] : NAN;
+      __syncthreads();
+      if ((int)threadIdx.x < p.n_img - 1 && p.img_ids[1 + threadIdx.x] == id) scr->raw = raw_img;   // a zeroed column (ids are unique)
+      const bool chain = __syncthreads_or((int)threadIdx.x < p.n_img - 1 && p.img_ids[threadIdx.x] == lp_prev);
+      if (lp_step >= 0 && lp_step < p.ld_out) {
+        const size_t at = (size_t)g * p.ld_out + lp_step;
+        lp_store(scr, scr->raw, chain, lp.chosen + at, lp.top_ids ? lp.top_ids + at * lp.n_top : nullptr,
+                 lp.top ? lp.top + at * lp.n_top : nullptr, lp.n_top);
+      }
+    }
+  }
   if (threadIdx.x != 0) return;
   if (slots) slot_advance(p, g, result);
   else lockstep_store(p, g, result);
@@ -1663,9 +1841,11 @@ static TailP slot_tail(const sx_slot_step_args* a) {
                a->live, a->n_new, a->max_new, a->force_at, a->pos, a->ctx, a->status, a->force_id, a->eos_id};
 }
 
-// The one launcher behind the five entry points. slots: the in-flight form (every pointer but out_ids is required, ld_out is the row
-// capacity), else the lock-step form. sampled: the entry point takes a sx_sample_args, which must then be there.
-static int launch_next_token(const char* who, const TailP& p, bool slots, const sx_sample_args* sample, bool sampled, void* stream) {
+// The one launcher behind the seven entry points. slots: the in-flight form (every pointer but out_ids is required, ld_out is the row
+// capacity), else the lock-step form. sampled: the entry point takes a sx_sample_args, which must then be there. lp: the LP form
+// (sx_sample_next_b_lp / sx_sample_next_slots_lp); NULL launches exactly what the five older entry points always launched.
+static int launch_next_token(const char* who, const TailP& p, bool slots, const sx_sample_args* sample, bool sampled, void* stream,
+                             const sx_logprob_args* lp = nullptr) {
   SX_CHECK(p.logits && p.img_ids && p.prev && p.next, "%s: null pointer", who);
   SX_CHECK(p.n_img >= 2 && p.n_img <= 1024 && p.G >= 1, "%s: n_img=%d G=%d", who, p.n_img, p.G);
   if (slots) {
@@ -1676,13 +1856,23 @@ static int launch_next_token(const char* who, const TailP& p, bool slots, const 
     SX_CHECK(!p.out_ids || p.step, "%s: out_ids needs step_dev", who);
     SX_CHECK(!sampled || p.G == 1 || p.ld_logits >= p.vocab, "%s: vocab=%d ld_logits=%d", who, p.vocab, p.ld_logits);
   }
+  SampleP s;
   if (sampled) {
-    SampleP s;
     if (int rc = sample_params(sample, p.vocab, who, &s)) return rc;
     SX_CHECK(slots || s.token_index, "%s: token_index is required", who);
-    hipLaunchKernelGGL(next_token_kernel<true>, dim3(p.G), dim3(1024), 0, ST, p, s);
+  }
+  if (!lp) {        // (first in the source: the two older instantiations keep their place in the code object)
+    if (sampled) hipLaunchKernelGGL(next_token_kernel<true>, dim3(p.G), dim3(1024), 0, ST, p, s, NoLogprobP{});
+    else hipLaunchKernelGGL(next_token_kernel<false>, dim3(p.G), dim3(1024), 0, ST, p, NoSampleP{}, NoLogprobP{});
   } else {
-    hipLaunchKernelGGL(next_token_kernel<false>, dim3(p.G), dim3(1024), 0, ST, p, NoSampleP{});
+    SX_CHECK(lp->want && lp->chosen && p.step, "%s: sx_logprob_args needs want, chosen and step", who);
+    SX_CHECK(lp->n_top >= 0 && lp->n_top <= LP_MAX_TOP && (lp->n_top == 0 || (lp->top_ids && lp->top)),
+             "%s: n_top=%d (0 .. %d, with top_ids and top)", who, lp->n_top, LP_MAX_TOP);
+    SX_CHECK(p.vocab >= 1 && p.vocab <= SMP_MAX_VOCAB && p.ld_logits >= p.vocab && p.ld_out >= 1,
+             "%s: vocab=%d (1 .. %d) ld_logits=%d ld_out=%d", who, p.vocab, SMP_MAX_VOCAB, p.ld_logits, p.ld_out);
+    const LogprobP l{lp->want, lp->chosen, lp->top_ids, lp->top, lp->n_top};
+    if (sampled) hipLaunchKernelGGL((next_token_kernel<true, true>), dim3(p.G), dim3(1024), 0, ST, p, s, l);
+    else hipLaunchKernelGGL((next_token_kernel<false, true>), dim3(p.G), dim3(1024), 0, ST, p, NoSampleP{}, l);
   }
   SX_HIP_LAUNCH_CHECK();
   return SX_OK;
@@ -1711,6 +1901,27 @@ extern "C" int sx_greedy_next_slots(const sx_slot_step_args* a, void* stream) {
 }
 extern "C" int sx_sample_next_slots(const sx_slot_step_args* a, const sx_sample_args* sample, void* stream) {
   return launch_next_token("sx_sample_next_slots", slot_tail(a), true, sample, true, stream);
+}
+extern "C" int sx_sample_next_b_lp(float* logits, int ld_logits, int vocab, const int32_t* img_ids_dev, int n_img,
+                                   const int32_t* prev_id_dev, int32_t* next_id_dev, int32_t* out_ids, int ld_out,
+                                   const int32_t* step_dev, int G, const sx_sample_args* sample, const sx_logprob_args* lp, void* stream) {
+  SX_CHECK(lp, "sx_sample_next_b_lp: null sx_logprob_args");
+  return launch_next_token("sx_sample_next_b_lp", TailP{logits, img_ids_dev, prev_id_dev, next_id_dev, out_ids, const_cast<int32_t*>(step_dev),
+                                                        ld_logits, vocab, n_img, ld_out, G}, false, sample, sample != nullptr, stream, lp);
+}
+extern "C" int sx_sample_next_slots_lp(const sx_slot_step_args* a, const sx_sample_args* sample, const sx_logprob_args* lp, void* stream) {
+  SX_CHECK(lp, "sx_sample_next_slots_lp: null sx_logprob_args");
+  return launch_next_token("sx_sample_next_slots_lp", slot_tail(a), true, sample, sample != nullptr, stream, lp);
+}
+extern "C" int sx_token_logprobs(const float* logits, int64_t ld, int vocab, const int32_t* targets, float* chosen, int32_t* top_ids,
+                                 float* top, int n_top, int rows, void* stream) {
+  SX_CHECK(logits && targets && chosen, "sx_token_logprobs: null pointer");
+  SX_CHECK(rows >= 1 && vocab >= 1 && ld >= vocab, "sx_token_logprobs: rows=%d vocab=%d ld=%lld", rows, vocab, (long long)ld);
+  SX_CHECK(n_top >= 0 && n_top <= LP_MAX_TOP && (n_top == 0 || (top_ids && top)), "sx_token_logprobs: n_top=%d (0 .. %d, with top_ids and top)",
+           n_top, LP_MAX_TOP);
+  hipLaunchKernelGGL(token_logprobs_kernel<>, dim3(rows), dim3(1024), 0, ST, logits, ld, vocab, targets, chosen, top_ids, top, n_top);
+  SX_HIP_LAUNCH_CHECK();
+  return SX_OK;
 }
 
 // ---- speculative decoding: the accept rule and the prompt-lookup drafter (include/seedx_hip.h: sx_spec_accept, sx_spec_draft_ngram) ---

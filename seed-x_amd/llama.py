@@ -160,10 +160,13 @@ class SlotState:
         # int32 [G] adapter table slot per slot, beside pos / ctx / step (the module's P["lora"]["sel"], which the adapter step reads):
         # written at admission (LlamaForCausalLM.set_adapters), -1 for parked slots and slots without an adapter; None: max_adapters = 0
         self.adapter = None
+        # a LogprobState (slot_state(logprobs=n_top)): the step ends in the LP tail and has graphs of its own. None: the step as ever
+        self.logprobs = None
 
     def key(self):
         return tuple(t.data_ptr() for t in (self.live, self.n_new, self.max_new, self.force_at, self.status)) \
-            + (self.force_id, self.eos_id) + (self.sampling.key() if self.sampling is not None else ())
+            + (self.force_id, self.eos_id) + (self.sampling.key() if self.sampling is not None else ()) \
+            + (self.logprobs.key() if self.logprobs is not None else ())
 
 
 class SampleState:
@@ -217,8 +220,40 @@ class SampleState:
         return out
 
 
+class LogprobState:
+    """Where the LP tail of the token step records (sx_logprob_args; seedx_amd.sampling.token_logprobs states the rule): ``want`` int32
+    [G] (0: the row records nothing) and, per row and token index, ``chosen`` fp32 [G, rows] — the log-probability of the emitted id —
+    and ``top_ids`` int32 / ``top`` fp32 [G, rows, n_top], the n_top most likely ids of the raw row. ``rows`` is out_ids' row capacity;
+    ``bind`` (re)allocates the three buffers for it, NaN / -1 filled. The pointers are part of the captured graph's key."""
+
+    def __init__(self, G, n_top, device, rows=None):
+        if isinstance(n_top, bool) or not 0 <= int(n_top) <= 8:
+            raise ValueError(f"LogprobState: n_top must be an int in 0 .. 8, got {n_top!r}")
+        self.G, self.n_top, self.device = int(G), int(n_top), device
+        self.want = torch.zeros(self.G, dtype=torch.int32, device=device)
+        self.chosen = self.top_ids = self.top = None
+        if rows is not None:
+            self.bind(rows)
+
+    def bind(self, rows):
+        if self.chosen is None or self.chosen.shape[1] != int(rows):
+            self.chosen = torch.full((self.G, int(rows)), float("nan"), dtype=torch.float32, device=self.device)
+            self.top_ids = torch.full((self.G, int(rows), self.n_top), -1, dtype=torch.int32, device=self.device)
+            self.top = torch.full((self.G, int(rows), self.n_top), float("nan"), dtype=torch.float32, device=self.device)
+        return self
+
+    def key(self):
+        return ("lp", self.n_top) + tuple(t.data_ptr() for t in (self.want, self.chosen, self.top_ids, self.top))
+
+    def forced(self, g, start, n):
+        """Rows [start, start + n) of sequence g hold ids the host forced (an image chunk): NaN / -1, the model did not choose."""
+        self.chosen[g, start:start + n] = float("nan")
+        self.top_ids[g, start:start + n] = -1
+        self.top[g, start:start + n] = float("nan")
+
+
 class LlamaForCausalLM:
-    KV_FORMATS = (None, "fp8_e4m3", "fp8_e4m3_emulated")
+    KV_FORMATS =(None, "fp8_e4m3", "fp8_e4m3_emulated")
     WEIGHT_FORMATS = (None, "fp8_e4m3", "mxfp4")
     WEIGHT_RESIDENCIES = (None, "tiles")
 
@@ -454,6 +489,10 @@ class LlamaForCausalLM:
         self._graph_ad = self._slot_graph_ad = self._sample_graph_ad = self._slot_sample_graph_ad = None
         # the verify step of speculative decoding (decode_step(..., spec=True)): graphs of its own, greedy and sampled
         self._spec_graph = self._spec_sample_graph = None
+        # a step that ends in the LP tail (a LogprobState) never shares a graph with the eight plain ones above
+        for attr in ("_graph", "_slot_graph", "_sample_graph", "_slot_sample_graph"):
+            setattr(self, attr + "_lp", None)
+            setattr(self, attr + "_lp_ad", None)
 
     def memory_footprint(self):
         """Bytes this module will hold on its GPU once packed (per rank): 16-bit weights, their decode-tile copy (precise mode: always;
@@ -1315,14 +1354,17 @@ class LlamaForCausalLM:
     __call__ = forward
 
     # ---- in-flight batching: slot states ---------------------------------------------------------------------------------
-    def slot_state(self, force_id=-1, eos_id=-1, sampling=False):
+    def slot_state(self, force_id=-1, eos_id=-1, sampling=False, logprobs=None):
         """A fresh SlotState with EVERY slot parked (the module's pos / ctx / step take the idle values; ``reset()`` undoes that).
         ``sampling``: the state carries a SampleState (``.sampling``, all rows greedy until set) and its token step ends in
-        sx_sample_next_slots instead of sx_greedy_next_slots."""
+        sx_sample_next_slots instead of sx_greedy_next_slots. ``logprobs`` = n_top (0 .. 8): the state carries a LogprobState
+        (``.logprobs``, no row recording until ``want`` is set) and its token step ends in sx_sample_next_slots_lp."""
         if self.tp > 1:
             raise NotImplementedError("in-flight batching (slot states) is single-rank: tensor-parallel ranks are not supported")
         self._pack()
         st = SlotState(self.G, self.device, force_id, eos_id, sampling)
+        if logprobs is not None:
+            st.logprobs = LogprobState(self.G, logprobs, self.device)
         if sampling and self.spec_tokens:
             T = self.spec_tokens + 1
             st.sampling.rows = (SampleState(self.G * T, self.device), T)
@@ -1410,7 +1452,7 @@ class LlamaForCausalLM:
             slots.logits = held[2]
         held[1].replay()
 
-    def _decode_step_body(self, img_ids_dev, out_ids, hid_buf, slots=None, sampling=None, adapters=False):
+    def _decode_step_body(self, img_ids_dev, out_ids, hid_buf, slots=None, sampling=None, adapters=False, logprobs=None):
         """cur[G] → embedding → 40 layers → final norm → lm_head → logits rule + argmax → cur[G]. Records the post-norm
         hidden state of each INPUT token at hid_buf[g, step[g]] (what seed_x.py:196 collects) and the new id at
         out_ids[g, step[g]]; then step += 1. Everything stays on the device. ``slots`` (a SlotState): the tail is ONE
@@ -1426,13 +1468,17 @@ class LlamaForCausalLM:
         # same gathered logits with the same seed and index
         ss = sampling if slots is None else slots.sampling
         sample = {} if ss is None else dict(sample=ss, n_kept=ss.n_kept, p_chosen=ss.p_chosen)
+        # LP step: the same tail with the record of the raw row (a LogprobState), greedy or sampled
+        lp = logprobs if slots is None else slots.logprobs
+        if lp is not None:
+            sample["lp"] = lp
         if slots is not None:
-            tail = ops.sample_next_slots if sample else ops.greedy_next_slots
+            tail = ops.next_slots_lp if lp is not None else ops.sample_next_slots if sample else ops.greedy_next_slots
             tail(logits, self.V, img_ids_dev, P["cur"], slots.live, slots.n_new, slots.max_new, slots.force_at, P["pos"], P["ctx"],
                  P["step"], out_ids, slots.status, force_id=slots.force_id, eos_id=slots.eos_id, **sample)
             slots.logits = logits
             return
-        tail = ops.sample_next_b if sample else ops.greedy_next_b
+        tail = ops.next_b_lp if lp is not None else ops.sample_next_b if sample else ops.greedy_next_b
         tail(logits, self.V, img_ids_dev, P["cur"], out_ids, P["step"], **sample)
         ops.add_i32(P["step"], 1)
 
@@ -1463,7 +1509,8 @@ class LlamaForCausalLM:
         if ids:
             S["hist"][slot, start:start + len(ids)] = torch.tensor(ids, dtype=torch.int32, device=self.device)
 
-    def decode_step(self, img_ids_dev, out_ids, hid_buf, use_graph=True, slots=None, sampling=None, adapters=None, spec=False, draft="ngram"):
+    def decode_step(self, img_ids_dev, out_ids, hid_buf, use_graph=True, slots=None, sampling=None, adapters=None, spec=False, draft="ngram",
+                    logprobs=None):
         """out_ids: int32 [G, rows]; hid_buf: fp32 [G, rows, H]. ``slots``: a SlotState → the in-flight step (its captured graph is
         kept apart from the lock-step one, so one graph serves an engine's lifetime whatever else runs in between). ``sampling``: a
         SampleState → the lock-step step ends in sx_sample_next_b (token index = step[g]); a slot state brings its own
@@ -1471,8 +1518,27 @@ class LlamaForCausalLM:
         and the parameters are read from device memory at replay.
         ``adapters``: None (default) → the adapter token step runs iff some sequence has an adapter (set_adapters); True / False force
         it. The adapter step has captured graphs of its own; a step in which no sequence has an adapter runs the calls and graphs it
-        ran before adapters existed."""
+        ran before adapters existed.
+        ``logprobs``: a LogprobState → the lock-step step ends in the LP tail (sx_sample_next_b_lp: rows with ``want`` set record the
+        log-probability of their id and the top list at [g, step[g]]); a slot state brings its own (``slots.logprobs``,
+        sx_sample_next_slots_lp). Only the tail changes, so it works with every weight_format, weight_residency, kv_format, kv_pages,
+        adapters and sampling; the step has captured graphs of its own, and a step without a state runs the calls and graphs it always ran.
+        ValueError with the verify step (``spec=True``) and on tensor-parallel ranks: follow-ups."""
         P = self._pack()
+        lp = logprobs if slots is None else getattr(slots, "logprobs", None)
+        if lp is not None:
+            if slots is not None and logprobs is not None:
+                raise ValueError("LlamaForCausalLM.decode_step: a slot state carries its own logprob state (slot_state(logprobs=n_top))")
+            if spec:
+                raise ValueError("LlamaForCausalLM.decode_step: token log-probabilities from the verify step of speculative decoding "
+                                 "(spec=True with a logprob state) are not built (follow-up: records for the G*T candidate rows)")
+            if self.tp > 1:
+                raise ValueError(f"LlamaForCausalLM.decode_step: token log-probabilities on tp={self.tp} tensor-parallel ranks are not built "
+                                 "(follow-up: every rank would record from the gathered logits)")
+            assert lp.G == self.G and out_ids.is_contiguous()
+            lp.bind(out_ids.shape[1])
+        elif logprobs is not None:
+            raise ValueError("LlamaForCausalLM.decode_step: a slot state carries its own logprob state (slot_state(logprobs=n_top))")
         if spec:
             # the verify step of speculative decoding (spec_tokens > 0, a slot state): graphs of its own, greedy and sampled; without
             # ``spec`` a model built with spec_tokens runs the plain steps and graphs below. ``draft``: "ngram" → the step starts with
@@ -1502,7 +1568,7 @@ class LlamaForCausalLM:
             assert out_ids.is_contiguous() and slots.G == self.G
             assert sampling is None, "a slot state carries its own sampling state (slot_state(sampling=True))"
         assert sampling is None or sampling.G == self.G
-        body = lambda: self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling, adapters)
+        body = lambda: self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling, adapters, logprobs)
         if not use_graph or not self.comm.graph_safe:
             return body()
         if slots is None:
@@ -1510,5 +1576,7 @@ class LlamaForCausalLM:
         else:
             attr = "_slot_graph" if slots.sampling is None else "_slot_sample_graph"
         key = (img_ids_dev.data_ptr(), out_ids.data_ptr(), hid_buf.data_ptr(), tuple(out_ids.shape)) \
-            + (slots.key() if slots is not None else ()) + (("sample",) + sampling.key() if sampling is not None else ())
-        self._replay(attr + ("_ad" if adapters else ""), key, body, [slots.live, slots.n_new, slots.status] if slots is not None else [], slots)
+            + (slots.key() if slots is not None else ()) + (("sample",) + sampling.key() if sampling is not None else ()) \
+            + (logprobs.key() if logprobs is not None else ())
+        self._replay(attr + ("_lp" if lp is not None else "") + ("_ad" if adapters else ""), key, body,
+                     [slots.live, slots.n_new, slots.status] if slots is not None else [], slots)

@@ -1094,13 +1094,20 @@ def attn_decode_fused(qkv, kcache, vcache, pos_dev, cos_tab, sin_tab, scale, H, 
     return ot if out_tiled else out
 
 
-def _next_lockstep(logits, vocab, img_ids_dev, cur_dev, out_ids, step_dev, sample=None):
-    """The lock-step tail of the token step: sx_greedy_next_b, or sx_sample_next_b when ``sample`` (a filled SampleArgs) is given."""
+def _next_lockstep(logits, vocab, img_ids_dev, cur_dev, out_ids, step_dev, sample=None, lp=None):
+    """The lock-step tail of the token step: sx_greedy_next_b, or sx_sample_next_b when ``sample`` (a filled SampleArgs) is given;
+    ``lp`` (a logprob state): sx_sample_next_b_lp, whose row capacity is the state's."""
     lib = _lib.load()
     assert logits.dtype == torch.float32 and logits.stride(1) == 1
+    ld_out = out_ids.stride(0) if out_ids is not None else 0
+    if lp is not None:
+        la, ld_out = _logprob_args(lp, logits.shape[0], out_ids)
+        assert step_dev is not None, "the LP tail needs step_dev"
     args = (_p(logits), logits.stride(0), vocab, _p(img_ids_dev), img_ids_dev.numel(), _p(cur_dev), _p(cur_dev), _p(out_ids),
-            out_ids.stride(0) if out_ids is not None else 0, _p(step_dev), logits.shape[0])
-    if sample is None:
+            ld_out, _p(step_dev), logits.shape[0])
+    if lp is not None:
+        check(lib.sx_sample_next_b_lp(*args, C.byref(sample) if sample is not None else None, C.byref(la), _stream()), "sx_sample_next_b_lp")
+    elif sample is None:
         check(lib.sx_greedy_next_b(*args, _stream()), "sx_greedy_next_b")
     else:
         check(lib.sx_sample_next_b(*args, C.byref(sample), _stream()), "sx_sample_next_b")
@@ -1172,6 +1179,57 @@ def sample_next_slots(logits, vocab, img_ids_dev, cur, live, n_new, max_new, for
                         status, force_id, eos_id)
     s = _sample_args(sample, logits.shape[0], None, n_kept, p_chosen)
     check(_lib.load().sx_sample_next_slots(C.byref(a), C.byref(s), _stream()), "sx_sample_next_slots")
+
+
+def _logprob_args(lp, G, out_ids):
+    """(sx_logprob_args, row capacity) from a logprob state (llama.LogprobState or anything with its tensors): ``want`` int32 [G],
+    ``chosen`` fp32 [G, rows], ``top_ids`` int32 / ``top`` fp32 [G, rows, n_top] (unused when n_top = 0). ``out_ids`` shares the capacity."""
+    n, rows = int(lp.n_top), lp.chosen.shape[1]
+    assert 0 <= n <= 8, "logprobs: n_top in 0 .. 8"
+    assert lp.want.dtype == torch.int32 and lp.want.is_contiguous() and lp.want.numel() == G
+    assert lp.chosen.dtype == torch.float32 and lp.chosen.is_contiguous() and lp.chosen.shape == (G, rows)
+    assert out_ids is None or (out_ids.is_contiguous() and out_ids.shape[1] == rows), "logprobs: the buffers share out_ids' row capacity"
+    if n:
+        assert lp.top_ids.dtype == torch.int32 and lp.top_ids.is_contiguous() and lp.top_ids.shape == (G, rows, n)
+        assert lp.top.dtype == torch.float32 and lp.top.is_contiguous() and lp.top.shape == (G, rows, n)
+    d = lambda t: _p(t).value                             # (GPU tensors only: no CPU fallback)
+    return _lib.LogprobArgs(want=d(lp.want), chosen=d(lp.chosen), top_ids=d(lp.top_ids) if n else None, top=d(lp.top) if n else None,
+                            n_top=n, reserved=0), rows
+
+
+def token_logprobs(logits, vocab, targets, n_top=0):
+    """sx_token_logprobs: logits fp32 [rows, ld] (columns >= vocab are never read), targets int32 [rows] → (chosen fp32 [rows],
+    top_ids int32 [rows, n_top], top fp32 [rows, n_top]): lp(target) and the n_top largest lp of each RAW row
+    (seedx_amd.sampling.token_logprobs states the rule)."""
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1 and 0 <= int(n_top) <= 8
+    R = logits.shape[0]
+    assert targets.dtype == torch.int32 and targets.is_contiguous() and targets.numel() == R
+    chosen = torch.empty(R, dtype=torch.float32, device=logits.device)
+    top_ids = torch.empty((R, n_top), dtype=torch.int32, device=logits.device)
+    top = torch.empty((R, n_top), dtype=torch.float32, device=logits.device)
+    check(_lib.load().sx_token_logprobs(_p(logits), logits.stride(0), int(vocab), _p(targets), _p(chosen), _p(top_ids) if n_top else None,
+                                        _p(top) if n_top else None, int(n_top), R, _stream()), "sx_token_logprobs")
+    return chosen, top_ids, top
+
+
+def next_b_lp(logits, vocab, img_ids_dev, cur_dev, out_ids, step_dev, lp, sample=None, token_index=None, n_kept=None, p_chosen=None):
+    """greedy_next_b (``sample`` None) or sample_next_b with the record of sx_sample_next_b_lp: rows with ``lp.want`` != 0 store the
+    log-probability of their id and the top list at [g, step[g]] of the state's buffers; everything else is the call without ``lp``."""
+    if sample is not None:
+        token_index = step_dev if token_index is None else token_index
+        sample = _sample_args(sample, logits.shape[0], token_index, n_kept, p_chosen)
+    _next_lockstep(logits, vocab, img_ids_dev, cur_dev, out_ids, step_dev, sample, lp)
+
+
+def next_slots_lp(logits, vocab, img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, out_ids, status, lp, sample=None,
+                  force_id=-1, eos_id=-1, n_kept=None, p_chosen=None):
+    """greedy_next_slots (``sample`` None) or sample_next_slots with the record of sx_sample_next_slots_lp (next_b_lp's, per live slot)."""
+    a = _slot_step_args("next_slots_lp", logits, vocab, img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, out_ids,
+                        status, force_id, eos_id)
+    la, a.ld_out = _logprob_args(lp, logits.shape[0], out_ids)
+    s = _sample_args(sample, logits.shape[0], None, n_kept, p_chosen) if sample is not None else None
+    check(_lib.load().sx_sample_next_slots_lp(C.byref(a), C.byref(s) if s is not None else None, C.byref(la), _stream()),
+          "sx_sample_next_slots_lp")
 
 
 def _i32s(who, *ts):

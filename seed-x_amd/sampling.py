@@ -78,6 +78,66 @@ def nucleus(logits_row, temperature, top_k, top_p):
     return kept, wk / wk.sum(), larger
 
 
+MAX_TOP_LOGPROBS = 8
+
+
+def token_logprobs(row, targets=None, n_top=0):
+    """The log-probability rule the device kernels implement (sx_token_logprobs and the LP decode tail), in numpy fp64. ``row``: the
+    RAW fp32 logits row x[0..V) — what lm_head produced, before the image-token rule's in-place zeroing, temperature, top-k and top-p —
+    or [R, V] rows; ``targets``: one id per row (None: no chosen value). lp(v) = x[v] - logsumexp(x).
+    Returns (chosen [R] fp64 or None, top_ids [R, n_top] int64, top [R, n_top] fp64), without the leading axis for a 1-D row. The top
+    list holds the n_top largest x, ties lowest index first; entries past V are id -1, value -inf. x[v] = -inf gives -inf. A row that
+    holds NaN (or whose logsumexp is not finite: +inf, nothing but -inf) gives NaN values and top ids -1; a target outside [0, V) NaN."""
+    x = np.asarray(row, dtype=np.float64)
+    flat = x.ndim == 1
+    x = np.atleast_2d(x)
+    R, V = x.shape
+    n_top = int(n_top)
+    assert n_top >= 0
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        m = x.max(axis=1, keepdims=True)
+        lp = (x - m) - np.log(np.exp(x - m).sum(axis=1, keepdims=True))
+    bad = np.isnan(lp).any(axis=1)
+    lp[bad] = np.nan
+    k = min(n_top, V)
+    order = np.argsort(-x, axis=1, kind="stable")[:, :k]     # descending value, ascending index among equals
+    top_ids = np.full((R, n_top), -1, dtype=np.int64)
+    top = np.full((R, n_top), -np.inf)
+    top_ids[:, :k] = order
+    top[:, :k] = np.take_along_axis(lp, order, axis=1)
+    top_ids[bad] = -1
+    top[bad] = np.nan
+    chosen = None
+    if targets is not None:
+        t = np.asarray(targets, dtype=np.int64).reshape(R)
+        ok = (t >= 0) & (t < V)
+        chosen = np.where(ok, lp[np.arange(R), np.where(ok, t, 0)], np.nan)
+    if flat:
+        return (None if chosen is None else chosen[0]), top_ids[0], top[0]
+    return chosen, top_ids, top
+
+
+def logprobs_from_request(req):
+    """The ``"logprobs"`` key of a request dict: None (absent: the request records nothing) or N, an int in 0 .. 8 — the chosen token's
+    log-probability and the N most likely alternatives per generated token. Anything else is a ValueError."""
+    n = req.get("logprobs")
+    if n is None:
+        return None
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= int(n) <= MAX_TOP_LOGPROBS:
+        raise ValueError(f"logprobs must be an int in 0 .. {MAX_TOP_LOGPROBS} (0: the chosen token only), got {n!r}")
+    return int(n)
+
+
+def logprobs_result(token_ids, chosen, top_ids, top, n):
+    """The ``'logprobs'`` entry of a result: one record per generated id in generation order, the top lists trimmed to the request's
+    ``n``. chosen [T]; top_ids / top [T, >= n] (or anything when n = 0). Arrays or tensors; what comes in goes out, sliced."""
+    T = len(token_ids)
+    assert len(chosen) == T and (n == 0 or (top_ids.shape[0] == T and top_ids.shape[1] >= n and top.shape == top_ids.shape))
+    if n == 0:
+        top_ids, top = top_ids[:T, :0], top[:T, :0]
+    return {"token_ids": token_ids, "token_logprobs": chosen, "top_ids": top_ids[:, :n], "top_logprobs": top[:, :n]}
+
+
 class SamplingParams:
     """How one request picks its tokens. ``do_sample=False`` is the greedy arg-max (the other fields are then inert). Defaults: the
     reference's temperature 0.7 / top_p 0.5 (seed_x.py:130-145) and transformers' generation default top_k 50, which a sampled

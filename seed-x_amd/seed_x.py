@@ -18,7 +18,8 @@ import torch
 
 from . import ops
 from .inflight import PrefixIndex, SlotScheduler, plan_admission, tag_signatures
-from .sampling import SamplingParams
+from .llama import LogprobState
+from .sampling import SamplingParams, logprobs_from_request, logprobs_result
 
 BOI_TOKEN = '<img>'
 EOI_TOKEN = '</img>'
@@ -199,9 +200,19 @@ class ContinuousLVLM:
         unmerged, beside requests under other adapters or none; every result carries ``'adapter'``. Without such a request the call
         runs the calls and captured graphs it always ran. ``reuse_cache`` re-prefills a sequence whose adapter changed.
         On a paged KV cache (``LlamaForCausalLM(kv_pages=N)``) every sequence reserves prompt + ``max_new_tokens`` rows up front and a
-        ``reuse_cache`` turn extends its reservation; RuntimeError naming the shortfall if the pool is too small."""
+        ``reuse_cache`` turn extends its reservation; RuntimeError naming the shortfall if the pool is too small.
+        A request may carry ``"logprobs": N`` (an int in 0 .. 8; ValueError otherwise, before anything is touched): its result gains
+        ``'logprobs'`` = {'token_ids', 'token_logprobs', 'top_ids', 'top_logprobs'}, one record per generated id in generation order —
+        the log-probability of the id under the model's RAW distribution (seedx_amd.sampling.token_logprobs: before the image-token
+        rule, temperature, top-k and top-p) and the N most likely ids with theirs. The first record comes from the LP lock-step tail on
+        the prefill's logits (sx_sample_next_b_lp), the later ones from the LP token step. Ids the model did not choose — the forced image
+        ids and ``</img>``, step-wise or as a host-driven chunk, and a ``force_image_at`` replacement — record NaN and top ids -1.
+        Without such a request the call runs exactly the path it always ran."""
         llm = self.llm
+        asks = [logprobs_from_request(req) for req in requests]
         params = [SamplingParams.from_request(req, world=llm.comm.world) for req in requests]     # refuses seed=None on tp > 1 ranks
+        if any(n is not None for n in asks) and llm.comm.world > 1:
+            raise ValueError(f"generate_batch: \"logprobs\" on tp={llm.comm.world} tensor-parallel ranks is not built (follow-up)")
         names = [req.get("adapter") for req in requests]
         for n in names:
             llm._adapter_index(n)                       # unknown name / feature off: ValueError before anything is touched
@@ -247,7 +258,12 @@ class ContinuousLVLM:
             llm.set_adapters(range(G), names)           # the per-sequence adapter index the token step reads (-1: none)
         self.last_prefill_tokens = [int(x.shape[0]) for x in xs]
         P["cur"].copy_(torch.tensor(last_ids, dtype=torch.int32))
-        if ss is not None:
+        lps = None
+        if any(n is not None for n in asks):            # the LP tail, here and in every token step; rows that did not ask record nothing
+            lps = LogprobState(G, max(n for n in asks if n is not None), dev, rows)
+            lps.want.copy_(torch.tensor([int(n is not None) for n in asks], dtype=torch.int32))
+            ops.next_b_lp(logits, llm.V, img_ids_dev, P["cur"], out_ids, P["step"], lps, ss)     # token index 0
+        elif ss is not None:
             ops.sample_next_b(logits, llm.V, img_ids_dev, P["cur"], out_ids, P["step"], ss)      # token index 0
         else:
             ops.greedy_next_b(logits, llm.V, img_ids_dev, P["cur"], out_ids, P["step"])
@@ -264,6 +280,8 @@ class ContinuousLVLM:
                 P["cur"][g] = boi_id
                 out_ids[g, n_new[g] - 1] = boi_id
                 cur[g] = boi_id
+                if asks[g] is not None:
+                    lps.forced(g, n_new[g] - 1, 1)       # the record made there describes the id that was replaced
 
         def finished(g):
             return n_new[g] >= max_new_tokens or (eos_token_id is not None and cur[g] == eos_token_id)
@@ -278,6 +296,8 @@ class ContinuousLVLM:
             if hit:
                 self._forced_image_chunk(hit, n_new, img_ids, hid, out_ids, [names[g] for g in hit] if named else None)
                 for g in hit:
+                    if asks[g] is not None:
+                        lps.forced(g, n_new[g], nchunk)
                     n_new[g] += nchunk
                     P["step"][g] = n_new[g]
                     P["cur"][g] = eoi_id
@@ -286,7 +306,8 @@ class ContinuousLVLM:
                         done[g], final_n[g] = True, n_new[g]
             if all(done):
                 break
-            llm.decode_step(img_ids_dev, out_ids, hid, use_graph=self.use_graph, sampling=ss)   # one token for every sequence
+            llm.decode_step(img_ids_dev, out_ids, hid, use_graph=self.use_graph, sampling=ss,   # one token for every sequence
+                            **(dict(logprobs=lps) if lps is not None else {}))
             cur = P["cur"].tolist()                                                          # the only read-back per step
             llm.comm.check()                              # (tensor-parallel only: + 4 bytes) a timed-out collective must not pass
             for g in range(G):
@@ -307,6 +328,9 @@ class ContinuousLVLM:
             if params[g] is not None:
                 results[-1]['seed'] = params[g].seed
             results[-1]['adapter'] = names[g]
+            if asks[g] is not None:
+                results[-1]['logprobs'] = logprobs_result(generate_ids, lps.chosen[g, :n].cpu(), lps.top_ids[g, :n].cpu().long(),
+                                                          lps.top[g, :n].cpu(), asks[g])
         return results
 
     @staticmethod
@@ -397,10 +421,21 @@ class ContinuousLVLM:
         admission stays deterministic (with an ample pool it is exactly the admission above). A request that can never fit — more pages
         than the pool has, or more rows than ``max_cache_len`` — raises ValueError before anything is touched.
         ``last_inflight_stats`` gains page_waits and peak_pages (inflight.simulate_paged predicts them and the step counts).
-        ``prefix_cache`` raises ValueError there: prefix reuse on pages means sharing pages by reference, a follow-up."""
+        ``prefix_cache`` raises ValueError there: prefix reuse on pages means sharing pages by reference, a follow-up.
+        A request may carry ``"logprobs": N`` as in generate_batch (same result entry, same NaN / -1 convention for forced ids): a queue
+        with at least one such request runs the LP token step on a slot state of its own (``want`` is written per slot at admission;
+        slots whose request did not ask record nothing), a queue without one takes the states and graphs it always took. A request's
+        records depend on its own logits only — never on its slot, its neighbours or the largest N in the queue. With
+        ``agent.speculative`` a logprob request raises ValueError (follow-up)."""
         llm = self.llm
+        requests = list(requests)
+        asks = [logprobs_from_request(req) for req in requests]
         if llm.comm.world > 1:
             raise NotImplementedError("generate_inflight is single-rank: tensor-parallel ranks are not supported")
+        n_top = max([n for n in asks if n is not None], default=None)
+        if n_top is not None and self.speculative:
+            raise ValueError("generate_inflight: \"logprobs\" with agent.speculative is not built (follow-up: records from the verify "
+                             "step's candidate rows); switch agent.speculative off for calls that ask for log-probabilities")
         prefix_cache, prefix_min_tokens = bool(self.prefix_cache), int(self.prefix_min_tokens)
         paged = bool(llm.kv_pages)
         if paged and prefix_cache:
@@ -461,9 +496,14 @@ class ContinuousLVLM:
         owned(llm.reset)                                 # bumps kv_epoch: the cross-turn records no longer describe the cache
         self._conv = {}
         which = "state_sampled" if sampled else "state"        # two slot states, two captured steps: neither disturbs the other
-        if keep[which] is None:
-            keep[which] = owned(lambda: llm.slot_state(force_id=boi_id, eos_id=eos, sampling=sampled))
+        if n_top is not None:                                  # ... and one more pair per n_top for the LP step
+            which += f"_lp{n_top}"
+        if keep.get(which) is None:
+            keep[which] = owned(lambda: llm.slot_state(force_id=boi_id, eos_id=eos, sampling=sampled, logprobs=n_top))
         st, img_ids_dev, out_ids, hid = keep[which], keep["img_ids_dev"], keep["out_ids"], keep["hid"]
+        lps = st.logprobs
+        if lps is not None:
+            lps.bind(out_ids.shape[1]).want.zero_()
         owned(llm.park_slots, range(G), st)
         sched = SlotScheduler(G, N, max_admit)
         results = [None] * N
@@ -503,6 +543,9 @@ class ContinuousLVLM:
             if params[r] is not None:
                 results[r]['seed'] = params[r].seed
             results[r]['adapter'] = names[r]
+            if asks[r] is not None:
+                results[r]['logprobs'] = logprobs_result(generate_ids, lps.chosen[g, :n].cpu(), lps.top_ids[g, :n].cpu().long(),
+                                                         lps.top[g, :n].cpu(), asks[r])
             if on_result is not None:
                 on_result(r, results[r])
 
@@ -534,6 +577,20 @@ class ContinuousLVLM:
             first = torch.tensor(last_ids, dtype=torch.int32, device=dev)
             if sampled:                                  # the slots take their requests' parameters; token index 0 is drawn here
                 st.sampling.set_rows(slots, [params[r] for _, r in adm])
+            if lps is not None:                          # the first record: the LP lock-step tail on the prefill's logits, one row per slot
+                wants = [int(asks[r] is not None) for _, r in adm]
+                llm._slot_write(lps.want, slots, wants)
+                rec = LogprobState(len(slots), n_top, dev, rows=1)
+                rec.want.copy_(torch.tensor(wants, dtype=torch.int32))
+                zero = torch.zeros(len(slots), dtype=torch.int32, device=dev)
+                ops.next_b_lp(logits.contiguous(), llm.V, img_ids_dev, first, None, zero, rec,
+                              st.sampling.gather(slots) if sampled else None, token_index=zero)
+                at = torch.tensor(slots, device=dev)
+                lps.chosen[at, 0], lps.top_ids[at, 0], lps.top[at, 0] = rec.chosen[:, 0], rec.top_ids[:, 0], rec.top[:, 0]
+                for i, (g, r) in enumerate(adm):
+                    if force_at[r] == 0 and wants[i]:
+                        lps.forced(g, 0, 1)              # (synthetic weights) the id is replaced below: the model did not choose it
+            elif sampled:
                 ops.sample_next_b(logits.contiguous(), llm.V, img_ids_dev, first, None, None, st.sampling.gather(slots),
                                   token_index=torch.zeros(len(slots), dtype=torch.int32, device=dev))
             else:
@@ -604,6 +661,8 @@ class ContinuousLVLM:
                 self._forced_image_chunk(hit, n_new, img_ids, hid, out_ids,                 # the other slots wait, as in generate_batch
                                          [names[sched.slot_req[g]] for g in hit] if named else None)
                 for g in hit:
+                    if asks[sched.slot_req[g]] is not None:
+                        lps.forced(g, n_new[g], nchunk)
                     if spec:                             # the block's ids at the positions they were fed (</img> is the new current token)
                         llm.spec_write_history(g, plen[g] + n_new[g] - 1, img_ids)
                     n_new[g] += nchunk
@@ -649,23 +708,87 @@ class ContinuousLVLM:
         self.last_inflight_stats = stats
         return results
 
+    @_clears_adapters
+    @torch.no_grad()
+    def score(self, tokenizer, requests, n_top=0):
+        """Likelihood scoring of given continuations (what multiple-choice benchmarks ask). Each request is generate_batch's prompt keys
+        (optionally ``"adapter"``) plus ``"continuations"``: a list of non-empty id lists. On sequence 0 the context is prefilled ONCE
+        (the logits of its last row score a continuation's first id); each continuation then rewinds the sequence to the end of the
+        context (``set_position``) and runs its ids but the last as one chunk with all-row logits, and sx_token_logprobs scores the rows
+        (ops.token_logprobs; the raw distribution, as for ``"logprobs"``). Returns, per request, a list with one dict per continuation:
+        ``'token_logprobs'`` fp32 [len], ``'sum'`` (their sum, in fp64 on the host) and, with ``n_top`` in 1 .. 8, ``'top_ids'`` /
+        ``'top_logprobs'`` [len, n_top]. A continuation's scores do not depend on the others or on their order. Works on contiguous, FP8
+        and paged caches (a paged one reserves context + longest continuation and gives the pages back). The LLM's caches are reset
+        before and after. Spreading candidates over slots, strings as continuations and prompt log-probabilities are out of scope."""
+        llm = self.llm
+        if isinstance(n_top, bool) or not isinstance(n_top, int) or not 0 <= n_top <= 8:
+            raise ValueError(f"score: n_top must be an int in 0 .. 8, got {n_top!r}")
+        if llm.comm.world > 1:
+            raise ValueError(f"score on tp={llm.comm.world} tensor-parallel ranks is not built (follow-up)")
+        requests = list(requests)
+        for r, req in enumerate(requests):
+            conts = req.get("continuations")
+            if not conts or any(len(c) < 1 for c in conts):
+                raise ValueError(f"score: request {r} needs \"continuations\": a non-empty list of non-empty id lists")
+            llm._adapter_index(req.get("adapter"))      # unknown name / feature off: ValueError before anything is touched
+        dev = llm.device
+        P = llm._pack()
+        self._conv = {}
+        if self._inflight is not None:
+            self._inflight["prefix"] = None
+        out = []
+        try:
+            for req in requests:
+                conts = [[int(i) for i in c] for c in req["continuations"]]
+                name = req.get("adapter")
+                kw = dict(adapters=[name]) if name is not None else {}
+                llm.reset()
+                ids, x = self._prompt_embeds(tokenizer, req)
+                need = len(ids) + max(len(c) for c in conts) - 1
+                assert need <= llm.Tmax, "KV cache too small for the context + the longest continuation"
+                if llm.kv_pages:
+                    llm._kv_need(0, need, f"score, a context of {len(ids)} rows + the longest continuation")
+                first, _ = llm.forward_embeds_batch([x], [0], **kw)                          # [1, Vpad]: the context's last row
+                res = []
+                for c in conts:
+                    rows = first
+                    if len(c) > 1:
+                        llm.set_position(0, len(ids))
+                        xe = ops.embedding(torch.tensor(c[:-1], dtype=torch.int32, device=dev), P["embed"])
+                        _, hs = llm.forward_embeds_batch([xe], [0], need_logits=False, **kw)
+                        rows = torch.cat([first, llm._lm_head(hs[0])])                       # plumbing
+                    lp, ti, tv = ops.token_logprobs(rows.contiguous(), llm.V, torch.tensor(c, dtype=torch.int32, device=dev), n_top)
+                    lp = lp.cpu()
+                    rec = {"token_logprobs": lp, "sum": float(lp.double().sum())}
+                    if n_top:
+                        rec.update(top_ids=ti.cpu().long(), top_logprobs=tv.cpu())
+                    res.append(rec)
+                out.append(res)
+        finally:
+            llm.reset()                                  # (a paged cache gets its pages back)
+        return out
+
     @torch.no_grad()
     def generate(self, tokenizer, prompt=None, input_ids=None, image_embeds=None, embeds_cmp_mask=None,
                  ids_cmp_mask=None, logits_processor=None, num_img_gen_tokens=64, temperature=0.7, num_beams=1,
                  max_new_tokens=120, top_p=0.5, dtype=torch.float16, device='cuda', patch_positions=None,
-                 eos_token_id="auto", force_image_at=None, reuse_cache=False, do_sample=False, top_k=50, seed=None, adapter=None):
+                 eos_token_id="auto", force_image_at=None, reuse_cache=False, do_sample=False, top_k=50, seed=None, adapter=None,
+                 logprobs=None):
         """Reference signature (seed_x.py:130-145). Greedy by default (do_sample=False, num_beams=1 — temperature/top_p are inert
         in the reference too, :175-189). ``do_sample=True`` makes ``temperature`` / ``top_p`` live (defaults: the reference's 0.7 /
         0.5) together with ``top_k`` (50, transformers' generation default) and ``seed`` (None: 64 bits from os.urandom): the seeded
         device-side rule of seedx_amd.sampling; the result then carries ``'seed'``. ``eos_token_id``: "auto" →
         tokenizer.eos_token_id; None disables the EOS stop. On tensor-parallel ranks ``do_sample=True`` needs an explicit ``seed``, the
         same on every rank (ValueError otherwise). ``adapter``: name of a LoRA adapter resident on the LLM (``llm.load_adapter``) the
-        request runs under, unmerged; the result carries ``'adapter'``."""
+        request runs under, unmerged; the result carries ``'adapter'``. ``logprobs``: N in 0 .. 8 → the result carries ``'logprobs'``
+        (generate_batch: per generated id its log-probability under the raw distribution and the N most likely ids)."""
         assert logits_processor is None, "the AutoImageTokenGenerationProcessor rule is fused on the device"
         assert num_beams == 1
         assert self.llm.G == 1, "this LLM was built for lock-step batches: use generate_batch()"
         req = dict(prompt=prompt, input_ids=input_ids, image_embeds=image_embeds, embeds_cmp_mask=embeds_cmp_mask,
                    ids_cmp_mask=ids_cmp_mask, patch_positions=patch_positions)
+        if logprobs is not None:
+            req["logprobs"] = logprobs
         if do_sample:
             req.update(do_sample=True, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
         if adapter is not None:
