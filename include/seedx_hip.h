@@ -66,7 +66,7 @@ int sx_version(void);
  * ------------------------------------------------------------------------------------------------ */
 typedef struct sx_gemm_args {
   const void* A;         /* 16-bit, LINEAR: [M][K]; CONV3X3: [B][Hin][Win][Cin]                    */
-  const void* W;         /* 16-bit, [N][K]   (CONV3X3: K = 9*Cin ordered (ky,kx,cin))              */
+  const void* W;         /* 16-bit, [N][K]   (CONV3X3: K = 9*Cin ordered (ky,kx,cin); upsample = 2: [4][N][4*Cin]) */
   void* C;               /* [M][N_out] of out_dtype, row stride ldc elements                        */
   const float* bias;     /* [N] fp32 or NULL                                                        */
   const float* bias2d;   /* [M / bias2d_rows][N] fp32 or NULL  (per-sample time-embedding add)      */
@@ -84,7 +84,16 @@ typedef struct sx_gemm_args {
   /* conv geometry (a_mode == SX_A_CONV3X3): M = B*Hout*Wout, K = 9*Cin */
   int32_t B, Hin, Win, Cin, Hout, Wout;
   int32_t stride;   /* 1 or 2 (padding: see pad_mode)                                                */
-  int32_t upsample; /* 1 = input is nearest-2x upsampled on the fly (Hout = 2*Hin)                   */
+  int32_t upsample; /* 1 = input is nearest-2x upsampled on the fly (Hout = 2*Hin)
+                       2 = the same convolution from PHASE-PACKED weights: output parity (a, c) = phase 2a + c sees only 2 x 2 distinct
+                       source pixels, so the 3x3 taps that share one are summed at pack time (16 products per input pixel, not 36):
+                         W[2a + c][n][(2u + v) Cin + ch] = sum_{ky in R(a,u)} sum_{kx in R(c,v)} w[n][ky][kx][ch],
+                         R(0,0) = {0}, R(0,1) = {1,2}, R(1,0) = {0,1}, R(1,1) = {2}
+                         y[b][2i + a][2j + c][n] = bias[n] + sum_{u,v,ch} W[2a + c][n][(2u + v) Cin + ch] x[b][i + a - 1 + u][j + c - 1 + v][ch]
+                       K = 4*Cin, M = 4*B*Hin*Win = B*Hout*Wout (GEMM rows run (phase, b, i, j); C is still the [B][Hout][Wout][N] image),
+                       stride 1, pad_mode 0, no residual, no fused GroupNorm statistics (sx_gemm_gn fails); bias2d_rows = Hout*Wout.
+                       Ping-pong 256-row tiles only: fails unless B*Hin*Win % 256 == 0 (a tile lies inside one phase) — such shapes
+                       keep upsample = 1 */
   int32_t ld_bias2d; /* row stride of bias2d in floats (0 = N): lets one GEMM produce every resnet's time add    */
   int32_t pad_mode; /* 0 = zero pad 1 on every side; 1 = pad 0 top/left and 1 bottom/right (diffusers Downsample2D with
                        padding=0 + F.pad(x, (0,1,0,1)): the stride-2 convs of the VAE encoder [ext])                 */

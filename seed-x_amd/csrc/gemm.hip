@@ -464,9 +464,19 @@ static int gemm_impl(const sx_gemm_args* a, double* gn_stats, int gn_groups, int
   p.ldb2 = a->ld_bias2d > 0 ? a->ld_bias2d : a->N;
   p.pad = 1;
   uint64_t a_bytes;
+  // upsample = 2: the nearest-2x up-sampler as four phase convolutions with 2x2 pre-summed taps (ping-pong tiles only, gemm_pp.hip)
+  const bool phases = a->a_mode == SX_A_CONV3X3 && a->upsample == 2;
   if (a->a_mode == SX_A_CONV3X3) {
-    SX_CHECK(a->Cin % 64 == 0 && a->K == 9 * a->Cin, "sx_gemm conv: Cin=%d K=%d", a->Cin, a->K);
+    SX_CHECK(a->upsample >= 0 && a->upsample <= 2, "sx_gemm conv: upsample=%d", a->upsample);
+    SX_CHECK(a->Cin % 64 == 0 && a->K == (phases ? 4 : 9) * a->Cin, "sx_gemm conv: Cin=%d K=%d", a->Cin, a->K);
     SX_CHECK(a->stride == 1 || a->stride == 2, "sx_gemm conv: stride");
+    if (phases) {
+      SX_CHECK(a->stride == 1 && a->pad_mode == 0, "sx_gemm conv: upsample = 2 is stride 1, pad 1");
+      SX_CHECK((int64_t)a->B * a->Hin * a->Win % 256 == 0,
+               "sx_gemm conv: upsample = 2 needs B*Hin*Win %% 256 == 0 (B=%d Hin=%d Win=%d): a 256-row tile must not straddle a phase",
+               a->B, a->Hin, a->Win);
+      SX_CHECK(!a->residual && !gn_stats, "sx_gemm conv: upsample = 2 takes no residual and no GroupNorm statistics");
+    }
     SX_CHECK(a->M == a->B * a->Hout * a->Wout, "sx_gemm conv: M != B*Hout*Wout");
     const int hv = a->upsample ? 2 * a->Hin : a->Hin, wv = a->upsample ? 2 * a->Win : a->Win;
     SX_CHECK(a->pad_mode == 0 || a->pad_mode == 1, "sx_gemm conv: pad_mode");
@@ -481,7 +491,7 @@ static int gemm_impl(const sx_gemm_args* a, double* gn_stats, int gn_groups, int
     SX_CHECK(a->a_mode == SX_A_LINEAR, "sx_gemm: bad a_mode");
     a_bytes = (uint64_t)a->M * Kk * 2;
   }
-  const uint64_t w_bytes = (uint64_t)a->N * a->K * 2;
+  const uint64_t w_bytes = (uint64_t)a->N * a->K * 2 * (phases ? 4 : 1);
   SX_CHECK(a_bytes < 0x7fffffffull && w_bytes < 0x7fffffffull, "sx_gemm: operand exceeds 2 GiB descriptor range");
   p.a_bytes = (unsigned)a_bytes;
   p.w_bytes = (unsigned)w_bytes;
@@ -504,7 +514,7 @@ static int gemm_impl(const sx_gemm_args* a, double* gn_stats, int gn_groups, int
     }
   }
   unsigned allow = 0x7f;
-  if (ln) allow = 0;            // ping-pong tiles or nothing
+  if (ln || phases) allow = 0;  // ping-pong tiles or nothing
   allow |= pp_supported(p, a->dtype, 256, a->a_mode) ? 0x80u : 0u;
   allow |= pp_supported(p, a->dtype, 320, a->a_mode) ? 0x100u : 0u;
   SX_CHECK(!(g_force_tile == 7 || g_force_tile == 8) || ((allow >> g_force_tile) & 1u),
@@ -517,7 +527,10 @@ static int gemm_impl(const sx_gemm_args* a, double* gn_stats, int gn_groups, int
              a->N, a->K, plain);
     allow = 1u << plain;
   }
-  const int cfg = pick_tile(a->M, a->N, Kk, a->glu != 0, a->a_mode == SX_A_CONV3X3, g_force_tile, allow);
+  SX_CHECK(!phases || allow, "sx_gemm conv: upsample = 2 has no ping-pong kernel for this epilogue");
+  // a forced lock-step tile does not apply to the phase mode (those kernels do not know it)
+  const int force = (phases && g_force_tile != 7 && g_force_tile != 8) ? -1 : g_force_tile;
+  const int cfg = pick_tile(a->M, a->N, Kk, a->glu != 0, a->a_mode == SX_A_CONV3X3, force, allow);
   if (cfg == 7 || cfg == 8) {
     // fused GroupNorm statistics: fp32 output of all N columns, whole 256-row tiles inside one sample, even channels per group
     if (gn_stats && a->out_dtype == SX_F32 && !a->glu && a->act == SX_ACT_NONE && p.n_valid == a->N && a->N % gn_groups == 0 &&

@@ -34,6 +34,11 @@
 namespace sxk_gemm {
 
 #define SX_A_CONV3X3_UP 2   // internal: 3x3 conv over a nearest-2x upsampled input (stride 1, pad 1)
+// internal: the same convolution as four 2x2 convolutions over the SOURCE image, one per output parity (a, c) ("phase"), with the 3x3
+// taps that land on one source pixel summed at pack time (sx_gemm_args.upsample = 2): K = 4 Cin, rows ordered (phase, b, i, j),
+// W = [4][N][4 Cin]; phase (a, c) reads source pixels (i + a - 1 + u, j + c - 1 + v), u, v in {0, 1}, and writes output pixel
+// (2i + a, 2j + c). A 256-row tile lies inside one phase (host gate: B Hin Win % 256 == 0)
+#define SX_A_CONV3X3_PH 3
 
 #define PP_SYNC()                            \
   do {                                       \
@@ -67,6 +72,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
   int tile_m, tile_n;
   if (!tile_coords(p, blockIdx.x, gridDim.x, tile_m, tile_n)) return;  // padding block (exits before any barrier)
   const int m0 = tile_m * BM, n0 = tile_n * BN;
+  const int ph = (AMODE == SX_A_CONV3X3_PH) ? m0 / (p.M >> 2) : 0;   // output parity 2a + c of this tile (workgroup-uniform)
 
   // LayerNorm fold, consumer: the tile's 256 (sum, sum of squares) pairs are requested HERE, ahead of the DMA prologue, and turned
   // into (rstd, -rstd mu) in the 2 KB of LDS behind the operand ring once the prologue is issued — at the epilogue's start the same
@@ -92,6 +98,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
   //       a_msk = bit t set iff tap t = 3*dy + dx reads inside the image (and the row is < M); with nearest-2x upsampling
   //       bits 9 / 10 hold the parity of the output row / column: the source pixel of tap (dy, dx) is then
   //       ((oy>>1) + ((py + dy - 1) >> 1), (ox>>1) + ((px + dx - 1) >> 1)) — no per-tap divisions or branches in the loop
+  // PHASES: a_off = byte offset of source pixel (i + a - 1, j + c - 1) = tap (0, 0) of the phase's 2x2 filter, a_msk = 4 validity bits
   unsigned a_off[4], a_msk[4];
   int a_lrow[4];
 #pragma unroll
@@ -101,6 +108,18 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
     if (AMODE == SX_A_LINEAR) {
       a_off[s] = (row < p.M) ? (unsigned)row * (unsigned)p.K * 2u + gchunk : 0xC0000000u;
       a_msk[s] = 0;
+    } else if (AMODE == SX_A_CONV3X3_PH) {
+      const int r = row - ph * (p.M >> 2);                        // pixel index (b Hin + i) Win + j of the source image
+      const int q = r / p.Win, j = r - q * p.Win, i = q % p.Hin;
+      const int sy = i + (ph >> 1) - 1, sx = j + (ph & 1) - 1;
+      unsigned msk = 0;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int iy = sy + (t >> 1), ix = sx + (t & 1);
+        if (row < p.M && iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win) msk |= 1u << t;
+      }
+      a_off[s] = (unsigned)((r + ((ph >> 1) - 1) * p.Win + (ph & 1) - 1) * p.Cin) * 2u + gchunk;
+      a_msk[s] = msk;
     } else {
       const int hw = p.Hout * p.Wout;
       const int b = row / hw, rem = row - b * hw;
@@ -123,10 +142,11 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
     }
   }
   unsigned w_off[NB];
+  const unsigned w_ph = (unsigned)ph * (unsigned)p.N * (unsigned)p.Kw * 2u;   // this phase's [N][Kw] weight (0 outside the phase mode)
 #pragma unroll
   for (int i = 0; i < NB; ++i) {
     const int row = n0 + (wave * NB + i) * 8 + rl;
-    w_off[i] = (row < p.N) ? (unsigned)row * (unsigned)p.Kw * 2u + gchunk : 0xC0000000u;
+    w_off[i] = (row < p.N) ? w_ph + (unsigned)row * (unsigned)p.Kw * 2u + gchunk : 0xC0000000u;
   }
   const int cpt = (AMODE != SX_A_LINEAR) ? p.Cin / 64 : 1;  // k-tiles per filter tap
   const int nkt = p.K / 64;
@@ -135,8 +155,9 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
   // filter-tap walkers of the two A streams (conv only): kx = state of the k-tile whose A0 rows are issued next (u + 2),
   // kz = state of the k-tile whose A1 rows are issued next (u + 1). Advanced incrementally: no division in the loop.
   struct Tap { int cc, dy, dx; };
+  constexpr int TW = (AMODE == SX_A_CONV3X3_PH) ? 2 : 3;   // filter width the walker wraps at
   auto tap_next = [&](Tap& t) {
-    if (++t.cc == cpt) { t.cc = 0; if (++t.dx == 3) { t.dx = 0; ++t.dy; } }
+    if (++t.cc == cpt) { t.cc = 0; if (++t.dx == TW) { t.dx = 0; ++t.dy; } }
   };
 
   // k-tile offset shared by every DMA of a k-tile: kt * 128 B, or 2 GiB for k-tiles past the end (zero fill, never read)
@@ -147,7 +168,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
     if (AMODE == SX_A_LINEAR) {
       voff = a_off[s] + koff_of(kt);
     } else {
-      const int tap = t.dy * 3 + t.dx;                                  // wave-uniform
+      const int tap = t.dy * TW + t.dx;                                 // wave-uniform
       const bool ok = ((a_msk[s] >> tap) & 1u) != 0 && kt < nkt;
       unsigned o;
       if (AMODE == SX_A_CONV3X3_UP) {
@@ -319,9 +340,16 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
     for (int i = 0; i < FN; ++i) bv[i] = *(const f32x4_t*)(p.bias + ncol[i]);
   }
   // per-sample bias rows (time-embedding add of the resnet convs): a tile inside one sample adds it to the bias vector once
-  const bool b2_uniform = p.bias2d && (m0 / p.bias2d_rows) == ((m0 + BM - 1 < p.M ? m0 + BM - 1 : p.M - 1) / p.bias2d_rows);
+  // row of C (and of bias2d's sample count) that GEMM row m is stored to: m itself, or in the phase mode output pixel (2i + a, 2j + c)
+  auto out_row = [&](int m) -> int {
+    if (AMODE != SX_A_CONV3X3_PH) return m;
+    const int r = m - ph * (p.M >> 2);
+    const int q = r / p.Win, j = r - q * p.Win;                     // q = b Hin + i: output image row 2q + a (Hout = 2 Hin)
+    return (2 * q + (ph >> 1)) * p.Wout + 2 * j + (ph & 1);
+  };
+  const bool b2_uniform = p.bias2d && (out_row(m0) / p.bias2d_rows) == (out_row(m0 + BM - 1 < p.M ? m0 + BM - 1 : p.M - 1) / p.bias2d_rows);
   if (b2_uniform) {
-    const float* b2 = p.bias2d + (size_t)(m0 / p.bias2d_rows) * p.ldb2;
+    const float* b2 = p.bias2d + (size_t)(out_row(m0) / p.bias2d_rows) * p.ldb2;
 #pragma unroll
     for (int i = 0; i < FN; ++i) bv[i] += *(const f32x4_t*)(b2 + ncol[i]);
   }
@@ -370,6 +398,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
     const int m = m0 + g * 128 + j * 16 + (lane & 15);
     const bool mok = m < p.M;
     const int mc = mok ? m : p.M - 1;
+    const int mo = out_row(m);             // row of C this lane stores to
     f32x4_t v[FN];
     if constexpr (LN == 1) {
       const f32x2_t ab = *(const f32x2_t*)(ln_lds + 2 * (g * 128 + j * 16 + (lane & 15)));
@@ -380,7 +409,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
       for (int i = 0; i < FN; ++i) v[i] = acc[i][j] + bv[i];
     }
     if (b2_rows) {
-      const float* b2 = p.bias2d + (size_t)(mc / p.bias2d_rows) * p.ldb2;
+      const float* b2 = p.bias2d + (size_t)(out_row(mc) / p.bias2d_rows) * p.ldb2;
 #pragma unroll
       for (int i = 0; i < FN; ++i) v[i] += *(const f32x4_t*)(b2 + ncol[i]);
     }
@@ -406,7 +435,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
     if (OUT32) {
 #pragma unroll
       for (int i = 0; i < FN; ++i)
-        if (mok && nok[i]) *(f32x4_t*)((float*)p.C + (size_t)m * p.ldc + nout[i]) = v[i];
+        if (mok && nok[i]) *(f32x4_t*)((float*)p.C + (size_t)mo * p.ldc + nout[i]) = v[i];
       if constexpr (LN == 2) {
         // the row's 16-bit copy (the operand of the GEMM behind the folded LayerNorm) and this lane's share of its two sums
         float s1 = 0.f, s2 = 0.f;
@@ -479,12 +508,12 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmP p) {
             const u32x4_t w4 = {s0[0], s1[0], s0[1], s1[1]};
             const int q = lane >> 4;
             const int col = n0 + wc * TN + i * 16 + (q & 1) * 16 + (q >> 1) * 8;
-            *(u32x4_t*)((unsigned short*)p.C + (size_t)m * p.ldc + col) = w4;
+            *(u32x4_t*)((unsigned short*)p.C + (size_t)mo * p.ldc + col) = w4;
           }
           continue;
         }
         if (!GLU && wide && (i & 1) && pair_ok[i >> 1]) continue;  // stored with its even partner
-        if (mok && nok[i]) *(u32x2_t*)((unsigned short*)p.C + (size_t)m * p.ldc + nout[i]) = pack4(v[i]);
+        if (mok && nok[i]) *(u32x2_t*)((unsigned short*)p.C + (size_t)mo * p.ldc + nout[i]) = pack4(v[i]);
       }
     }
   }
@@ -622,9 +651,26 @@ bool pp_supported(const GemmP& p, int dtype, int bn, int a_mode) {
   return bn == 256 || bn == 320;
 }
 
+// the phase-packed up-sampler (sx_gemm_args.upsample = 2): plain epilogue, fp32 or 16-bit output. Every instantiation has its case in
+// tests/test_upsample_phases.py (which parses this function)
+template <typename TT>
+static int launch_phases(const GemmP& p, int e, int bn, hipStream_t st) {
+#define PH_CASE(BNV, O32) return launch_one<TT, BNV, SX_A_CONV3X3_PH, O32, SX_ACT_NONE, false>(p, st)
+  if (bn == 256) {
+    if (e == 0) PH_CASE(256, false);
+    if (e == 4) PH_CASE(256, true);
+  } else {
+    if (e == 0) PH_CASE(320, false);
+    if (e == 4) PH_CASE(320, true);
+  }
+#undef PH_CASE
+  return -1;
+}
+
 template <typename TT>
 static int launch_t(const GemmP& p, int dtype, int bn, int a_mode, hipStream_t st) {
   const int e = epi_code(p, dtype);
+  if (a_mode == SX_A_CONV3X3 && p.upsample == 2) return launch_phases<TT>(p, e, bn, st);
 #define PP_CASE(BNV, AM, O32, ACTV, GLUV) return launch_one<TT, BNV, AM, O32, ACTV, GLUV>(p, st)
   if (p.ln_in) {
     if (e == 2) return launch_one<TT, 256, SX_A_LINEAR, false, SX_ACT_GELU, true, 1>(p, st);

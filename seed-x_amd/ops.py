@@ -189,23 +189,72 @@ def gemm(a, w, bias=None, bias2d=None, bias2d_rows=0, residual=None, res_mod=0, 
     return out
 
 
+_PHASE_TAPS = {(0, 0): (0,), (0, 1): (1, 2), (1, 0): (0, 1), (1, 1): (2,)}   # R(parity, phase tap): the 3x3 taps that share a source pixel
+
+
+def pack_upsample_phases(w, planes=1, dtype=None, rounded=True):
+    """Weights of a 3x3 / pad 1 conv over a nearest-2x up-sampled image → the four 2x2 phase filters over the SOURCE image
+    (sx_gemm_args.upsample = 2: 16 products per input pixel, not 36). w: [Cout, 9*C] in (ky, kx, c) order. Output pixel (2i + a, 2j + c)
+    reads source pixels (i + a - 1 + u, j + c - 1 + v), u, v in {0, 1}; the taps that land on one of them are summed in fp64:
+        Wp[2a + c][n][(2u + v) C + ch] = sum_{ky in R(a, u)} sum_{kx in R(c, v)} w[n][ky][kx][ch],   R = _PHASE_TAPS
+    and rounded ONCE: planes = 1 → to `dtype` (default w's); planes = 3 (the fp32-grade VAE) → to fp32, then split per tap into the
+    bf16 planes [hi | lo | hi] of vae.pack_planes. Returns [4, Cout, 4*planes*C] contiguous (rounded=False: the fp64 sums, planes = 1)."""
+    assert w.dim() == 2 and w.shape[1] % 9 == 0 and planes in (1, 3)
+    Cout, C = w.shape[0], w.shape[1] // 9
+    w9 = w.detach().double().reshape(Cout, 3, 3, C)
+    wp = torch.zeros((4, Cout, 2, 2, C), dtype=torch.float64, device=w.device)
+    for (a, u), kys in _PHASE_TAPS.items():
+        for (c, v), kxs in _PHASE_TAPS.items():
+            for ky in kys:
+                for kx in kxs:
+                    wp[2 * a + c, :, u, v] += w9[:, ky, kx]
+    if not rounded:
+        assert planes == 1
+        return wp.view(4, Cout, 4 * C)
+    if planes == 1:
+        return wp.to(dtype or w.dtype).view(4, Cout, 4 * C).contiguous()
+    s32 = wp.float()
+    hi = s32.to(torch.bfloat16)
+    lo = (s32 - hi.float()).to(torch.bfloat16)
+    return torch.cat([hi, lo, hi], dim=4).view(4, Cout, 12 * C).contiguous()
+
+
+def upsample_phases_ok(B, H, W):
+    """The shape gate of sx_gemm's upsample = 2: a 256-row ping-pong tile must lie inside one output parity."""
+    return (B * H * W) % 256 == 0
+
+
 def conv3x3(x, w, bias=None, bias2d=None, residual=None, stride=1, upsample=False, out_dtype=None, act=None,
-            n_valid=0, pad_mode=0, gn=None):
+            n_valid=0, pad_mode=0, gn=None, w_phases=None, out=None):
     """3x3 / pad 1 convolution as implicit GEMM. x: [B, H, W, Cin] 16-bit NHWC contiguous; w: [Cout, 9*Cin]
     ((ky,kx,cin)-ordered). Returns [B, Hout*Wout, Cout] (NHWC flattened). bias2d: [B, Cout] fp32 per-sample add.
-    residual: fp32 [B*Hout*Wout, Cout]. pad_mode 1 = pad only bottom/right (VAE encoder's stride-2 convs)."""
+    residual: fp32 [B*Hout*Wout, Cout]. pad_mode 1 = pad only bottom/right (VAE encoder's stride-2 convs).
+    w_phases (upsample only): pack_upsample_phases(w) [4, Cout, 4*Cin]. Used when the shape gate holds and the call has neither a
+    residual nor fused GroupNorm statistics (upsample_phases_ok; 16 taps per input pixel); every other call runs the 36-tap gather
+    from w as before. out: optional [B*Hout*Wout, n_store] contiguous tensor of out_dtype to store into."""
     lib = _lib.load()
-    assert x.dim() == 4 and x.is_contiguous() and w.is_contiguous()
+    assert x.dim() == 4 and x.is_contiguous()
     B, H, W, Cin = x.shape
-    Cout, K = w.shape
-    assert K == 9 * Cin
+    phases = (w_phases is not None and upsample and stride == 1 and pad_mode == 0 and residual is None and gn is None
+              and act is None and upsample_phases_ok(B, H, W))
+    if phases:
+        assert w_phases.dim() == 3 and w_phases.shape[0] == 4 and w_phases.shape[2] == 4 * Cin and w_phases.dtype == x.dtype
+        w = w_phases
+        Cout, K = w.shape[1], 4 * Cin
+    else:
+        assert w is not None, "conv3x3: this call needs the 36-tap weight (the phase gate does not hold)"
+        Cout, K = w.shape
+        assert K == 9 * Cin
+    assert w.is_contiguous()
     hv, wv = (2 * H, 2 * W) if upsample else (H, W)
     padsum = 1 if pad_mode else 2
     Hout, Wout = (hv + padsum - 3) // stride + 1, (wv + padsum - 3) // stride + 1
     M = B * Hout * Wout
     out_dtype = out_dtype or x.dtype
     n_store = n_valid if n_valid else Cout
-    out = torch.empty((M, n_store), dtype=out_dtype, device=x.device)
+    if out is None:
+        out = torch.empty((M, n_store), dtype=out_dtype, device=x.device)
+    assert out.shape == (M, n_store) and out.dtype == out_dtype and out.is_contiguous()
     args = GemmArgs()
     args.A, args.W, args.C = x.data_ptr(), w.data_ptr(), out.data_ptr()
     args.bias = _f32c(bias).data_ptr() if bias is not None else None
@@ -227,7 +276,7 @@ def conv3x3(x, w, bias=None, bias2d=None, residual=None, stride=1, upsample=Fals
     args.a_mode = SX_A_CONV3X3
     args.B, args.Hin, args.Win, args.Cin, args.Hout, args.Wout = B, H, W, Cin, Hout, Wout
     args.stride = stride
-    args.upsample = 1 if upsample else 0
+    args.upsample = (2 if phases else 1) if upsample else 0
     args.pad_mode = pad_mode
     _launch_gemm(lib, args, gn, "sx_gemm(conv3x3)")
     return out.view(B, Hout * Wout, n_store)

@@ -240,6 +240,11 @@ class UNet2DConditionModel:
             if i != len(boc) - 1:
                 n = f"up_blocks.{i}.upsamplers.0.conv"
                 blk["up"] = (conv16(n + ".weight"), f32(n + ".bias"))
+                # the same weight as four 2x2 phase filters (16 taps per input pixel): used when the run-time shape passes the gate
+                # (ops.conv3x3); the 36-tap copy stays for the other shapes and for the row-sharded forward
+                # — summed in fp64 from the checkpoint's own values, rounded once to the operand dtype
+                w = sd[n + ".weight"].detach().to(dev)
+                blk["up_ph"] = ops.pack_upsample_phases(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1), dtype=dt)
             P["up"].append(blk)
         P["norm_out"] = (f32("conv_norm_out.weight"), f32("conv_norm_out.bias"))
         wo = conv16("conv_out.weight")
@@ -280,7 +285,8 @@ class UNet2DConditionModel:
             return None
         return ops.GnStats(self._gn_arena[i], self.cfg["norm_groups"], HW)
 
-    def _conv(self, h16, B, Hc, Wc, w, bias=None, bias2d=None, residual=None, stride=1, upsample=False, n_valid=0, gn=None):
+    def _conv(self, h16, B, Hc, Wc, w, bias=None, bias2d=None, residual=None, stride=1, upsample=False, n_valid=0, gn=None,
+              w_phases=None):
         """3x3 conv on this rank's slab. h16: 16-bit [B, Hl*Wc, Cin] (Hl = Hc / tp rows). Returns fp32 [B, Hl'*Wc', Cout].
         With tp > 1 the slab is extended by the neighbours' boundary rows (seqpar.with_halo) so that no output pixel sees a
         wrong zero padding; rows computed from the artificial padding of the halo itself are dropped."""
@@ -288,7 +294,7 @@ class UNet2DConditionModel:
         Cin = h16.shape[-1]
         if tp == 1:
             return ops.conv3x3(h16.view(B, Hc, Wc, Cin), w, bias=bias, bias2d=bias2d, residual=residual, stride=stride,
-                               upsample=upsample, out_dtype=torch.float32, n_valid=n_valid, gn=gn)
+                               upsample=upsample, out_dtype=torch.float32, n_valid=n_valid, gn=gn, w_phases=w_phases)
         from . import seqpar
         Hl = Hc // tp
         Co = n_valid or w.shape[0]
@@ -513,7 +519,7 @@ class UNet2DConditionModel:
                     x, st = self._transformer(blk["attn"][j], x, B, ctx[ti], Hc, Wc, st_in=st)
                     ti += 1
             if blk["up"] is not None:
-                x = self._conv(ops.cast(x, dt), B, Hc, Wc, blk["up"][0], bias=blk["up"][1], upsample=True)
+                x = self._conv(ops.cast(x, dt), B, Hc, Wc, blk["up"][0], bias=blk["up"][1], upsample=True, w_phases=blk["up_ph"])
                 Hc, Wc = Hc * 2, Wc * 2
                 st = None
         h = self._gn(x, P["norm_out"], 1e-5, True, Hc, Wc, stats=st)

@@ -305,6 +305,10 @@ class AutoencoderKL:
             if i != len(boc) - 1:
                 n = f"decoder.up_blocks.{i}.upsamplers.0.conv"
                 blk["up"] = (conv16(n + ".weight"), f32(n + ".bias"))
+                # four 2x2 phase filters of the same weight (ops.pack_upsample_phases): summed in fp64 from the fp32 taps, then one
+                # plane of the operand dtype or the three bf16 planes of the summed weight. The 36-tap copy serves the shapes the
+                # phase gate refuses
+                blk["up_ph"] = ops.pack_upsample_phases(conv32(n + ".weight"), planes=3 if split else 1, dtype=dt)
             P["up"].append(blk)
         P["norm_out"] = (f32("decoder.conv_norm_out.weight"), f32("decoder.conv_norm_out.bias"))
         wo = conv32("decoder.conv_out.weight")
@@ -448,7 +452,8 @@ class AutoencoderKL:
             for r in blk["res"]:
                 x = self._resnet(r, x, H, W)
             if blk["up"] is not None:
-                x = ops.conv3x3(self._A(x).view(1, H, W, -1), blk["up"][0], bias=blk["up"][1], upsample=True, out_dtype=f32)
+                x = ops.conv3x3(self._A(x).view(1, H, W, -1), blk["up"][0], bias=blk["up"][1], upsample=True, out_dtype=f32,
+                                w_phases=blk["up_ph"])
                 H, W = 2 * H, 2 * W
         hN = self._gn(x, P["norm_out"], True, planes=P["p_out"])
         y = self._conv(P["p_out"], hN.view(1, H, W, -1), P["conv_out"][0], bias=P["conv_out"][1], out_dtype=f32,
