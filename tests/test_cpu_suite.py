@@ -1019,6 +1019,67 @@ def test_gemv_matrix_covers_every_launched_kernel():
     assert {(gv.n_blocks(c), c["S"]) for c in gv.SKINNY if c["S"] and c["ws"] == "full"} == {(mb, s) for mb in (1, 2, 4) for s in (2, 8)}
 
 
+def test_attn_norm_matrix_covers_every_launched_kernel():
+    """tests/test_attn_norm_matrix_gpu.py's case tables reach every instantiation that the host code of norm.hip and attn.hip launches
+    (parsed from the sources): the 15 layernorm_kernel<DT, NV> and 3 layernorm_block_kernel<DT>, both gn_stats_kernel<TWO> and
+    gn_apply_kernel<TWO>, the 3 softmax_rows_kernel, the 4 attn_kernel<TT, DP> and 2 attn_small_kernel<TT>; every GroupNorm thread
+    count at every slot count that C <= 3072 allows; and the shapes on both sides of every dispatch boundary. kernel_of_* restate
+    the dispatch rules by hand (source_kernels holds the lines they restate), so an instantiation added later has no case here."""
+    from tests import test_attn_norm_matrix_gpu as am
+    src = am.source_kernels()
+    assert [len(src[k]) for k in ("ln_wave", "ln_block", "gn_stats", "gn_apply", "softmax", "attn", "attn_small")] == [15, 3, 2, 2, 3, 4, 2]
+    ids = [c["id"] for c in am.ATTN + am.LN + am.GN + am.SM]
+    assert len(ids) == len(set(ids))
+    # LayerNorm: every instantiation with every output type and every mode; the NV boundaries from both sides; rows % 4 != 0
+    ln = [c for c in am.LN if not c["tiled"]]
+    for kern in src["ln_wave"] | src["ln_block"]:
+        have = {(c["o"], c["mode"]) for c in ln if am.kernel_of_ln(c) == kern}
+        assert have == {(o, mode) for o in am.ALL_DT for mode in am.LN_MODES}, kern
+    assert {am.kernel_of_ln(c) for c in am.LN} == src["ln_wave"] | src["ln_block"]
+    wave_n4 = {c["cols"] // 4 for c in ln if c["rows"] > 32}
+    assert {1, 192, 193, 320, 321, 512, 513, 1024, 1025, 1536} <= wave_n4 and all(c["rows"] % 4 for c in ln if c["rows"] > 32)
+    assert {c["rows"] for c in ln if c["rows"] <= 32} == {1, 16, 17, 32} and {c["rows"] for c in ln if c["rows"] > 32} == {33, 37}
+    tiled = [c for c in am.LN if c["tiled"]]
+    assert {(c["rows"], c["cols"], c["o"]) for c in tiled} == {(r, n, o) for r in (1, 15, 16, 17, 32) for n in (32, 5120) for o in ("f16", "bf16")}
+    assert {am.kernel_of_ln(c) for c in tiled} == src["ln_block"]
+    # GroupNorm: both kernels with and without a second source; T x slots over every legal C of 32 groups; the apply loop's rounds
+    assert {k for c in am.GN for k in am.kernel_of_gn(c)} == src["gn_stats"] | src["gn_apply"]
+    legal = [C_ for C_ in range(64, am.GN_MAX_C + 1, 64)]
+    want = {(am.gn_threads(C_), am.gn_slots(C_)) for C_ in legal}
+    assert want == {(128, 1), (160, 1), (160, 3), (256, 1), (256, 2), (256, 3), (320, 1), (320, 2)}
+    assert {(am.gn_threads(c["C"]), am.gn_slots(c["C"])) for c in am.GN} == want
+    assert {c["C"] for c in am.GN} >= {64, 320, 512, 640, 960, 1024, 1280, 1920, 2560, 3072} and {c["HW"] for c in am.GN} >= {1, 3, 7, 8, 37, 100}
+    assert {(c["C1"], c["C"] - c["C1"]) for c in am.GN if c["C1"]} == {(640, 320), (320, 640), (4, 60), (1280, 1280)}
+    assert {c["out"] for c in am.GN} == {"f16", "bf16", "f32", "bf16x3", "f16x2"} and {c["groups"] for c in am.GN} == {1, 32, 64}
+    assert any(am.gn_rows(c)[0] > 4 and am.gn_apply_rounds(c) >= 3 for c in am.GN) and {am.gn_rows(c) for c in am.GN if c["HW"] == 4200} == {(5, 17), (5, 132)}
+    # row softmax
+    assert {am.kernel_of_sm(c) for c in am.SM} == src["softmax"]
+    assert {(c["rows"], c["cols"]) for c in am.SM} == {(1, 4), (3, 260), (5, 1024), (2, 1028), (2, 4100), (1, 16384)}
+    # attention: every instantiation at every family of cases
+    big = [c for c in am.ATTN if not c["small"]]
+    assert {am.kernel_of_attn(c) for c in big} == src["attn"] and {am.kernel_of_attn(c) for c in am.ATTN if c["small"]} == src["attn_small"]
+    fam = lambda c: c["id"].split("-B")[0].rsplit("-", 1)[0]
+    for kern in src["attn"]:
+        have = {fam(c) for c in big if am.kernel_of_attn(c) == kern}
+        assert have >= {"hd", "skv", "sq", "causal", "stair-up", "stair-first", "scale4"} | {f"lay-{n}" for n in ("qb0", "bsh3d", "bs3hd", "kvfused", "kvdiff", "opad", "gap")}, (kern, have)
+    assert {c["D"] for c in big} >= {8, 16, 40, 56, 64, 72, 96, 104, 128} and all(c["B"] * c["H"] <= 6 for c in am.ATTN)
+    for D in (64, 128):
+        assert {c["Skv"] for c in big if c["D"] == D and fam(c) == "skv"} == {1, 63, 64, 65, 127, 128, 129, 700}
+        assert {c["Sq"] for c in big if c["D"] == D and fam(c) == "sq"} == {1, 31, 32, 33, 127, 128, 129, 300}
+        assert {(c["Sq"], c["Skv"]) for c in big if c["D"] == D and c["causal"]} == {(1, 1), (1, 65), (64, 229), (129, 129), (200, 333), (300, 300)}
+    assert {c["B"] * c["H"] * -(-c["Sq"] // 128) for c in big if fam(c) == "grid"} == {1, 7, 9, 24}
+    for tt in ("F16", "BF16"):
+        small = [c for c in am.ATTN if am.kernel_of_attn(c) == ("attn_small_kernel", tt)]
+        assert {c["D"] for c in small} == {8, 64, 160, 256} and {c["Skv"] for c in small} >= {1, 63, 64, 65, 1536}
+        assert {c["Sq"] for c in small} >= {1, 3, 4, 5, 64} and {c["B"] * c["H"] * c["Sq"] % 4 for c in small} == {0, 1, 2, 3}
+        assert {c["layout"] for c in small} == {"plain", "qb0", "kvfused", "gap"}
+    # the planted positions are injective and start at the edges
+    for Sq, Skv in ((130, 200), (70, 700), (300, 100), (70, 1), (5, 65)):
+        pos = am.plant_positions(Sq, Skv, False)
+        assert len(pos) == len(set(pos)) == min(Sq, Skv) and all(0 <= p < Skv for p in pos)
+    assert am.plant_positions(130, 200, False)[:8] == [0, 63, 64, 127, 128, 191, 198, 199] and am.plant_positions(3, 10, True) == [7, 8, 9]
+
+
 def test_gemv_matrix_k_values_reach_every_peeled_round():
     """For every skinny instantiation, dtype and weight format, the four waves' (full, rem) of its unsplit cases — by the kernel's own
     k-slice formula — cover full in {0, 1, 2, odd >= 3, even >= 4} with every rem in 0 .. U-1 (all but the wave without k-steps), the
