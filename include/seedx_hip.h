@@ -478,6 +478,39 @@ int sx_sample_next_b_lp(float* logits, int ld_logits, int vocab, const int32_t* 
                         const int32_t* prev_id_dev, int32_t* next_id_dev, int32_t* out_ids, int ld_out,
                         const int32_t* step_dev, int G, const sx_sample_args* sample, const sx_logprob_args* lp, void* stream);
 int sx_sample_next_slots_lp(const sx_slot_step_args* args, const sx_sample_args* sample, const sx_logprob_args* lp, void* stream);
+/* Per-request logits controls on the device (seedx_amd.sampling.apply_controls states the rule in numpy fp32, one IEEE rounding per
+ * written operation; the kernel runs each as one instruction). Row g with on[g] != 0: with c = counts[g][v] (bit 30: v occurs in the
+ * prompt; c & 0xFFFFFF = n, times generated) and k the token index (step[g] in the slot form, token_index[g] in lock-step),
+ *   1. rep != 1 and (mark or n > 0):  y = y < 0 ? y * rep : y * rep_inv            (rep_inv = float32(1 / rep), made by the host)
+ *   2. n > 0:                         t = frequency * float(n); t = t + presence; y = y - t
+ *   3. every bias entry j with 0 <= bias_ids[g][j] < vocab, in list order:  y[id] = y[id] + bias[g][j]     (-inf bans the id)
+ *   4. eos_id >= 0 and k < min_new[g]:  y[eos_id] = -inf                 (the slot form takes sx_slot_step_args.eos_id, lock-step eos_id below)
+ * then the processor rule, and the arg-max or draw, of the uncontrolled call run on y. The edited row is written to work[g][0..ld_logits)
+ * and the rule's zeroing happens THERE: the logits row of a controlled row stays exactly what lm_head wrote, so the LP record is of
+ * the raw row. After the emitted id is known (slot form: after the force_at replacement) counts[g][id] += 1 for 0 <= id < vocab.
+ * A row with on[g] == 0 and every parked slot: bit for bit the call without controls (in-place zeroing included), nothing counted. */
+typedef struct sx_logits_ctl_args {
+  const int32_t* on;            /* [G]: 0 = the row runs as without controls                                                       */
+  int32_t* counts;              /* [G][ld_counts]: bit 30 = prompt mark, low 24 bits = times generated                             */
+  float* work;                  /* [G][ld_logits]: the edited rows (rows with on = 0 are not written)                              */
+  const float* rep;             /* [G] repetition penalty, finite > 0 (1 = off)                                                    */
+  const float* rep_inv;         /* [G] float32(1 / rep)                                                                            */
+  const float* presence;        /* [G]                                                                                             */
+  const float* frequency;       /* [G]                                                                                             */
+  const int32_t* min_new;       /* [G]                                                                                             */
+  const int32_t* bias_ids;      /* [G][16], -1 = empty                                                                             */
+  const float* bias;            /* [G][16]                                                                                         */
+  const int32_t* token_index;   /* [G], lock-step form only (the slot form uses step); may be NULL there                           */
+  int32_t ld_counts, eos_id;    /* eos_id: lock-step form only, -1 = none                                                          */
+} sx_logits_ctl_args;
+/* sx_sample_next_b_lp's / sx_sample_next_slots_lp's arguments with sample and lp both nullable (greedy, sampled, LP, sampled + LP) and
+ * the controls above; ctl is required. vocab of any size for the greedy form without lp; ld_logits >= vocab, ld_counts >= vocab. */
+int sx_next_b_ctl(float* logits, int ld_logits, int vocab, const int32_t* img_ids_dev, int n_img,
+                  const int32_t* prev_id_dev, int32_t* next_id_dev, int32_t* out_ids, int ld_out,
+                  const int32_t* step_dev, int G, const sx_sample_args* sample, const sx_logprob_args* lp,
+                  const sx_logits_ctl_args* ctl, void* stream);
+int sx_next_slots_ctl(const sx_slot_step_args* args, const sx_sample_args* sample, const sx_logprob_args* lp,
+                      const sx_logits_ctl_args* ctl, void* stream);
 
 /* Speculative decoding (lossless): the token step carries T = K + 1 rows per slot — row g*T is the slot's current token, rows g*T + 1 ..
  * g*T + n_draft[g] K drafted continuations — and sx_greedy_next_b / sx_sample_next_b over the G*T rows (previous id = the row's input,

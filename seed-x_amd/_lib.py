@@ -84,6 +84,12 @@ class LogprobArgs(C.Structure):
     _fields_ = [("want", c_vp), ("chosen", c_vp), ("top_ids", c_vp), ("top", c_vp), ("n_top", c_i32), ("reserved", c_i32)]
 
 
+class LogitsCtlArgs(C.Structure):
+    _fields_ = [("on", c_vp), ("counts", c_vp), ("work", c_vp), ("rep", c_vp), ("rep_inv", c_vp), ("presence", c_vp),
+                ("frequency", c_vp), ("min_new", c_vp), ("bias_ids", c_vp), ("bias", c_vp), ("token_index", c_vp),
+                ("ld_counts", c_i32), ("eos_id", c_i32)]
+
+
 class SpecAcceptArgs(C.Structure):
     _fields_ = [("cand", c_vp), ("rows_in", c_vp), ("n_draft", c_vp), ("cur", c_vp), ("live", c_vp), ("n_new", c_vp), ("max_new", c_vp),
                 ("force_at", c_vp), ("pos", c_vp), ("ctx", c_vp), ("step", c_vp), ("out_ids", c_vp), ("status", c_vp), ("hist", c_vp),
@@ -170,6 +176,9 @@ SIGNATURES = {
     "sx_sample_next_b_lp": [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, C.POINTER(SampleArgs),
                             C.POINTER(LogprobArgs), c_vp],
     "sx_sample_next_slots_lp": [C.POINTER(SlotStepArgs), C.POINTER(SampleArgs), C.POINTER(LogprobArgs), c_vp],
+    "sx_next_b_ctl": [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, C.POINTER(SampleArgs),
+                      C.POINTER(LogprobArgs), C.POINTER(LogitsCtlArgs), c_vp],
+    "sx_next_slots_ctl": [C.POINTER(SlotStepArgs), C.POINTER(SampleArgs), C.POINTER(LogprobArgs), C.POINTER(LogitsCtlArgs), c_vp],
     "sx_spec_accept": [C.POINTER(SpecAcceptArgs), c_vp],
     "sx_spec_draft_ngram": [C.POINTER(SpecDraftArgs), c_vp],
     "sx_scatter_rows_spec": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp],

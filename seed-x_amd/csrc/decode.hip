@@ -1488,13 +1488,98 @@ __global__ __launch_bounds__(1024) void token_logprobs_kernel(const float* logit
 // greedy id; the greedy instantiation holds nothing of the sampler. LP: rows with want[g] != 0 also record the log-probability of the
 // id they emit and the n_top largest of the row, at [g][step[g]] under out_ids' guard. The statistics are taken from the raw row BEFORE
 // the rule zeroes its image columns, whose raw values the threads that zero them keep; nothing else of the tail changes.
-template <bool SAMPLE, bool LP = false>
+// CTL: per-request logits controls (seedx_amd.sampling.apply_controls states the rule; include/seedx_hip.h sx_logits_ctl_args). A row
+// with on[g] != 0 is NOT edited in place: its edited copy goes to work[g][0..ld), the image rule and the id functions run on that copy, and
+// the logits row stays what lm_head wrote (so the LP record is of the RAW row, no fix-up). A row with on[g] == 0 and every parked slot take
+// the path of the instantiations without CTL, the in-place zeroing included. After the emitted id is known thread 0 of a controlled row
+// counts it.
+struct CtlP {
+  const int* on;
+  int* counts;
+  float* work;
+  const float* rep;
+  const float* rep_inv;
+  const float* presence;
+  const float* frequency;
+  const int* min_new;
+  const int* bias_ids;
+  const float* bias;
+  const int* token_index;
+  int ld_counts, eos_id;
+};
+struct NoCtlP {};
+constexpr int CTL_MAX_BIAS = 16;
+
+// One IEEE fp32 operation each, as written: this file is built with -ffast-math, under which f * n + a contracts to v_fmac_f32 whatever
+// the fp pragmas say; a single-instruction asm statement is opaque to that.
+__device__ __forceinline__ float ctl_mul(float a, float b) {
+  float d = 0.f;
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("v_mul_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+#endif
+  return d;
+}
+__device__ __forceinline__ float ctl_add(float a, float b) {
+  float d = 0.f;
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("v_add_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+#endif
+  return d;
+}
+__device__ __forceinline__ float ctl_sub(float a, float b) {
+  float d = 0.f;
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("v_sub_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+#endif
+  return d;
+}
+
+// Steps 1-4 of the rule for row g: work[0..ld) = the edited row (columns >= vocab are copied). k: the token index. Ends behind a barrier.
+__device__ __forceinline__ void ctl_edit_row(const float* row, float* work, const CtlP& c, int g, int vocab, int ld, int eos, int k) {
+  const int* cnt = c.counts + (size_t)g * c.ld_counts;
+  const float r = c.rep[g], rinv = c.rep_inv[g], a = c.presence[g], f = c.frequency[g];
+  const bool rep_on = r != 1.0f;
+  for (int i = threadIdx.x; i < ld; i += 1024) {
+    float y = row[i];
+    if (i < vocab) {
+      const int w = cnt[i];
+      const int n = w & 0xFFFFFF;
+      if (rep_on && ((w & (1 << 30)) || n > 0)) y = y < 0.f ? ctl_mul(y, r) : ctl_mul(y, rinv);
+      if (n > 0) y = ctl_sub(y, ctl_add(ctl_mul(f, (float)n), a));
+    }
+    work[i] = y;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {                           // entries in list order (an id named twice takes both), then the EOS mask
+    for (int j = 0; j < CTL_MAX_BIAS; ++j) {
+      const int id = c.bias_ids[(size_t)g * CTL_MAX_BIAS + j];
+      if (id >= 0 && id < vocab) work[id] = ctl_add(work[id], c.bias[(size_t)g * CTL_MAX_BIAS + j]);
+    }
+    if (eos >= 0 && eos < vocab && k < c.min_new[g]) work[eos] = -INFINITY;
+  }
+  __syncthreads();
+}
+
+template <bool SAMPLE, bool LP = false, bool CTL = false>
 __global__ __launch_bounds__(1024) void next_token_kernel(const TailP p, const std::conditional_t<SAMPLE, SampleP, NoSampleP> s,
-                                                          const std::conditional_t<LP, LogprobP, NoLogprobP> lp) {
+                                                          const std::conditional_t<LP, LogprobP, NoLogprobP> lp,
+                                                          const std::conditional_t<CTL, CtlP, NoCtlP> c) {
   const int g = blockIdx.x;
   const bool slots = p.live != nullptr;
   if (slots && p.live[g] == 0) return;              // parked (uniform over the workgroup: no barrier is skipped by a part of it)
   float* row = p.logits + (size_t)g * p.ld_logits;
+  [[maybe_unused]] float* raw_row = row;            // CTL: what the LP record reads; `row` becomes the working row of a controlled row
+  [[maybe_unused]] bool ctl_on = false;
+  if constexpr (CTL) {
+    ctl_on = c.on[g] != 0;                          // (uniform over the workgroup)
+    if (ctl_on) {
+      // everything thread 0 rewrites after the id is known is read here, ahead of the barriers
+      const int k = slots ? p.step[g] : c.token_index[g];
+      float* work = c.work + (size_t)g * p.ld_logits;
+      ctl_edit_row(row, work, c, g, p.vocab, p.ld_logits, slots ? p.eos_id : c.eos_id, k);
+      row = work;
+    }
+  }
   [[maybe_unused]] bool rec = false;
   [[maybe_unused]] float raw_img = 0.f;
   [[maybe_unused]] int lp_prev = 0, lp_step = 0, lp_forced = -1;
@@ -1508,8 +1593,8 @@ __global__ __launch_bounds__(1024) void next_token_kernel(const TailP p, const s
       lp_prev = p.prev[g];
       lp_step = p.step[g];
       if (slots && p.force_at[g] >= 0 && p.n_new[g] == p.force_at[g]) lp_forced = p.force_id;
-      row_logprob_stats(row, p.vocab, lp.n_top, scr);
-      if ((int)threadIdx.x < p.n_img - 1) raw_img = row[p.img_ids[1 + threadIdx.x]];
+      row_logprob_stats(raw_row, p.vocab, lp.n_top, scr);
+      if ((int)threadIdx.x < p.n_img - 1) raw_img = raw_row[p.img_ids[1 + threadIdx.x]];
     }
   }
   // every thread reads prev[g] and the token index before the first barrier of the id functions; thread 0 stores to next[g] (which
@@ -1522,7 +1607,7 @@ __global__ __launch_bounds__(1024) void next_token_kernel(const TailP p, const s
   if constexpr (LP) {
     if (rec) {
       const int id = lp_forced >= 0 ? lp_forced : result;        // the id slot_advance emits
-      if (threadIdx.x == 0) scr->raw = id >= 0 && id < p.vocab ? row[id] : NAN;
+      if (threadIdx.x == 0) scr->raw = id >= 0 && id < p.vocab ? raw_row[id] : NAN;
       __syncthreads();
       if ((int)threadIdx.x < p.n_img - 1 && p.img_ids[1 + threadIdx.x] == id) scr->raw = raw_img;   // a zeroed column (ids are unique)
       const bool chain = __syncthreads_or((int)threadIdx.x < p.n_img - 1 && p.img_ids[threadIdx.x] == lp_prev);
@@ -1534,6 +1619,13 @@ __global__ __launch_bounds__(1024) void next_token_kernel(const TailP p, const s
     }
   }
   if (threadIdx.x != 0) return;
+  if constexpr (CTL) {
+    if (ctl_on) {                                   // the id the row EMITS: in the slot form the one behind the force_at replacement
+      int id = result;
+      if (slots && p.force_at[g] >= 0 && p.n_new[g] == p.force_at[g]) id = p.force_id;
+      if (id >= 0 && id < p.vocab) c.counts[(size_t)g * c.ld_counts + id] += 1;
+    }
+  }
   if (slots) slot_advance(p, g, result);
   else lockstep_store(p, g, result);
 }
@@ -1841,11 +1933,12 @@ static TailP slot_tail(const sx_slot_step_args* a) {
                a->live, a->n_new, a->max_new, a->force_at, a->pos, a->ctx, a->status, a->force_id, a->eos_id};
 }
 
-// The one launcher behind the seven entry points. slots: the in-flight form (every pointer but out_ids is required, ld_out is the row
+// The one launcher behind the nine entry points. slots: the in-flight form (every pointer but out_ids is required, ld_out is the row
 // capacity), else the lock-step form. sampled: the entry point takes a sx_sample_args, which must then be there. lp: the LP form
-// (sx_sample_next_b_lp / sx_sample_next_slots_lp); NULL launches exactly what the five older entry points always launched.
+// (sx_sample_next_b_lp / sx_sample_next_slots_lp); NULL launches exactly what the five older entry points always launched. ctl: the
+// controlled forms (sx_next_b_ctl / sx_next_slots_ctl), any of the four combinations of sample and lp.
 static int launch_next_token(const char* who, const TailP& p, bool slots, const sx_sample_args* sample, bool sampled, void* stream,
-                             const sx_logprob_args* lp = nullptr) {
+                             const sx_logprob_args* lp = nullptr, const sx_logits_ctl_args* ctl = nullptr) {
   SX_CHECK(p.logits && p.img_ids && p.prev && p.next, "%s: null pointer", who);
   SX_CHECK(p.n_img >= 2 && p.n_img <= 1024 && p.G >= 1, "%s: n_img=%d G=%d", who, p.n_img, p.G);
   if (slots) {
@@ -1859,20 +1952,38 @@ static int launch_next_token(const char* who, const TailP& p, bool slots, const 
   SampleP s;
   if (sampled) {
     if (int rc = sample_params(sample, p.vocab, who, &s)) return rc;
-    SX_CHECK(slots || s.token_index, "%s: token_index is required", who);
+    SX_CHECK(slots || s.token_index || (ctl && ctl->token_index), "%s: token_index is required", who);
+    if (!slots && !s.token_index) s.token_index = ctl->token_index;
   }
-  if (!lp) {        // (first in the source: the two older instantiations keep their place in the code object)
-    if (sampled) hipLaunchKernelGGL(next_token_kernel<true>, dim3(p.G), dim3(1024), 0, ST, p, s, NoLogprobP{});
-    else hipLaunchKernelGGL(next_token_kernel<false>, dim3(p.G), dim3(1024), 0, ST, p, NoSampleP{}, NoLogprobP{});
-  } else {
+  LogprobP l{};
+  if (lp) {
     SX_CHECK(lp->want && lp->chosen && p.step, "%s: sx_logprob_args needs want, chosen and step", who);
     SX_CHECK(lp->n_top >= 0 && lp->n_top <= LP_MAX_TOP && (lp->n_top == 0 || (lp->top_ids && lp->top)),
              "%s: n_top=%d (0 .. %d, with top_ids and top)", who, lp->n_top, LP_MAX_TOP);
     SX_CHECK(p.vocab >= 1 && p.vocab <= SMP_MAX_VOCAB && p.ld_logits >= p.vocab && p.ld_out >= 1,
              "%s: vocab=%d (1 .. %d) ld_logits=%d ld_out=%d", who, p.vocab, SMP_MAX_VOCAB, p.ld_logits, p.ld_out);
-    const LogprobP l{lp->want, lp->chosen, lp->top_ids, lp->top, lp->n_top};
-    if (sampled) hipLaunchKernelGGL((next_token_kernel<true, true>), dim3(p.G), dim3(1024), 0, ST, p, s, l);
-    else hipLaunchKernelGGL((next_token_kernel<false, true>), dim3(p.G), dim3(1024), 0, ST, p, NoSampleP{}, l);
+    l = LogprobP{lp->want, lp->chosen, lp->top_ids, lp->top, lp->n_top};
+  }
+  if (!ctl && !lp) {        // (first in the source: the two older instantiations keep their place in the code object)
+    if (sampled) hipLaunchKernelGGL(next_token_kernel<true>, dim3(p.G), dim3(1024), 0, ST, p, s, NoLogprobP{}, NoCtlP{});
+    else hipLaunchKernelGGL(next_token_kernel<false>, dim3(p.G), dim3(1024), 0, ST, p, NoSampleP{}, NoLogprobP{}, NoCtlP{});
+  } else if (!ctl) {
+    if (sampled) hipLaunchKernelGGL((next_token_kernel<true, true>), dim3(p.G), dim3(1024), 0, ST, p, s, l, NoCtlP{});
+    else hipLaunchKernelGGL((next_token_kernel<false, true>), dim3(p.G), dim3(1024), 0, ST, p, NoSampleP{}, l, NoCtlP{});
+  } else {
+    // the controlled forms: every row's working copy is ld_logits wide, the count words ld_counts; nothing is read past vocab
+    SX_CHECK(ctl->on && ctl->counts && ctl->work && ctl->rep && ctl->rep_inv && ctl->presence && ctl->frequency && ctl->min_new &&
+                 ctl->bias_ids && ctl->bias, "%s: null pointer in sx_logits_ctl_args", who);
+    SX_CHECK(p.vocab >= 1 && p.ld_logits >= p.vocab && ctl->ld_counts >= p.vocab, "%s: vocab=%d ld_logits=%d ld_counts=%d", who, p.vocab,
+             p.ld_logits, ctl->ld_counts);
+    SX_CHECK(slots || ctl->token_index, "%s: sx_logits_ctl_args.token_index is required in the lock-step form", who);
+    SX_CHECK(ctl->eos_id >= -1 && ctl->eos_id < p.vocab, "%s: sx_logits_ctl_args.eos_id=%d", who, ctl->eos_id);
+    const CtlP c{ctl->on, ctl->counts, ctl->work, ctl->rep, ctl->rep_inv, ctl->presence, ctl->frequency, ctl->min_new, ctl->bias_ids,
+                 ctl->bias, ctl->token_index, ctl->ld_counts, ctl->eos_id};
+    if (sampled && lp) hipLaunchKernelGGL((next_token_kernel<true, true, true>), dim3(p.G), dim3(1024), 0, ST, p, s, l, c);
+    else if (sampled) hipLaunchKernelGGL((next_token_kernel<true, false, true>), dim3(p.G), dim3(1024), 0, ST, p, s, NoLogprobP{}, c);
+    else if (lp) hipLaunchKernelGGL((next_token_kernel<false, true, true>), dim3(p.G), dim3(1024), 0, ST, p, NoSampleP{}, l, c);
+    else hipLaunchKernelGGL((next_token_kernel<false, false, true>), dim3(p.G), dim3(1024), 0, ST, p, NoSampleP{}, NoLogprobP{}, c);
   }
   SX_HIP_LAUNCH_CHECK();
   return SX_OK;
@@ -1912,6 +2023,19 @@ extern "C" int sx_sample_next_b_lp(float* logits, int ld_logits, int vocab, cons
 extern "C" int sx_sample_next_slots_lp(const sx_slot_step_args* a, const sx_sample_args* sample, const sx_logprob_args* lp, void* stream) {
   SX_CHECK(lp, "sx_sample_next_slots_lp: null sx_logprob_args");
   return launch_next_token("sx_sample_next_slots_lp", slot_tail(a), true, sample, sample != nullptr, stream, lp);
+}
+extern "C" int sx_next_b_ctl(float* logits, int ld_logits, int vocab, const int32_t* img_ids_dev, int n_img,
+                             const int32_t* prev_id_dev, int32_t* next_id_dev, int32_t* out_ids, int ld_out,
+                             const int32_t* step_dev, int G, const sx_sample_args* sample, const sx_logprob_args* lp,
+                             const sx_logits_ctl_args* ctl, void* stream) {
+  SX_CHECK(ctl, "sx_next_b_ctl: null sx_logits_ctl_args");
+  return launch_next_token("sx_next_b_ctl", TailP{logits, img_ids_dev, prev_id_dev, next_id_dev, out_ids, const_cast<int32_t*>(step_dev),
+                                                  ld_logits, vocab, n_img, ld_out, G}, false, sample, sample != nullptr, stream, lp, ctl);
+}
+extern "C" int sx_next_slots_ctl(const sx_slot_step_args* a, const sx_sample_args* sample, const sx_logprob_args* lp,
+                                 const sx_logits_ctl_args* ctl, void* stream) {
+  SX_CHECK(ctl, "sx_next_slots_ctl: null sx_logits_ctl_args");
+  return launch_next_token("sx_next_slots_ctl", slot_tail(a), true, sample, sample != nullptr, stream, lp, ctl);
 }
 extern "C" int sx_token_logprobs(const float* logits, int64_t ld, int vocab, const int32_t* targets, float* chosen, int32_t* top_ids,
                                  float* top, int n_top, int rows, void* stream) {

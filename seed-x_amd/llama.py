@@ -162,11 +162,13 @@ class SlotState:
         self.adapter = None
         # a LogprobState (slot_state(logprobs=n_top)): the step ends in the LP tail and has graphs of its own. None: the step as ever
         self.logprobs = None
+        # a ControlState (slot_state(controls=True)): the step ends in the controlled tail (sx_next_slots_ctl) and has graphs of its own
+        self.controls = None
 
     def key(self):
         return tuple(t.data_ptr() for t in (self.live, self.n_new, self.max_new, self.force_at, self.status)) \
             + (self.force_id, self.eos_id) + (self.sampling.key() if self.sampling is not None else ()) \
-            + (self.logprobs.key() if self.logprobs is not None else ())
+            + (self.logprobs.key() if self.logprobs is not None else ()) + (self.controls.key() if self.controls is not None else ())
 
 
 class SampleState:
@@ -250,6 +252,85 @@ class LogprobState:
         self.chosen[g, start:start + n] = float("nan")
         self.top_ids[g, start:start + n] = -1
         self.top[g, start:start + n] = float("nan")
+
+
+class ControlState:
+    """Per-row logits controls of the token step on the device (sx_logits_ctl_args; seedx_amd.sampling.apply_controls states the rule):
+    ``on`` int32 [G] (0: the row runs as without controls), ``counts`` int32 [G, ld] (bit 30: the id occurs in the prompt; low 24 bits:
+    times generated — the tail counts every id a controlled row emits), ``work`` fp32 [G, ld] (the edited rows; the logits rows
+    themselves stay raw), ``rep`` / ``rep_inv`` / ``presence`` / ``frequency`` fp32 [G], ``min_new`` int32 [G], ``bias_ids`` int32 /
+    ``bias`` fp32 [G, 16] (-1: empty). ``ld`` is the logits' row stride. The kernels read everything at launch, so one captured step
+    serves any mix of controlled and uncontrolled rows; the pointers are part of the graph key. A fresh state has every row off."""
+    N_BIAS = 16
+
+    def __init__(self, G, V, ld, device):
+        assert int(ld) >= int(V) >= 1
+        self.G, self.V, self.ld, self.device = int(G), int(V), int(ld), device
+        i32, f32 = torch.int32, torch.float32
+        self.on = torch.zeros(G, dtype=i32, device=device)
+        self.counts = torch.zeros((G, self.ld), dtype=i32, device=device)
+        self.work = torch.zeros((G, self.ld), dtype=f32, device=device)
+        self.rep = torch.ones(G, dtype=f32, device=device)
+        self.rep_inv = torch.ones(G, dtype=f32, device=device)
+        self.presence = torch.zeros(G, dtype=f32, device=device)
+        self.frequency = torch.zeros(G, dtype=f32, device=device)
+        self.min_new = torch.zeros(G, dtype=i32, device=device)
+        self.bias_ids = torch.full((G, self.N_BIAS), -1, dtype=i32, device=device)
+        self.bias = torch.zeros((G, self.N_BIAS), dtype=f32, device=device)
+
+    def key(self):
+        return ("ctl",) + tuple(t.data_ptr() for t in (self.on, self.counts, self.work, self.rep, self.rep_inv, self.presence,
+                                                       self.frequency, self.min_new, self.bias_ids, self.bias))
+
+    def set_rows(self, rows, params, prompt_ids=None):
+        """rows[i] takes params[i] (a sampling.ControlParams, or None: the row runs without controls) and starts a request: its counts
+        are zeroed and the ids of prompt_ids[i] (a sequence of ints; ids outside [0, V) — image placeholders — are skipped) marked."""
+        rows = list(rows)
+        if not rows:
+            return
+        idx = torch.tensor(rows, dtype=torch.int64, device=self.device)
+        i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=self.device)
+        f32 = lambda v: torch.tensor(v, dtype=torch.float32, device=self.device)
+        on = [p is not None for p in params]
+        self.on.index_copy_(0, idx, i32([int(o) for o in on]))
+        self.rep.index_copy_(0, idx, f32([p.repetition_penalty if o else 1.0 for p, o in zip(params, on)]))
+        self.rep_inv.index_copy_(0, idx, f32([p.rep_inv if o else 1.0 for p, o in zip(params, on)]))
+        self.presence.index_copy_(0, idx, f32([p.presence_penalty if o else 0.0 for p, o in zip(params, on)]))
+        self.frequency.index_copy_(0, idx, f32([p.frequency_penalty if o else 0.0 for p, o in zip(params, on)]))
+        self.min_new.index_copy_(0, idx, i32([p.min_new_tokens if o else 0 for p, o in zip(params, on)]))
+        ids, bias = [], []
+        for p, o in zip(params, on):
+            ent = list(p.logit_bias) if o else []
+            assert len(ent) <= self.N_BIAS and all(0 <= i < self.V for i, _ in ent), "logit_bias: at most 16 ids inside the vocabulary"
+            ids.append([i for i, _ in ent] + [-1] * (self.N_BIAS - len(ent)))
+            bias.append([b for _, b in ent] + [0.0] * (self.N_BIAS - len(ent)))
+        self.bias_ids.index_copy_(0, idx, i32(ids))
+        self.bias.index_copy_(0, idx, f32(bias))
+        self.counts.index_fill_(0, idx, 0)
+        for i, g in enumerate(rows):
+            pid = [] if prompt_ids is None or prompt_ids[i] is None else [int(t) for t in prompt_ids[i]]
+            pid = sorted({t for t in pid if 0 <= t < self.V})
+            if on[i] and pid:
+                self.counts[g].index_fill_(0, torch.tensor(pid, dtype=torch.int64, device=self.device), 1 << 30)
+
+    def gather(self, rows):
+        """A state of len(rows) rows holding copies of the given rows (parameters AND counts): what the first token of admitted
+        requests, taken from the prefill logits, is chosen with. The copy's tail counts into the copy; ``count`` puts the id into the
+        real table."""
+        out = ControlState(len(rows), self.V, self.ld, self.device)
+        idx = torch.tensor(list(rows), dtype=torch.int64, device=self.device)
+        for k in ("on", "counts", "rep", "rep_inv", "presence", "frequency", "min_new", "bias_ids", "bias"):
+            getattr(out, k).copy_(getattr(self, k).index_select(0, idx))
+        return out
+
+    def count(self, rows, ids):
+        """counts[rows[i], ids[i]] += 1: ids the HOST emitted for controlled rows (the first token, a forced image block). Ids outside
+        [0, V) leave no trace, as in the tail."""
+        pairs = [(int(g), int(t)) for g, t in zip(rows, ids) if 0 <= int(t) < self.V]
+        if pairs:
+            g = torch.tensor([a for a, _ in pairs], dtype=torch.int64, device=self.device)
+            t = torch.tensor([b for _, b in pairs], dtype=torch.int64, device=self.device)
+            self.counts.index_put_((g, t), torch.ones(len(pairs), dtype=torch.int32, device=self.device), accumulate=True)
 
 
 class LlamaForCausalLM:
@@ -424,6 +505,7 @@ class LlamaForCausalLM:
         self._sd, self._P = None, None
         self._drop_graphs()
         self._sample_state = None
+        self._control_state = None
         self.kv_epoch = 0               # bumped whenever the KV cache is reset or written outside generate_batch
 
     def _kv_name(self):
@@ -493,6 +575,9 @@ class LlamaForCausalLM:
         for attr in ("_graph", "_slot_graph", "_sample_graph", "_slot_sample_graph"):
             setattr(self, attr + "_lp", None)
             setattr(self, attr + "_lp_ad", None)
+            # ... and a step that ends in the controlled tail (a ControlState) has graphs of its own beside each of the sixteen
+            for mid in ("", "_ad", "_lp", "_lp_ad"):
+                setattr(self, attr + mid + "_ctl", None)
 
     def memory_footprint(self):
         """Bytes this module will hold on its GPU once packed (per rank): 16-bit weights, their decode-tile copy (precise mode: always;
@@ -1354,17 +1439,21 @@ class LlamaForCausalLM:
     __call__ = forward
 
     # ---- in-flight batching: slot states ---------------------------------------------------------------------------------
-    def slot_state(self, force_id=-1, eos_id=-1, sampling=False, logprobs=None):
+    def slot_state(self, force_id=-1, eos_id=-1, sampling=False, logprobs=None, controls=False):
         """A fresh SlotState with EVERY slot parked (the module's pos / ctx / step take the idle values; ``reset()`` undoes that).
         ``sampling``: the state carries a SampleState (``.sampling``, all rows greedy until set) and its token step ends in
         sx_sample_next_slots instead of sx_greedy_next_slots. ``logprobs`` = n_top (0 .. 8): the state carries a LogprobState
-        (``.logprobs``, no row recording until ``want`` is set) and its token step ends in sx_sample_next_slots_lp."""
+        (``.logprobs``, no row recording until ``want`` is set) and its token step ends in sx_sample_next_slots_lp. ``controls``: the
+        state carries a ControlState (``.controls``, every row off until set) and its token step ends in sx_next_slots_ctl — greedy,
+        sampled, with or without the record."""
         if self.tp > 1:
             raise NotImplementedError("in-flight batching (slot states) is single-rank: tensor-parallel ranks are not supported")
         self._pack()
         st = SlotState(self.G, self.device, force_id, eos_id, sampling)
         if logprobs is not None:
             st.logprobs = LogprobState(self.G, logprobs, self.device)
+        if controls:
+            st.controls = self.control_state(fresh=True)
         if sampling and self.spec_tokens:
             T = self.spec_tokens + 1
             st.sampling.rows = (SampleState(self.G * T, self.device), T)
@@ -1404,6 +1493,16 @@ class LlamaForCausalLM:
         if self._sample_state is None:
             self._sample_state = SampleState(self.G, self.device)
         return self._sample_state
+
+    def control_state(self, fresh=False):
+        """A ControlState for this model's logits rows ([G, Vpad] fp32). The lock-step step's (``decode_step(..., controls=...)``) is
+        made once — its pointers are part of the captured graph's key; ``fresh``: a new one (a slot state owns its own)."""
+        self._pack()
+        if fresh:
+            return ControlState(self.G, self.V, self.Vpad, self.device)
+        if getattr(self, "_control_state", None) is None:
+            self._control_state = ControlState(self.G, self.V, self.Vpad, self.device)
+        return self._control_state
 
     def _step_tail(self, x, hid_buf, sel=None, tok=None):
         """The end of every token step: final norm → the post-norm fp32 rows into hid_buf (row g at step[g]; verify step: row (g, t) at
@@ -1452,7 +1551,8 @@ class LlamaForCausalLM:
             slots.logits = held[2]
         held[1].replay()
 
-    def _decode_step_body(self, img_ids_dev, out_ids, hid_buf, slots=None, sampling=None, adapters=False, logprobs=None):
+    def _decode_step_body(self, img_ids_dev, out_ids, hid_buf, slots=None, sampling=None, adapters=False, logprobs=None, controls=None,
+                          eos_id=-1):
         """cur[G] → embedding → 40 layers → final norm → lm_head → logits rule + argmax → cur[G]. Records the post-norm
         hidden state of each INPUT token at hid_buf[g, step[g]] (what seed_x.py:196 collects) and the new id at
         out_ids[g, step[g]]; then step += 1. Everything stays on the device. ``slots`` (a SlotState): the tail is ONE
@@ -1472,13 +1572,20 @@ class LlamaForCausalLM:
         lp = logprobs if slots is None else slots.logprobs
         if lp is not None:
             sample["lp"] = lp
+        # controlled step: the same tail again, ids from the edited copy of every controlled row (a ControlState)
+        ctl = controls if slots is None else slots.controls
+        if ctl is not None:
+            sample["ctl"] = ctl
         if slots is not None:
-            tail = ops.next_slots_lp if lp is not None else ops.sample_next_slots if sample else ops.greedy_next_slots
+            tail = ops.next_slots_ctl if ctl is not None else ops.next_slots_lp if lp is not None else ops.sample_next_slots if sample \
+                else ops.greedy_next_slots
             tail(logits, self.V, img_ids_dev, P["cur"], slots.live, slots.n_new, slots.max_new, slots.force_at, P["pos"], P["ctx"],
                  P["step"], out_ids, slots.status, force_id=slots.force_id, eos_id=slots.eos_id, **sample)
             slots.logits = logits
             return
-        tail = ops.next_b_lp if lp is not None else ops.sample_next_b if sample else ops.greedy_next_b
+        if ctl is not None:
+            sample["eos_id"] = eos_id
+        tail = ops.next_b_ctl if ctl is not None else ops.next_b_lp if lp is not None else ops.sample_next_b if sample else ops.greedy_next_b
         tail(logits, self.V, img_ids_dev, P["cur"], out_ids, P["step"], **sample)
         ops.add_i32(P["step"], 1)
 
@@ -1510,7 +1617,7 @@ class LlamaForCausalLM:
             S["hist"][slot, start:start + len(ids)] = torch.tensor(ids, dtype=torch.int32, device=self.device)
 
     def decode_step(self, img_ids_dev, out_ids, hid_buf, use_graph=True, slots=None, sampling=None, adapters=None, spec=False, draft="ngram",
-                    logprobs=None):
+                    logprobs=None, controls=None, eos_id=-1):
         """out_ids: int32 [G, rows]; hid_buf: fp32 [G, rows, H]. ``slots``: a SlotState → the in-flight step (its captured graph is
         kept apart from the lock-step one, so one graph serves an engine's lifetime whatever else runs in between). ``sampling``: a
         SampleState → the lock-step step ends in sx_sample_next_b (token index = step[g]); a slot state brings its own
@@ -1523,8 +1630,23 @@ class LlamaForCausalLM:
         log-probability of their id and the top list at [g, step[g]]); a slot state brings its own (``slots.logprobs``,
         sx_sample_next_slots_lp). Only the tail changes, so it works with every weight_format, weight_residency, kv_format, kv_pages,
         adapters and sampling; the step has captured graphs of its own, and a step without a state runs the calls and graphs it always ran.
-        ValueError with the verify step (``spec=True``) and on tensor-parallel ranks: follow-ups."""
+        ValueError with the verify step (``spec=True``) and on tensor-parallel ranks: follow-ups.
+        ``controls``: a ControlState → the lock-step step ends in the controlled tail (sx_next_b_ctl, token index = step[g], ``eos_id``
+        the column min_new_tokens masks); a slot state brings its own (``slots.controls``, sx_next_slots_ctl). Again only the tail
+        changes, graphs of its own (attribute suffix ``_ctl``), and a step without a state runs the calls and graphs it always ran.
+        ValueError with the verify step and on tensor-parallel ranks: follow-ups."""
         P = self._pack()
+        ctl = controls if slots is None else getattr(slots, "controls", None)
+        if slots is not None and controls is not None:
+            raise ValueError("LlamaForCausalLM.decode_step: a slot state carries its own control state (slot_state(controls=True))")
+        if ctl is not None:
+            if spec:
+                raise ValueError("LlamaForCausalLM.decode_step: logits controls in the verify step of speculative decoding (spec=True with "
+                                 "a control state) are not built (follow-up: counts that advance with the accepted run)")
+            if self.tp > 1:
+                raise ValueError(f"LlamaForCausalLM.decode_step: logits controls on tp={self.tp} tensor-parallel ranks are not built "
+                                 "(follow-up: every rank would edit and count on the gathered logits)")
+            assert ctl.G == self.G and ctl.V == self.V and ctl.ld == self.Vpad
         lp = logprobs if slots is None else getattr(slots, "logprobs", None)
         if lp is not None:
             if slots is not None and logprobs is not None:
@@ -1568,7 +1690,7 @@ class LlamaForCausalLM:
             assert out_ids.is_contiguous() and slots.G == self.G
             assert sampling is None, "a slot state carries its own sampling state (slot_state(sampling=True))"
         assert sampling is None or sampling.G == self.G
-        body = lambda: self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling, adapters, logprobs)
+        body = lambda: self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling, adapters, logprobs, controls, eos_id)
         if not use_graph or not self.comm.graph_safe:
             return body()
         if slots is None:
@@ -1577,6 +1699,8 @@ class LlamaForCausalLM:
             attr = "_slot_graph" if slots.sampling is None else "_slot_sample_graph"
         key = (img_ids_dev.data_ptr(), out_ids.data_ptr(), hid_buf.data_ptr(), tuple(out_ids.shape)) \
             + (slots.key() if slots is not None else ()) + (("sample",) + sampling.key() if sampling is not None else ()) \
-            + (logprobs.key() if logprobs is not None else ())
-        self._replay(attr + ("_lp" if lp is not None else "") + ("_ad" if adapters else ""), key, body,
-                     [slots.live, slots.n_new, slots.status] if slots is not None else [], slots)
+            + (logprobs.key() if logprobs is not None else ()) + (controls.key() + (int(eos_id),) if controls is not None else ())
+        # (the controlled tail counts the id it emits: warm-up and capture run the step, so the counts are put back like the counters)
+        self._replay(attr + ("_lp" if lp is not None else "") + ("_ad" if adapters else "") + ("_ctl" if ctl is not None else ""), key, body,
+                     ([slots.live, slots.n_new, slots.status] if slots is not None else []) + ([ctl.counts] if ctl is not None else []),
+                     slots)

@@ -1281,6 +1281,65 @@ def next_slots_lp(logits, vocab, img_ids_dev, cur, live, n_new, max_new, force_a
           "sx_sample_next_slots_lp")
 
 
+def _ctl_args(ctl, logits, vocab, token_index=None, eos_id=-1):
+    """sx_logits_ctl_args from a control state (llama.ControlState or anything with its tensors): ``on`` / ``min_new`` int32 [G],
+    ``counts`` int32 [G, ld_counts], ``work`` fp32 [G, ld] with the logits' row stride, ``rep`` / ``rep_inv`` / ``presence`` /
+    ``frequency`` fp32 [G], ``bias_ids`` int32 / ``bias`` fp32 [G, 16]."""
+    G, i32, f32 = logits.shape[0], torch.int32, torch.float32
+    for t, dt, shape in ((ctl.on, i32, (G,)), (ctl.min_new, i32, (G,)), (ctl.rep, f32, (G,)), (ctl.rep_inv, f32, (G,)),
+                         (ctl.presence, f32, (G,)), (ctl.frequency, f32, (G,)), (ctl.bias_ids, i32, (G, 16)), (ctl.bias, f32, (G, 16))):
+        assert t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape, "logits controls: contiguous [G] / [G, 16] tensors"
+    assert ctl.counts.dtype == i32 and ctl.counts.is_contiguous() and ctl.counts.shape[0] == G and ctl.counts.shape[1] >= vocab
+    assert ctl.work.dtype == f32 and ctl.work.is_contiguous() and tuple(ctl.work.shape) == (G, logits.stride(0)) and logits.stride(0) >= vocab, \
+        "logits controls: work is fp32 [G, the logits' row stride]"
+    assert token_index is None or (token_index.dtype == i32 and token_index.is_contiguous() and token_index.numel() == G)
+    d = lambda t: None if t is None else _p(t).value      # (GPU tensors only: no CPU fallback)
+    return _lib.LogitsCtlArgs(on=d(ctl.on), counts=d(ctl.counts), work=d(ctl.work), rep=d(ctl.rep), rep_inv=d(ctl.rep_inv),
+                              presence=d(ctl.presence), frequency=d(ctl.frequency), min_new=d(ctl.min_new), bias_ids=d(ctl.bias_ids),
+                              bias=d(ctl.bias), token_index=d(token_index), ld_counts=ctl.counts.shape[1], eos_id=int(eos_id))
+
+
+def next_b_ctl(logits, vocab, img_ids_dev, cur_dev, out_ids, step_dev, ctl, sample=None, lp=None, token_index=None, n_kept=None,
+               p_chosen=None, eos_id=-1):
+    """The lock-step tail with per-request logits controls (sx_next_b_ctl; seedx_amd.sampling.apply_controls states the rule): greedy
+    (``sample`` None) or sampled, with or without the LP record (``lp``). Rows with ``ctl.on`` != 0 take their id from the edited copy
+    of their row in ``ctl.work`` — the logits row itself stays untouched — and count it in ``ctl.counts``; the others run as without
+    ``ctl``. ``token_index`` int32 [G] (default ``step_dev``) is the sampler's and min_new_tokens' index; ``eos_id``: the column that
+    min_new_tokens masks (-1: none)."""
+    lib = _lib.load()
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    G = logits.shape[0]
+    token_index = step_dev if token_index is None else token_index
+    assert token_index is not None, "next_b_ctl: token_index (or step_dev) is required"
+    ld_out = out_ids.stride(0) if out_ids is not None else 0
+    la = None
+    if lp is not None:
+        la, ld_out = _logprob_args(lp, G, out_ids)
+        assert step_dev is not None, "the LP tail needs step_dev"
+    sa = _sample_args(sample, G, token_index, n_kept, p_chosen) if sample is not None else None
+    ca = _ctl_args(ctl, logits, vocab, token_index, eos_id)
+    check(lib.sx_next_b_ctl(_p(logits), logits.stride(0), vocab, _p(img_ids_dev), img_ids_dev.numel(), _p(cur_dev), _p(cur_dev), _p(out_ids),
+                            ld_out, _p(step_dev), G, C.byref(sa) if sa is not None else None, C.byref(la) if la is not None else None,
+                            C.byref(ca), _stream()), "sx_next_b_ctl")
+
+
+def next_slots_ctl(logits, vocab, img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, out_ids, status, ctl, sample=None,
+                   lp=None, force_id=-1, eos_id=-1, n_kept=None, p_chosen=None):
+    """The in-flight tail with per-request logits controls (sx_next_slots_ctl): greedy_next_slots / sample_next_slots / next_slots_lp
+    with next_b_ctl's edit per live slot; the token index is ``step[g]``, the masked column the call's ``eos_id``, and the id counted is
+    the one the slot emits (behind the force_at replacement). Parked slots and slots with ``ctl.on`` = 0 are as without ``ctl``."""
+    a = _slot_step_args("next_slots_ctl", logits, vocab, img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, out_ids,
+                        status, force_id, eos_id)
+    G = logits.shape[0]
+    la = None
+    if lp is not None:
+        la, a.ld_out = _logprob_args(lp, G, out_ids)
+    s = _sample_args(sample, G, None, n_kept, p_chosen) if sample is not None else None
+    ca = _ctl_args(ctl, logits, vocab, None, eos_id)
+    check(_lib.load().sx_next_slots_ctl(C.byref(a), C.byref(s) if s is not None else None, C.byref(la) if la is not None else None,
+                                        C.byref(ca), _stream()), "sx_next_slots_ctl")
+
+
 def _i32s(who, *ts):
     for t in ts:
         assert t.dtype == torch.int32 and t.is_contiguous(), f"{who}: contiguous int32 tensors"

@@ -177,3 +177,135 @@ class SamplingParams:
     def __repr__(self):
         return (f"SamplingParams(do_sample={self.do_sample}, temperature={self.temperature}, top_k={self.top_k}, "
                 f"top_p={self.top_p}, seed={self.seed})")
+
+
+# ---- per-request logits controls: repetition / presence / frequency penalties, logit bias, min_new_tokens ---------------------------
+MAX_LOGIT_BIAS = 16
+COUNT_MARK = 1 << 30          # bit 30 of a count word: the id occurs in the prompt
+COUNT_MASK = 0xFFFFFF         # low 24 bits of a count word: how often the id was generated
+CONTROL_KEYS = ("repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias", "min_new_tokens")
+
+
+class ControlParams:
+    """The logits controls of one request (the rule: ``apply_controls``). ``repetition_penalty`` finite > 0 (1.0: off, transformers'
+    RepetitionPenaltyLogitsProcessor over prompt and generated ids); ``presence_penalty`` / ``frequency_penalty`` finite (0.0: off, the
+    OpenAI definition: generated ids only, the prompt does not count); ``logit_bias`` {id: bias} or None, at most 16 entries, a bias
+    finite or -inf (-inf bans the id; the ids are checked against the vocabulary by ``check_vocab``); ``min_new_tokens`` >= 0 (the EOS
+    column is -inf while fewer tokens were generated; no-op in a call without an EOS id). Malformed values are a ValueError.
+    ``rep_inv`` is float32(1 / repetition_penalty), computed in fp64 and rounded once: what the kernel multiplies by."""
+    __slots__ = ("repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias", "min_new_tokens", "rep_inv")
+
+    def __init__(self, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None, min_new_tokens=0):
+        def num(name, v):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError(f"{name} must be a number, got {v!r}")
+            return float(v)
+        r = num("repetition_penalty", repetition_penalty)
+        def fin32(v):                                   # finite as the float32 the device holds
+            with np.errstate(over="ignore", under="ignore"):
+                return bool(np.isfinite(np.float32(v)))
+        if not (np.isfinite(r) and r > 0 and np.float32(r) > 0 and fin32(r) and fin32(1.0 / r)):
+            raise ValueError(f"repetition_penalty must be a finite number > 0 (1.0 disables it), got {repetition_penalty!r}")
+        a, f = num("presence_penalty", presence_penalty), num("frequency_penalty", frequency_penalty)
+        for name, v in (("presence_penalty", a), ("frequency_penalty", f)):
+            if not fin32(v):
+                raise ValueError(f"{name} must be a finite number, got {v!r}")
+        bias = []
+        if logit_bias is not None:
+            if not isinstance(logit_bias, dict):
+                raise ValueError(f"logit_bias must be a dict {{id: bias}} or None, got {logit_bias!r}")
+            if len(logit_bias) > MAX_LOGIT_BIAS:
+                raise ValueError(f"logit_bias holds {len(logit_bias)} entries, at most {MAX_LOGIT_BIAS} are supported")
+            for i, b in logit_bias.items():
+                if isinstance(i, bool) or not isinstance(i, (int, np.integer)) or int(i) < 0:
+                    raise ValueError(f"logit_bias ids must be ints >= 0, got {i!r}")
+                b = num(f"logit_bias[{i!r}]", b)
+                if not (fin32(b) or b == -np.inf):
+                    raise ValueError(f"logit_bias[{i!r}] must be finite or -inf (-inf bans the id), got {b!r}")
+                bias.append((int(i), b))
+        m = min_new_tokens
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or int(m) < 0:
+            raise ValueError(f"min_new_tokens must be an int >= 0, got {min_new_tokens!r}")
+        self.repetition_penalty, self.presence_penalty, self.frequency_penalty = r, a, f
+        self.logit_bias, self.min_new_tokens = tuple(bias), int(m)
+        self.rep_inv = float(np.float32(1.0 / r))
+
+    def is_default(self):
+        return (np.float32(self.repetition_penalty) == 1 and np.float32(self.presence_penalty) == 0
+                and np.float32(self.frequency_penalty) == 0 and not self.logit_bias and self.min_new_tokens == 0)
+
+    def check_vocab(self, vocab):
+        for i, _ in self.logit_bias:
+            if not i < int(vocab):
+                raise ValueError(f"logit_bias id {i} lies outside the vocabulary [0, {int(vocab)})")
+        return self
+
+    @classmethod
+    def from_request(cls, req, vocab=None):
+        """The control keys of a generate_batch / generate_inflight request dict (``generate`` takes the same names as kwargs); None
+        when every one of them is absent, None or at its default: such a request runs the calls and graphs it always ran."""
+        kw = {k: req[k] for k in CONTROL_KEYS if req.get(k) is not None}
+        if not kw:
+            return None
+        p = cls(**kw)
+        if vocab is not None:
+            p.check_vocab(vocab)
+        return None if p.is_default() else p
+
+    def as_dict(self):
+        """What a result's ``'controls'`` entry holds: the values the device used."""
+        return {"repetition_penalty": self.repetition_penalty, "presence_penalty": self.presence_penalty,
+                "frequency_penalty": self.frequency_penalty, "logit_bias": dict(self.logit_bias), "min_new_tokens": self.min_new_tokens}
+
+    def __repr__(self):
+        return "ControlParams(" + ", ".join(f"{k}={v!r}" for k, v in self.as_dict().items()) + ")"
+
+
+def count_words(vocab, prompt_ids=(), generated_ids=()):
+    """The count words c[0..vocab) of a request: bit 30 set for every id of the prompt, the low 24 bits the number of times the id was
+    generated. Ids outside [0, vocab) (placeholders of image rows) leave no trace."""
+    c = np.zeros(int(vocab), dtype=np.int32)
+    p = np.asarray(list(prompt_ids), dtype=np.int64).reshape(-1)
+    c[p[(p >= 0) & (p < vocab)]] = COUNT_MARK
+    g = np.asarray(list(generated_ids), dtype=np.int64).reshape(-1)
+    g = g[(g >= 0) & (g < vocab)]
+    c += np.bincount(g, minlength=int(vocab)).astype(np.int32)
+    return c
+
+
+def apply_controls(row, counts, params, eos_id=-1, token_index=0):
+    """The rule of the device-side logits controls (next_token_kernel<.., CTL> in csrc/decode.hip, sx_next_b_ctl / sx_next_slots_ctl), in
+    numpy FLOAT32 with one IEEE rounding per written operation: the kernel, the tests and a user are held to these words, bit for bit.
+
+    ``row``: the raw fp32 logits x[0..V). ``counts``: int32 [V], per id the word c with mark = bit 30 (the id occurs in the prompt) and
+    n = c & 0xFFFFFF (times generated so far). ``params``: a ControlParams. ``token_index`` k: the 0-based index of the token being
+    chosen within its request (the sampler's). Returns y, a new fp32 array:
+
+      1. r != 1 and (mark or n > 0):   y = y * r if y < 0 else y * rinv,  rinv = float32(1 / r) rounded once from fp64. A MULTIPLY by
+         the rounded reciprocal, where transformers' RepetitionPenaltyLogitsProcessor divides (x / r): the two may differ by one ulp.
+      2. n > 0:                        t = f * float32(n);  t = t + a;  y = y - t     (a = presence, f = frequency penalty; with
+         a = f = 0 the identity on the bits)
+      3. every logit_bias entry, in the dict's order:  y[id] = y[id] + b             (b = -inf bans the id)
+      4. eos_id >= 0 and k < min_new_tokens:  y[eos_id] = -inf
+
+    The image-token rule then runs on y (a row inside the image chain is forced whatever the controls say; otherwise the image columns
+    img_ids[1:] are zeroed, which overwrites any control on them), and then the arg-max or the seeded draw of the uncontrolled call."""
+    f32 = np.float32
+    y = np.array(row, dtype=f32).reshape(-1).copy()
+    c = np.asarray(counts, dtype=np.int64).reshape(-1)
+    assert c.size == y.size
+    n = c & COUNT_MASK
+    seen = ((c & COUNT_MARK) != 0) | (n > 0)
+    r, rinv = f32(params.repetition_penalty), f32(params.rep_inv)
+    a, f = f32(params.presence_penalty), f32(params.frequency_penalty)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        if r != f32(1):
+            y = np.where(seen, np.where(y < 0, y * r, y * rinv), y).astype(f32)
+        t = (f * n.astype(f32)).astype(f32)
+        t = (t + a).astype(f32)
+        y = np.where(n > 0, (y - t).astype(f32), y).astype(f32)
+        for i, b in params.logit_bias:
+            y[i] = f32(y[i] + f32(b))
+    if int(eos_id) >= 0 and int(token_index) < params.min_new_tokens:
+        y[int(eos_id)] = -np.inf
+    return y

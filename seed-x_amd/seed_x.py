@@ -19,7 +19,7 @@ import torch
 from . import ops
 from .inflight import PrefixIndex, SlotScheduler, plan_admission, tag_signatures
 from .llama import LogprobState
-from .sampling import SamplingParams, logprobs_from_request, logprobs_result
+from .sampling import ControlParams, SamplingParams, logprobs_from_request, logprobs_result
 
 BOI_TOKEN = '<img>'
 EOI_TOKEN = '</img>'
@@ -207,10 +207,29 @@ class ContinuousLVLM:
         rule, temperature, top-k and top-p) and the N most likely ids with theirs. The first record comes from the LP lock-step tail on
         the prefill's logits (sx_sample_next_b_lp), the later ones from the LP token step. Ids the model did not choose — the forced image
         ids and ``</img>``, step-wise or as a host-driven chunk, and a ``force_image_at`` replacement — record NaN and top ids -1.
-        Without such a request the call runs exactly the path it always ran."""
+        Without such a request the call runs exactly the path it always ran.
+        A request may carry logits controls — ``repetition_penalty``, ``presence_penalty``, ``frequency_penalty``, ``logit_bias``
+        ({id: bias}, at most 16, -inf bans the id) and ``min_new_tokens`` (sampling.ControlParams; malformed values are a ValueError
+        before anything is touched): they are applied to its logits row on the device inside the tail of the token step, ahead of the
+        image-token rule and the arg-max or draw (seedx_amd.sampling.apply_controls states the rule; sx_next_b_ctl), for the prefill's
+        first token (index 0) as for every later one, and its result gains ``'controls'``. Log-probabilities stay those of the RAW
+        row. Without such a request the call runs the calls and graphs it always ran. ValueError together with ``force_image_at``
+        (synthetic-weights pinning: a follow-up) and on tensor-parallel ranks (follow-up: edit and count on the gathered logits)."""
         llm = self.llm
         asks = [logprobs_from_request(req) for req in requests]
+        ctls = [ControlParams.from_request(req) for req in requests]
+        controlled = any(c is not None for c in ctls)
+        if controlled and force_image_at is not None:
+            raise ValueError("generate_batch: logits controls together with force_image_at are not built (follow-up: counting the "
+                             "replaced id in the lock-step form); drop one of the two")
         params = [SamplingParams.from_request(req, world=llm.comm.world) for req in requests]     # refuses seed=None on tp > 1 ranks
+        if controlled:
+            if llm.comm.world > 1:
+                raise ValueError(f"generate_batch: logits controls on tp={llm.comm.world} tensor-parallel ranks are not built (follow-up: "
+                                 "every rank would edit and count on the gathered logits)")
+            for c in ctls:
+                if c is not None:
+                    c.check_vocab(llm.V)
         if any(n is not None for n in asks) and llm.comm.world > 1:
             raise ValueError(f"generate_batch: \"logprobs\" on tp={llm.comm.world} tensor-parallel ranks is not built (follow-up)")
         names = [req.get("adapter") for req in requests]
@@ -262,6 +281,12 @@ class ContinuousLVLM:
         if any(n is not None for n in asks):            # the LP tail, here and in every token step; rows that did not ask record nothing
             lps = LogprobState(G, max(n for n in asks if n is not None), dev, rows)
             lps.want.copy_(torch.tensor([int(n is not None) for n in asks], dtype=torch.int32))
+        cs, eos_dev = None, -1 if eos_token_id is None else int(eos_token_id)
+        if controlled:                                   # the controlled tail, here and in every token step; rows without controls run as ever
+            cs = llm.control_state()
+            cs.set_rows(range(G), ctls, [ids for ids, _ in prompts])
+            ops.next_b_ctl(logits, llm.V, img_ids_dev, P["cur"], out_ids, P["step"], cs, sample=ss, lp=lps, eos_id=eos_dev)   # token index 0
+        elif lps is not None:
             ops.next_b_lp(logits, llm.V, img_ids_dev, P["cur"], out_ids, P["step"], lps, ss)     # token index 0
         elif ss is not None:
             ops.sample_next_b(logits, llm.V, img_ids_dev, P["cur"], out_ids, P["step"], ss)      # token index 0
@@ -298,6 +323,8 @@ class ContinuousLVLM:
                 for g in hit:
                     if asks[g] is not None:
                         lps.forced(g, n_new[g], nchunk)
+                    if ctls[g] is not None:              # the host emitted these ids: counted like the tail's
+                        cs.count([g] * nchunk, img_ids[1:])
                     n_new[g] += nchunk
                     P["step"][g] = n_new[g]
                     P["cur"][g] = eoi_id
@@ -307,7 +334,8 @@ class ContinuousLVLM:
             if all(done):
                 break
             llm.decode_step(img_ids_dev, out_ids, hid, use_graph=self.use_graph, sampling=ss,   # one token for every sequence
-                            **(dict(logprobs=lps) if lps is not None else {}))
+                            **(dict(logprobs=lps) if lps is not None else {}),
+                            **(dict(controls=cs, eos_id=eos_dev) if cs is not None else {}))
             cur = P["cur"].tolist()                                                          # the only read-back per step
             llm.comm.check()                              # (tensor-parallel only: + 4 bytes) a timed-out collective must not pass
             for g in range(G):
@@ -331,6 +359,8 @@ class ContinuousLVLM:
             if asks[g] is not None:
                 results[-1]['logprobs'] = logprobs_result(generate_ids, lps.chosen[g, :n].cpu(), lps.top_ids[g, :n].cpu().long(),
                                                           lps.top[g, :n].cpu(), asks[g])
+            if ctls[g] is not None:
+                results[-1]['controls'] = ctls[g].as_dict()
         return results
 
     @staticmethod
@@ -426,10 +456,30 @@ class ContinuousLVLM:
         with at least one such request runs the LP token step on a slot state of its own (``want`` is written per slot at admission;
         slots whose request did not ask record nothing), a queue without one takes the states and graphs it always took. A request's
         records depend on its own logits only — never on its slot, its neighbours or the largest N in the queue. With
-        ``agent.speculative`` a logprob request raises ValueError (follow-up)."""
+        ``agent.speculative`` a logprob request raises ValueError (follow-up).
+        A request may carry logits controls as in generate_batch (``repetition_penalty``, ``presence_penalty``, ``frequency_penalty``,
+        ``logit_bias``, ``min_new_tokens``; its result gains ``'controls'``): a queue with at least one such request runs the
+        controlled token step (sx_next_slots_ctl) on a slot state of its own — parameters, prompt marks and zeroed counts are written
+        per slot at admission, slots whose request carries none run as ever — and a queue without one takes the states and graphs it
+        always took. The ids depend on the request alone, never on its slot or its neighbours. ValueError with ``agent.speculative``
+        (follow-up: counts that advance with the accepted run) and with ``force_image_at`` on the same request (follow-up)."""
         llm = self.llm
         requests = list(requests)
         asks = [logprobs_from_request(req) for req in requests]
+        ctls = [ControlParams.from_request(req) for req in requests]
+        controlled = any(c is not None for c in ctls)
+        if controlled and self.speculative:
+            raise ValueError("generate_inflight: logits controls with agent.speculative are not built (follow-up: counts that advance with "
+                             "the verify step's accepted run); switch agent.speculative off for calls that carry controls")
+        for r, (c, req) in enumerate(zip(ctls, requests)):
+            if c is not None and req.get("force_image_at") is not None:
+                raise ValueError(f"generate_inflight: request {r} carries logits controls and force_image_at: not built (follow-up); drop "
+                                 "one of the two")
+        if controlled and llm.comm.world > 1:
+            raise ValueError(f"generate_inflight: logits controls on tp={llm.comm.world} tensor-parallel ranks are not built (follow-up)")
+        for c in ctls:
+            if c is not None:
+                c.check_vocab(llm.V)
         if llm.comm.world > 1:
             raise NotImplementedError("generate_inflight is single-rank: tensor-parallel ranks are not supported")
         n_top = max([n for n in asks if n is not None], default=None)
@@ -498,10 +548,16 @@ class ContinuousLVLM:
         which = "state_sampled" if sampled else "state"        # two slot states, two captured steps: neither disturbs the other
         if n_top is not None:                                  # ... and one more pair per n_top for the LP step
             which += f"_lp{n_top}"
+        if controlled:                                         # ... and one more of each for the controlled step
+            which += "_ctl"
         if keep.get(which) is None:
-            keep[which] = owned(lambda: llm.slot_state(force_id=boi_id, eos_id=eos, sampling=sampled, logprobs=n_top))
+            keep[which] = owned(lambda: llm.slot_state(force_id=boi_id, eos_id=eos, sampling=sampled, logprobs=n_top,
+                                                       **(dict(controls=True) if controlled else {})))
         st, img_ids_dev, out_ids, hid = keep[which], keep["img_ids_dev"], keep["out_ids"], keep["hid"]
         lps = st.logprobs
+        cs = st.controls
+        if cs is not None:
+            cs.on.zero_()
         if lps is not None:
             lps.bind(out_ids.shape[1]).want.zero_()
         owned(llm.park_slots, range(G), st)
@@ -546,6 +602,8 @@ class ContinuousLVLM:
             if asks[r] is not None:
                 results[r]['logprobs'] = logprobs_result(generate_ids, lps.chosen[g, :n].cpu(), lps.top_ids[g, :n].cpu().long(),
                                                          lps.top[g, :n].cpu(), asks[r])
+            if ctls[r] is not None:
+                results[r]['controls'] = ctls[r].as_dict()
             if on_result is not None:
                 on_result(r, results[r])
 
@@ -556,12 +614,13 @@ class ContinuousLVLM:
             # ONE batched prefill over the admitted slots; token 1 of each comes from it (host-side stop test: not in the graph).
             # ``starts`` (prefix_cache): rows [0, starts[i]) of slot i's prompt are in its cache already, the rest is forwarded
             slots = [g for g, _ in adm]
-            xs, last_ids = [], []
+            xs, last_ids, pids = [], [], []
             for i, (g, r) in enumerate(adm):
                 ids, x = prompts.pop(r)[:2] if starts is not None else self._prompt_embeds(tokenizer, requests[r])
                 assert len(ids) + budget[r] + K <= llm.Tmax, "KV cache too small for prompt + max_new_tokens (+ spec_tokens draft rows)"
                 xs.append(x if starts is None else x[starts[i]:])
                 last_ids.append(ids[-1])
+                pids.append(ids)
                 if spec:                                 # the drafter's history: the prompt's ids by cache position (image rows: placeholders)
                     plen[g] = len(ids)
                     llm.spec_write_history(g, 0, ids)
@@ -577,19 +636,29 @@ class ContinuousLVLM:
             first = torch.tensor(last_ids, dtype=torch.int32, device=dev)
             if sampled:                                  # the slots take their requests' parameters; token index 0 is drawn here
                 st.sampling.set_rows(slots, [params[r] for _, r in adm])
+            if cs is not None:                           # the slots take their requests' controls: parameters, prompt marks, zero counts
+                cs.set_rows(slots, [ctls[r] for _, r in adm], pids)
             if lps is not None:                          # the first record: the LP lock-step tail on the prefill's logits, one row per slot
                 wants = [int(asks[r] is not None) for _, r in adm]
                 llm._slot_write(lps.want, slots, wants)
                 rec = LogprobState(len(slots), n_top, dev, rows=1)
                 rec.want.copy_(torch.tensor(wants, dtype=torch.int32))
                 zero = torch.zeros(len(slots), dtype=torch.int32, device=dev)
-                ops.next_b_lp(logits.contiguous(), llm.V, img_ids_dev, first, None, zero, rec,
-                              st.sampling.gather(slots) if sampled else None, token_index=zero)
+                if cs is not None:                       # ... of the raw row, the id from the controlled one
+                    ops.next_b_ctl(logits.contiguous(), llm.V, img_ids_dev, first, None, zero, cs.gather(slots),
+                                   sample=st.sampling.gather(slots) if sampled else None, lp=rec, token_index=zero, eos_id=eos)
+                else:
+                    ops.next_b_lp(logits.contiguous(), llm.V, img_ids_dev, first, None, zero, rec,
+                                  st.sampling.gather(slots) if sampled else None, token_index=zero)
                 at = torch.tensor(slots, device=dev)
                 lps.chosen[at, 0], lps.top_ids[at, 0], lps.top[at, 0] = rec.chosen[:, 0], rec.top_ids[:, 0], rec.top[:, 0]
                 for i, (g, r) in enumerate(adm):
                     if force_at[r] == 0 and wants[i]:
                         lps.forced(g, 0, 1)              # (synthetic weights) the id is replaced below: the model did not choose it
+            elif cs is not None:                         # token index 0 by the same rule, on a copy of the slots' rows of the state
+                zero = torch.zeros(len(slots), dtype=torch.int32, device=dev)
+                ops.next_b_ctl(logits.contiguous(), llm.V, img_ids_dev, first, None, zero, cs.gather(slots),
+                               sample=st.sampling.gather(slots) if sampled else None, token_index=zero, eos_id=eos)
             elif sampled:
                 ops.sample_next_b(logits.contiguous(), llm.V, img_ids_dev, first, None, None, st.sampling.gather(slots),
                                   token_index=torch.zeros(len(slots), dtype=torch.int32, device=dev))
@@ -606,6 +675,9 @@ class ContinuousLVLM:
                 n_new[g] = 1
             out_ids[torch.tensor(slots, device=dev), 0] = torch.tensor([cur[g] for g in slots], dtype=torch.int32, device=dev)
             llm._slot_write(P["cur"], slots, [cur[g] for g in slots])
+            if cs is not None:                           # the first id in the real table (the tail above counted into the copy)
+                own = [g for g, r in adm if ctls[r] is not None]
+                cs.count(own, [cur[g] for g in own])
             if spec:
                 for g in slots:
                     llm.spec_write_history(g, plen[g], [cur[g]])
@@ -663,6 +735,8 @@ class ContinuousLVLM:
                 for g in hit:
                     if asks[sched.slot_req[g]] is not None:
                         lps.forced(g, n_new[g], nchunk)
+                    if ctls[sched.slot_req[g]] is not None:      # the host emitted these ids: counted like the tail's
+                        cs.count([g] * nchunk, img_ids[1:])
                     if spec:                             # the block's ids at the positions they were fed (</img> is the new current token)
                         llm.spec_write_history(g, plen[g] + n_new[g] - 1, img_ids)
                     n_new[g] += nchunk
@@ -773,7 +847,8 @@ class ContinuousLVLM:
                  ids_cmp_mask=None, logits_processor=None, num_img_gen_tokens=64, temperature=0.7, num_beams=1,
                  max_new_tokens=120, top_p=0.5, dtype=torch.float16, device='cuda', patch_positions=None,
                  eos_token_id="auto", force_image_at=None, reuse_cache=False, do_sample=False, top_k=50, seed=None, adapter=None,
-                 logprobs=None):
+                 logprobs=None, repetition_penalty=None, presence_penalty=None, frequency_penalty=None, logit_bias=None,
+                 min_new_tokens=None):
         """Reference signature (seed_x.py:130-145). Greedy by default (do_sample=False, num_beams=1 — temperature/top_p are inert
         in the reference too, :175-189). ``do_sample=True`` makes ``temperature`` / ``top_p`` live (defaults: the reference's 0.7 /
         0.5) together with ``top_k`` (50, transformers' generation default) and ``seed`` (None: 64 bits from os.urandom): the seeded
@@ -781,7 +856,10 @@ class ContinuousLVLM:
         tokenizer.eos_token_id; None disables the EOS stop. On tensor-parallel ranks ``do_sample=True`` needs an explicit ``seed``, the
         same on every rank (ValueError otherwise). ``adapter``: name of a LoRA adapter resident on the LLM (``llm.load_adapter``) the
         request runs under, unmerged; the result carries ``'adapter'``. ``logprobs``: N in 0 .. 8 → the result carries ``'logprobs'``
-        (generate_batch: per generated id its log-probability under the raw distribution and the N most likely ids)."""
+        (generate_batch: per generated id its log-probability under the raw distribution and the N most likely ids).
+        ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` / ``logit_bias`` / ``min_new_tokens``: the device-side
+        logits controls of generate_batch (what a reference user passes through ``logits_processor`` / ``generation_config``; a
+        host-supplied processor list itself stays refused); the result then carries ``'controls'``."""
         assert logits_processor is None, "the AutoImageTokenGenerationProcessor rule is fused on the device"
         assert num_beams == 1
         assert self.llm.G == 1, "this LLM was built for lock-step batches: use generate_batch()"
@@ -793,5 +871,7 @@ class ContinuousLVLM:
             req.update(do_sample=True, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
         if adapter is not None:
             req["adapter"] = adapter
+        req.update(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
+                   logit_bias=logit_bias, min_new_tokens=min_new_tokens)
         return self.generate_batch(tokenizer, [req], num_img_gen_tokens, max_new_tokens, eos_token_id, force_image_at,
                                    reuse_cache)[0]
