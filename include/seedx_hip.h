@@ -398,7 +398,7 @@ int sx_add_i32_n(int32_t* p, int delta, int n, void* stream);
  *     AFTER the arg-max (synthetic weights only; force_at -1 = never). id goes to out_ids[g][step[g]] (if 0 <= step[g] < ld_out)
  *     and to cur[g]; n_new, step, pos and ctx advance by one. Stop rule: id == eos_id (eos_id -1 = none) or n_new >= max_new[g]
  *     → live = 0 and the slot is parked: step = -1, pos = -1, ctx = 0. Those are the idle values every kernel of the token step
- *     honours (no cache, log or id store; the attention kernels read at most key row 0 of the slot's own cache and stay finite).
+ *     honours (no cache, log or id store; the attention kernels read no key row for the slot and return 0 for it).
  *   status[g] = { id, live, n_new, n_new at the finish or -1 }: what the host reads once per token step. */
 typedef struct sx_slot_step_args {
   float* logits;                /* [G][ld_logits] fp32; the rule zeroes the image-token columns of LIVE rows in place              */
@@ -712,8 +712,9 @@ typedef struct sx_attn_f32_args {
    * [G*T][H][nsplit][D + 2] always): q / k_new / v_new are rows g*T + t, row t sits at position pos0[g] + t. The launch equals, bit
    * for bit, T successive T = 1 calls of this form with the same nsplit, v16 and dtype (call t on row t at position pos0[g] + t) in
    * the context planes, the k rows and the v rows of every row whose position lies in [0, Tmax); every K / V row of a (head,
-   * sequence, split) is loaded once for the T query rows. pos0[g] < 0 idles all T rows of the slot; a row at or past Tmax writes no
-   * cache row; both stay finite. */
+   * sequence, split) is loaded once for the T query rows. pos0[g] < 0 (a parked slot, here and in every causal form) idles all T rows
+   * of the slot: they read no key row, write no cache row and come out as 0, whatever a reused cache still holds; a row at or past
+   * Tmax writes no cache row and stays finite. */
   const float* rope_cos;    /* [Tmax][D/2] fp32 (rounded to the planes' dtype inside, like sx_rope_kv_append_f32)                    */
   const float* rope_sin;
   const float* k_new;
@@ -734,7 +735,7 @@ typedef struct sx_attn_f32_args {
    * page_stride elements apart; v16 as above) and page_table is device int32 [G][ceil(Tmax / page size)]: key row t of sequence g lives
    * in page page_table[g][t >> page_shift] at row t & (page size - 1). cache_seq_stride and the K / V strides are unused. Page 0 is the
    * NULL page — all zeros, never handed out, never written: an entry without a reservation names it, so whatever the contiguous kernels
-   * read from rows nobody owns (a parked slot's key row 0, the MFMA tile's rows past the last visible key) reads finite zeros, and the
+   * read from rows nobody owns (the MFMA tile's rows past the last visible key) reads finite zeros, and the
    * fused append of a row whose entry is 0 writes nothing. Entries are clamped to [0, n_pages]: a wrong table gives wrong numbers, never
    * a wild address. The table is read at launch (at replay under a captured graph); one lookup per page (VALU kernels) or per 32-key
    * tile (MFMA kernel). Every launch has the bits of the contiguous call on a cache holding the same rows. */

@@ -1058,7 +1058,7 @@ __device__ __forceinline__ int greedy_next_id(float* logits, int vocab, const in
 //     step = -1  → scatter_rows_step_kernel and the out_ids guard drop the row,
 //     pos  = -1  → the RoPE / append kernels and both fused attention kernels write nothing (pos_ok is false),
 //     ctx  =  0  → ctx == pos + 1 as always: the plain attention sees no key (its combine yields 0, not 0 / 0); the fp32 attention
-//                  clamps pos to 0 and reads key row 0 of the slot's own cache, which a request wrote or the allocation zeroed,
+//                  sees no key either (kend = 0: a reused slot's stale rows are never read) and yields 0 as well,
 // and this kernel returns for it before it touches anything, the in-place zeroing of its logits row included.
 // A live slot takes the next id by the shared rule, stores it, advances its four counters and tests the stop rule (EOS or budget) on
 // the device; a slot that stops parks itself here, so the very next replay of the captured step already treats it as idle.

@@ -471,6 +471,7 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnF32P p) {
 #pragma unroll
   for (int c = 0; c < DC; ++c) dvalid[c] = c * 128 + dl * 8 < D;
   int pos0 = p.causal ? p.pos0_dev[g] : p.Tmax;   // not causal: every row sees all Tmax keys
+  const bool parked = pos0 < 0;                   // a parked slot sees no key: its rows are 0, whatever a reused cache still holds
   if (pos0 < 0) pos0 = 0;
   const int nq = min(QB, p.T - q0);
   float qv[QB][DW], o[QB][DW], m_run[QB], l_run[QB];
@@ -573,6 +574,7 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnF32P p) {
       if (pos_ok) kend = min(kend, praw);             // the cache rows below pos; the new key comes from registers
     }
   }
+  if (parked) kend = 0;                               // (stale rows of a reused slot are finite but arbitrary: v = +-max would not stay finite)
   if constexpr (PAGED) {                              // one trip, and ONE table lookup, per page the key range touches
     for (int pi = kbeg >> p.pshift; pi < ((kend + (1 << p.pshift) - 1) >> p.pshift); ++pi) {
       const int pb = pi << p.pshift;                  // the page's first key row; t counts from it
@@ -670,8 +672,8 @@ __global__ __launch_bounds__(128) void attn_f32_combine_kernel(const AttnF32P p)
 //     found in the cache — here they come from LDS, where group t parked row t's rotated q, k and (rounded under V16) v — and last the
 //     row's own key by group 0;
 //   * the arithmetic: rope_rot (its two T = 1 contractions), attn_score, attn_key_update, attn_merge_groups, attn_merge_waves above, shared with attn_f32_kernel.
-// A parked slot (pos0 < 0) idles ALL its rows like the T = 1 launch idles its one (they read key row 0 of the slot's own cache, write
-// no cache row, stay finite); a row at or past Tmax writes no cache row. The partials go to part[G*T][H][nsplit][D + 2]; the combine is
+// A parked slot (pos0 < 0) idles ALL its rows like the T = 1 launch idles its one (they read no key row, write no cache row and
+// come out as 0); a row at or past Tmax writes no cache row. The partials go to part[G*T][H][nsplit][D + 2]; the combine is
 // attn_f32_combine_kernel over G*T rows.
 template <typename TT, int TQ, bool V16>
 __global__ __launch_bounds__(256) void attn_f32_verify_kernel(const AttnF32P p) {
@@ -685,7 +687,7 @@ __global__ __launch_bounds__(256) void attn_f32_verify_kernel(const AttnF32P p) 
   const int praw0 = p.pos0_dev[g];
   const bool parked = praw0 < 0;
   const int pos0 = parked ? 0 : praw0;
-  const int climit = parked ? 1 : min(pos0, p.Tmax);    // cache rows this launch may read: those below pos0 (parked: key row 0)
+  const int climit = parked ? 0 : min(pos0, p.Tmax);    // cache rows this launch may read: those below pos0 (parked: none)
   const float* kh = p.kc + (size_t)g * p.seq_stride + (size_t)h * p.head_stride;
   const size_t vbase = (size_t)g * p.seq_stride + (size_t)h * p.head_stride;
   float qv[TQ][8], o[TQ][8], m_run[TQ], l_run[TQ];
@@ -706,7 +708,7 @@ __global__ __launch_bounds__(256) void attn_f32_verify_kernel(const AttnF32P p) 
     if (i < T) {                                        // uniform over the workgroup
       const int pr = pos0 + i;
       const bool pos_ok = !parked && pr < p.Tmax;
-      const int kend = parked ? 1 : min(p.Tmax, pr + 1);
+      const int kend = parked ? 1 : min(p.Tmax, pr + 1);   // (parked: only keeps chunk > 0; climit = 0 and own = false, no key is walked)
       const int chunk = ((kend + p.nsplit - 1) / p.nsplit + 15) & ~15;
       kb[i] = sp * chunk;
       ke[i] = min(kend, kb[i] + chunk);
@@ -866,6 +868,7 @@ __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const AttnF32P p) {
   const int q0 = blockIdx.x * 128 + wave * 32;
   if (q0 >= p.T) return;                                       // (no barriers in this kernel)
   int pos0 = p.pos0_dev[g];
+  const bool parked = pos0 < 0;                                 // a parked slot sees no key: its rows are 0
   if (pos0 < 0) pos0 = 0;
   const int qi = q0 + l32;                                      // this lane's query row (column of S^T / O^T)
   const bool qok = qi < p.T;
@@ -892,7 +895,7 @@ __global__ __launch_bounds__(256) void attn_f32_mfma_kernel(const AttnF32P p) {
     for (int j = 0; j < 16; ++j) o[b][j] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;
   const int q_last = min(p.T, q0 + 32) - 1;
-  const int kend = min(p.Tmax, pos0 + q_last + 1);              // keys 0 .. kend - 1 are visible to the wave's last row
+  const int kend = parked ? 0 : min(p.Tmax, pos0 + q_last + 1); // keys 0 .. kend - 1 are visible to the wave's last row
   const int vis = pos0 + qi;                                    // last key this lane's row may see
   for (int k0 = 0; k0 < kend; k0 += 32) {
     // ---- S^T tile = K[k0 .. k0+31] · Q^T ----

@@ -1080,6 +1080,92 @@ def test_attn_norm_matrix_covers_every_launched_kernel():
     assert am.plant_positions(130, 200, False)[:8] == [0, 63, 64, 127, 128, 191, 198, 199] and am.plant_positions(3, 10, True) == [7, 8, 9]
 
 
+def test_precise_matrix_covers_every_launched_kernel():
+    """tests/test_precise_matrix_gpu.py's case tables reach every instantiation that the host code of precise.hip launches (parsed from the
+    source; every hipLaunchKernelGGL statement of the file is accounted for): the 46 attn_f32_kernel, 8 attn_f32_verify_kernel, 10
+    attn_f32_mfma_kernel and 2 attn_f32_combine_kernel of sx_attention_f32, the 4 + 4 rope_kv_f32(_paged)_kernel, both
+    rmsnorm_planes_kernel and split16_kernel; rope_kv_q8_kernel is covered by tests/test_fp8_kv_gpu.py. Every case family has its cases
+    at both dtypes, with the sizes on both sides of every dispatch and walk boundary."""
+    from tests import test_precise_matrix_gpu as pm
+    src = pm.source_kernels()
+    assert [len(src[k]) for k in ("attn", "verify", "mfma", "combine", "rope", "rope_paged", "rms", "split16")] == [46, 8, 10, 2, 4, 4, 2, 2]
+    assert pm.COVERED_ELSEWHERE == {"rope_kv_q8_kernel": "tests/test_fp8_kv_gpu.py"}
+    fp8 = open(os.path.join(ROOT, "tests", "test_fp8_kv_gpu.py")).read()
+    assert "kv_scales=" in fp8 and "kv_emulate=True" in fp8, "test_fp8_kv_gpu.py no longer appends through rope_kv_q8_kernel<TT, EMUL> (codes and the twin)"
+    ids = [c["id"] for c in pm.ATTN + pm.ROPE + pm.RMS + pm.SPLIT16]
+    assert len(ids) == len(set(ids))
+    reached = {k for c in pm.ATTN for k in pm.kernel_of_attn(c)}
+    assert reached == src["attn"] | src["verify"] | src["mfma"] | src["combine"], (sorted(map(str, (src["attn"] | src["verify"] | src["mfma"] | src["combine"]) ^ reached)))
+    assert {pm.kernel_of_rope(c) for c in pm.ROPE} == src["rope"] | src["rope_paged"]
+    assert {pm.kernel_of_rms(c) for c in pm.RMS} == src["rms"] and {pm.kernel_of_split16(c) for c in pm.SPLIT16} == src["split16"]
+    for dt in pm.DTYPES:
+        A = [c for c in pm.ATTN if c["dt"] == dt]
+        F = lambda *fams: [c for c in A if c["fam"] in fams]
+        assert {c["fam"] for c in A} == set(pm.FAMILIES), set(pm.FAMILIES) ^ {c["fam"] for c in A}
+        assert all(1 <= c["H"] <= 3 and 1 <= c["G"] <= 4 and c["Tmax"] <= 1536 for c in A)
+        assert all(p <= c["Tmax"] + pm.PADROWS - c["T"] for c in A for p in c["pos0"]), "a position runs past the NaN rows behind the caches"
+        # VALU: head dims of both DC, every QB with a partial last block, the positions, the key counts of the non-causal form
+        assert {c["D"] for c in F("valu-d")} == {8, 64, 104, 120, 128} and {c["D"] for c in F("valu-dc2")} == {136, 160, 256}
+        assert {c["causal"] for c in F("valu-dc2")} == {True, False} and not any(c["v16"] or c["kv8"] or c["pshift"] for c in F("valu-dc2"))
+        assert {c["T"] for c in F("valu-t")} == {1, 2, 3, 4, 5, 8, 9, 15, 16, 17}
+        assert {pm.kernel_of_attn(c)[0][2] for c in F("valu-t") if c["T"] > 8} == {8} and {pm.kernel_of_attn(c)[0][2] for c in F("valu-t") if 1 < c["T"] <= 8} == {4}
+        pos = {p for c in F("valu-pos") for p in c["pos0"]}
+        assert {0, 15, 16, 17, -1} <= pos and {pm.kernel_of_attn(c)[0][:1] + pm.kernel_of_attn(c)[0][2:3] for c in A if min(c["pos0"]) < 0} >= \
+            {("attn_f32_kernel", 1), ("attn_f32_kernel", 4), ("attn_f32_kernel", 8), ("attn_f32_verify_kernel", 4), ("attn_f32_verify_kernel", 8)}
+        assert any(pm.is_mfma(c) and min(c["pos0"]) < 0 for c in A), "a parked slot beside live ones in every kernel"
+        assert any(c["pos0"][0] == c["Tmax"] - c["T"] for c in F("valu-pos")) and any(max(c["pos0"]) + c["T"] > c["Tmax"] for c in F("valu-pos"))
+        assert {c["Tmax"] for c in F("valu-nc")} == {1, 15, 16, 17, 129} and not any(c["causal"] for c in F("valu-nc"))
+        for T in (1, 3, 12):
+            st = {(c["v16"], c["kv8"], c["pshift"]) for c in F("valu-store") if c["T"] == T and c["D"] == 128}
+            assert st >= {(False, 0, 0), (True, 0, 0), (False, 1, 0), (False, 0, 5), (False, 0, 6), (False, 0, 7)}, (T, st)
+        tiled = [c for c in A if c["tiled"]]
+        assert {c["G"] * c["T"] for c in tiled} >= {1, 16, 17, 32} and all(c["H"] * c["D"] % 32 == 0 and c["G"] * c["T"] <= 32 for c in tiled)
+        assert any(c["strided"] for c in A if not c["causal"]) and {c["T"] for c in F("strided")} >= {1, 3, 12, 40}
+        # key splits: nsplit x kend around 16 nsplit, with every storage form
+        sp = F("split")
+        assert {c["nsplit"] for c in sp} >= set(pm.SPLIT_NS) == {2, 3, 6, 16, 64}
+        for ns in pm.SPLIT_NS:
+            assert {c["pos0"][0] + 1 for c in sp if c["nsplit"] == ns} >= {16 * ns - 1, 16 * ns, 16 * ns + 1, 1, 1499}, ns
+        assert {(c["v16"], c["kv8"], bool(c["pshift"])) for c in sp} >= {(False, 0, False), (True, 0, False), (False, 1, False), (False, 0, True)}
+        assert {c["pshift"] for c in sp} >= {5, 6, 7}
+        sr = F("split-rope")
+        assert all(c["rope"] and c["T"] == 1 and c["nsplit"] > 1 for c in sr) and {c["kv8"] for c in sr} == {0, 1, 2} and {c["pshift"] for c in sr} == {0, 5, 6, 7}
+        assert any(p % pm.split_chunk(p + 1, c["nsplit"]) == 0 and p > 0 for c in sr for p in c["pos0"][:1])
+        assert any(c["pshift"] and c["pos0"][1] % (1 << c["pshift"]) == 0 and c["pos0"][1] > 0 for c in sr)
+        assert any(c["Tmax"] - 1 in c["pos0"] and c["Tmax"] in c["pos0"] for c in sr)
+        f1 = F("fused1")
+        assert all(c["rope"] and c["T"] == 1 and c["nsplit"] == 1 for c in f1) and {c["kv8"] for c in f1} == {0, 1, 2} and {c["pshift"] for c in f1} == {0, 5, 6, 7}
+        # the verify form
+        ve = F("verify")
+        assert {c["T"] for c in ve} == {2, 4, 5, 8} and {c["nsplit"] for c in ve} == {1, 2, 6} and {c["v16"] for c in ve} == {False, True}
+        assert max(c["G"] * c["T"] for c in ve) == 32 and any(min(c["pos0"]) < 0 for c in ve) and any(max(c["pos0"]) + c["T"] - 1 == c["Tmax"] for c in ve)
+        assert any((c["pos0"][0] + 1) // (16 * c["nsplit"]) != (c["pos0"][0] + c["T"]) // (16 * c["nsplit"]) for c in ve if c["nsplit"] > 1)
+        assert any(p // 16 != (p + c["T"] - 1) // 16 for c in ve for p in c["pos0"] if p >= 0)
+        # the MFMA kernel and its twins
+        mf, tw = F("mfma"), F("mfma-twin")
+        assert {c["T"] for c in mf} == set(pm.MFMA_T) == {9, 31, 32, 33, 127, 128, 129, 165} and {c["pos0"][0] for c in mf} == set(pm.MFMA_POS) == {0, 5, 31, 32, 200}
+        assert all(pm.is_mfma(c) for c in mf + F("stale") if c["T"] > 8) and not any(pm.is_mfma(c) for c in tw)
+        assert [c["seed"] for c in tw] == [c["id"] for c in mf], "every MFMA case has a VALU twin on the same data"
+        assert any(c["pos0"][0] + c["T"] > c["Tmax"] for c in mf)
+        assert {(c["v16"], c["kv8"], c["pshift"]) for c in mf} >= {(False, 0, 0), (True, 0, 0), (False, 1, 0), (False, 0, 5), (False, 0, 6), (False, 0, 7)}
+        stl = F("stale")
+        assert {c["pos0"][0] + c["T"] for c in stl if c["T"] > 8} >= {63, 64, 65} and any(min(c["pos0"]) < 0 for c in stl)
+        # scale: one case per kernel family
+        for fam in ("scale4", "stair", "first"):
+            kinds = {pm.kernel_of_attn(c)[0][0] + ("/split" if len(pm.kernel_of_attn(c)) > 1 and not pm.is_verify(c) else "") for c in F(fam)}
+            assert kinds == {"attn_f32_kernel", "attn_f32_kernel/split", "attn_f32_verify_kernel", "attn_f32_mfma_kernel"}, (fam, kinds)
+            assert any(c["D"] > 128 for c in F(fam)) and any(c["rope"] and c["T"] == 1 for c in F(fam))
+        assert all(c["scale_mul"] == 4.0 for c in F("scale4"))
+    # the other entry points
+    assert {c["D"] for c in pm.ROPE} == {8, 64, 104, 128, 160, 256} and {c["T"] for c in pm.ROPE} == {1, 5, 37} and {c["pos"] for c in pm.ROPE} == {"zero", "cross", "past", "negative"}
+    assert {c["pshift"] for c in pm.ROPE if c["D"] == 128} == {0, 5, 6, 7} and {c["pshift"] for c in pm.ROPE if c["D"] != 128} == {0}
+    assert {c["cols"] for c in pm.RMS} == {8, 2040, 2048, 2056, 4104, 5120} and {c["rows"] for c in pm.RMS} == {1, 16, 17, 32}
+    assert {c["mode"] for c in pm.RMS} == {"y32", "planes", "both"} and {c["cols"] for c in pm.RMS if c["tiled"]} == {2048, 5120}
+    assert {c["rows"] for c in pm.SPLIT16 if c["tiled"]} == {1, 15, 16, 17, 31, 32} and {c["rows"] for c in pm.SPLIT16 if not c["tiled"]} >= {33, 300}
+    assert {c["cols"] for c in pm.SPLIT16} == {8, 32, 40, 2080} and {c["cols"] for c in pm.SPLIT16 if c["tiled"]} == {32, 2080}
+    assert {65504.0, -65504.0, pm.BELOW_65520, 65520.0, 131008.0, 0.0} <= set(pm.SPLIT_SPECIALS) and pm.BELOW_65520 < 65520.0
+
+
 def test_gemv_matrix_k_values_reach_every_peeled_round():
     """For every skinny instantiation, dtype and weight format, the four waves' (full, rem) of its unsplit cases — by the kernel's own
     k-slice formula — cover full in {0, 1, 2, odd >= 3, even >= 4} with every rem in 0 .. U-1 (all but the wave without k-steps), the
