@@ -511,6 +511,36 @@ int sx_next_b_ctl(float* logits, int ld_logits, int vocab, const int32_t* img_id
                   const sx_logits_ctl_args* ctl, void* stream);
 int sx_next_slots_ctl(const sx_slot_step_args* args, const sx_sample_args* sample, const sx_logprob_args* lp,
                       const sx_logits_ctl_args* ctl, void* stream);
+/* Constrained decoding: a token-level deterministic automaton per grammar, resident on the device as a dense table
+ * (seedx_amd.grammar builds it on the host and states the rule in numpy fp32: constrain_row, advance). Row g is CONSTRAINED when
+ * 0 <= table[g] < n_tables and 0 <= state[g] < n_states; with T = trans[table[g]][state[g]] and F = flags[table[g]]:
+ *   working row: the row gets one in ctl->work whether or not ctl->on[g] is set - with on[g] != 0 steps 1-4 of the controls rule ran
+ *                first, as in sx_next_b_ctl; with on[g] == 0 it is a plain copy of the row and nothing is counted;
+ *   mask:        y[v] = -inf where T[v] < 0 (v != eos); y[eos] keeps its value iff F[state[g]] & 1, else -inf; nothing else changes
+ *                (eos: sx_slot_step_args.eos_id in the slot form, eos_id below in lock-step; -1 = none);
+ *   id:          the processor rule (chain forcing, zeroing of the image columns) is SKIPPED for the row - its zeroing would lift banned
+ *                image columns from -inf to 0.0, and the host never constrains a row inside the image chain; the arg-max or the seeded
+ *                draw then runs on the working row, unchanged. The logits row stays raw: the LP record describes the raw distribution;
+ *   advance:     on the id the row emits (slot form: behind the force_at replacement) state[g] = DONE (-2) on EOS, else s' = T[id];
+ *                DONE if s' < 0 (reachable only when every admissible logit was -inf already) or s' is final (F[s'] & 2), else s'.
+ * In the slot form the stop rule gains "or the new state is DONE": the slot parks itself exactly as on EOS or budget (same idle values,
+ * same status row). In the lock-step form the row runs unconstrained from then on; the host cuts the request there.
+ * Every other row (table[g] < 0, state[g] < 0, or either out of range): bit for bit sx_next_b_ctl / sx_next_slots_ctl, the in-place
+ * zeroing of an uncontrolled row included. A parked slot reads and writes nothing, state included.
+ * trans is read two ids per dword: ld_v is even and >= vocab, trans 4-byte aligned; 1 <= n_states <= 32767. */
+typedef struct sx_token_fsm_args {
+  const int32_t* table;   /* [G]: grammar index of the row, -1 = unconstrained                 */
+  int32_t* state;         /* [G]: in/out; < 0 (DONE) = the row runs unconstrained             */
+  const int16_t* trans;   /* [n_tables][n_states][ld_v], -1 = banned                          */
+  const int32_t* flags;   /* [n_tables][n_states]: bit 0 accepting, bit 1 final               */
+  int32_t n_tables, n_states, ld_v, eos_id;   /* eos_id: lock-step form only, -1 = none       */
+} sx_token_fsm_args;
+int sx_next_b_fsm(float* logits, int ld_logits, int vocab, const int32_t* img_ids_dev, int n_img,
+                  const int32_t* prev_id_dev, int32_t* next_id_dev, int32_t* out_ids, int ld_out,
+                  const int32_t* step_dev, int G, const sx_sample_args* sample, const sx_logprob_args* lp,
+                  const sx_logits_ctl_args* ctl, const sx_token_fsm_args* fsm, void* stream);
+int sx_next_slots_fsm(const sx_slot_step_args* args, const sx_sample_args* sample, const sx_logprob_args* lp,
+                      const sx_logits_ctl_args* ctl, const sx_token_fsm_args* fsm, void* stream);
 
 /* Speculative decoding (lossless): the token step carries T = K + 1 rows per slot — row g*T is the slot's current token, rows g*T + 1 ..
  * g*T + n_draft[g] K drafted continuations — and sx_greedy_next_b / sx_sample_next_b over the G*T rows (previous id = the row's input,

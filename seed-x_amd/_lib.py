@@ -90,6 +90,11 @@ class LogitsCtlArgs(C.Structure):
                 ("ld_counts", c_i32), ("eos_id", c_i32)]
 
 
+class TokenFsmArgs(C.Structure):
+    _fields_ = [("table", c_vp), ("state", c_vp), ("trans", c_vp), ("flags", c_vp), ("n_tables", c_i32), ("n_states", c_i32),
+                ("ld_v", c_i32), ("eos_id", c_i32)]
+
+
 class SpecAcceptArgs(C.Structure):
     _fields_ = [("cand", c_vp), ("rows_in", c_vp), ("n_draft", c_vp), ("cur", c_vp), ("live", c_vp), ("n_new", c_vp), ("max_new", c_vp),
                 ("force_at", c_vp), ("pos", c_vp), ("ctx", c_vp), ("step", c_vp), ("out_ids", c_vp), ("status", c_vp), ("hist", c_vp),
@@ -179,6 +184,10 @@ SIGNATURES = {
     "sx_next_b_ctl": [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, C.POINTER(SampleArgs),
                       C.POINTER(LogprobArgs), C.POINTER(LogitsCtlArgs), c_vp],
     "sx_next_slots_ctl": [C.POINTER(SlotStepArgs), C.POINTER(SampleArgs), C.POINTER(LogprobArgs), C.POINTER(LogitsCtlArgs), c_vp],
+    "sx_next_b_fsm": [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, C.POINTER(SampleArgs),
+                      C.POINTER(LogprobArgs), C.POINTER(LogitsCtlArgs), C.POINTER(TokenFsmArgs), c_vp],
+    "sx_next_slots_fsm": [C.POINTER(SlotStepArgs), C.POINTER(SampleArgs), C.POINTER(LogprobArgs), C.POINTER(LogitsCtlArgs),
+                          C.POINTER(TokenFsmArgs), c_vp],
     "sx_spec_accept": [C.POINTER(SpecAcceptArgs), c_vp],
     "sx_spec_draft_ngram": [C.POINTER(SpecDraftArgs), c_vp],
     "sx_scatter_rows_spec": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp],

@@ -1311,7 +1311,9 @@ __device__ __forceinline__ void lockstep_store(const TailP& p, int g, int result
 }
 
 // the slot advance of a live slot (thread 0): force_at, the id log, the counters, the stop rule, parking, the status row
-__device__ __forceinline__ void slot_advance(const TailP& p, int g, int result) {
+// (ALSO: the FSM form's "or the grammar is done" joins the stop rule)
+template <bool ALSO = false>
+__device__ __forceinline__ void slot_advance(const TailP& p, int g, int result, [[maybe_unused]] bool also_stop = false) {
   int n = p.n_new[g];
   const int fa = p.force_at[g];
   if (fa >= 0 && n == fa) result = p.force_id;      // synthetic weights only: replaced AFTER the full arg-max / draw (no work skipped)
@@ -1320,7 +1322,8 @@ __device__ __forceinline__ void slot_advance(const TailP& p, int g, int result) 
   p.next[g] = result;
   n += 1;
   p.n_new[g] = n;
-  const bool stop = (p.eos_id >= 0 && result == p.eos_id) || n >= p.max_new[g];
+  bool stop = (p.eos_id >= 0 && result == p.eos_id) || n >= p.max_new[g];
+  if constexpr (ALSO) stop = stop || also_stop;
   if (stop) {
     p.live[g] = 0;
     p.step[g] = -1;
@@ -1560,10 +1563,50 @@ __device__ __forceinline__ void ctl_edit_row(const float* row, float* work, cons
   __syncthreads();
 }
 
-template <bool SAMPLE, bool LP = false, bool CTL = false>
+// FSM (on the CTL family only: the controls carry the working rows): constrained decoding by a token automaton (seedx_amd.grammar states
+// the rule: constrain_row, advance; include/seedx_hip.h sx_token_fsm_args). Row g is constrained when 0 <= table[g] < n_tables and
+// 0 <= state[g] < n_states. Such a row always gets a working row (a plain copy when on[g] == 0, the controlled row otherwise), in which
+// every id its table row bans becomes -inf and EOS survives only in an accepting state; the image rule is skipped for it (n_img = 0 to
+// the id functions: its zeroing would lift banned image columns to 0.0); the arg-max or the draw is the unchanged one; thread 0 advances
+// the state on the id the row emits, and in the slot form a state that becomes DONE stops the slot. Every other row: the CTL path.
+struct FsmP {
+  const int* table;
+  int* state;
+  const short* trans;
+  const int* flags;
+  int n_tables, n_states, ld_v, eos_id;
+};
+struct CtlFsmP : CtlP {           // one kernel argument, so that the argument list of the older instantiations stays what it was
+  FsmP f;
+};
+constexpr int FSM_DONE = -2;
+
+// work[0..ld) = src[0..ld) with the banned columns -inf (src may be work). trow: the state's table row, int16 [ld_v >= vocab], ld_v even
+// and the row 4-byte aligned: one dword holds the next states of two neighbouring ids. Ends behind a barrier.
+__device__ __forceinline__ void fsm_mask_row(const float* src, float* work, const short* trow, bool accepting, int vocab, int ld, int eos) {
+  for (int i = 2 * (int)threadIdx.x; i < ld; i += 2048) {
+    const unsigned pair = i < vocab ? *reinterpret_cast<const unsigned*>(trow + i) : 0u;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int col = i + e;
+      if (col < ld) {
+        float y = src[col];
+        if (col < vocab) {
+          const bool ban = col == eos ? !accepting : (short)(pair >> (16 * e)) < 0;
+          if (ban) y = -INFINITY;
+        }
+        work[col] = y;
+      }
+    }
+  }
+  __syncthreads();
+}
+
+template <bool SAMPLE, bool LP = false, bool CTL = false, bool FSM = false>
 __global__ __launch_bounds__(1024) void next_token_kernel(const TailP p, const std::conditional_t<SAMPLE, SampleP, NoSampleP> s,
                                                           const std::conditional_t<LP, LogprobP, NoLogprobP> lp,
-                                                          const std::conditional_t<CTL, CtlP, NoCtlP> c) {
+                                                          const std::conditional_t<FSM, CtlFsmP, std::conditional_t<CTL, CtlP, NoCtlP>> c) {
+  static_assert(CTL || !FSM, "the FSM form lives on the CTL family: the controls carry the working rows");
   const int g = blockIdx.x;
   const bool slots = p.live != nullptr;
   if (slots && p.live[g] == 0) return;              // parked (uniform over the workgroup: no barrier is skipped by a part of it)
@@ -1577,6 +1620,20 @@ __global__ __launch_bounds__(1024) void next_token_kernel(const TailP p, const s
       const int k = slots ? p.step[g] : c.token_index[g];
       float* work = c.work + (size_t)g * p.ld_logits;
       ctl_edit_row(row, work, c, g, p.vocab, p.ld_logits, slots ? p.eos_id : c.eos_id, k);
+      row = work;
+    }
+  }
+  [[maybe_unused]] bool fsm_on = false;
+  [[maybe_unused]] const short* trow = nullptr;
+  [[maybe_unused]] const int* frow = nullptr;
+  if constexpr (FSM) {
+    const int tab = c.f.table[g], st = c.f.state[g];    // (uniform; state[g] is rewritten by thread 0 behind the id functions' barriers)
+    fsm_on = tab >= 0 && tab < c.f.n_tables && st >= 0 && st < c.f.n_states;
+    if (fsm_on) {
+      frow = c.f.flags + (size_t)tab * c.f.n_states;
+      trow = c.f.trans + ((size_t)tab * c.f.n_states + st) * c.f.ld_v;
+      float* work = c.work + (size_t)g * p.ld_logits;
+      fsm_mask_row(row, work, trow, (frow[st] & 1) != 0, p.vocab, p.ld_logits, slots ? p.eos_id : c.f.eos_id);
       row = work;
     }
   }
@@ -1600,7 +1657,13 @@ __global__ __launch_bounds__(1024) void next_token_kernel(const TailP p, const s
   // every thread reads prev[g] and the token index before the first barrier of the id functions; thread 0 stores to next[g] (which
   // may be prev[g]) and step[g] after the last one
   int result;
-  if constexpr (SAMPLE)
+  if constexpr (FSM) {
+    const int n_img = fsm_on ? 0 : p.n_img;             // a constrained row: no chain, no zeroing
+    if constexpr (SAMPLE)
+      result = sample_next_id(row, p.vocab, p.img_ids, n_img, p.prev[g], s, g, slots ? p.step[g] : s.token_index[g]);
+    else
+      result = greedy_next_id(row, p.vocab, p.img_ids, n_img, p.prev[g]);
+  } else if constexpr (SAMPLE)
     result = sample_next_id(row, p.vocab, p.img_ids, p.n_img, p.prev[g], s, g, slots ? p.step[g] : s.token_index[g]);
   else
     result = greedy_next_id(row, p.vocab, p.img_ids, p.n_img, p.prev[g]);
@@ -1626,8 +1689,28 @@ __global__ __launch_bounds__(1024) void next_token_kernel(const TailP p, const s
       if (id >= 0 && id < p.vocab) c.counts[(size_t)g * c.ld_counts + id] += 1;
     }
   }
-  if (slots) slot_advance(p, g, result);
-  else lockstep_store(p, g, result);
+  [[maybe_unused]] bool fsm_stop = false;
+  if constexpr (FSM) {
+    if (fsm_on) {                                   // advance on the id the row EMITS; DONE: EOS, an inadmissible id, or a final state
+      int id = result;
+      if (slots && p.force_at[g] >= 0 && p.n_new[g] == p.force_at[g]) id = p.force_id;
+      const int eos = slots ? p.eos_id : c.f.eos_id;
+      int ns = FSM_DONE;
+      if (!(eos >= 0 && id == eos) && id >= 0 && id < p.vocab) {
+        const int t = trow[id];
+        if (t >= 0 && t < c.f.n_states && !(frow[t] & 2)) ns = t;
+      }
+      c.f.state[g] = ns;
+      fsm_stop = ns < 0;
+    }
+  }
+  if constexpr (FSM) {
+    if (slots) slot_advance<true>(p, g, result, fsm_stop);
+    else lockstep_store(p, g, result);
+  } else {
+    if (slots) slot_advance(p, g, result);
+    else lockstep_store(p, g, result);
+  }
 }
 
 inline dim3 gs_grid(int64_t n) {
@@ -1933,12 +2016,14 @@ static TailP slot_tail(const sx_slot_step_args* a) {
                a->live, a->n_new, a->max_new, a->force_at, a->pos, a->ctx, a->status, a->force_id, a->eos_id};
 }
 
-// The one launcher behind the nine entry points. slots: the in-flight form (every pointer but out_ids is required, ld_out is the row
+// The one launcher behind the eleven entry points. slots: the in-flight form (every pointer but out_ids is required, ld_out is the row
 // capacity), else the lock-step form. sampled: the entry point takes a sx_sample_args, which must then be there. lp: the LP form
 // (sx_sample_next_b_lp / sx_sample_next_slots_lp); NULL launches exactly what the five older entry points always launched. ctl: the
-// controlled forms (sx_next_b_ctl / sx_next_slots_ctl), any of the four combinations of sample and lp.
+// controlled forms (sx_next_b_ctl / sx_next_slots_ctl), any of the four combinations of sample and lp. fsm: the constrained forms
+// (sx_next_b_fsm / sx_next_slots_fsm), on top of ctl.
 static int launch_next_token(const char* who, const TailP& p, bool slots, const sx_sample_args* sample, bool sampled, void* stream,
-                             const sx_logprob_args* lp = nullptr, const sx_logits_ctl_args* ctl = nullptr) {
+                             const sx_logprob_args* lp = nullptr, const sx_logits_ctl_args* ctl = nullptr,
+                             const sx_token_fsm_args* fsm = nullptr) {
   SX_CHECK(p.logits && p.img_ids && p.prev && p.next, "%s: null pointer", who);
   SX_CHECK(p.n_img >= 2 && p.n_img <= 1024 && p.G >= 1, "%s: n_img=%d G=%d", who, p.n_img, p.G);
   if (slots) {
@@ -1980,7 +2065,23 @@ static int launch_next_token(const char* who, const TailP& p, bool slots, const 
     SX_CHECK(ctl->eos_id >= -1 && ctl->eos_id < p.vocab, "%s: sx_logits_ctl_args.eos_id=%d", who, ctl->eos_id);
     const CtlP c{ctl->on, ctl->counts, ctl->work, ctl->rep, ctl->rep_inv, ctl->presence, ctl->frequency, ctl->min_new, ctl->bias_ids,
                  ctl->bias, ctl->token_index, ctl->ld_counts, ctl->eos_id};
-    if (sampled && lp) hipLaunchKernelGGL((next_token_kernel<true, true, true>), dim3(p.G), dim3(1024), 0, ST, p, s, l, c);
+    if (fsm) {
+      // the constrained forms: a table row is ld_v int16 wide and read two ids per dword up to vocab; table[g] and state[g] live on the
+      // device and are range-checked by the kernel (a row outside [0, n_tables) x [0, n_states) runs unconstrained)
+      SX_CHECK(fsm->table && fsm->state && fsm->trans && fsm->flags, "%s: null pointer in sx_token_fsm_args", who);
+      SX_CHECK(fsm->n_tables >= 1 && fsm->n_states >= 1 && fsm->n_states <= 32767, "%s: sx_token_fsm_args n_tables=%d n_states=%d (>= 1, "
+               "1 .. 32767)", who, fsm->n_tables, fsm->n_states);
+      SX_CHECK(fsm->ld_v >= p.vocab && fsm->ld_v % 2 == 0 && ((uintptr_t)fsm->trans & 3) == 0,
+               "%s: sx_token_fsm_args.ld_v=%d must be even and >= vocab=%d, trans 4-byte aligned", who, fsm->ld_v, p.vocab);
+      SX_CHECK(fsm->eos_id >= -1 && fsm->eos_id < p.vocab, "%s: sx_token_fsm_args.eos_id=%d", who, fsm->eos_id);
+      CtlFsmP cf;
+      static_cast<CtlP&>(cf) = c;
+      cf.f = FsmP{fsm->table, fsm->state, fsm->trans, fsm->flags, fsm->n_tables, fsm->n_states, fsm->ld_v, fsm->eos_id};
+      if (sampled && lp) hipLaunchKernelGGL((next_token_kernel<true, true, true, true>), dim3(p.G), dim3(1024), 0, ST, p, s, l, cf);
+      else if (sampled) hipLaunchKernelGGL((next_token_kernel<true, false, true, true>), dim3(p.G), dim3(1024), 0, ST, p, s, NoLogprobP{}, cf);
+      else if (lp) hipLaunchKernelGGL((next_token_kernel<false, true, true, true>), dim3(p.G), dim3(1024), 0, ST, p, NoSampleP{}, l, cf);
+      else hipLaunchKernelGGL((next_token_kernel<false, false, true, true>), dim3(p.G), dim3(1024), 0, ST, p, NoSampleP{}, NoLogprobP{}, cf);
+    } else if (sampled && lp) hipLaunchKernelGGL((next_token_kernel<true, true, true>), dim3(p.G), dim3(1024), 0, ST, p, s, l, c);
     else if (sampled) hipLaunchKernelGGL((next_token_kernel<true, false, true>), dim3(p.G), dim3(1024), 0, ST, p, s, NoLogprobP{}, c);
     else if (lp) hipLaunchKernelGGL((next_token_kernel<false, true, true>), dim3(p.G), dim3(1024), 0, ST, p, NoSampleP{}, l, c);
     else hipLaunchKernelGGL((next_token_kernel<false, false, true>), dim3(p.G), dim3(1024), 0, ST, p, NoSampleP{}, NoLogprobP{}, c);
@@ -2036,6 +2137,19 @@ extern "C" int sx_next_slots_ctl(const sx_slot_step_args* a, const sx_sample_arg
                                  const sx_logits_ctl_args* ctl, void* stream) {
   SX_CHECK(ctl, "sx_next_slots_ctl: null sx_logits_ctl_args");
   return launch_next_token("sx_next_slots_ctl", slot_tail(a), true, sample, sample != nullptr, stream, lp, ctl);
+}
+extern "C" int sx_next_b_fsm(float* logits, int ld_logits, int vocab, const int32_t* img_ids_dev, int n_img,
+                             const int32_t* prev_id_dev, int32_t* next_id_dev, int32_t* out_ids, int ld_out,
+                             const int32_t* step_dev, int G, const sx_sample_args* sample, const sx_logprob_args* lp,
+                             const sx_logits_ctl_args* ctl, const sx_token_fsm_args* fsm, void* stream) {
+  SX_CHECK(ctl && fsm, "sx_next_b_fsm: null sx_logits_ctl_args / sx_token_fsm_args");
+  return launch_next_token("sx_next_b_fsm", TailP{logits, img_ids_dev, prev_id_dev, next_id_dev, out_ids, const_cast<int32_t*>(step_dev),
+                                                  ld_logits, vocab, n_img, ld_out, G}, false, sample, sample != nullptr, stream, lp, ctl, fsm);
+}
+extern "C" int sx_next_slots_fsm(const sx_slot_step_args* a, const sx_sample_args* sample, const sx_logprob_args* lp,
+                                 const sx_logits_ctl_args* ctl, const sx_token_fsm_args* fsm, void* stream) {
+  SX_CHECK(ctl && fsm, "sx_next_slots_fsm: null sx_logits_ctl_args / sx_token_fsm_args");
+  return launch_next_token("sx_next_slots_fsm", slot_tail(a), true, sample, sample != nullptr, stream, lp, ctl, fsm);
 }
 extern "C" int sx_token_logprobs(const float* logits, int64_t ld, int vocab, const int32_t* targets, float* chosen, int32_t* top_ids,
                                  float* top, int n_top, int rows, void* stream) {

@@ -164,11 +164,14 @@ class SlotState:
         self.logprobs = None
         # a ControlState (slot_state(controls=True)): the step ends in the controlled tail (sx_next_slots_ctl) and has graphs of its own
         self.controls = None
+        # a GrammarState (slot_state(grammar=True)): the step ends in the constrained tail (sx_next_slots_fsm), graphs of its own again
+        self.grammar = None
 
     def key(self):
         return tuple(t.data_ptr() for t in (self.live, self.n_new, self.max_new, self.force_at, self.status)) \
             + (self.force_id, self.eos_id) + (self.sampling.key() if self.sampling is not None else ()) \
-            + (self.logprobs.key() if self.logprobs is not None else ()) + (self.controls.key() if self.controls is not None else ())
+            + (self.logprobs.key() if self.logprobs is not None else ()) + (self.controls.key() if self.controls is not None else ()) \
+            + (self.grammar.key() if self.grammar is not None else ())
 
 
 class SampleState:
@@ -333,13 +336,52 @@ class ControlState:
             self.counts.index_put_((g, t), torch.ones(len(pairs), dtype=torch.int32, device=self.device), accumulate=True)
 
 
+class GrammarState:
+    """Per-row state of constrained decoding on the device (sx_token_fsm_args; seedx_amd.grammar states the rule): ``table`` int32 [G]
+    (index of the row's grammar in the model's resident table, -1: unconstrained) and ``state`` int32 [G] (the automaton's state; the
+    tail advances it on every id a constrained row emits, DONE = -2: the row runs unconstrained). ``trans`` / ``flags`` are the MODEL's
+    tables (``llm.load_grammar`` writes them in place), so one captured step serves any mix of grammars; the pointers are part of the
+    graph key. A fresh state has every row unconstrained."""
+
+    def __init__(self, owner):
+        T = owner._P["grammar"]
+        self.owner, self.G, self.device = owner, owner.G, owner.device
+        self.trans, self.flags = T["trans"], T["flags"]
+        self.table = torch.full((self.G,), -1, dtype=torch.int32, device=self.device)
+        self.state = torch.full((self.G,), -2, dtype=torch.int32, device=self.device)
+
+    def key(self):
+        return ("fsm",) + tuple(t.data_ptr() for t in (self.table, self.state, self.trans, self.flags))
+
+    def set_rows(self, slots, names):
+        """slots[i] starts a request under the resident grammar names[i] (None: unconstrained): its table index, and state 0. An
+        unknown name is a ValueError, never an unconstrained row."""
+        slots = list(slots)
+        idx = [self.owner._grammar_index(n) for n in names]
+        self.owner._slot_write(self.table, slots, idx)
+        self.owner._slot_write(self.state, slots, [0 if i >= 0 else -2 for i in idx])
+
+    def gather(self, rows):
+        """A state of len(rows) rows holding copies of the given rows: what the first token of admitted requests, taken from the
+        prefill logits, is chosen with. ``scatter`` puts the advanced states back."""
+        out = GrammarState.__new__(GrammarState)
+        out.owner, out.G, out.device, out.trans, out.flags = self.owner, len(rows), self.device, self.trans, self.flags
+        idx = torch.tensor(list(rows), dtype=torch.int64, device=self.device)
+        out.table, out.state = self.table.index_select(0, idx), self.state.index_select(0, idx)
+        return out
+
+    def scatter(self, rows, part):
+        self.state.index_copy_(0, torch.tensor(list(rows), dtype=torch.int64, device=self.device), part.state)
+
+
 class LlamaForCausalLM:
     KV_FORMATS =(None, "fp8_e4m3", "fp8_e4m3_emulated")
     WEIGHT_FORMATS = (None, "fp8_e4m3", "mxfp4")
     WEIGHT_RESIDENCIES = (None, "tiles")
 
     def __init__(self, config, max_cache_len=None, max_batch=1, comm=None, precise=None, kv_v16=None, weight_format=None, kv_format=None,
-                 weight_residency=None, max_adapters=0, lora_rank=32, spec_tokens=0, kv_pages=0, kv_page_size=64):
+                 weight_residency=None, max_adapters=0, lora_rank=32, spec_tokens=0, kv_pages=0, kv_page_size=64, max_grammars=0,
+                 grammar_states=256):
         self.config = config if not isinstance(config, dict) else LlamaConfigLite(**config)
         c = self.config
         self.H, self.nh, self.L = c.hidden_size, c.num_attention_heads, c.num_hidden_layers
@@ -450,6 +492,16 @@ class LlamaForCausalLM:
             self._need_tiled_precise("max_adapters", "the pre-activation addend exists on the MFMA skinny GEMM only")
             if self.lora_rank < 8 or self.lora_rank % 8 or 3 * self.lora_rank > 512:
                 raise ValueError(f"LlamaForCausalLM: lora_rank={lora_rank} must be a multiple of 8 in 8 .. 168")
+        # constrained decoding (grammar.py; opt-in: ``max_grammars`` > 0 preallocates that many token automata of up to ``grammar_states``
+        # states, int16 [max_grammars][grammar_states][Vpad] + flags): only the tail of the token step changes, so every weight_format,
+        # weight_residency, kv_format, kv_pages, adapter, sampling, logprob and control setting keeps working. 0: nothing is allocated,
+        # nothing is launched differently
+        self.max_grammars, self.grammar_states = int(max_grammars), int(grammar_states)
+        self._grammars = {}
+        if self.max_grammars < 0:
+            raise ValueError(f"LlamaForCausalLM: max_grammars={max_grammars} must be >= 0")
+        if self.max_grammars and not 2 <= self.grammar_states <= 32767:
+            raise ValueError(f"LlamaForCausalLM: grammar_states={grammar_states} must be in 2 .. 32767 (next states are int16)")
         # lossless speculative decoding (spec.py; opt-in: ``spec_tokens=K`` drafted tokens per sequence and step): the verify step
         # (``decode_step(..., slots=st, spec=True)``) carries K + 1 rows per slot through the skinny GEMMs — the weights stream once
         # whatever the row count — and keeps the longest prefix the model itself would have produced (sx_spec_accept). 0: nothing is
@@ -506,7 +558,8 @@ class LlamaForCausalLM:
         self._drop_graphs()
         self._sample_state = None
         self._control_state = None
-        self.kv_epoch = 0               # bumped whenever the KV cache is reset or written outside generate_batch
+        self._grammar_state = self._off_control_state = None
+        self.kv_epoch = 0              # bumped whenever the KV cache is reset or written outside generate_batch
 
     def _kv_name(self):
         """The KV cache's format in words (log line and fit guard)."""
@@ -578,6 +631,7 @@ class LlamaForCausalLM:
             # ... and a step that ends in the controlled tail (a ControlState) has graphs of its own beside each of the sixteen
             for mid in ("", "_ad", "_lp", "_lp_ad"):
                 setattr(self, attr + mid + "_ctl", None)
+                setattr(self, attr + mid + "_fsm", None)       # ... and so has a step that ends in the constrained tail (a GrammarState)
 
     def memory_footprint(self):
         """Bytes this module will hold on its GPU once packed (per rank): 16-bit weights, their decode-tile copy (precise mode: always;
@@ -602,6 +656,8 @@ class LlamaForCausalLM:
         ad = {"adapters": self.max_adapters * self._adapter_slot_bytes()} if self.max_adapters else {}
         if self.spec_tokens:                    # the verify step's own buffers (_pack: P["spec"])
             ad["spec_decode"] = self._spec_bytes()
+        if self.max_grammars:                   # the resident token automata: int16 next states over the padded vocabulary + int32 flags
+            ad["grammars"] = self.max_grammars * self.grammar_states * (self.Vpad * 2 + 4)
         if self.weight_residency == "tiles":
             # no row-major projection is held: embedding + lm_head + the one prefill scratch buffer (the largest per-rank projection)
             scratch = self._scratch_elems() * 2
@@ -873,6 +929,18 @@ class LlamaForCausalLM:
             assert held == fp["adapters"], (held, fp["adapters"])                 # memory_footprint() prices what is held
             P["lora"] = T
             self._sel_host = [-1] * G
+        if self.max_grammars:
+            # a free table slot bans everything and accepts nothing; no row points at one (GrammarState.set_rows resolves names)
+            T = {"trans": torch.full((self.max_grammars, self.grammar_states, self.Vpad), -1, dtype=torch.int16, device=dev),
+                 "flags": torch.zeros((self.max_grammars, self.grammar_states), dtype=torch.int32, device=dev)}
+            held = sum(t.numel() * t.element_size() for t in T.values())
+            assert held == fp["grammars"], (held, fp["grammars"])                 # memory_footprint() prices what is held
+            for a, f in self._grammars.values():                                  # a re-pack keeps the resident grammars
+                trans, flags = f.table(self.grammar_states, self.Vpad)
+                T["trans"][a].copy_(torch.from_numpy(trans))
+                T["flags"][a].copy_(torch.from_numpy(flags))
+            P["grammar"] = T
+            self._grammar_state = None
         if self.spec_tokens:
             # the verify step's own buffers; the plain step keeps its workspace, scratch and graphs untouched
             R = G * (self.spec_tokens + 1)
@@ -891,6 +959,72 @@ class LlamaForCausalLM:
         self._sd = None
         self._drop_graphs()
         return P
+
+    # ---- resident grammars (grammar.py) ---------------------------------------------------------------------------------
+    @property
+    def grammars(self):
+        """Names of the resident grammars."""
+        return sorted(self._grammars)
+
+    def _grammar_index(self, name):
+        """Table slot of a request's grammar: None → -1 (unconstrained); an unknown name is an error, never an unconstrained row."""
+        if name is None:
+            return -1
+        if not self.max_grammars:
+            raise ValueError(f"LlamaForCausalLM: grammar {name!r} requested but the model was built with max_grammars=0")
+        if name not in self._grammars:
+            raise ValueError(f"LlamaForCausalLM: unknown grammar {name!r} (resident: {self.grammars})")
+        return self._grammars[name][0]
+
+    def grammar(self, name):
+        """The grammar.TokenFSM resident under ``name`` (the engines walk it on the host for ``complete``)."""
+        self._grammar_index(name)
+        return self._grammars[name][1]
+
+    def load_grammar(self, name, fsm):
+        """Make a grammar.TokenFSM resident under ``name``: its table is written IN PLACE into a free slot of the model's table
+        (allocated at pack time), so captured token steps stay valid. ValueError for a full table, a duplicate name, a grammar with
+        more states than ``grammar_states`` or another vocabulary, or a model built with ``max_grammars=0``."""
+        if not self.max_grammars:
+            raise ValueError("LlamaForCausalLM.load_grammar: the model was built with max_grammars=0")
+        if name in self._grammars:
+            raise ValueError(f"LlamaForCausalLM.load_grammar: a grammar named {name!r} is resident already (unload_grammar first)")
+        if len(self._grammars) >= self.max_grammars:
+            raise ValueError(f"LlamaForCausalLM.load_grammar: all {self.max_grammars} grammar slots are in use ({self.grammars})")
+        if fsm.n_states > self.grammar_states:
+            raise ValueError(f"LlamaForCausalLM.load_grammar: grammar {name!r} has {fsm.n_states} states, the model was built with "
+                             f"grammar_states={self.grammar_states}")
+        if fsm.vocab_size != self.V:
+            raise ValueError(f"LlamaForCausalLM.load_grammar: grammar {name!r} is over {fsm.vocab_size} ids, the model's vocabulary has {self.V}")
+        T = self._pack()["grammar"]
+        a = min(set(range(self.max_grammars)) - {i for i, _ in self._grammars.values()})
+        trans, flags = fsm.table(self.grammar_states, self.Vpad)
+        T["trans"][a].copy_(torch.from_numpy(trans))
+        T["flags"][a].copy_(torch.from_numpy(flags))
+        self._grammars[name] = (a, fsm)
+        return a
+
+    def unload_grammar(self, name):
+        """Free ``name``'s table slot (it bans everything and accepts nothing again), in place."""
+        a = self._grammar_index(name)
+        if a < 0:
+            raise ValueError("LlamaForCausalLM.unload_grammar: no grammar named")
+        T = self._pack()["grammar"]
+        T["trans"][a].fill_(-1)
+        T["flags"][a].zero_()
+        del self._grammars[name]
+
+    def grammar_state(self, fresh=False):
+        """A GrammarState over this model's table. The lock-step step's (``decode_step(..., grammar=...)``) is made once — its pointers
+        are part of the captured graph's key; ``fresh``: a new one (a slot state owns its own)."""
+        if not self.max_grammars:
+            raise ValueError("LlamaForCausalLM.grammar_state: the model was built with max_grammars=0")
+        self._pack()
+        if fresh:
+            return GrammarState(self)
+        if getattr(self, "_grammar_state", None) is None:
+            self._grammar_state = GrammarState(self)
+        return self._grammar_state
 
     # ---- unmerged LoRA adapters (lora.py) ---------------------------------------------------------------------------------
     @property
@@ -1439,21 +1573,27 @@ class LlamaForCausalLM:
     __call__ = forward
 
     # ---- in-flight batching: slot states ---------------------------------------------------------------------------------
-    def slot_state(self, force_id=-1, eos_id=-1, sampling=False, logprobs=None, controls=False):
+    def slot_state(self, force_id=-1, eos_id=-1, sampling=False, logprobs=None, controls=False, grammar=False):
         """A fresh SlotState with EVERY slot parked (the module's pos / ctx / step take the idle values; ``reset()`` undoes that).
         ``sampling``: the state carries a SampleState (``.sampling``, all rows greedy until set) and its token step ends in
         sx_sample_next_slots instead of sx_greedy_next_slots. ``logprobs`` = n_top (0 .. 8): the state carries a LogprobState
         (``.logprobs``, no row recording until ``want`` is set) and its token step ends in sx_sample_next_slots_lp. ``controls``: the
         state carries a ControlState (``.controls``, every row off until set) and its token step ends in sx_next_slots_ctl — greedy,
-        sampled, with or without the record."""
+        sampled, with or without the record. ``grammar``: the state carries a GrammarState (``.grammar``, every row unconstrained until
+        set) beside a ControlState (the constrained tail works on the controls' working rows) and its token step ends in
+        sx_next_slots_fsm."""
+        if grammar and not self.max_grammars:
+            raise ValueError("LlamaForCausalLM.slot_state: grammar=True on a model built with max_grammars=0")
         if self.tp > 1:
             raise NotImplementedError("in-flight batching (slot states) is single-rank: tensor-parallel ranks are not supported")
         self._pack()
         st = SlotState(self.G, self.device, force_id, eos_id, sampling)
         if logprobs is not None:
             st.logprobs = LogprobState(self.G, logprobs, self.device)
-        if controls:
+        if controls or grammar:
             st.controls = self.control_state(fresh=True)
+        if grammar:
+            st.grammar = self.grammar_state(fresh=True)
         if sampling and self.spec_tokens:
             T = self.spec_tokens + 1
             st.sampling.rows = (SampleState(self.G * T, self.device), T)
@@ -1504,6 +1644,12 @@ class LlamaForCausalLM:
             self._control_state = ControlState(self.G, self.V, self.Vpad, self.device)
         return self._control_state
 
+    def _off_controls(self):
+        """A ControlState with every row off, never set: the working rows of a lock-step grammar step that carries no controls."""
+        if getattr(self, "_off_control_state", None) is None:
+            self._off_control_state = ControlState(self.G, self.V, self.Vpad, self.device)
+        return self._off_control_state
+
     def _step_tail(self, x, hid_buf, sel=None, tok=None):
         """The end of every token step: final norm → the post-norm fp32 rows into hid_buf (row g at step[g]; verify step: row (g, t) at
         step[g] + t, ``tok`` takes the token indices) → lm_head logits fp32 [rows, Vpad / tp]. ``sel``: the adapter step — the final
@@ -1552,7 +1698,7 @@ class LlamaForCausalLM:
         held[1].replay()
 
     def _decode_step_body(self, img_ids_dev, out_ids, hid_buf, slots=None, sampling=None, adapters=False, logprobs=None, controls=None,
-                          eos_id=-1):
+                          eos_id=-1, grammar=None):
         """cur[G] → embedding → 40 layers → final norm → lm_head → logits rule + argmax → cur[G]. Records the post-norm
         hidden state of each INPUT token at hid_buf[g, step[g]] (what seed_x.py:196 collects) and the new id at
         out_ids[g, step[g]]; then step += 1. Everything stays on the device. ``slots`` (a SlotState): the tail is ONE
@@ -1576,8 +1722,12 @@ class LlamaForCausalLM:
         ctl = controls if slots is None else slots.controls
         if ctl is not None:
             sample["ctl"] = ctl
+        # constrained step: the same tail once more, with a token automaton per row (a GrammarState) on the controls' working rows
+        fsm = grammar if slots is None else slots.grammar
+        if fsm is not None:
+            sample["fsm"] = fsm
         if slots is not None:
-            tail = ops.next_slots_ctl if ctl is not None else ops.next_slots_lp if lp is not None else ops.sample_next_slots if sample \
+            tail = ops.next_slots_fsm if fsm is not None else ops.next_slots_ctl if ctl is not None else ops.next_slots_lp if lp is not None else ops.sample_next_slots if sample \
                 else ops.greedy_next_slots
             tail(logits, self.V, img_ids_dev, P["cur"], slots.live, slots.n_new, slots.max_new, slots.force_at, P["pos"], P["ctx"],
                  P["step"], out_ids, slots.status, force_id=slots.force_id, eos_id=slots.eos_id, **sample)
@@ -1585,7 +1735,7 @@ class LlamaForCausalLM:
             return
         if ctl is not None:
             sample["eos_id"] = eos_id
-        tail = ops.next_b_ctl if ctl is not None else ops.next_b_lp if lp is not None else ops.sample_next_b if sample else ops.greedy_next_b
+        tail = ops.next_b_fsm if fsm is not None else ops.next_b_ctl if ctl is not None else ops.next_b_lp if lp is not None else ops.sample_next_b if sample else ops.greedy_next_b
         tail(logits, self.V, img_ids_dev, P["cur"], out_ids, P["step"], **sample)
         ops.add_i32(P["step"], 1)
 
@@ -1617,7 +1767,7 @@ class LlamaForCausalLM:
             S["hist"][slot, start:start + len(ids)] = torch.tensor(ids, dtype=torch.int32, device=self.device)
 
     def decode_step(self, img_ids_dev, out_ids, hid_buf, use_graph=True, slots=None, sampling=None, adapters=None, spec=False, draft="ngram",
-                    logprobs=None, controls=None, eos_id=-1):
+                    logprobs=None, controls=None, eos_id=-1, grammar=None):
         """out_ids: int32 [G, rows]; hid_buf: fp32 [G, rows, H]. ``slots``: a SlotState → the in-flight step (its captured graph is
         kept apart from the lock-step one, so one graph serves an engine's lifetime whatever else runs in between). ``sampling``: a
         SampleState → the lock-step step ends in sx_sample_next_b (token index = step[g]); a slot state brings its own
@@ -1634,8 +1784,26 @@ class LlamaForCausalLM:
         ``controls``: a ControlState → the lock-step step ends in the controlled tail (sx_next_b_ctl, token index = step[g], ``eos_id``
         the column min_new_tokens masks); a slot state brings its own (``slots.controls``, sx_next_slots_ctl). Again only the tail
         changes, graphs of its own (attribute suffix ``_ctl``), and a step without a state runs the calls and graphs it always ran.
-        ValueError with the verify step and on tensor-parallel ranks: follow-ups."""
+        ValueError with the verify step and on tensor-parallel ranks: follow-ups.
+        ``grammar``: a GrammarState → the lock-step step ends in the constrained tail (sx_next_b_fsm; ``eos_id`` is the column that
+        survives in accepting states only; without ``controls`` the module's control state with every row off carries the working
+        rows); a slot state brings its own (``slots.grammar``, sx_next_slots_fsm). Only the tail changes, graphs of its own (attribute
+        suffix ``_fsm``), and a step without a state runs the calls and graphs it always ran. ValueError with the verify step and on
+        tensor-parallel ranks: follow-ups."""
         P = self._pack()
+        fsm = grammar if slots is None else getattr(slots, "grammar", None)
+        if slots is not None and grammar is not None:
+            raise ValueError("LlamaForCausalLM.decode_step: a slot state carries its own grammar state (slot_state(grammar=True))")
+        if fsm is not None:
+            if spec:
+                raise ValueError("LlamaForCausalLM.decode_step: a grammar in the verify step of speculative decoding (spec=True with a "
+                                 "grammar state) is not built (follow-up: automaton states that advance with the accepted run)")
+            if self.tp > 1:
+                raise ValueError(f"LlamaForCausalLM.decode_step: grammars on tp={self.tp} tensor-parallel ranks are not built "
+                                 "(follow-up: every rank would mask and advance on the gathered logits)")
+            assert fsm.G == self.G and fsm.trans is P["grammar"]["trans"]
+            if slots is None and controls is None:
+                controls = self._off_controls()
         ctl = controls if slots is None else getattr(slots, "controls", None)
         if slots is not None and controls is not None:
             raise ValueError("LlamaForCausalLM.decode_step: a slot state carries its own control state (slot_state(controls=True))")
@@ -1690,7 +1858,7 @@ class LlamaForCausalLM:
             assert out_ids.is_contiguous() and slots.G == self.G
             assert sampling is None, "a slot state carries its own sampling state (slot_state(sampling=True))"
         assert sampling is None or sampling.G == self.G
-        body = lambda: self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling, adapters, logprobs, controls, eos_id)
+        body = lambda: self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling, adapters, logprobs, controls, eos_id, grammar)
         if not use_graph or not self.comm.graph_safe:
             return body()
         if slots is None:
@@ -1699,8 +1867,11 @@ class LlamaForCausalLM:
             attr = "_slot_graph" if slots.sampling is None else "_slot_sample_graph"
         key = (img_ids_dev.data_ptr(), out_ids.data_ptr(), hid_buf.data_ptr(), tuple(out_ids.shape)) \
             + (slots.key() if slots is not None else ()) + (("sample",) + sampling.key() if sampling is not None else ()) \
-            + (logprobs.key() if logprobs is not None else ()) + (controls.key() + (int(eos_id),) if controls is not None else ())
+            + (logprobs.key() if logprobs is not None else ()) + (controls.key() + (int(eos_id),) if controls is not None else ()) \
+            + (grammar.key() if grammar is not None else ())
         # (the controlled tail counts the id it emits: warm-up and capture run the step, so the counts are put back like the counters)
-        self._replay(attr + ("_lp" if lp is not None else "") + ("_ad" if adapters else "") + ("_ctl" if ctl is not None else ""), key, body,
-                     ([slots.live, slots.n_new, slots.status] if slots is not None else []) + ([ctl.counts] if ctl is not None else []),
-                     slots)
+        # (... and the constrained tail advances the automaton states: put back likewise)
+        self._replay(attr + ("_lp" if lp is not None else "") + ("_ad" if adapters else "")
+                     + ("_fsm" if fsm is not None else "_ctl" if ctl is not None else ""), key, body,
+                     ([slots.live, slots.n_new, slots.status] if slots is not None else []) + ([ctl.counts] if ctl is not None else [])
+                     + ([fsm.state] if fsm is not None else []), slots)

@@ -1340,6 +1340,64 @@ def next_slots_ctl(logits, vocab, img_ids_dev, cur, live, n_new, max_new, force_
                                         C.byref(ca), _stream()), "sx_next_slots_ctl")
 
 
+def _fsm_args(fsm, logits, vocab, eos_id=-1):
+    """sx_token_fsm_args from a grammar state (llama.GrammarState or anything with its tensors): ``table`` / ``state`` int32 [G],
+    ``trans`` int16 [n_tables, n_states, ld_v] and ``flags`` int32 [n_tables, n_states]. The shapes are checked here, so that the kernel's
+    range test of table[g] and state[g] is all that stands between a row and the table."""
+    G, i32 = logits.shape[0], torch.int32
+    for t in (fsm.table, fsm.state):
+        assert t.dtype == i32 and t.is_contiguous() and tuple(t.shape) == (G,), "token automaton: table / state are contiguous int32 [G]"
+    tr, fl = fsm.trans, fsm.flags
+    assert tr.dtype == torch.int16 and tr.is_contiguous() and tr.dim() == 3, "token automaton: trans is int16 [n_tables, n_states, ld_v]"
+    assert fl.dtype == i32 and fl.is_contiguous() and tuple(fl.shape) == tuple(tr.shape[:2]), "token automaton: flags is int32 [n_tables, n_states]"
+    # (ld_v even and >= vocab: the entry point refuses anything else)
+    return _lib.TokenFsmArgs(table=_p(fsm.table).value, state=_p(fsm.state).value, trans=_p(tr).value, flags=_p(fl).value,
+                             n_tables=tr.shape[0], n_states=tr.shape[1], ld_v=tr.shape[2], eos_id=int(eos_id))
+
+
+def next_b_fsm(logits, vocab, img_ids_dev, cur_dev, out_ids, step_dev, ctl, fsm, sample=None, lp=None, token_index=None, n_kept=None,
+               p_chosen=None, eos_id=-1):
+    """The lock-step tail with a token automaton per row (sx_next_b_fsm; seedx_amd.grammar states the rule): next_b_ctl, and a row with
+    ``fsm.table[g]`` >= 0 and ``fsm.state[g]`` >= 0 takes its id from a working row in ``ctl.work`` (the controlled row, or a plain copy
+    with ``ctl.on[g]`` = 0) in which the ids its table row bans are -inf and ``eos_id`` survives only in an accepting state; the image
+    rule is skipped for it, and ``fsm.state[g]`` advances on the id it emits (DONE = -2: the row runs unconstrained from then on).
+    Every other row is next_b_ctl's, bit for bit. ``eos_id`` serves min_new_tokens and the automaton alike."""
+    lib = _lib.load()
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    G = logits.shape[0]
+    token_index = step_dev if token_index is None else token_index
+    assert token_index is not None, "next_b_fsm: token_index (or step_dev) is required"
+    ld_out = out_ids.stride(0) if out_ids is not None else 0
+    la = None
+    if lp is not None:
+        la, ld_out = _logprob_args(lp, G, out_ids)
+        assert step_dev is not None, "the LP tail needs step_dev"
+    sa = _sample_args(sample, G, token_index, n_kept, p_chosen) if sample is not None else None
+    ca = _ctl_args(ctl, logits, vocab, token_index, eos_id)
+    fa = _fsm_args(fsm, logits, vocab, eos_id)
+    check(lib.sx_next_b_fsm(_p(logits), logits.stride(0), vocab, _p(img_ids_dev), img_ids_dev.numel(), _p(cur_dev), _p(cur_dev), _p(out_ids),
+                            ld_out, _p(step_dev), G, C.byref(sa) if sa is not None else None, C.byref(la) if la is not None else None,
+                            C.byref(ca), C.byref(fa), _stream()), "sx_next_b_fsm")
+
+
+def next_slots_fsm(logits, vocab, img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, out_ids, status, ctl, fsm, sample=None,
+                   lp=None, force_id=-1, eos_id=-1, n_kept=None, p_chosen=None):
+    """The in-flight tail with a token automaton per slot (sx_next_slots_fsm): next_slots_ctl with next_b_fsm's mask and advance per live
+    slot; a slot whose state becomes DONE stops and parks itself exactly as on EOS or budget. Parked slots read and write nothing,
+    ``fsm.state`` included; slots with ``fsm.table`` < 0 or ``fsm.state`` < 0 are next_slots_ctl's."""
+    a = _slot_step_args("next_slots_fsm", logits, vocab, img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, out_ids,
+                        status, force_id, eos_id)
+    G = logits.shape[0]
+    la = None
+    if lp is not None:
+        la, a.ld_out = _logprob_args(lp, G, out_ids)
+    s = _sample_args(sample, G, None, n_kept, p_chosen) if sample is not None else None
+    ca = _ctl_args(ctl, logits, vocab, None, eos_id)
+    fa = _fsm_args(fsm, logits, vocab, -1)
+    check(_lib.load().sx_next_slots_fsm(C.byref(a), C.byref(s) if s is not None else None, C.byref(la) if la is not None else None,
+                                        C.byref(ca), C.byref(fa), _stream()), "sx_next_slots_fsm")
+
+
 def _i32s(who, *ts):
     for t in ts:
         assert t.dtype == torch.int32 and t.is_contiguous(), f"{who}: contiguous int32 tensors"

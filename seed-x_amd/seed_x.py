@@ -17,6 +17,7 @@ import functools
 import torch
 
 from . import ops
+from .grammar import DONE, advance
 from .inflight import PrefixIndex, SlotScheduler, plan_admission, tag_signatures
 from .llama import LogprobState
 from .sampling import ControlParams, SamplingParams, logprobs_from_request, logprobs_result
@@ -182,6 +183,64 @@ class ContinuousLVLM:
             sig = torch.cat([sig, self._row_sig(e)])
         self._conv[g] = (list(ids) + list(gen_ids_fed), sig, self.llm.kv_epoch, adapter)
 
+    # ---- constrained decoding (grammar.py): what the engines check before anything is touched ------------------------------
+    def _grammar_names(self, who, requests, force_flags):
+        """The requests' ``"grammar"`` names (None: unconstrained). ValueError for what is not built or not there: tensor-parallel
+        ranks, agent.speculative, a model built with max_grammars=0, an unknown name, force_image_at on the same request."""
+        llm = self.llm
+        names = [req.get("grammar") for req in requests]
+        if all(n is None for n in names):
+            return names
+        world = llm.comm.world if getattr(llm, "comm", None) is not None else 1
+        if world > 1:
+            raise ValueError(f"{who}: a \"grammar\" on tp={world} tensor-parallel ranks is not built (follow-up: every rank would mask and "
+                             "advance on the gathered logits)")
+        if who == "generate_inflight" and self.speculative:
+            raise ValueError(f"{who}: a \"grammar\" with agent.speculative is not built (follow-up: automaton states that advance with the "
+                             "verify step's accepted run); switch agent.speculative off for calls that carry a grammar")
+        if not getattr(llm, "max_grammars", 0):
+            raise ValueError(f"{who}: a request names the grammar {next(n for n in names if n is not None)!r} but the model was built with "
+                             "max_grammars=0 (LlamaForCausalLM(..., max_grammars=N), then llm.load_grammar(name, fsm))")
+        for r, n in enumerate(names):
+            if n is None:
+                continue
+            if n not in llm.grammars:
+                raise ValueError(f"{who}: request {r} names the unknown grammar {n!r} (resident: {llm.grammars})")
+            if force_flags[r]:
+                raise ValueError(f"{who}: request {r} carries a grammar and force_image_at: not built (follow-up: the replaced id would "
+                                 "have to be an admissible one); drop one of the two")
+        return names
+
+    def _grammar_prompts(self, who, tokenizer, requests, names, img_ids):
+        """... and what needs the tokenizer: a constrained request may not start inside the image chain (the constrained row skips the
+        chain's forcing), and its grammar may not admit the image block."""
+        chain = set(img_ids[:-1])
+        for r, n in enumerate(names):
+            if n is None:
+                continue
+            last = self._prompt_ids(tokenizer, requests[r])[-1]
+            if last in chain:
+                raise ValueError(f"{who}: request {r} carries a grammar but its prompt ends inside the image block (id {last}): not built "
+                                 "(follow-up: a grammar that starts behind the forced block)")
+            fsm = self.llm.grammar(n)
+            if (fsm.trans[:, [i for i in img_ids if 0 <= i < fsm.vocab_size]] >= 0).any():
+                raise ValueError(f"{who}: grammar {n!r} admits ids of the image block (follow-up); build it with banned_ids = the block "
+                                 "(ContinuousLVLM.image_block_ids)")
+
+    @classmethod
+    def image_block_ids(cls, tokenizer, num_img_gen_tokens=64):
+        """The ids of ``<img>``, ``<img_i>`` and ``</img>``: what a grammar's ``banned_ids`` must hold."""
+        return cls._special_ids(tokenizer, num_img_gen_tokens, None)[0]
+
+    @staticmethod
+    def _grammar_result(fsm, name, generate_ids, eos):
+        """``{'name', 'complete'}``: the walk over the generated ids on the host; a trailing EOS is not part of it."""
+        ids = [int(t) for t in generate_ids]
+        if ids and eos is not None and eos >= 0 and ids[-1] == eos:
+            ids = ids[:-1]
+        _, used, complete = fsm.walk(ids)
+        return {'name': name, 'complete': bool(complete and used == len(ids))}
+
     @_clears_adapters
     @torch.no_grad()
     def generate_batch(self, tokenizer, requests, num_img_gen_tokens=64, max_new_tokens=120, eos_token_id="auto",
@@ -214,8 +273,21 @@ class ContinuousLVLM:
         image-token rule and the arg-max or draw (seedx_amd.sampling.apply_controls states the rule; sx_next_b_ctl), for the prefill's
         first token (index 0) as for every later one, and its result gains ``'controls'``. Log-probabilities stay those of the RAW
         row. Without such a request the call runs the calls and graphs it always ran. ValueError together with ``force_image_at``
-        (synthetic-weights pinning: a follow-up) and on tensor-parallel ranks (follow-up: edit and count on the gathered logits)."""
+        (synthetic-weights pinning: a follow-up) and on tensor-parallel ranks (follow-up: edit and count on the gathered logits).
+        A request may carry ``"grammar": name`` — a token automaton resident on the LLM (``llm.load_grammar(name, fsm)``,
+        seedx_amd.grammar): its ids are then chosen among those the automaton admits, by a mask applied on the device inside the tail
+        of the token step (sx_next_b_fsm: behind the controls, in place of the image-token rule, ahead of the arg-max or draw), for the
+        prefill's first token as for every later one; the row is cut at the token on which its walk finishes (a final state, or EOS
+        in an accepting one) and its result gains ``'grammar'`` = {'name', 'complete'} — ``complete`` is the host's walk over the
+        generated ids (a trailing EOS apart); a budget that runs out mid-grammar gives False. Log-probabilities stay those of the RAW
+        row. Without such a request the call runs the calls and graphs it always ran. ValueError, before anything is touched, for a
+        model built with max_grammars=0, an unknown name, ``force_image_at`` (follow-up), a prompt that ends inside the image block
+        (follow-up), a grammar that admits the image block (follow-up) and tensor-parallel ranks (follow-up)."""
         llm = self.llm
+        gnames = self._grammar_names("generate_batch", requests, [force_image_at is not None] * len(requests))
+        constrained = any(n is not None for n in gnames)
+        if constrained:
+            self._grammar_prompts("generate_batch", tokenizer, requests, gnames, self._special_ids(tokenizer, num_img_gen_tokens, None)[0])
         asks = [logprobs_from_request(req) for req in requests]
         ctls = [ControlParams.from_request(req) for req in requests]
         controlled = any(c is not None for c in ctls)
@@ -281,8 +353,15 @@ class ContinuousLVLM:
         if any(n is not None for n in asks):            # the LP tail, here and in every token step; rows that did not ask record nothing
             lps = LogprobState(G, max(n for n in asks if n is not None), dev, rows)
             lps.want.copy_(torch.tensor([int(n is not None) for n in asks], dtype=torch.int32))
-        cs, eos_dev = None, -1 if eos_token_id is None else int(eos_token_id)
-        if controlled:                                   # the controlled tail, here and in every token step; rows without controls run as ever
+        cs, gs, eos_dev = None, None, -1 if eos_token_id is None else int(eos_token_id)
+        fsms = [llm.grammar(n) if n is not None else None for n in gnames]
+        gstate = [0 if f is not None else DONE for f in fsms]        # host mirror of the automaton states, advanced on the read-back ids
+        if constrained:                                  # the constrained tail, here and in every token step; its working rows are the controls'
+            cs, gs = llm.control_state(), llm.grammar_state()
+            cs.set_rows(range(G), ctls, [ids for ids, _ in prompts])
+            gs.set_rows(range(G), gnames)
+            ops.next_b_fsm(logits, llm.V, img_ids_dev, P["cur"], out_ids, P["step"], cs, gs, sample=ss, lp=lps, eos_id=eos_dev)   # token index 0
+        elif controlled:                                   # the controlled tail, here and in every token step; rows without controls run as ever
             cs = llm.control_state()
             cs.set_rows(range(G), ctls, [ids for ids, _ in prompts])
             ops.next_b_ctl(logits, llm.V, img_ids_dev, P["cur"], out_ids, P["step"], cs, sample=ss, lp=lps, eos_id=eos_dev)   # token index 0
@@ -309,9 +388,14 @@ class ContinuousLVLM:
                     lps.forced(g, n_new[g] - 1, 1)       # the record made there describes the id that was replaced
 
         def finished(g):
-            return n_new[g] >= max_new_tokens or (eos_token_id is not None and cur[g] == eos_token_id)
+            return n_new[g] >= max_new_tokens or (eos_token_id is not None and cur[g] == eos_token_id) or (fsms[g] is not None and gstate[g] < 0)
+
+        def walk(g):                                     # the device did the same on the same id (grammar.advance)
+            if fsms[g] is not None and gstate[g] >= 0:
+                gstate[g] = advance(fsms[g], gstate[g], cur[g], eos_dev)
         for g in range(G):
             force(g)
+            walk(g)
         done = [finished(g) for g in range(G)]
         final_n = [n_new[g] if done[g] else None for g in range(G)]
         # ---- token loop ---------------------------------------------------------------------------------------------
@@ -335,7 +419,8 @@ class ContinuousLVLM:
                 break
             llm.decode_step(img_ids_dev, out_ids, hid, use_graph=self.use_graph, sampling=ss,   # one token for every sequence
                             **(dict(logprobs=lps) if lps is not None else {}),
-                            **(dict(controls=cs, eos_id=eos_dev) if cs is not None else {}))
+                            **(dict(controls=cs, eos_id=eos_dev) if cs is not None else {}),
+                            **(dict(grammar=gs) if gs is not None else {}))
             cur = P["cur"].tolist()                                                          # the only read-back per step
             llm.comm.check()                              # (tensor-parallel only: + 4 bytes) a timed-out collective must not pass
             for g in range(G):
@@ -343,6 +428,7 @@ class ContinuousLVLM:
                     continue
                 n_new[g] += 1
                 force(g)
+                walk(g)
                 if finished(g):
                     done[g], final_n[g] = True, n_new[g]
 
@@ -361,6 +447,8 @@ class ContinuousLVLM:
                                                           lps.top[g, :n].cpu(), asks[g])
             if ctls[g] is not None:
                 results[-1]['controls'] = ctls[g].as_dict()
+            if fsms[g] is not None:
+                results[-1]['grammar'] = self._grammar_result(fsms[g], gnames[g], generate_ids.tolist(), eos_dev)
         return results
 
     @staticmethod
@@ -462,9 +550,18 @@ class ContinuousLVLM:
         controlled token step (sx_next_slots_ctl) on a slot state of its own — parameters, prompt marks and zeroed counts are written
         per slot at admission, slots whose request carries none run as ever — and a queue without one takes the states and graphs it
         always took. The ids depend on the request alone, never on its slot or its neighbours. ValueError with ``agent.speculative``
-        (follow-up: counts that advance with the accepted run) and with ``force_image_at`` on the same request (follow-up)."""
+        (follow-up: counts that advance with the accepted run) and with ``force_image_at`` on the same request (follow-up).
+        A request may carry ``"grammar": name`` as in generate_batch (its result gains ``'grammar'``): a queue with at least one such
+        request runs the constrained token step (sx_next_slots_fsm) on a slot state of its own — table index and state 0 are written
+        per slot at admission, the device advances the state, and a slot whose automaton finishes parks itself like one that met EOS
+        — and a queue without one takes the states and graphs it always took. The ids depend on the request alone. The refusals are
+        generate_batch's, plus ``agent.speculative`` (follow-up)."""
         llm = self.llm
         requests = list(requests)
+        gnames = self._grammar_names("generate_inflight", requests, [req.get("force_image_at") is not None for req in requests])
+        constrained = any(n is not None for n in gnames)
+        if constrained:
+            self._grammar_prompts("generate_inflight", tokenizer, requests, gnames, self._special_ids(tokenizer, num_img_gen_tokens, None)[0])
         asks = [logprobs_from_request(req) for req in requests]
         ctls = [ControlParams.from_request(req) for req in requests]
         controlled = any(c is not None for c in ctls)
@@ -500,6 +597,7 @@ class ContinuousLVLM:
         P = llm._pack()
         img_ids, boi_id, eoi_id, eos_token_id = self._special_ids(tokenizer, num_img_gen_tokens, eos_token_id)
         eos = -1 if eos_token_id is None else int(eos_token_id)
+        fsms = [llm.grammar(n) if n is not None else None for n in gnames]
         nchunk = num_img_gen_tokens + 1
         budget = [int(req.get("max_new_tokens") or max_new_tokens) for req in requests]
         force_at = [-1 if req.get("force_image_at") is None else int(req["force_image_at"]) for req in requests]
@@ -550,12 +648,20 @@ class ContinuousLVLM:
             which += f"_lp{n_top}"
         if controlled:                                         # ... and one more of each for the controlled step
             which += "_ctl"
+        if constrained:                                        # ... and for the constrained step
+            which += "_fsm"
         if keep.get(which) is None:
             keep[which] = owned(lambda: llm.slot_state(force_id=boi_id, eos_id=eos, sampling=sampled, logprobs=n_top,
-                                                       **(dict(controls=True) if controlled else {})))
+                                                       **(dict(controls=True) if controlled else {}),
+                                                       **(dict(grammar=True) if constrained else {})))
         st, img_ids_dev, out_ids, hid = keep[which], keep["img_ids_dev"], keep["out_ids"], keep["hid"]
         lps = st.logprobs
         cs = st.controls
+        gs = st.grammar
+        gfin = set()                                     # slots whose automaton finished on the prefill's first token
+        if gs is not None:
+            gs.table.fill_(-1)
+            gs.state.fill_(DONE)
         if cs is not None:
             cs.on.zero_()
         if lps is not None:
@@ -604,11 +710,14 @@ class ContinuousLVLM:
                                                          lps.top[g, :n].cpu(), asks[r])
             if ctls[r] is not None:
                 results[r]['controls'] = ctls[r].as_dict()
+            if fsms[r] is not None:
+                results[r]['grammar'] = self._grammar_result(fsms[r], gnames[r], generate_ids.tolist(), eos)
+            gfin.discard(g)
             if on_result is not None:
                 on_result(r, results[r])
 
         def stopped(g):
-            return n_new[g] >= budget[sched.slot_req[g]] or (eos >= 0 and cur[g] == eos)
+            return n_new[g] >= budget[sched.slot_req[g]] or (eos >= 0 and cur[g] == eos) or g in gfin
 
         def admit_round(adm, starts=None):
             # ONE batched prefill over the admitted slots; token 1 of each comes from it (host-side stop test: not in the graph).
@@ -638,13 +747,20 @@ class ContinuousLVLM:
                 st.sampling.set_rows(slots, [params[r] for _, r in adm])
             if cs is not None:                           # the slots take their requests' controls: parameters, prompt marks, zero counts
                 cs.set_rows(slots, [ctls[r] for _, r in adm], pids)
+            part = None
+            if gs is not None:                           # the slots take their requests' grammars: table index, state 0
+                gs.set_rows(slots, [gnames[r] for _, r in adm])
+                part = gs.gather(slots)
             if lps is not None:                          # the first record: the LP lock-step tail on the prefill's logits, one row per slot
                 wants = [int(asks[r] is not None) for _, r in adm]
                 llm._slot_write(lps.want, slots, wants)
                 rec = LogprobState(len(slots), n_top, dev, rows=1)
                 rec.want.copy_(torch.tensor(wants, dtype=torch.int32))
                 zero = torch.zeros(len(slots), dtype=torch.int32, device=dev)
-                if cs is not None:                       # ... of the raw row, the id from the controlled one
+                if gs is not None:                       # ... of the raw row, the id from the constrained one
+                    ops.next_b_fsm(logits.contiguous(), llm.V, img_ids_dev, first, None, zero, cs.gather(slots), part,
+                                   sample=st.sampling.gather(slots) if sampled else None, lp=rec, token_index=zero, eos_id=eos)
+                elif cs is not None:                     # ... of the raw row, the id from the controlled one
                     ops.next_b_ctl(logits.contiguous(), llm.V, img_ids_dev, first, None, zero, cs.gather(slots),
                                    sample=st.sampling.gather(slots) if sampled else None, lp=rec, token_index=zero, eos_id=eos)
                 else:
@@ -655,6 +771,10 @@ class ContinuousLVLM:
                 for i, (g, r) in enumerate(adm):
                     if force_at[r] == 0 and wants[i]:
                         lps.forced(g, 0, 1)              # (synthetic weights) the id is replaced below: the model did not choose it
+            elif gs is not None:                         # token index 0 through sx_next_b_fsm, like every later one
+                zero = torch.zeros(len(slots), dtype=torch.int32, device=dev)
+                ops.next_b_fsm(logits.contiguous(), llm.V, img_ids_dev, first, None, zero, cs.gather(slots), part,
+                               sample=st.sampling.gather(slots) if sampled else None, token_index=zero, eos_id=eos)
             elif cs is not None:                         # token index 0 by the same rule, on a copy of the slots' rows of the state
                 zero = torch.zeros(len(slots), dtype=torch.int32, device=dev)
                 ops.next_b_ctl(logits.contiguous(), llm.V, img_ids_dev, first, None, zero, cs.gather(slots),
@@ -665,6 +785,9 @@ class ContinuousLVLM:
             else:
                 ops.greedy_next_b(logits.contiguous(), llm.V, img_ids_dev, first, None, None)
             first = first.tolist()
+            if gs is not None:                           # the advanced states go to the slots; an automaton may be done already
+                gs.scatter(slots, part)
+                gfin.update(g for (g, r), s in zip(adm, part.state.tolist()) if fsms[r] is not None and s < 0)
             llm.comm.check()
             stats["admissions"] += len(adm)
             stats["prefill_passes"] += 1
@@ -848,7 +971,7 @@ class ContinuousLVLM:
                  max_new_tokens=120, top_p=0.5, dtype=torch.float16, device='cuda', patch_positions=None,
                  eos_token_id="auto", force_image_at=None, reuse_cache=False, do_sample=False, top_k=50, seed=None, adapter=None,
                  logprobs=None, repetition_penalty=None, presence_penalty=None, frequency_penalty=None, logit_bias=None,
-                 min_new_tokens=None):
+                 min_new_tokens=None, grammar=None):
         """Reference signature (seed_x.py:130-145). Greedy by default (do_sample=False, num_beams=1 — temperature/top_p are inert
         in the reference too, :175-189). ``do_sample=True`` makes ``temperature`` / ``top_p`` live (defaults: the reference's 0.7 /
         0.5) together with ``top_k`` (50, transformers' generation default) and ``seed`` (None: 64 bits from os.urandom): the seeded
@@ -859,7 +982,8 @@ class ContinuousLVLM:
         (generate_batch: per generated id its log-probability under the raw distribution and the N most likely ids).
         ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` / ``logit_bias`` / ``min_new_tokens``: the device-side
         logits controls of generate_batch (what a reference user passes through ``logits_processor`` / ``generation_config``; a
-        host-supplied processor list itself stays refused); the result then carries ``'controls'``."""
+        host-supplied processor list itself stays refused); the result then carries ``'controls'``. ``grammar``: name of a token
+        automaton resident on the LLM (``llm.load_grammar``) that constrains the ids (generate_batch); the result carries ``'grammar'``."""
         assert logits_processor is None, "the AutoImageTokenGenerationProcessor rule is fused on the device"
         assert num_beams == 1
         assert self.llm.G == 1, "this LLM was built for lock-step batches: use generate_batch()"
@@ -873,5 +997,7 @@ class ContinuousLVLM:
             req["adapter"] = adapter
         req.update(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty,
                    logit_bias=logit_bias, min_new_tokens=min_new_tokens)
+        if grammar is not None:
+            req["grammar"] = grammar
         return self.generate_batch(tokenizer, [req], num_img_gen_tokens, max_new_tokens, eos_token_id, force_image_at,
                                    reuse_cache)[0]
