@@ -801,7 +801,8 @@ int sx_nhwc_to_nchw(const float* src, int ld, float* dst, int B, int C, int HW, 
 int sx_add_i32(int32_t* p, int delta, void* stream);
 /* profiling hook: one empty dispatch of `profile_marker_kernel` (tools/kstats_step.py cuts a rocprofv3 kernel trace at these) */
 int sx_profile_marker(int tag, void* stream);
-/* y = silu(x) as 16-bit (ResnetBlock2D.time_emb_proj input: nonlinearity(temb), diffusers [ext]) */
+/* y = silu(x) as 16-bit (ResnetBlock2D.time_emb_proj input: nonlinearity(temb), diffusers [ext]); the exponential and the quotient are
+ * taken in fp64 and rounded once, so the result holds down to the smallest normal of the output type; n = 0 is SX_OK, like sx_cast */
 int sx_silu_cast(const float* x, void* y, int dtype, int64_t n, void* stream);
 
 /* Fused classifier-free guidance + Euler step on fp32 latents (NHWC [1][HW][C], n = HW*C; eps [nb][HW][C]).

@@ -315,12 +315,17 @@ extern "C" int sx_profile_marker(int tag, void* stream) {
 __global__ void silu_cast_kernel(const float* x, void* y, int dt, int64_t n) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float v = silu_f(x[i]);
+    // silu_f's x / (1 + e) is x * rcp(1 + e) under -ffast-math, and v_rcp_f32 flushes a subnormal reciprocal: silu(-88) = -5.3e-37, a
+    // normal bf16, came out as -0 (and __expf(-x) is inf from 88.7 on, where silu is still -2.6e-37). In fp64 the exponential and the
+    // quotient have the range; n is 1280 per image, so the cost does not show.
+    const double xv = (double)x[i];
+    const float v = (float)(xv / (1.0 + exp(-xv)));
     ((unsigned short*)y)[i] = dt == SX_BF16 ? BF16::from_f32(v) : F16::from_f32(v);
   }
 }
 extern "C" int sx_silu_cast(const float* x, void* y, int dtype, int64_t n, void* stream) {
-  SX_CHECK(x && y && (dtype == SX_F16 || dtype == SX_BF16), "sx_silu_cast: bad args");
+  SX_CHECK(x && y && n >= 0 && (dtype == SX_F16 || dtype == SX_BF16), "sx_silu_cast: bad args");
+  if (n == 0) return SX_OK;               // like sx_cast: an empty tensor is no error (a grid of 0 blocks is one)
   hipLaunchKernelGGL(silu_cast_kernel, dim3((unsigned)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256)), dim3(256), 0,
                      ST, x, y, dtype, n);
   SX_HIP_LAUNCH_CHECK();

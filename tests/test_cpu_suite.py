@@ -1347,3 +1347,149 @@ def test_llm_mode_selection_and_memory_footprint(monkeypatch):
     assert m.memory_footprint()["kv_cache"] == 40 * 16 * 40 * 1024 * 128 * 6
     plain = LlamaForCausalLM(dict(cfg), max_cache_len=1024, max_batch=4, precise=False)
     assert plain.memory_footprint()["decode_tiles"] == 0 and plain.memory_footprint()["kv_cache"] == 40 * 4 * 40 * 1024 * 128 * 4
+
+
+def test_glue_matrix_covers_every_launched_kernel():
+    """tests/test_glue_matrix_gpu.py's case tables reach every (kernel, template arguments) that a hipLaunchKernelGGL of elementwise.hip and
+    preproc.hip launches and those of the glue kernels of decode.hip (rope_kv_append, embedding, scatter_rows, _step, _spec), parsed from the
+    sources: the bf16 and fp16 forms of patchify, im2col3x3, embedding and rope_kv_append, the C = 1 and C = 3 forms of both resample passes.
+    profile_marker_kernel (an empty named dispatch) is the one listed exception. The tables hold the cases the matrix was specified with."""
+    from tests import test_glue_matrix_gpu as gm
+    kernels, cap = gm.source_kernels()
+    assert set(gm.COVERED_ELSEWHERE) == {"profile_marker_kernel"}
+    want = {k for k in kernels if k[0] not in gm.COVERED_ELSEWHERE}
+    got = gm.reached()
+    assert got == want, sorted(got ^ want)
+    assert len(want) == 31 and {k for k in want if k[1]} == {(n, t) for n in ("patchify_kernel", "im2col3x3_kernel", "embedding_kernel", "rope_kv_append_kernel")
+                                                              for t in ("F16", "BF16")} | {(n, t) for n in ("resample_h_kernel", "resample_v_kernel") for t in ("1", "3")}
+    ids = [c["id"] for t in gm.TABLES.values() for c in t]
+    assert len(ids) == len(set(ids))
+    T = gm.TABLES
+    assert {(c["s"], c["d"]) for c in T["CAST"]} == {(s, d) for s in ("f32", "f16", "bf16") for d in ("f32", "f16", "bf16")}
+    assert {c["n"] for c in T["CAST"]} == {1, 3, 4, 5, 1001, 4 * 1048576 + 259}
+    assert {(c["role"], c["rows"], c["cols"]) for c in T["SPLIT"]} >= {(r, a, b) for r in (0, 1) for a, b in ((1, 4), (7, 12), (3, 1000))}
+    assert {c["cols"] for c in T["COPY2D"]} == {4, 64, 1000} and 0 in {c["rows"] for c in T["COPY2D"]} and {c["n"] for c in T["ADD"]} == {1, 257, 1048576 + 257}
+    for tab in ("PATCHIFY", "IM2COL", "EMBED", "ROPE", "SILU"):
+        assert {c["dt"] for c in T[tab]} == {"f16", "bf16"}, tab
+    assert {(c["B"], c["S"], c["P"], c["Kpad"]) for c in T["PATCHIFY"]} == {(1, 14, 14, 588), (2, 28, 14, 640), (1, 6, 2, 16), (3, 448, 14, 640)}
+    assert {(c["B"], c["H"], c["W"], c["Cin"], c["Kpad"]) for c in T["IM2COL"]} >= {(1, 1, 1, 4, 64), (2, 5, 4, 6, 64), (1, 3, 7, 8, 72)}
+    assert {(c["C"], c["HW"]) for c in T["LAYOUT"]} >= {(a, b) for a in (4, 8, 5) for b in (1, 64, 1000)}
+    small = [c for c in T["HALO"] if not c["cap"]]
+    assert {(c["B"], c["Hl"], c["W"], c["C"], c["prev"], c["next"], c["left"], c["bottom"]) for c in small} == \
+        {(B, Hl, W, C_, p, n, l, b) for B, Hl, W in ((1, 1, 1), (2, 3, 5)) for C_ in (8, 24) for p in (False, True) for n in (False, True) for l in (0, 1) for b in (0, 1)}
+    big = T["HALO"][-1]
+    assert big["C"] == 8 and big["W"] + big["left"] == 4096 and big["Hl"] + 1 + big["bottom"] == 4097
+    assert {c["n"] for c in T["ADD_I32"]} == {1, 5, 64} and {c["dim"] for c in T["EMBED"]} == {8, 64, 5120} and 0 in {c["n"] for c in T["SCATTER"]}
+    assert {c["T"] for c in T["MARKER"]} == {1, 255, 256, 257, 4097} and {c["C"] for c in T["RESAMPLE"]} == {1, 3}
+    r1 = [c for c in T["RESAMPLE"] if c["C"] == 1]
+    assert any(c["Hout"] == c["Hin"] for c in r1) and any(c["Wout"] == c["Win"] for c in r1) and any((c["Hin"], c["Win"]) == (10, 10) and c["cap"] for c in r1)
+    assert {(c["k"], c["B"], c["L"], c["D"]) for c in T["AVGPOOL"]} == {(k, B, L, D) for k in (1, 4, 64) for B, L, D in ((1, 4, 1), (2, 256, 96), (1, 64, 5120)) if L % k == 0}
+    assert {c["n"] for c in T["SILU"]} == {1, 1280, 1048576 + 257} and {(c["B"], c["T"], c["D"]) for c in T["L2NORM"]} >= {(1, 1, 1), (3, 24, 256), (2, 64, 4097)}
+    for dt in ("f16", "bf16"):
+        R = [c for c in T["ROPE"] if c["dt"] == dt]
+        assert {c["D"] for c in R} == {64, 128, 112} and {c["G"] for c in R} == {1, 3} and {c["T"] for c in R if not c["cap"]} == {1, 5}
+        assert {p for c in R if not c["cap"] for p in c["pos"]} == {0, 7, gm.ROPE_TMAX - 1, gm.ROPE_TMAX - 2, -1}
+        assert any(c["T"] == 5 and gm.ROPE_TMAX - 2 in c["pos"] for c in R) and {c["b"] for c in R} == {True, False} and all(c["pad"] > 0 for c in R if c["b"])
+        # every position is a table row or one that the contract drops; none is further out than the rows of one launch
+        assert all(-1 <= p and p + c["T"] <= c["Tmax"] + c["T"] for c in R for p in c["pos"])
+    assert {(c["mode"], c["ld"], c["scaled"]) for c in T["EULER"]} == {(m, ld, s) for m in (0, 1) for ld, s in ((4, True), (8, True), (4, False))}
+    assert all(c["HW"] * c["C"] == 2 * 64 * 4 for c in T["EULER"])
+    assert {(c["o"], c["dim"], c["idx"]) for c in T["TSEMB"]} == {(o, d, i) for o in ("f32", "f16", "bf16") for d in (2, 256, 320) for i in (None, 0, 3, 6)}
+    assert gm.TS_T == (0.0, 1.0, 20.5, 448.0, 981.0, 999.0, 1024.0) and all(c["idx"] is None or 0 <= c["idx"] < len(gm.TS_T) for c in T["TSEMB"])
+
+
+def test_glue_matrix_cap_cases_exceed_the_parsed_grid_caps():
+    """Every 'past the cap' case of tests/test_glue_matrix_gpu.py against the caps parsed from grid_for (elementwise.hip, preproc.hip), gs_grid
+    (decode.hip), sx_silu_cast and sx_halo_pack: a changed cap cannot silently turn them into single-trip cases. Every capped kernel has one."""
+    from tests import test_glue_matrix_gpu as gm
+    _, cap = gm.source_kernels()
+    assert cap == dict(elementwise=4096 * 256, preproc=8192 * 256, decode=4096 * 256, silu_cast=4096 * 256, halo_pack=65536 * 256)
+    cases = gm.cap_cases()
+    for table, cid, which, trips in cases:
+        assert trips > cap[which], (table, cid, trips, cap[which])
+        assert trips < 2 * cap[which] or table == "CAST", (table, cid, "more than two trips: a smaller case would do")
+    assert {t for t, _, _, _ in cases} == set(gm.CAP_OF), set(gm.CAP_OF) - {t for t, _, _, _ in cases}
+    big = [c for c in gm.TABLES["HALO"] if c["cap"]]
+    assert len(big) == 1 and big[0]["cap"] == big[0]["B"] * (big[0]["Hl"] + 1 + big[0]["bottom"]) * (big[0]["W"] + big[0]["left"]) * (big[0]["C"] // 8) > 16777216
+
+
+def test_glue_matrix_references_against_independent_statements():
+    """The references of tests/test_glue_matrix_gpu.py on the CPU against independent statements of the same operation: the unfold-based patchify /
+    im2col against the index formulas of the kernels' comments, the fp64 timestep embedding against oracle.restated_unet.timestep_embedding, the two
+    Euler modes against oracle.restated_unet.t2i_loop / edit_loop driven by a stub UNet that returns preset eps, l2norm against F.normalize and the
+    token pooling against F.avg_pool1d."""
+    import torch.nn.functional as F
+    from tests import test_glue_matrix_gpu as gm
+    g = torch.Generator().manual_seed(11)
+    # patchify: k = c P P + py P + px of patch (gy, gx)
+    B, S, P, Kpad = 2, 6, 2, 16
+    img = torch.randn(B, 3, S, S, generator=g)
+    ref = gm.patchify_ref(img, P, Kpad, torch.float32)
+    G = S // P
+    for b in range(B):
+        for gy in range(G):
+            for gx in range(G):
+                row = ref[(b * G + gy) * G + gx]
+                assert torch.equal(row[:12], img[b, :, gy * P:(gy + 1) * P, gx * P:(gx + 1) * P].reshape(-1)) and torch.equal(row[12:], torch.zeros(4))
+    # im2col: k = (ky 3 + kx) Cin + c, zeros outside the image
+    B, H, W, Cin, Kpad = 2, 3, 4, 5, 48
+    x = torch.randn(B, H, W, Cin, generator=g)
+    ref = gm.im2col_ref(x, Kpad, torch.float32)
+    for b in range(B):
+        for oy in range(H):
+            for ox in range(W):
+                row = ref[(b * H + oy) * W + ox]
+                for tap in range(9):
+                    iy, ix = oy + tap // 3 - 1, ox + tap % 3 - 1
+                    want = x[b, iy, ix] if 0 <= iy < H and 0 <= ix < W else torch.zeros(Cin)
+                    assert torch.equal(row[tap * Cin:(tap + 1) * Cin], want)
+                assert torch.equal(row[9 * Cin:], torch.zeros(Kpad - 9 * Cin))
+    one = gm.im2col_ref(torch.ones(1, 1, 1, 4), 64, torch.float32)
+    assert int((one != 0).sum()) == 4 and torch.equal(one[0, 16:20], torch.ones(4))
+    # timestep embedding: the fp32 restatement sits E32 units from the fp64 reference, a handful
+    t = torch.tensor(gm.TS_T)
+    for dim in (2, 256, 320):
+        r, arg = gm.tsemb_ref(t, dim)
+        assert r.dtype == torch.float64 and torch.allclose(r.float(), ru.timestep_embedding(t, dim), atol=2e-4, rtol=0)
+        e32 = gm.tsemb_e32(dim)
+        assert 0.0 < e32 < 16.0, (dim, e32)
+    # Euler: three steps of the loops of the reference pipelines with preset eps
+    n, steps = 4 * 8 * 8, 3
+    _, sig, init = ru.euler_tables(steps)
+    lat0 = torch.randn(1, 4, 8, 8, generator=g) * init
+    dummy = torch.zeros(1, 2, 4)
+    for mode, nb in ((0, 2), (1, 3)):
+        eps = torch.randn(steps, nb, 4, 8, 8, generator=g)
+        calls = iter(range(steps))
+        stub = lambda inp, ts, ehs, te, tid: eps[next(calls)]
+        if mode == 0:
+            want = ru.t2i_loop(stub, lat0, dummy, dummy, dummy, dummy, dummy, steps, guidance_scale=gm.GS)
+        else:
+            want = ru.edit_loop(stub, lat0, torch.zeros(3, 4, 8, 8), dummy, dummy, dummy, dummy, dummy, steps, guidance_scale=gm.GS, image_guidance_scale=gm.IGS)
+        x = lat0.reshape(-1).double()
+        for i in range(steps):
+            x, bound, xs, sbound = gm.euler_ref(mode, x, eps[i].reshape(nb, n), float(sig[i]), float(sig[i + 1]), gm.GS, gm.IGS)
+            assert bool((bound > 0).all()) and torch.allclose(xs, x / math.sqrt(float(sig[i + 1]) ** 2 + 1.0), rtol=1e-14, atol=0)
+        assert torch.allclose(x.float(), want.reshape(-1), rtol=2e-4, atol=2e-4), (mode, float((x.float() - want.reshape(-1)).abs().max()))
+    assert gm.c1_euler(7.5, 1.5) == 40.0 and gm.c1_euler(0.0, 0.0) == 13.0
+    # l2norm and token pooling
+    x = torch.randn(3, 24, 16, generator=g)
+    x[1, :, 7] = 0
+    ref, bound = gm.l2norm_ref(x, 1e-12)
+    assert torch.allclose(ref, F.normalize(x.double(), dim=1), rtol=1e-14, atol=0) and bool((ref[1, :, 7] == 0).all())
+    x = torch.randn(2, 64, 12, generator=g)
+    for k in (1, 4, 64):
+        ref, bound = gm.avgpool_ref(x, k)
+        assert torch.allclose(ref, F.avg_pool1d(x.double().transpose(1, 2), k).transpose(1, 2), rtol=1e-14, atol=1e-300)
+    # rope: against the complex rotation, from the tables rounded to the type
+    cos, sin = gm.rope_tables(16, 8, "cpu")
+    xq = torch.randn(5, 2, 8, generator=g).half()
+    rows = torch.tensor([0, 3, 15, 0, 7])
+    ref, bound = gm.rope_ref(xq, cos, sin, rows, torch.float16)
+    z = torch.complex(xq[..., :4].double(), xq[..., 4:].double()) * torch.complex(cos.half().double()[rows], sin.half().double()[rows])[:, None, :]
+    assert torch.allclose(ref, torch.cat([z.real, z.imag], -1), rtol=1e-14, atol=1e-300) and torch.equal(ref[0], xq[0].double())
+    # halo: borders
+    xh = torch.arange(2 * 3 * 5 * 8, dtype=torch.int16).view(2, 3, 5, 8) + 1
+    out = gm.halo_ref(xh, None, xh[:, 0] + 500, 1, 1)
+    assert out.shape == (2, 5, 6, 8) and int(out[:, 0].abs().sum()) == 0 and int(out[:, :, 0].abs().sum()) == 0 and torch.equal(out[:, 1:4, 1:], xh)
+    assert torch.equal(out[:, 4, 1:], xh[:, 0] + 500) and int(gm.halo_ref(xh, None, xh[:, 0], 0, 0).shape[1]) == 4
