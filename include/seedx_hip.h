@@ -541,6 +541,42 @@ int sx_next_b_fsm(float* logits, int ld_logits, int vocab, const int32_t* img_id
                   const sx_logits_ctl_args* ctl, const sx_token_fsm_args* fsm, void* stream);
 int sx_next_slots_fsm(const sx_slot_step_args* args, const sx_sample_args* sample, const sx_logprob_args* lp,
                       const sx_logits_ctl_args* ctl, const sx_token_fsm_args* fsm, void* stream);
+/* Sequence rules: stop sequences and no_repeat_ngram_size (seedx_amd.sampling states them in numpy: ngram_banned, apply_no_repeat,
+ * stop_match). They need the ORDER of the ids a request has seen: hist[g][0 .. hist_len[g]) holds its prompt ids (image placeholders
+ * included) followed by every id it emitted, prompt_len[g] of them the prompt. For a row with on[g] != 0, in this order:
+ *   ban:     with n = ngram[g] > 0 and L = hist_len[g] the row gets a working row in ctl->work (the controlled row when ctl->on[g] is
+ *            set, a plain copy otherwise) in which, for every i in [0, L - n] with hist[i .. i+n-1) == hist[L-n+1 .. L), column
+ *            hist[i+n-1] is -inf (ids outside [0, vocab) ban nothing but take part in the comparison); nothing else changes. The
+ *            grammar mask (fsm may be NULL), the processor rule and the arg-max or draw then run as in sx_next_b_fsm / sx_next_b_ctl;
+ *            the logits row stays raw, so the LP record describes the raw distribution. Inside the image chain the forced id wins;
+ *   append:  the id the row emits (slot form: behind the force_at replacement) goes to hist[g][hist_len[g]] and hist_len[g] += 1;
+ *            a history that is full (hist_len[g] == ld_hist) takes nothing more and matches nothing;
+ *   stop:    matched[g] = the lowest j < n_stop[g] for which the GENERATED ids (hist[prompt_len[g] .. hist_len[g])) end with
+ *            stop_ids[g][j][0 .. stop_len[g][j]), else -1. A stop that would straddle the end of the prompt does not match.
+ * In the slot form a match joins the stop rule: the slot parks itself exactly as on EOS or budget (same idle values, same status row);
+ * the matched ids stay in the id log. In the lock-step form matched is all that is written; the host cuts the request there.
+ * A row with on[g] == 0 and every parked slot: bit for bit sx_next_b_ctl / sx_next_slots_ctl (with fsm: the _fsm entry points), and its
+ * history, hist_len and matched are not touched. Per-row values out of range are clamped on the device (ngram to 0 .. 8, n_stop to
+ * 0 .. 4, stop_len to 1 .. 8, hist_len to 0 .. ld_hist): a wrong table gives wrong ids, never a wild address. ld_hist >= 1. */
+typedef struct sx_seq_rule_args {
+  const int32_t* on;            /* [G]: 0 = the row runs as without sequence rules                   */
+  const int32_t* ngram;         /* [G]: no_repeat_ngram_size, 0 = off, at most 8                     */
+  int32_t* hist;                /* [G][ld_hist]: prompt ids, then the emitted ids                    */
+  int32_t* hist_len;            /* [G]: in/out                                                       */
+  const int32_t* prompt_len;    /* [G]                                                               */
+  const int32_t* n_stop;        /* [G]: 0 .. 4                                                       */
+  const int32_t* stop_len;      /* [G][4]: 1 .. 8 for j < n_stop[g]                                  */
+  const int32_t* stop_ids;      /* [G][4][8]                                                         */
+  int32_t* matched;             /* [G]: out, index of the matched stop sequence or -1                */
+  int32_t ld_hist, reserved;
+} sx_seq_rule_args;
+/* sx_next_b_fsm's / sx_next_slots_fsm's arguments with fsm nullable, and the rules above; ctl and seq are required. */
+int sx_next_b_seq(float* logits, int ld_logits, int vocab, const int32_t* img_ids_dev, int n_img,
+                  const int32_t* prev_id_dev, int32_t* next_id_dev, int32_t* out_ids, int ld_out,
+                  const int32_t* step_dev, int G, const sx_sample_args* sample, const sx_logprob_args* lp,
+                  const sx_logits_ctl_args* ctl, const sx_token_fsm_args* fsm, const sx_seq_rule_args* seq, void* stream);
+int sx_next_slots_seq(const sx_slot_step_args* args, const sx_sample_args* sample, const sx_logprob_args* lp,
+                      const sx_logits_ctl_args* ctl, const sx_token_fsm_args* fsm, const sx_seq_rule_args* seq, void* stream);
 
 /* Speculative decoding (lossless): the token step carries T = K + 1 rows per slot — row g*T is the slot's current token, rows g*T + 1 ..
  * g*T + n_draft[g] K drafted continuations — and sx_greedy_next_b / sx_sample_next_b over the G*T rows (previous id = the row's input,

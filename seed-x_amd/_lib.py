@@ -95,6 +95,11 @@ class TokenFsmArgs(C.Structure):
                 ("ld_v", c_i32), ("eos_id", c_i32)]
 
 
+class SeqRuleArgs(C.Structure):
+    _fields_ = [("on", c_vp), ("ngram", c_vp), ("hist", c_vp), ("hist_len", c_vp), ("prompt_len", c_vp), ("n_stop", c_vp),
+                ("stop_len", c_vp), ("stop_ids", c_vp), ("matched", c_vp), ("ld_hist", c_i32), ("reserved", c_i32)]
+
+
 class SpecAcceptArgs(C.Structure):
     _fields_ = [("cand", c_vp), ("rows_in", c_vp), ("n_draft", c_vp), ("cur", c_vp), ("live", c_vp), ("n_new", c_vp), ("max_new", c_vp),
                 ("force_at", c_vp), ("pos", c_vp), ("ctx", c_vp), ("step", c_vp), ("out_ids", c_vp), ("status", c_vp), ("hist", c_vp),
@@ -188,6 +193,10 @@ SIGNATURES = {
                       C.POINTER(LogprobArgs), C.POINTER(LogitsCtlArgs), C.POINTER(TokenFsmArgs), c_vp],
     "sx_next_slots_fsm": [C.POINTER(SlotStepArgs), C.POINTER(SampleArgs), C.POINTER(LogprobArgs), C.POINTER(LogitsCtlArgs),
                           C.POINTER(TokenFsmArgs), c_vp],
+    "sx_next_b_seq": [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, C.POINTER(SampleArgs),
+                      C.POINTER(LogprobArgs), C.POINTER(LogitsCtlArgs), C.POINTER(TokenFsmArgs), C.POINTER(SeqRuleArgs), c_vp],
+    "sx_next_slots_seq": [C.POINTER(SlotStepArgs), C.POINTER(SampleArgs), C.POINTER(LogprobArgs), C.POINTER(LogitsCtlArgs),
+                          C.POINTER(TokenFsmArgs), C.POINTER(SeqRuleArgs), c_vp],
     "sx_spec_accept": [C.POINTER(SpecAcceptArgs), c_vp],
     "sx_spec_draft_ngram": [C.POINTER(SpecDraftArgs), c_vp],
     "sx_scatter_rows_spec": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp],

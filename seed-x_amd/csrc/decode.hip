@@ -1602,11 +1602,88 @@ __device__ __forceinline__ void fsm_mask_row(const float* src, float* work, cons
   __syncthreads();
 }
 
-template <bool SAMPLE, bool LP = false, bool CTL = false, bool FSM = false>
+// SEQ (on the CTL family only): per-request sequence rules that need the ORDER of the ids a request has seen (seedx_amd.sampling states
+// them: ngram_banned / apply_no_repeat / stop_match; include/seedx_hip.h sx_seq_rule_args). hist[g][0 .. hist_len[g]) is the request's
+// prompt followed by every id it emitted. A row with on[g] != 0 and ngram[g] = n > 0 gets a working row (the controlled one, or a plain
+// copy) in which every id that would complete an n-gram already in the history is -inf, ahead of the grammar mask and the image rule;
+// thread 0 appends the id the row emits and tests the stop sequences against the tail of the generated part; in the slot form a match
+// stops the slot. A row with on[g] == 0 and every parked slot: the CTL / FSM path, history and matched untouched.
+struct SeqP {
+  const int* on;
+  const int* ngram;
+  int* hist;
+  int* hist_len;
+  const int* prompt_len;
+  const int* n_stop;
+  const int* stop_len;
+  const int* stop_ids;
+  int* matched;
+  int ld_hist;
+};
+struct CtlSeqP : CtlP {
+  SeqP q;
+};
+struct CtlFsmSeqP : CtlFsmP {
+  SeqP q;
+};
+constexpr int SEQ_MAX_NGRAM = 8, SEQ_MAX_STOP = 4, SEQ_MAX_STOP_LEN = 8;
+
+// work[0..ld) = src[0..ld) (src may be work) with the columns banned by the history -inf. The tail hist[L-n+1 .. L) is staged once in
+// LDS; thread t takes the start positions t, t + 1024, ... of [0, L - n]: neighbouring threads read neighbouring ids. Several threads may
+// ban the same column: they store the same value. Ends behind a barrier.
+__device__ __forceinline__ void seq_ban_row(const float* src, float* work, const int* hist, int L, int n, int vocab, int ld) {
+  __shared__ int tail[SEQ_MAX_NGRAM];
+  if (src != work)
+    for (int i = threadIdx.x; i < ld; i += 1024) work[i] = src[i];
+  if ((int)threadIdx.x < n - 1 && L - n + 1 >= 0) tail[threadIdx.x] = hist[L - n + 1 + threadIdx.x];
+  __syncthreads();
+  for (int i = threadIdx.x; i <= L - n; i += 1024) {
+    bool same = true;
+    for (int j = 0; j < n - 1; ++j) same = same && hist[i + j] == tail[j];
+    if (same) {
+      const int id = hist[i + n - 1];
+      if (id >= 0 && id < vocab) work[id] = -INFINITY;
+    }
+  }
+  __syncthreads();
+}
+
+// thread 0, once the id the row emits is known: append it (bounded by ld_hist: a full history takes nothing more and matches nothing),
+// then the lowest stop sequence the generated ids end with, or -1
+__device__ __forceinline__ bool seq_append_match(const SeqP& q, int g, int id) {
+  int* hist = q.hist + (size_t)g * q.ld_hist;
+  int L = q.hist_len[g];
+  int m = -1;
+  if (L >= 0 && L < q.ld_hist) {
+    hist[L] = id;
+    L += 1;
+    q.hist_len[g] = L;
+    int pl = q.prompt_len[g];
+    pl = pl < 0 ? 0 : pl;
+    const int gen = L - pl;
+    int ns = q.n_stop[g];
+    ns = ns < 0 ? 0 : ns > SEQ_MAX_STOP ? SEQ_MAX_STOP : ns;
+    for (int j = 0; j < ns && m < 0; ++j) {
+      int sl = q.stop_len[(size_t)g * SEQ_MAX_STOP + j];
+      sl = sl < 1 ? 1 : sl > SEQ_MAX_STOP_LEN ? SEQ_MAX_STOP_LEN : sl;
+      if (sl > gen) continue;
+      const int* sid = q.stop_ids + ((size_t)g * SEQ_MAX_STOP + j) * SEQ_MAX_STOP_LEN;
+      bool same = true;
+      for (int k = 0; k < sl; ++k) same = same && hist[L - sl + k] == sid[k];
+      if (same) m = j;
+    }
+  }
+  q.matched[g] = m;
+  return m >= 0;
+}
+
+template <bool SAMPLE, bool LP = false, bool CTL = false, bool FSM = false, bool SEQ = false>
 __global__ __launch_bounds__(1024) void next_token_kernel(const TailP p, const std::conditional_t<SAMPLE, SampleP, NoSampleP> s,
                                                           const std::conditional_t<LP, LogprobP, NoLogprobP> lp,
-                                                          const std::conditional_t<FSM, CtlFsmP, std::conditional_t<CTL, CtlP, NoCtlP>> c) {
+                                                          const std::conditional_t<SEQ, std::conditional_t<FSM, CtlFsmSeqP, CtlSeqP>,
+                                                                                   std::conditional_t<FSM, CtlFsmP, std::conditional_t<CTL, CtlP, NoCtlP>>> c) {
   static_assert(CTL || !FSM, "the FSM form lives on the CTL family: the controls carry the working rows");
+  static_assert(CTL || !SEQ, "the SEQ form lives on the CTL family too");
   const int g = blockIdx.x;
   const bool slots = p.live != nullptr;
   if (slots && p.live[g] == 0) return;              // parked (uniform over the workgroup: no barrier is skipped by a part of it)
@@ -1621,6 +1698,20 @@ __global__ __launch_bounds__(1024) void next_token_kernel(const TailP p, const s
       float* work = c.work + (size_t)g * p.ld_logits;
       ctl_edit_row(row, work, c, g, p.vocab, p.ld_logits, slots ? p.eos_id : c.eos_id, k);
       row = work;
+    }
+  }
+  [[maybe_unused]] bool seq_on = false;
+  if constexpr (SEQ) {
+    seq_on = c.q.on[g] != 0;                        // (uniform over the workgroup)
+    if (seq_on) {
+      int n = c.q.ngram[g], L = c.q.hist_len[g];    // (hist and hist_len are rewritten by thread 0 behind the id functions' barriers)
+      n = n < 0 ? 0 : n > SEQ_MAX_NGRAM ? SEQ_MAX_NGRAM : n;
+      L = L < 0 ? 0 : L > c.q.ld_hist ? c.q.ld_hist : L;
+      if (n > 0) {
+        float* work = c.work + (size_t)g * p.ld_logits;
+        seq_ban_row(row, work, c.q.hist + (size_t)g * c.q.ld_hist, L, n, p.vocab, p.ld_logits);
+        row = work;
+      }
     }
   }
   [[maybe_unused]] bool fsm_on = false;
@@ -1704,7 +1795,16 @@ __global__ __launch_bounds__(1024) void next_token_kernel(const TailP p, const s
       fsm_stop = ns < 0;
     }
   }
-  if constexpr (FSM) {
+  if constexpr (SEQ) {
+    bool seq_stop = false;
+    if (seq_on) {                                   // the id the row EMITS goes to the history, then the stop sequences
+      int id = result;
+      if (slots && p.force_at[g] >= 0 && p.n_new[g] == p.force_at[g]) id = p.force_id;
+      seq_stop = seq_append_match(c.q, g, id);
+    }
+    if (slots) slot_advance<true>(p, g, result, fsm_stop || seq_stop);
+    else lockstep_store(p, g, result);
+  } else if constexpr (FSM) {
     if (slots) slot_advance<true>(p, g, result, fsm_stop);
     else lockstep_store(p, g, result);
   } else {
@@ -2016,14 +2116,15 @@ static TailP slot_tail(const sx_slot_step_args* a) {
                a->live, a->n_new, a->max_new, a->force_at, a->pos, a->ctx, a->status, a->force_id, a->eos_id};
 }
 
-// The one launcher behind the eleven entry points. slots: the in-flight form (every pointer but out_ids is required, ld_out is the row
+// The one launcher behind the thirteen entry points. slots: the in-flight form (every pointer but out_ids is required, ld_out is the row
 // capacity), else the lock-step form. sampled: the entry point takes a sx_sample_args, which must then be there. lp: the LP form
 // (sx_sample_next_b_lp / sx_sample_next_slots_lp); NULL launches exactly what the five older entry points always launched. ctl: the
 // controlled forms (sx_next_b_ctl / sx_next_slots_ctl), any of the four combinations of sample and lp. fsm: the constrained forms
-// (sx_next_b_fsm / sx_next_slots_fsm), on top of ctl.
+// (sx_next_b_fsm / sx_next_slots_fsm), on top of ctl. seq: the sequence-rule forms (sx_next_b_seq / sx_next_slots_seq), on top of ctl, with
+// or without fsm.
 static int launch_next_token(const char* who, const TailP& p, bool slots, const sx_sample_args* sample, bool sampled, void* stream,
                              const sx_logprob_args* lp = nullptr, const sx_logits_ctl_args* ctl = nullptr,
-                             const sx_token_fsm_args* fsm = nullptr) {
+                             const sx_token_fsm_args* fsm = nullptr, const sx_seq_rule_args* seq = nullptr) {
   SX_CHECK(p.logits && p.img_ids && p.prev && p.next, "%s: null pointer", who);
   SX_CHECK(p.n_img >= 2 && p.n_img <= 1024 && p.G >= 1, "%s: n_img=%d G=%d", who, p.n_img, p.G);
   if (slots) {
@@ -2065,6 +2166,7 @@ static int launch_next_token(const char* who, const TailP& p, bool slots, const 
     SX_CHECK(ctl->eos_id >= -1 && ctl->eos_id < p.vocab, "%s: sx_logits_ctl_args.eos_id=%d", who, ctl->eos_id);
     const CtlP c{ctl->on, ctl->counts, ctl->work, ctl->rep, ctl->rep_inv, ctl->presence, ctl->frequency, ctl->min_new, ctl->bias_ids,
                  ctl->bias, ctl->token_index, ctl->ld_counts, ctl->eos_id};
+    CtlFsmP cf;
     if (fsm) {
       // the constrained forms: a table row is ld_v int16 wide and read two ids per dword up to vocab; table[g] and state[g] live on the
       // device and are range-checked by the kernel (a row outside [0, n_tables) x [0, n_states) runs unconstrained)
@@ -2074,9 +2176,12 @@ static int launch_next_token(const char* who, const TailP& p, bool slots, const 
       SX_CHECK(fsm->ld_v >= p.vocab && fsm->ld_v % 2 == 0 && ((uintptr_t)fsm->trans & 3) == 0,
                "%s: sx_token_fsm_args.ld_v=%d must be even and >= vocab=%d, trans 4-byte aligned", who, fsm->ld_v, p.vocab);
       SX_CHECK(fsm->eos_id >= -1 && fsm->eos_id < p.vocab, "%s: sx_token_fsm_args.eos_id=%d", who, fsm->eos_id);
-      CtlFsmP cf;
       static_cast<CtlP&>(cf) = c;
       cf.f = FsmP{fsm->table, fsm->state, fsm->trans, fsm->flags, fsm->n_tables, fsm->n_states, fsm->ld_v, fsm->eos_id};
+    }
+    if (seq) {
+      // (the sequence-rule forms are launched at the end, behind every older instantiation)
+    } else if (fsm) {
       if (sampled && lp) hipLaunchKernelGGL((next_token_kernel<true, true, true, true>), dim3(p.G), dim3(1024), 0, ST, p, s, l, cf);
       else if (sampled) hipLaunchKernelGGL((next_token_kernel<true, false, true, true>), dim3(p.G), dim3(1024), 0, ST, p, s, NoLogprobP{}, cf);
       else if (lp) hipLaunchKernelGGL((next_token_kernel<false, true, true, true>), dim3(p.G), dim3(1024), 0, ST, p, NoSampleP{}, l, cf);
@@ -2085,6 +2190,32 @@ static int launch_next_token(const char* who, const TailP& p, bool slots, const 
     else if (sampled) hipLaunchKernelGGL((next_token_kernel<true, false, true>), dim3(p.G), dim3(1024), 0, ST, p, s, NoLogprobP{}, c);
     else if (lp) hipLaunchKernelGGL((next_token_kernel<false, true, true>), dim3(p.G), dim3(1024), 0, ST, p, NoSampleP{}, l, c);
     else hipLaunchKernelGGL((next_token_kernel<false, false, true>), dim3(p.G), dim3(1024), 0, ST, p, NoSampleP{}, NoLogprobP{}, c);
+    if (seq) {
+      // the sequence-rule forms: a history row is ld_hist ids wide and never read or written past it; ngram[g], n_stop[g] and
+      // stop_len[g][j] live on the device and are clamped by the kernel (a wrong table gives wrong ids, never a wild address)
+      SX_CHECK(seq->on && seq->ngram && seq->hist && seq->hist_len && seq->prompt_len && seq->n_stop && seq->stop_len && seq->stop_ids &&
+                   seq->matched, "%s: null pointer in sx_seq_rule_args", who);
+      SX_CHECK(seq->ld_hist >= 1, "%s: sx_seq_rule_args.ld_hist=%d (>= 1)", who, seq->ld_hist);
+      const SeqP q{seq->on, seq->ngram, seq->hist, seq->hist_len, seq->prompt_len, seq->n_stop, seq->stop_len, seq->stop_ids, seq->matched,
+                   seq->ld_hist};
+      if (fsm) {
+        CtlFsmSeqP cq;
+        static_cast<CtlFsmP&>(cq) = cf;
+        cq.q = q;
+        if (sampled && lp) hipLaunchKernelGGL((next_token_kernel<true, true, true, true, true>), dim3(p.G), dim3(1024), 0, ST, p, s, l, cq);
+        else if (sampled) hipLaunchKernelGGL((next_token_kernel<true, false, true, true, true>), dim3(p.G), dim3(1024), 0, ST, p, s, NoLogprobP{}, cq);
+        else if (lp) hipLaunchKernelGGL((next_token_kernel<false, true, true, true, true>), dim3(p.G), dim3(1024), 0, ST, p, NoSampleP{}, l, cq);
+        else hipLaunchKernelGGL((next_token_kernel<false, false, true, true, true>), dim3(p.G), dim3(1024), 0, ST, p, NoSampleP{}, NoLogprobP{}, cq);
+      } else {
+        CtlSeqP cq;
+        static_cast<CtlP&>(cq) = c;
+        cq.q = q;
+        if (sampled && lp) hipLaunchKernelGGL((next_token_kernel<true, true, true, false, true>), dim3(p.G), dim3(1024), 0, ST, p, s, l, cq);
+        else if (sampled) hipLaunchKernelGGL((next_token_kernel<true, false, true, false, true>), dim3(p.G), dim3(1024), 0, ST, p, s, NoLogprobP{}, cq);
+        else if (lp) hipLaunchKernelGGL((next_token_kernel<false, true, true, false, true>), dim3(p.G), dim3(1024), 0, ST, p, NoSampleP{}, l, cq);
+        else hipLaunchKernelGGL((next_token_kernel<false, false, true, false, true>), dim3(p.G), dim3(1024), 0, ST, p, NoSampleP{}, NoLogprobP{}, cq);
+      }
+    }
   }
   SX_HIP_LAUNCH_CHECK();
   return SX_OK;
@@ -2150,6 +2281,19 @@ extern "C" int sx_next_slots_fsm(const sx_slot_step_args* a, const sx_sample_arg
                                  const sx_logits_ctl_args* ctl, const sx_token_fsm_args* fsm, void* stream) {
   SX_CHECK(ctl && fsm, "sx_next_slots_fsm: null sx_logits_ctl_args / sx_token_fsm_args");
   return launch_next_token("sx_next_slots_fsm", slot_tail(a), true, sample, sample != nullptr, stream, lp, ctl, fsm);
+}
+extern "C" int sx_next_b_seq(float* logits, int ld_logits, int vocab, const int32_t* img_ids_dev, int n_img,
+                             const int32_t* prev_id_dev, int32_t* next_id_dev, int32_t* out_ids, int ld_out,
+                             const int32_t* step_dev, int G, const sx_sample_args* sample, const sx_logprob_args* lp,
+                             const sx_logits_ctl_args* ctl, const sx_token_fsm_args* fsm, const sx_seq_rule_args* seq, void* stream) {
+  SX_CHECK(ctl && seq, "sx_next_b_seq: null sx_logits_ctl_args / sx_seq_rule_args");
+  return launch_next_token("sx_next_b_seq", TailP{logits, img_ids_dev, prev_id_dev, next_id_dev, out_ids, const_cast<int32_t*>(step_dev),
+                                                  ld_logits, vocab, n_img, ld_out, G}, false, sample, sample != nullptr, stream, lp, ctl, fsm, seq);
+}
+extern "C" int sx_next_slots_seq(const sx_slot_step_args* a, const sx_sample_args* sample, const sx_logprob_args* lp,
+                                 const sx_logits_ctl_args* ctl, const sx_token_fsm_args* fsm, const sx_seq_rule_args* seq, void* stream) {
+  SX_CHECK(ctl && seq, "sx_next_slots_seq: null sx_logits_ctl_args / sx_seq_rule_args");
+  return launch_next_token("sx_next_slots_seq", slot_tail(a), true, sample, sample != nullptr, stream, lp, ctl, fsm, seq);
 }
 extern "C" int sx_token_logprobs(const float* logits, int64_t ld, int vocab, const int32_t* targets, float* chosen, int32_t* top_ids,
                                  float* top, int n_top, int rows, void* stream) {

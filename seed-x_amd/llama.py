@@ -166,12 +166,14 @@ class SlotState:
         self.controls = None
         # a GrammarState (slot_state(grammar=True)): the step ends in the constrained tail (sx_next_slots_fsm), graphs of its own again
         self.grammar = None
+        # a SeqRuleState (slot_state(seq_rules=True)): the step ends in the sequence-rule tail (sx_next_slots_seq), graphs of its own
+        self.seq_rules = None
 
     def key(self):
         return tuple(t.data_ptr() for t in (self.live, self.n_new, self.max_new, self.force_at, self.status)) \
             + (self.force_id, self.eos_id) + (self.sampling.key() if self.sampling is not None else ()) \
             + (self.logprobs.key() if self.logprobs is not None else ()) + (self.controls.key() if self.controls is not None else ()) \
-            + (self.grammar.key() if self.grammar is not None else ())
+            + (self.grammar.key() if self.grammar is not None else ()) + (self.seq_rules.key() if self.seq_rules is not None else ())
 
 
 class SampleState:
@@ -372,6 +374,91 @@ class GrammarState:
 
     def scatter(self, rows, part):
         self.state.index_copy_(0, torch.tensor(list(rows), dtype=torch.int64, device=self.device), part.state)
+
+
+class SeqRuleState:
+    """Per-row sequence rules of the token step on the device (sx_seq_rule_args; seedx_amd.sampling states the rules: apply_no_repeat,
+    stop_match): ``on`` int32 [G] (0: the row runs as without rules), ``ngram`` int32 [G] (no_repeat_ngram_size, 0: off), ``hist`` int32
+    [G, ld_hist] (the request's prompt ids followed by every id it emitted; the tail appends), ``hist_len`` / ``prompt_len`` int32 [G],
+    ``n_stop`` int32 [G], ``stop_len`` int32 [G, 4], ``stop_ids`` int32 [G, 4, 8] and ``matched`` int32 [G] (the stop sequence the
+    generated ids end with, -1: none). ``ld_hist`` is at least the model's max_cache_len: no request holds more ids than cache rows.
+    The kernels read everything at launch, so one captured step serves any mix of rows; the pointers are part of the graph key. The
+    host keeps mirrors of ``ngram`` / ``n_stop`` / ``stop_len`` (``host_limits``: what ops checks without a device read). A fresh state
+    has every row off."""
+
+    def __init__(self, G, V, ld_hist, device):
+        assert int(G) >= 1 and int(ld_hist) >= 1
+        self.G, self.V, self.ld_hist, self.device = int(G), int(V), int(ld_hist), device
+        z = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=device)
+        self.on, self.ngram, self.hist_len, self.prompt_len, self.n_stop = z(G), z(G), z(G), z(G), z(G)
+        self.hist, self.stop_len, self.stop_ids = z(G, self.ld_hist), z(G, 4), z(G, 4, 8)
+        self.matched = torch.full((self.G,), -1, dtype=torch.int32, device=device)
+        self._ngram_h, self._n_stop_h, self._stop_len_h = [0] * self.G, [0] * self.G, [[0] * 4 for _ in range(self.G)]
+
+    def key(self):
+        return ("seq",) + tuple(t.data_ptr() for t in (self.on, self.ngram, self.hist, self.hist_len, self.prompt_len, self.n_stop,
+                                                       self.stop_len, self.stop_ids, self.matched))
+
+    def host_limits(self):
+        return self._ngram_h, self._n_stop_h, self._stop_len_h
+
+    def tensors(self):
+        """What a warm-up or capture of the step rewrites (put back by the caller like the counters)."""
+        return [self.hist_len, self.matched]             # (an id the step left past hist_len is never read)
+
+    def set_rows(self, rows, params, prompt_ids=None):
+        """rows[i] takes params[i] (a sampling.SeqParams, or None: the row runs without rules) and starts a request: its history is
+        prompt_ids[i] (a sequence of ints, image placeholders included), hist_len = prompt_len = its length, matched = -1."""
+        rows = list(rows)
+        if not rows:
+            return
+        idx = torch.tensor(rows, dtype=torch.int64, device=self.device)
+        i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=self.device)
+        on = [p is not None for p in params]
+        pids = [[int(t) for t in prompt_ids[i]] if o and prompt_ids is not None and prompt_ids[i] is not None else []
+                for i, o in enumerate(on)]
+        assert all(len(p) <= self.ld_hist for p in pids), "sequence rules: a prompt longer than the id history"
+        ngram = [p.no_repeat_ngram_size if o else 0 for p, o in zip(params, on)]
+        stops = [list(p.stop) if o else [] for p, o in zip(params, on)]
+        assert all(0 <= n <= 8 for n in ngram) and all(len(s) <= 4 and all(1 <= len(q) <= 8 for q in s) for s in stops)
+        slen = [[len(q) for q in s] + [0] * (4 - len(s)) for s in stops]
+        sids = [[list(q) + [-1] * (8 - len(q)) for q in s] + [[-1] * 8] * (4 - len(s)) for s in stops]
+        self.on.index_copy_(0, idx, i32([int(o) for o in on]))
+        self.ngram.index_copy_(0, idx, i32(ngram))
+        self.n_stop.index_copy_(0, idx, i32([len(s) for s in stops]))
+        self.stop_len.index_copy_(0, idx, i32(slen))
+        self.stop_ids.index_copy_(0, idx, i32(sids))
+        self.hist_len.index_copy_(0, idx, i32([len(p) for p in pids]))
+        self.prompt_len.index_copy_(0, idx, i32([len(p) for p in pids]))
+        self.matched.index_fill_(0, idx, -1)
+        for g, p, n, s, sl in zip(rows, pids, ngram, stops, slen):
+            self._ngram_h[g], self._n_stop_h[g], self._stop_len_h[g] = n, len(s), sl
+            if p:
+                self.hist[g, :len(p)] = i32(p)
+
+    def gather(self, rows):
+        """A state of len(rows) rows holding copies of the given rows (parameters AND history): what the first token of admitted
+        requests, taken from the prefill logits, is chosen with. The copy's tail appends to the copy; ``append`` puts the id into the
+        real history."""
+        rows = list(rows)
+        out = SeqRuleState(len(rows), self.V, self.ld_hist, self.device)
+        idx = torch.tensor(rows, dtype=torch.int64, device=self.device)
+        for k in ("on", "ngram", "hist", "hist_len", "prompt_len", "n_stop", "stop_len", "stop_ids", "matched"):
+            getattr(out, k).copy_(getattr(self, k).index_select(0, idx))
+        out._ngram_h = [self._ngram_h[g] for g in rows]
+        out._n_stop_h = [self._n_stop_h[g] for g in rows]
+        out._stop_len_h = [list(self._stop_len_h[g]) for g in rows]
+        return out
+
+    def append(self, rows, ids):
+        """rows[i] = (g, at): row g's history takes ids[i] (a list of ids) at position ``at`` — its length as the host knows it, prompt
+        length + ids emitted so far — and hist_len[g] = at + len(ids[i]). For ids the HOST emitted for rows that carry rules (the first
+        token of an admitted request, a forced image block): small writes, no device read."""
+        for (g, at), new in zip(rows, ids):
+            new = [int(t) for t in new][:max(0, self.ld_hist - int(at))]
+            if new:
+                self.hist[g, at:at + len(new)] = torch.tensor(new, dtype=torch.int32, device=self.device)
+            self.hist_len[g] = int(at) + len(new)
 
 
 class LlamaForCausalLM:
@@ -632,6 +719,8 @@ class LlamaForCausalLM:
             for mid in ("", "_ad", "_lp", "_lp_ad"):
                 setattr(self, attr + mid + "_ctl", None)
                 setattr(self, attr + mid + "_fsm", None)       # ... and so has a step that ends in the constrained tail (a GrammarState)
+                setattr(self, attr + mid + "_seq", None)       # ... and one that ends in the sequence-rule tail (a SeqRuleState),
+                setattr(self, attr + mid + "_fsm_seq", None)   # without or with a grammar
 
     def memory_footprint(self):
         """Bytes this module will hold on its GPU once packed (per rank): 16-bit weights, their decode-tile copy (precise mode: always;
@@ -1573,7 +1662,7 @@ class LlamaForCausalLM:
     __call__ = forward
 
     # ---- in-flight batching: slot states ---------------------------------------------------------------------------------
-    def slot_state(self, force_id=-1, eos_id=-1, sampling=False, logprobs=None, controls=False, grammar=False):
+    def slot_state(self, force_id=-1, eos_id=-1, sampling=False, logprobs=None, controls=False, grammar=False, seq_rules=False):
         """A fresh SlotState with EVERY slot parked (the module's pos / ctx / step take the idle values; ``reset()`` undoes that).
         ``sampling``: the state carries a SampleState (``.sampling``, all rows greedy until set) and its token step ends in
         sx_sample_next_slots instead of sx_greedy_next_slots. ``logprobs`` = n_top (0 .. 8): the state carries a LogprobState
@@ -1581,7 +1670,9 @@ class LlamaForCausalLM:
         state carries a ControlState (``.controls``, every row off until set) and its token step ends in sx_next_slots_ctl — greedy,
         sampled, with or without the record. ``grammar``: the state carries a GrammarState (``.grammar``, every row unconstrained until
         set) beside a ControlState (the constrained tail works on the controls' working rows) and its token step ends in
-        sx_next_slots_fsm."""
+        sx_next_slots_fsm. ``seq_rules``: the state carries a SeqRuleState (``.seq_rules``, every row off until set) beside a
+        ControlState (the n-gram ban works on the controls' working rows) and its token step ends in sx_next_slots_seq, with or
+        without a grammar."""
         if grammar and not self.max_grammars:
             raise ValueError("LlamaForCausalLM.slot_state: grammar=True on a model built with max_grammars=0")
         if self.tp > 1:
@@ -1590,8 +1681,10 @@ class LlamaForCausalLM:
         st = SlotState(self.G, self.device, force_id, eos_id, sampling)
         if logprobs is not None:
             st.logprobs = LogprobState(self.G, logprobs, self.device)
-        if controls or grammar:
+        if controls or grammar or seq_rules:
             st.controls = self.control_state(fresh=True)
+        if seq_rules:
+            st.seq_rules = self.seq_rule_state(fresh=True)
         if grammar:
             st.grammar = self.grammar_state(fresh=True)
         if sampling and self.spec_tokens:
@@ -1643,6 +1736,16 @@ class LlamaForCausalLM:
         if getattr(self, "_control_state", None) is None:
             self._control_state = ControlState(self.G, self.V, self.Vpad, self.device)
         return self._control_state
+
+    def seq_rule_state(self, fresh=False):
+        """A SeqRuleState for this model (history rows of max_cache_len ids). The lock-step step's (``decode_step(..., seq_rules=...)``)
+        is made once — its pointers are part of the captured graph's key; ``fresh``: a new one (a slot state owns its own)."""
+        self._pack()
+        if fresh:
+            return SeqRuleState(self.G, self.V, self.Tmax, self.device)
+        if getattr(self, "_seq_rule_state", None) is None:
+            self._seq_rule_state = SeqRuleState(self.G, self.V, self.Tmax, self.device)
+        return self._seq_rule_state
 
     def _off_controls(self):
         """A ControlState with every row off, never set: the working rows of a lock-step grammar step that carries no controls."""
@@ -1698,7 +1801,7 @@ class LlamaForCausalLM:
         held[1].replay()
 
     def _decode_step_body(self, img_ids_dev, out_ids, hid_buf, slots=None, sampling=None, adapters=False, logprobs=None, controls=None,
-                          eos_id=-1, grammar=None):
+                          eos_id=-1, grammar=None, seq_rules=None):
         """cur[G] → embedding → 40 layers → final norm → lm_head → logits rule + argmax → cur[G]. Records the post-norm
         hidden state of each INPUT token at hid_buf[g, step[g]] (what seed_x.py:196 collects) and the new id at
         out_ids[g, step[g]]; then step += 1. Everything stays on the device. ``slots`` (a SlotState): the tail is ONE
@@ -1726,8 +1829,12 @@ class LlamaForCausalLM:
         fsm = grammar if slots is None else slots.grammar
         if fsm is not None:
             sample["fsm"] = fsm
+        # sequence-rule step: the same tail with the n-gram ban, the id history and the stop match (a SeqRuleState), fsm or not
+        seq = seq_rules if slots is None else slots.seq_rules
+        if seq is not None:
+            sample["seq"] = seq
         if slots is not None:
-            tail = ops.next_slots_fsm if fsm is not None else ops.next_slots_ctl if ctl is not None else ops.next_slots_lp if lp is not None else ops.sample_next_slots if sample \
+            tail = ops.next_slots_seq if seq is not None else ops.next_slots_fsm if fsm is not None else ops.next_slots_ctl if ctl is not None else ops.next_slots_lp if lp is not None else ops.sample_next_slots if sample \
                 else ops.greedy_next_slots
             tail(logits, self.V, img_ids_dev, P["cur"], slots.live, slots.n_new, slots.max_new, slots.force_at, P["pos"], P["ctx"],
                  P["step"], out_ids, slots.status, force_id=slots.force_id, eos_id=slots.eos_id, **sample)
@@ -1735,7 +1842,7 @@ class LlamaForCausalLM:
             return
         if ctl is not None:
             sample["eos_id"] = eos_id
-        tail = ops.next_b_fsm if fsm is not None else ops.next_b_ctl if ctl is not None else ops.next_b_lp if lp is not None else ops.sample_next_b if sample else ops.greedy_next_b
+        tail = ops.next_b_seq if seq is not None else ops.next_b_fsm if fsm is not None else ops.next_b_ctl if ctl is not None else ops.next_b_lp if lp is not None else ops.sample_next_b if sample else ops.greedy_next_b
         tail(logits, self.V, img_ids_dev, P["cur"], out_ids, P["step"], **sample)
         ops.add_i32(P["step"], 1)
 
@@ -1767,7 +1874,7 @@ class LlamaForCausalLM:
             S["hist"][slot, start:start + len(ids)] = torch.tensor(ids, dtype=torch.int32, device=self.device)
 
     def decode_step(self, img_ids_dev, out_ids, hid_buf, use_graph=True, slots=None, sampling=None, adapters=None, spec=False, draft="ngram",
-                    logprobs=None, controls=None, eos_id=-1, grammar=None):
+                    logprobs=None, controls=None, eos_id=-1, grammar=None, seq_rules=None):
         """out_ids: int32 [G, rows]; hid_buf: fp32 [G, rows, H]. ``slots``: a SlotState → the in-flight step (its captured graph is
         kept apart from the lock-step one, so one graph serves an engine's lifetime whatever else runs in between). ``sampling``: a
         SampleState → the lock-step step ends in sx_sample_next_b (token index = step[g]); a slot state brings its own
@@ -1789,8 +1896,27 @@ class LlamaForCausalLM:
         survives in accepting states only; without ``controls`` the module's control state with every row off carries the working
         rows); a slot state brings its own (``slots.grammar``, sx_next_slots_fsm). Only the tail changes, graphs of its own (attribute
         suffix ``_fsm``), and a step without a state runs the calls and graphs it always ran. ValueError with the verify step and on
-        tensor-parallel ranks: follow-ups."""
+        tensor-parallel ranks: follow-ups.
+        ``seq_rules``: a SeqRuleState → the lock-step step ends in the sequence-rule tail (sx_next_b_seq: no_repeat_ngram_size ban, id
+        history, stop match; with or without ``controls`` / ``grammar``, the module's control state with every row off carries the
+        working rows otherwise); a slot state brings its own (``slots.seq_rules``, sx_next_slots_seq, where a stop match parks the
+        slot). Only the tail changes, graphs of its own (attribute suffix ``_seq``), and a step without a state runs the calls and
+        graphs it always ran. ValueError with the verify step and on tensor-parallel ranks: follow-ups."""
         P = self._pack()
+        seq = seq_rules if slots is None else getattr(slots, "seq_rules", None)
+        if slots is not None and seq_rules is not None:
+            raise ValueError("LlamaForCausalLM.decode_step: a slot state carries its own sequence-rule state (slot_state(seq_rules=True))")
+        if seq is not None:
+            if spec:
+                raise ValueError("LlamaForCausalLM.decode_step: stop sequences / no_repeat_ngram_size in the verify step of speculative "
+                                 "decoding (spec=True with a sequence-rule state) are not built (follow-up: a ban and a stop match per "
+                                 "candidate row of the accepted run)")
+            if self.tp > 1:
+                raise ValueError(f"LlamaForCausalLM.decode_step: sequence rules on tp={self.tp} tensor-parallel ranks are not built "
+                                 "(follow-up: every rank would ban, append and match on the gathered logits)")
+            assert seq.G == self.G and seq.ld_hist >= self.Tmax
+            if slots is None and controls is None:
+                controls = self._off_controls()
         fsm = grammar if slots is None else getattr(slots, "grammar", None)
         if slots is not None and grammar is not None:
             raise ValueError("LlamaForCausalLM.decode_step: a slot state carries its own grammar state (slot_state(grammar=True))")
@@ -1858,7 +1984,8 @@ class LlamaForCausalLM:
             assert out_ids.is_contiguous() and slots.G == self.G
             assert sampling is None, "a slot state carries its own sampling state (slot_state(sampling=True))"
         assert sampling is None or sampling.G == self.G
-        body = lambda: self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling, adapters, logprobs, controls, eos_id, grammar)
+        body = lambda: self._decode_step_body(img_ids_dev, out_ids, hid_buf, slots, sampling, adapters, logprobs, controls, eos_id, grammar,
+                                              seq_rules)
         if not use_graph or not self.comm.graph_safe:
             return body()
         if slots is None:
@@ -1868,10 +1995,11 @@ class LlamaForCausalLM:
         key = (img_ids_dev.data_ptr(), out_ids.data_ptr(), hid_buf.data_ptr(), tuple(out_ids.shape)) \
             + (slots.key() if slots is not None else ()) + (("sample",) + sampling.key() if sampling is not None else ()) \
             + (logprobs.key() if logprobs is not None else ()) + (controls.key() + (int(eos_id),) if controls is not None else ()) \
-            + (grammar.key() if grammar is not None else ())
+            + (grammar.key() if grammar is not None else ()) + (seq_rules.key() if seq_rules is not None else ())
         # (the controlled tail counts the id it emits: warm-up and capture run the step, so the counts are put back like the counters)
         # (... and the constrained tail advances the automaton states: put back likewise)
         self._replay(attr + ("_lp" if lp is not None else "") + ("_ad" if adapters else "")
-                     + ("_fsm" if fsm is not None else "_ctl" if ctl is not None else ""), key, body,
+                     + ("_fsm" if fsm is not None else "_ctl" if ctl is not None and seq is None else "") + ("_seq" if seq is not None else ""),
+                     key, body,
                      ([slots.live, slots.n_new, slots.status] if slots is not None else []) + ([ctl.counts] if ctl is not None else [])
-                     + ([fsm.state] if fsm is not None else []), slots)
+                     + ([fsm.state] if fsm is not None else []) + (seq.tensors() if seq is not None else []), slots)

@@ -1398,6 +1398,83 @@ def next_slots_fsm(logits, vocab, img_ids_dev, cur, live, n_new, max_new, force_
                                         C.byref(ca), C.byref(fa), _stream()), "sx_next_slots_fsm")
 
 
+def _seq_args(who, seq, G):
+    """sx_seq_rule_args from a sequence-rule state (llama.SeqRuleState or anything with its tensors): ``on`` / ``ngram`` / ``hist_len`` /
+    ``prompt_len`` / ``n_stop`` / ``matched`` int32 [G], ``hist`` int32 [G, ld_hist], ``stop_len`` int32 [G, 4], ``stop_ids`` int32
+    [G, 4, 8]. Values the device would clamp are refused here (ValueError): ``ngram`` outside 0 .. 8, ``n_stop`` outside 0 .. 4, a
+    ``stop_len`` outside 1 .. 8 among a row's first ``n_stop``. A state that keeps host mirrors (``host_limits()`` → the three as lists)
+    is checked on those; any other state is read back from the device, except inside a graph capture, where nothing can be read."""
+    i32 = torch.int32
+    for t, shape in ((seq.on, (G,)), (seq.ngram, (G,)), (seq.hist_len, (G,)), (seq.prompt_len, (G,)), (seq.n_stop, (G,)),
+                     (seq.matched, (G,)), (seq.stop_len, (G, 4)), (seq.stop_ids, (G, 4, 8))):
+        assert t.dtype == i32 and t.is_contiguous() and tuple(t.shape) == shape, f"{who}: contiguous int32 [G] / [G, 4] / [G, 4, 8] tensors"
+    h = seq.hist
+    assert h.dtype == i32 and h.dim() == 2 and h.is_contiguous() and h.shape[0] == G, f"{who}: hist is contiguous int32 [G, ld_hist]"
+    lim = seq.host_limits() if hasattr(seq, "host_limits") else None
+    if lim is None and not torch.cuda.is_current_stream_capturing():
+        lim = (seq.ngram.tolist(), seq.n_stop.tolist(), seq.stop_len.tolist())
+    if lim is not None:
+        ngram, n_stop, stop_len = lim
+        for g in range(G):
+            if not 0 <= int(ngram[g]) <= 8:
+                raise ValueError(f"{who}: ngram[{g}]={int(ngram[g])} lies outside 0 .. 8")
+            if not 0 <= int(n_stop[g]) <= 4:
+                raise ValueError(f"{who}: n_stop[{g}]={int(n_stop[g])} lies outside 0 .. 4")
+            for j in range(int(n_stop[g])):
+                if not 1 <= int(stop_len[g][j]) <= 8:
+                    raise ValueError(f"{who}: stop_len[{g}][{j}]={int(stop_len[g][j])} lies outside 1 .. 8")
+    d = lambda t: _p(t).value                             # (GPU tensors only: no CPU fallback)
+    return _lib.SeqRuleArgs(on=d(seq.on), ngram=d(seq.ngram), hist=d(h), hist_len=d(seq.hist_len),
+                            prompt_len=d(seq.prompt_len), n_stop=d(seq.n_stop), stop_len=d(seq.stop_len), stop_ids=d(seq.stop_ids),
+                            matched=d(seq.matched), ld_hist=h.shape[1], reserved=0)
+
+
+def next_b_seq(logits, vocab, img_ids_dev, cur_dev, out_ids, step_dev, ctl, seq, fsm=None, sample=None, lp=None, token_index=None,
+               n_kept=None, p_chosen=None, eos_id=-1):
+    """The lock-step tail with sequence rules per row (sx_next_b_seq; seedx_amd.sampling states them: apply_no_repeat, stop_match):
+    next_b_ctl (``fsm`` None) or next_b_fsm, and a row with ``seq.on[g]`` != 0 has the ids that would repeat an n-gram of its history
+    banned in a working row in ``ctl.work`` (behind the controls, ahead of the grammar mask and the image rule), appends the id it emits
+    to ``seq.hist`` and reports in ``seq.matched[g]`` the stop sequence its generated ids now end with (-1: none). Every other row is
+    next_b_ctl's / next_b_fsm's, bit for bit, and its history is not touched."""
+    lib = _lib.load()
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    G = logits.shape[0]
+    token_index = step_dev if token_index is None else token_index
+    assert token_index is not None, "next_b_seq: token_index (or step_dev) is required"
+    ld_out = out_ids.stride(0) if out_ids is not None else 0
+    la = None
+    if lp is not None:
+        la, ld_out = _logprob_args(lp, G, out_ids)
+        assert step_dev is not None, "the LP tail needs step_dev"
+    sa = _sample_args(sample, G, token_index, n_kept, p_chosen) if sample is not None else None
+    ca = _ctl_args(ctl, logits, vocab, token_index, eos_id)
+    fa = _fsm_args(fsm, logits, vocab, eos_id) if fsm is not None else None
+    qa = _seq_args("next_b_seq", seq, G)
+    check(lib.sx_next_b_seq(_p(logits), logits.stride(0), vocab, _p(img_ids_dev), img_ids_dev.numel(), _p(cur_dev), _p(cur_dev), _p(out_ids),
+                            ld_out, _p(step_dev), G, C.byref(sa) if sa is not None else None, C.byref(la) if la is not None else None,
+                            C.byref(ca), C.byref(fa) if fa is not None else None, C.byref(qa), _stream()), "sx_next_b_seq")
+
+
+def next_slots_seq(logits, vocab, img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, out_ids, status, ctl, seq, fsm=None,
+                   sample=None, lp=None, force_id=-1, eos_id=-1, n_kept=None, p_chosen=None):
+    """The in-flight tail with sequence rules per slot (sx_next_slots_seq): next_slots_ctl / next_slots_fsm with next_b_seq's ban,
+    append and stop match per live slot; a slot whose generated ids end with one of its stop sequences stops and parks itself exactly
+    as on EOS or budget. Parked slots read and write nothing, their history included; slots with ``seq.on`` = 0 are next_slots_ctl's /
+    next_slots_fsm's."""
+    a = _slot_step_args("next_slots_seq", logits, vocab, img_ids_dev, cur, live, n_new, max_new, force_at, pos, ctx, step, out_ids,
+                        status, force_id, eos_id)
+    G = logits.shape[0]
+    la = None
+    if lp is not None:
+        la, a.ld_out = _logprob_args(lp, G, out_ids)
+    s = _sample_args(sample, G, None, n_kept, p_chosen) if sample is not None else None
+    ca = _ctl_args(ctl, logits, vocab, None, eos_id)
+    fa = _fsm_args(fsm, logits, vocab, -1) if fsm is not None else None
+    qa = _seq_args("next_slots_seq", seq, G)
+    check(_lib.load().sx_next_slots_seq(C.byref(a), C.byref(s) if s is not None else None, C.byref(la) if la is not None else None,
+                                        C.byref(ca), C.byref(fa) if fa is not None else None, C.byref(qa), _stream()), "sx_next_slots_seq")
+
+
 def _i32s(who, *ts):
     for t in ts:
         assert t.dtype == torch.int32 and t.is_contiguous(), f"{who}: contiguous int32 tensors"

@@ -309,3 +309,116 @@ def apply_controls(row, counts, params, eos_id=-1, token_index=0):
     if int(eos_id) >= 0 and int(token_index) < params.min_new_tokens:
         y[int(eos_id)] = -np.inf
     return y
+
+
+# ---- per-request sequence rules: stop sequences and no_repeat_ngram_size ----------------------------------------------------------
+MAX_STOP = 4                  # stop sequences per request
+MAX_STOP_LEN = 8              # ids per stop sequence
+MAX_NGRAM = 8                 # largest no_repeat_ngram_size
+SEQ_KEYS = ("stop", "no_repeat_ngram_size")
+
+
+class SeqParams:
+    """The sequence rules of one request (the rules: ``ngram_banned`` / ``apply_no_repeat`` / ``stop_match``). ``stop``: at most 4 stop
+    sequences of 1 .. 8 token ids each ([[ids], ...]; one flat list of ints counts as one sequence; the ids are checked against the
+    vocabulary by ``check_vocab``); a request ends on the token that completes one of them, and the matched ids stay in its result, as
+    the EOS id does. Strings are refused: how a string tokenises depends on what precedes it, so the caller passes ids.
+    ``no_repeat_ngram_size`` n in 0 .. 8 (0 or None: off): no n-gram of prompt + generated ids occurs twice (transformers'
+    NoRepeatNGramLogitsProcessor). Malformed values are a ValueError."""
+    __slots__ = ("stop", "no_repeat_ngram_size")
+
+    def __init__(self, stop=None, no_repeat_ngram_size=0):
+        is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+        seqs = []
+        if stop is not None:
+            if isinstance(stop, (str, bytes)) or (isinstance(stop, (list, tuple)) and any(isinstance(s, (str, bytes)) for s in stop)):
+                raise ValueError(f"stop must hold token ids, not strings (got {stop!r}): how a string tokenises depends on what precedes "
+                                 "it, so encode the stop sequences yourself and pass their ids")
+            if not isinstance(stop, (list, tuple)):
+                raise ValueError(f"stop must be a list of stop sequences [[ids], ...] (or one flat list of ids), got {stop!r}")
+            if stop and all(is_int(s) for s in stop):
+                stop = [stop]
+            if len(stop) > MAX_STOP:
+                raise ValueError(f"stop holds {len(stop)} sequences, at most {MAX_STOP} are supported")
+            for s in stop:
+                if not isinstance(s, (list, tuple)) or not all(is_int(t) for t in s):
+                    raise ValueError(f"every stop sequence must be a list of int token ids, got {s!r}")
+                if not 1 <= len(s) <= MAX_STOP_LEN:
+                    raise ValueError(f"a stop sequence must hold 1 .. {MAX_STOP_LEN} ids, got {len(s)}: {list(s)!r}")
+                if any(int(t) < 0 for t in s):
+                    raise ValueError(f"stop ids must be ints >= 0, got {list(s)!r}")
+                seqs.append(tuple(int(t) for t in s))
+        n = 0 if no_repeat_ngram_size is None else no_repeat_ngram_size
+        if not is_int(n) or not 0 <= int(n) <= MAX_NGRAM:
+            raise ValueError(f"no_repeat_ngram_size must be an int in 0 .. {MAX_NGRAM} (0 disables it), got {no_repeat_ngram_size!r}")
+        self.stop, self.no_repeat_ngram_size = tuple(seqs), int(n)
+
+    def is_default(self):
+        return not self.stop and self.no_repeat_ngram_size == 0
+
+    def check_vocab(self, vocab):
+        for s in self.stop:
+            for t in s:
+                if not t < int(vocab):
+                    raise ValueError(f"stop id {t} lies outside the vocabulary [0, {int(vocab)})")
+        return self
+
+    @classmethod
+    def from_request(cls, req, vocab=None):
+        """The sequence-rule keys of a generate_batch / generate_inflight request dict (``generate`` takes the same names as kwargs);
+        None when both are absent or off (None, 0, []): such a request runs the calls and graphs it always ran."""
+        kw = {k: req[k] for k in SEQ_KEYS if req.get(k) is not None}
+        if not kw:
+            return None
+        p = cls(**kw)
+        if vocab is not None:
+            p.check_vocab(vocab)
+        return None if p.is_default() else p
+
+    def as_dict(self):
+        """What a result's ``'seq_rules'`` entry starts from: the values the device used (the engines add ``'matched'``)."""
+        return {"stop": [list(s) for s in self.stop], "no_repeat_ngram_size": self.no_repeat_ngram_size}
+
+    def __repr__(self):
+        return "SeqParams(" + ", ".join(f"{k}={v!r}" for k, v in self.as_dict().items()) + ")"
+
+
+def ngram_banned(hist, n, vocab=None):
+    """The ids no_repeat_ngram_size = n bans for the next token (next_token_kernel<.., SEQ> in csrc/decode.hip, sx_next_b_seq /
+    sx_next_slots_seq). ``hist``: the request's prompt ids followed by every id generated so far, L = len(hist). For n >= 1 and every
+    i in [0, L - n]: if hist[i : i+n-1] == hist[L-n+1 : L] then hist[i+n-1] is banned (n = 1: the compared prefix is empty, every id of
+    the history is banned; L < n: no n-gram exists yet, nothing is banned). With ``vocab`` = V ids outside [0, V) — image placeholders —
+    ban nothing; they still take part in the comparison. This is transformers' NoRepeatNGramLogitsProcessor on one sequence."""
+    h = [int(t) for t in hist]
+    n, L = int(n), len(h)
+    out = set()
+    if n < 1:
+        return out
+    tail = h[L - n + 1:L] if n > 1 else []
+    for i in range(0, L - n + 1):
+        if h[i:i + n - 1] == tail:
+            t = h[i + n - 1]
+            if vocab is None or 0 <= t < int(vocab):
+                out.add(t)
+    return out
+
+
+def apply_no_repeat(row, hist, n):
+    """``row`` (fp32 [V]; a raw row or apply_controls' result) with the columns of ngram_banned(hist, n, V) set to -inf: a new array,
+    nothing else changes. The grammar mask, the image-token rule and the arg-max or draw then run on it."""
+    y = np.array(row, dtype=np.float32).reshape(-1).copy()
+    ban = sorted(ngram_banned(hist, n, y.size))
+    if ban:
+        y[ban] = -np.inf
+    return y
+
+
+def stop_match(generated, stops):
+    """The lowest index j for which the GENERATED ids end with stops[j], else None. Only generated ids are compared: a stop that would
+    straddle the end of the prompt does not match. The matched ids stay in the result, the way the EOS id does."""
+    g = [int(t) for t in generated]
+    for j, s in enumerate(stops):
+        s = [int(t) for t in s]
+        if 1 <= len(s) <= len(g) and g[len(g) - len(s):] == s:
+            return j
+    return None

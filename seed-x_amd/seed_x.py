@@ -20,7 +20,7 @@ from . import ops
 from .grammar import DONE, advance
 from .inflight import PrefixIndex, SlotScheduler, plan_admission, tag_signatures
 from .llama import LogprobState
-from .sampling import ControlParams, SamplingParams, logprobs_from_request, logprobs_result
+from .sampling import ControlParams, SamplingParams, SeqParams, logprobs_from_request, logprobs_result, stop_match
 
 BOI_TOKEN = '<img>'
 EOI_TOKEN = '</img>'
@@ -227,6 +227,36 @@ class ContinuousLVLM:
                 raise ValueError(f"{who}: grammar {n!r} admits ids of the image block (follow-up); build it with banned_ids = the block "
                                  "(ContinuousLVLM.image_block_ids)")
 
+    # ---- sequence rules (sampling.SeqParams): what the engines check before anything is touched -------------------------------------
+    def _seq_params(self, who, requests, force_flags):
+        """The requests' SeqParams (``"stop"`` / ``"no_repeat_ngram_size"``; None: the request carries neither). ValueError for malformed
+        values and for what is not built: force_image_at on the same request, agent.speculative, tensor-parallel ranks."""
+        llm = self.llm
+        seqs = [SeqParams.from_request(req) for req in requests]
+        if all(q is None for q in seqs):
+            return seqs
+        for r, q in enumerate(seqs):
+            if q is not None and force_flags[r]:
+                raise ValueError(f"{who}: request {r} carries stop sequences / no_repeat_ngram_size and force_image_at: not built "
+                                 "(follow-up: synthetic-weights pinning beside an id history); drop one of the two")
+        if who == "generate_inflight" and self.speculative:
+            raise ValueError(f"{who}: stop sequences / no_repeat_ngram_size with agent.speculative are not built (follow-up: a ban and a "
+                             "stop match per candidate row of the verify step's accepted run); switch agent.speculative off for calls "
+                             "that carry them")
+        world = llm.comm.world if getattr(llm, "comm", None) is not None else 1
+        if world > 1:
+            raise ValueError(f"{who}: stop sequences / no_repeat_ngram_size on tp={world} tensor-parallel ranks are not built (follow-up: "
+                             "every rank would ban, append and match on the gathered logits)")
+        for q in seqs:
+            if q is not None:
+                q.check_vocab(llm.V)
+        return seqs
+
+    @staticmethod
+    def _seq_result(q, matched):
+        """A result's ``'seq_rules'`` entry: the values the device used and the index of the stop sequence that ended the request."""
+        return dict(q.as_dict(), matched=None if matched is None or int(matched) < 0 else int(matched))
+
     @classmethod
     def image_block_ids(cls, tokenizer, num_img_gen_tokens=64):
         """The ids of ``<img>``, ``<img_i>`` and ``</img>``: what a grammar's ``banned_ids`` must hold."""
@@ -282,7 +312,17 @@ class ContinuousLVLM:
         generated ids (a trailing EOS apart); a budget that runs out mid-grammar gives False. Log-probabilities stay those of the RAW
         row. Without such a request the call runs the calls and graphs it always ran. ValueError, before anything is touched, for a
         model built with max_grammars=0, an unknown name, ``force_image_at`` (follow-up), a prompt that ends inside the image block
-        (follow-up), a grammar that admits the image block (follow-up) and tensor-parallel ranks (follow-up)."""
+        (follow-up), a grammar that admits the image block (follow-up) and tensor-parallel ranks (follow-up).
+        A request may carry sequence rules — ``"stop"``: [[ids], ...] (at most 4 sequences of 1 .. 8 token ids; one flat list counts as
+        one sequence; strings are refused) and ``"no_repeat_ngram_size"``: n in 0 .. 8 (sampling.SeqParams; malformed values are a
+        ValueError before anything is touched). The device keeps the request's id history (prompt ids, then every id it emits) and, inside
+        the tail of the token step (sx_next_b_seq: behind the controls, ahead of the grammar mask and the image-token rule), bans every
+        id that would repeat an n-gram of it (seedx_amd.sampling.apply_no_repeat, transformers' NoRepeatNGramLogitsProcessor); the row
+        is cut at the token on which its generated ids end with a stop sequence (sampling.stop_match; the matched ids stay in the
+        result, like the EOS id; a stop sequence that ends on a host-driven image block is tested behind the whole block) and its
+        result gains ``'seq_rules'`` = {'stop', 'no_repeat_ngram_size', 'matched'}. Log-probabilities stay those of the RAW row. Without
+        such a request the call runs the calls and graphs it always ran. ValueError with ``force_image_at`` (follow-up) and on
+        tensor-parallel ranks (follow-up)."""
         llm = self.llm
         gnames = self._grammar_names("generate_batch", requests, [force_image_at is not None] * len(requests))
         constrained = any(n is not None for n in gnames)
@@ -294,6 +334,8 @@ class ContinuousLVLM:
         if controlled and force_image_at is not None:
             raise ValueError("generate_batch: logits controls together with force_image_at are not built (follow-up: counting the "
                              "replaced id in the lock-step form); drop one of the two")
+        seqs = self._seq_params("generate_batch", requests, [force_image_at is not None] * len(requests))
+        ruled = any(q is not None for q in seqs)
         params = [SamplingParams.from_request(req, world=llm.comm.world) for req in requests]     # refuses seed=None on tp > 1 ranks
         if controlled:
             if llm.comm.world > 1:
@@ -356,7 +398,16 @@ class ContinuousLVLM:
         cs, gs, eos_dev = None, None, -1 if eos_token_id is None else int(eos_token_id)
         fsms = [llm.grammar(n) if n is not None else None for n in gnames]
         gstate = [0 if f is not None else DONE for f in fsms]        # host mirror of the automaton states, advanced on the read-back ids
-        if constrained:                                  # the constrained tail, here and in every token step; its working rows are the controls'
+        qs, gen, smatch = None, [[] for _ in range(G)], [None] * G   # host mirror of the generated ids of the rows that carry rules
+        if ruled:                                        # the sequence-rule tail, here and in every token step; working rows: the controls'
+            cs, qs = llm.control_state(), llm.seq_rule_state()
+            cs.set_rows(range(G), ctls, [ids for ids, _ in prompts])
+            qs.set_rows(range(G), seqs, [ids for ids, _ in prompts])
+            if constrained:
+                gs = llm.grammar_state()
+                gs.set_rows(range(G), gnames)
+            ops.next_b_seq(logits, llm.V, img_ids_dev, P["cur"], out_ids, P["step"], cs, qs, fsm=gs, sample=ss, lp=lps, eos_id=eos_dev)   # token index 0
+        elif constrained:                                  # the constrained tail, here and in every token step; its working rows are the controls'
             cs, gs = llm.control_state(), llm.grammar_state()
             cs.set_rows(range(G), ctls, [ids for ids, _ in prompts])
             gs.set_rows(range(G), gnames)
@@ -388,11 +439,15 @@ class ContinuousLVLM:
                     lps.forced(g, n_new[g] - 1, 1)       # the record made there describes the id that was replaced
 
         def finished(g):
-            return n_new[g] >= max_new_tokens or (eos_token_id is not None and cur[g] == eos_token_id) or (fsms[g] is not None and gstate[g] < 0)
+            return n_new[g] >= max_new_tokens or (eos_token_id is not None and cur[g] == eos_token_id) or (fsms[g] is not None and gstate[g] < 0) \
+                or smatch[g] is not None
 
-        def walk(g):                                     # the device did the same on the same id (grammar.advance)
+        def walk(g):                                     # the device did the same on the same id (grammar.advance; sampling.stop_match)
             if fsms[g] is not None and gstate[g] >= 0:
                 gstate[g] = advance(fsms[g], gstate[g], cur[g], eos_dev)
+            if seqs[g] is not None:
+                gen[g].append(cur[g])
+                smatch[g] = stop_match(gen[g], seqs[g].stop)
         for g in range(G):
             force(g)
             walk(g)
@@ -409,6 +464,10 @@ class ContinuousLVLM:
                         lps.forced(g, n_new[g], nchunk)
                     if ctls[g] is not None:              # the host emitted these ids: counted like the tail's
                         cs.count([g] * nchunk, img_ids[1:])
+                    if seqs[g] is not None:              # ... and go to the id history like the tail's
+                        qs.append([(g, len(prompts[g][0]) + n_new[g])], [img_ids[1:]])
+                        gen[g] += img_ids[1:]
+                        smatch[g] = stop_match(gen[g], seqs[g].stop)
                     n_new[g] += nchunk
                     P["step"][g] = n_new[g]
                     P["cur"][g] = eoi_id
@@ -420,7 +479,8 @@ class ContinuousLVLM:
             llm.decode_step(img_ids_dev, out_ids, hid, use_graph=self.use_graph, sampling=ss,   # one token for every sequence
                             **(dict(logprobs=lps) if lps is not None else {}),
                             **(dict(controls=cs, eos_id=eos_dev) if cs is not None else {}),
-                            **(dict(grammar=gs) if gs is not None else {}))
+                            **(dict(grammar=gs) if gs is not None else {}),
+                            **(dict(seq_rules=qs) if qs is not None else {}))
             cur = P["cur"].tolist()                                                          # the only read-back per step
             llm.comm.check()                              # (tensor-parallel only: + 4 bytes) a timed-out collective must not pass
             for g in range(G):
@@ -449,6 +509,8 @@ class ContinuousLVLM:
                 results[-1]['controls'] = ctls[g].as_dict()
             if fsms[g] is not None:
                 results[-1]['grammar'] = self._grammar_result(fsms[g], gnames[g], generate_ids.tolist(), eos_dev)
+            if seqs[g] is not None:
+                results[-1]['seq_rules'] = self._seq_result(seqs[g], smatch[g])
         return results
 
     @staticmethod
@@ -555,7 +617,14 @@ class ContinuousLVLM:
         request runs the constrained token step (sx_next_slots_fsm) on a slot state of its own — table index and state 0 are written
         per slot at admission, the device advances the state, and a slot whose automaton finishes parks itself like one that met EOS
         — and a queue without one takes the states and graphs it always took. The ids depend on the request alone. The refusals are
-        generate_batch's, plus ``agent.speculative`` (follow-up)."""
+        generate_batch's, plus ``agent.speculative`` (follow-up).
+        A request may carry ``"stop"`` / ``"no_repeat_ngram_size"`` as in generate_batch (its result gains ``'seq_rules'``): a queue with
+        at least one such request runs the sequence-rule token step (sx_next_slots_seq) on a slot state of its own — the rules and the
+        prompt's ids (image placeholders included) are written per slot at admission, the device appends every id it emits, bans
+        the ids that would repeat an n-gram, and a slot whose generated ids end with one of its stop sequences parks itself like one
+        that met EOS, so its slot and its pages are free for the next request at once; ``matched`` is read once per finished slot —
+        and a queue without one takes the states and graphs it always took. The ids depend on the request alone. ValueError with
+        ``agent.speculative`` and with ``force_image_at`` on the same request (follow-ups)."""
         llm = self.llm
         requests = list(requests)
         gnames = self._grammar_names("generate_inflight", requests, [req.get("force_image_at") is not None for req in requests])
@@ -572,6 +641,8 @@ class ContinuousLVLM:
             if c is not None and req.get("force_image_at") is not None:
                 raise ValueError(f"generate_inflight: request {r} carries logits controls and force_image_at: not built (follow-up); drop "
                                  "one of the two")
+        seqs = self._seq_params("generate_inflight", requests, [req.get("force_image_at") is not None for req in requests])
+        ruled = any(q is not None for q in seqs)
         if controlled and llm.comm.world > 1:
             raise ValueError(f"generate_inflight: logits controls on tp={llm.comm.world} tensor-parallel ranks are not built (follow-up)")
         for c in ctls:
@@ -650,14 +721,21 @@ class ContinuousLVLM:
             which += "_ctl"
         if constrained:                                        # ... and for the constrained step
             which += "_fsm"
+        if ruled:                                              # ... and for the sequence-rule step
+            which += "_seq"
         if keep.get(which) is None:
             keep[which] = owned(lambda: llm.slot_state(force_id=boi_id, eos_id=eos, sampling=sampled, logprobs=n_top,
                                                        **(dict(controls=True) if controlled else {}),
-                                                       **(dict(grammar=True) if constrained else {})))
+                                                       **(dict(grammar=True) if constrained else {}),
+                                                       **(dict(seq_rules=True) if ruled else {})))
         st, img_ids_dev, out_ids, hid = keep[which], keep["img_ids_dev"], keep["out_ids"], keep["hid"]
         lps = st.logprobs
         cs = st.controls
         gs = st.grammar
+        qs = st.seq_rules
+        gen, smatch, qlen = [[] for _ in range(G)], [None] * G, [0] * G    # host mirrors of the ruled slots: generated ids, match, prompt rows
+        if qs is not None:
+            qs.on.zero_()
         gfin = set()                                     # slots whose automaton finished on the prefill's first token
         if gs is not None:
             gs.table.fill_(-1)
@@ -712,12 +790,14 @@ class ContinuousLVLM:
                 results[r]['controls'] = ctls[r].as_dict()
             if fsms[r] is not None:
                 results[r]['grammar'] = self._grammar_result(fsms[r], gnames[r], generate_ids.tolist(), eos)
+            if seqs[r] is not None:                      # a slot the device parked on a stop sequence: one read per finished slot
+                results[r]['seq_rules'] = self._seq_result(seqs[r], smatch[g] if smatch[g] is not None else qs.matched[g].item())
             gfin.discard(g)
             if on_result is not None:
                 on_result(r, results[r])
 
         def stopped(g):
-            return n_new[g] >= budget[sched.slot_req[g]] or (eos >= 0 and cur[g] == eos) or g in gfin
+            return n_new[g] >= budget[sched.slot_req[g]] or (eos >= 0 and cur[g] == eos) or g in gfin or smatch[g] is not None
 
         def admit_round(adm, starts=None):
             # ONE batched prefill over the admitted slots; token 1 of each comes from it (host-side stop test: not in the graph).
@@ -751,13 +831,20 @@ class ContinuousLVLM:
             if gs is not None:                           # the slots take their requests' grammars: table index, state 0
                 gs.set_rows(slots, [gnames[r] for _, r in adm])
                 part = gs.gather(slots)
+            qpart = None
+            if qs is not None:                           # the slots take their requests' rules and their prompts' ids
+                qs.set_rows(slots, [seqs[r] for _, r in adm], pids)
+                qpart = qs.gather(slots)
             if lps is not None:                          # the first record: the LP lock-step tail on the prefill's logits, one row per slot
                 wants = [int(asks[r] is not None) for _, r in adm]
                 llm._slot_write(lps.want, slots, wants)
                 rec = LogprobState(len(slots), n_top, dev, rows=1)
                 rec.want.copy_(torch.tensor(wants, dtype=torch.int32))
                 zero = torch.zeros(len(slots), dtype=torch.int32, device=dev)
-                if gs is not None:                       # ... of the raw row, the id from the constrained one
+                if qs is not None:                       # ... of the raw row, the id from the row the rules (and a grammar) edited
+                    ops.next_b_seq(logits.contiguous(), llm.V, img_ids_dev, first, None, zero, cs.gather(slots), qpart, fsm=part,
+                                   sample=st.sampling.gather(slots) if sampled else None, lp=rec, token_index=zero, eos_id=eos)
+                elif gs is not None:                     # ... of the raw row, the id from the constrained one
                     ops.next_b_fsm(logits.contiguous(), llm.V, img_ids_dev, first, None, zero, cs.gather(slots), part,
                                    sample=st.sampling.gather(slots) if sampled else None, lp=rec, token_index=zero, eos_id=eos)
                 elif cs is not None:                     # ... of the raw row, the id from the controlled one
@@ -771,6 +858,10 @@ class ContinuousLVLM:
                 for i, (g, r) in enumerate(adm):
                     if force_at[r] == 0 and wants[i]:
                         lps.forced(g, 0, 1)              # (synthetic weights) the id is replaced below: the model did not choose it
+            elif qs is not None:                         # token index 0 through sx_next_b_seq, like every later one
+                zero = torch.zeros(len(slots), dtype=torch.int32, device=dev)
+                ops.next_b_seq(logits.contiguous(), llm.V, img_ids_dev, first, None, zero, cs.gather(slots), qpart, fsm=part,
+                               sample=st.sampling.gather(slots) if sampled else None, token_index=zero, eos_id=eos)
             elif gs is not None:                         # token index 0 through sx_next_b_fsm, like every later one
                 zero = torch.zeros(len(slots), dtype=torch.int32, device=dev)
                 ops.next_b_fsm(logits.contiguous(), llm.V, img_ids_dev, first, None, zero, cs.gather(slots), part,
@@ -796,6 +887,11 @@ class ContinuousLVLM:
             for i, (g, r) in enumerate(adm):
                 cur[g] = boi_id if force_at[r] == 0 else first[i]      # (synthetic weights: the pinned transcript, see generate_batch)
                 n_new[g] = 1
+                gen[g], smatch[g], qlen[g] = [], None, len(pids[i])
+                if seqs[r] is not None:                  # the first id in the real history (the tail above appended to the copy)
+                    qs.append([(g, qlen[g])], [[cur[g]]])
+                    gen[g] = [cur[g]]
+                    smatch[g] = stop_match(gen[g], seqs[r].stop)
             out_ids[torch.tensor(slots, device=dev), 0] = torch.tensor([cur[g] for g in slots], dtype=torch.int32, device=dev)
             llm._slot_write(P["cur"], slots, [cur[g] for g in slots])
             if cs is not None:                           # the first id in the real table (the tail above counted into the copy)
@@ -860,6 +956,10 @@ class ContinuousLVLM:
                         lps.forced(g, n_new[g], nchunk)
                     if ctls[sched.slot_req[g]] is not None:      # the host emitted these ids: counted like the tail's
                         cs.count([g] * nchunk, img_ids[1:])
+                    if seqs[sched.slot_req[g]] is not None:      # ... and go to the id history like the tail's
+                        qs.append([(g, qlen[g] + n_new[g])], [img_ids[1:]])
+                        gen[g] += img_ids[1:]
+                        smatch[g] = stop_match(gen[g], seqs[sched.slot_req[g]].stop)
                     if spec:                             # the block's ids at the positions they were fed (</img> is the new current token)
                         llm.spec_write_history(g, plen[g] + n_new[g] - 1, img_ids)
                     n_new[g] += nchunk
@@ -894,6 +994,8 @@ class ContinuousLVLM:
                     self.last_spec_emitted[sched.slot_req[g]].append(status[g][2] - n_new[g])
             for g in live:
                 cur[g], alive, n_new[g], fin_n = status[g]
+                if qs is not None and seqs[sched.slot_req[g]] is not None:
+                    gen[g].append(cur[g])
                 if not alive:
                     harvest(g, fin_n)
                     gone.append(g)
@@ -971,7 +1073,7 @@ class ContinuousLVLM:
                  max_new_tokens=120, top_p=0.5, dtype=torch.float16, device='cuda', patch_positions=None,
                  eos_token_id="auto", force_image_at=None, reuse_cache=False, do_sample=False, top_k=50, seed=None, adapter=None,
                  logprobs=None, repetition_penalty=None, presence_penalty=None, frequency_penalty=None, logit_bias=None,
-                 min_new_tokens=None, grammar=None):
+                 min_new_tokens=None, grammar=None, stop=None, no_repeat_ngram_size=None):
         """Reference signature (seed_x.py:130-145). Greedy by default (do_sample=False, num_beams=1 — temperature/top_p are inert
         in the reference too, :175-189). ``do_sample=True`` makes ``temperature`` / ``top_p`` live (defaults: the reference's 0.7 /
         0.5) together with ``top_k`` (50, transformers' generation default) and ``seed`` (None: 64 bits from os.urandom): the seeded
@@ -983,7 +1085,9 @@ class ContinuousLVLM:
         ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` / ``logit_bias`` / ``min_new_tokens``: the device-side
         logits controls of generate_batch (what a reference user passes through ``logits_processor`` / ``generation_config``; a
         host-supplied processor list itself stays refused); the result then carries ``'controls'``. ``grammar``: name of a token
-        automaton resident on the LLM (``llm.load_grammar``) that constrains the ids (generate_batch); the result carries ``'grammar'``."""
+        automaton resident on the LLM (``llm.load_grammar``) that constrains the ids (generate_batch); the result carries ``'grammar'``.
+        ``stop`` / ``no_repeat_ngram_size``: the device-side sequence rules of generate_batch (stop sequences as token ids; transformers'
+        no_repeat_ngram_size); the result then carries ``'seq_rules'``."""
         assert logits_processor is None, "the AutoImageTokenGenerationProcessor rule is fused on the device"
         assert num_beams == 1
         assert self.llm.G == 1, "this LLM was built for lock-step batches: use generate_batch()"
@@ -999,5 +1103,6 @@ class ContinuousLVLM:
                    logit_bias=logit_bias, min_new_tokens=min_new_tokens)
         if grammar is not None:
             req["grammar"] = grammar
+        req.update(stop=stop, no_repeat_ngram_size=no_repeat_ngram_size)
         return self.generate_batch(tokenizer, [req], num_img_gen_tokens, max_new_tokens, eos_token_id, force_image_at,
                                    reuse_cache)[0]
