@@ -854,6 +854,27 @@ int sx_cfg_euler_step(const float* eps, float* latents, float* scaled_next, cons
                       const int32_t* step_dev, int nb, int64_t n, int C, int ld_scaled, float gs, float igs, int mode,
                       void* stream);
 
+/* In-flight batching of the denoise loop: G generations ("slots") share ONE captured UNet step, rows ordered [branch][slot], and every
+ * slot carries its own step counter, schedule and guidance scales in device memory. Slot g is LIVE when 0 <= step_dev[g] < n_steps_dev[g],
+ * PARKED otherwise (the host parks a slot with step -1).
+ *
+ * sx_cfg_euler_step_slots: sx_cfg_euler_step on every live slot's n_slot = HW*C elements (eps [nb][G][HW][C], latents [G][HW][C],
+ * scaled_next [nb][G][HW][ld_scaled]) with sigma = sig_tab[g][step], sigma_next = sig_tab[g][step + 1] (sig_tab [G][ld_sig] fp32; both
+ * indices are clamped into [0, ld_sig), so a wrong table gives wrong numbers, never a wild address), gs_dev[g] and igs_dev[g]. The
+ * arithmetic is sx_cfg_euler_step's instruction for instruction: a live slot's result equals that kernel's on the slot's rows bit for
+ * bit. For a parked slot nothing is written: not its latents, not its rows of any branch of scaled_next. Channels C..ld_scaled-1 of
+ * scaled_next are never written. */
+int sx_cfg_euler_step_slots(const float* eps, float* latents, float* scaled_next, const float* sig_tab, int ld_sig,
+                            const int32_t* step_dev, const int32_t* n_steps_dev, const float* gs_dev, const float* igs_dev, int nb,
+                            int G, int64_t n_slot, int C, int ld_scaled, int mode, void* stream);
+/* out [nb*G][dim]: row k*G + g = sx_timestep_embedding's row for t = t_tab[g][step_dev[g]] (t_tab [G][ld_t] fp32), bit for bit; a slot
+ * whose step is outside [0, ld_t) (a parked slot: -1) embeds t = 0, which is finite */
+int sx_timestep_embedding_slots(const float* t_tab, int ld_t, const int32_t* step_dev, void* out, int G, int nb, int dim, int dtype,
+                                void* stream);
+/* last node of a slot step, in a launch of its own (every workgroup of sx_cfg_euler_step_slots reads the counters): a live slot's step
+ * becomes step + 1, or -1 once that reaches n_steps_dev[g] (the slot parks itself); a parked slot's becomes / stays -1 */
+int sx_denoise_advance(int32_t* step_dev, const int32_t* n_steps_dev, int G, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Image pre/post-processing: the byte work either side of the dense paths.
  * ------------------------------------------------------------------------------------------------ */

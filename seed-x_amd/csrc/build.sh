@@ -13,10 +13,10 @@ FAST="-ffast-math -fno-finite-math-only"
 if [ "$FORCE" = 1 ]; then rm -f "$HERE"/.obj/*.o; fi
 pids=()
 objs=()
-for f in gemm gemm_pp norm attn elementwise decode preproc comm precise lora; do
+for f in gemm gemm_pp norm attn elementwise decode preproc comm precise lora denoise_slots; do
   src="$HERE/$f.hip"; obj="$HERE/.obj/$f.o"
   objs+=("$obj")
-  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/sx_common.h" -nt "$obj" ] || [ "$HERE/gemm_common.h" -nt "$obj" ] || [ "$HERE/precise_rows.h" -nt "$obj" ] || [ "$HERE/../../include/seedx_hip.h" -nt "$obj" ]; then
+  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/sx_common.h" -nt "$obj" ] || [ "$HERE/gemm_common.h" -nt "$obj" ] || [ "$HERE/precise_rows.h" -nt "$obj" ] || [ "$HERE/glue_inline.h" -nt "$obj" ] || [ "$HERE/../../include/seedx_hip.h" -nt "$obj" ]; then
     extra="$FAST"
     if [ "$f" = "preproc" ] || [ "$f" = "precise" ] || [ "$f" = "lora" ]; then extra=""; fi   # integer / IEEE-exact float work, hi + lo operand splits, fixed fma chains: no fast-math
     # MFMA accumulators in arch VGPRs: the softmax / rescale VALU code touches every accumulator each KV tile, the

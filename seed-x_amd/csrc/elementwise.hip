@@ -1,6 +1,7 @@
 // Elementwise / layout kernels (HBM-bound; vectorised 8–16 B per lane, grid-stride).
 #include <stdarg.h>
 #include "sx_common.h"
+#include "glue_inline.h"
 
 // ---- error plumbing (shared by all translation units) -----------------------------------------------
 static thread_local char g_err[512] = "";
@@ -22,15 +23,7 @@ inline dim3 grid_for(int64_t n, int per_thread = 1) {
   return dim3((unsigned)blocks);
 }
 
-__device__ __forceinline__ float ld_as_f32(const void* p, int dt, int64_t i) {
-  if (dt == SX_F32) return ((const float*)p)[i];
-  const unsigned short u = ((const unsigned short*)p)[i];
-  return dt == SX_BF16 ? BF16::to_f32(u) : F16::to_f32(u);
-}
-__device__ __forceinline__ void st_from_f32(void* p, int dt, int64_t i, float v) {
-  if (dt == SX_F32) ((float*)p)[i] = v;
-  else ((unsigned short*)p)[i] = dt == SX_BF16 ? BF16::from_f32(v) : F16::from_f32(v);
-}
+using namespace sxk_glue;   // ld_as_f32 / st_from_f32, timestep_embedding_pair, cfg_euler_elem (shared with denoise_slots.hip)
 
 __global__ void cast_kernel(const void* src, int sdt, void* dst, int ddt, int64_t n) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -143,10 +136,7 @@ __global__ void timestep_embedding_kernel(const float* t, const int* idx_dev, vo
   const int total = n * half;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int j = i % half, r = i / half;
-    const float f = expf(-9.210340371976184f * (float)j / (float)half);  // ln(10000)
-    const float a = (fixed >= 0 ? t[fixed] : t[r]) * f;
-    st_from_f32(out, dt, (int64_t)r * dim + j, cosf(a));          // flip_sin_to_cos: cos first
-    st_from_f32(out, dt, (int64_t)r * dim + half + j, sinf(a));
+    timestep_embedding_pair(out, dt, dim, half, r, j, [&]() { return fixed >= 0 ? t[fixed] : t[r]; });
   }
 }
 
@@ -178,27 +168,8 @@ __global__ void cfg_euler_kernel(const float* eps, float* lat, float* scaled_nex
   const float sigma = sigmas[step], sigma_next = sigmas[step + 1];
   const float inv_next = rsqrtf(sigma_next * sigma_next + 1.0f);
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float x = lat[i];
-    float e;
-    if (mode == 0) {
-      const float eu = eps[i], et = eps[n + i];
-      e = eu + gs * (et - eu);
-    } else {
-      const float x0t = x - sigma * eps[i], x0i = x - sigma * eps[n + i], x0u = x - sigma * eps[2 * n + i];
-      const float x0 = x0u + gs * (x0t - x0i) + igs * (x0i - x0u);
-      e = (x0 - x) / (-sigma);
-    }
-    const float xn = x + e * (sigma_next - sigma);
-    lat[i] = xn;
-    if (scaled_next) {
-      const float sv = xn * inv_next;
-      const int64_t hw = i / C;
-      const int c = (int)(i - hw * C);
-      const int64_t HW = n / C;
-      for (int k = 0; k < nb; ++k) scaled_next[((int64_t)k * HW + hw) * ld + c] = sv;
-    }
-  }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    cfg_euler_elem(eps, lat, scaled_next, i, n, nb, C, ld, gs, igs, mode, sigma, sigma_next, inv_next);
 }
 
 __global__ void add_i32_kernel(int* p, int delta, int n) {

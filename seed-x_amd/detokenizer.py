@@ -16,6 +16,10 @@ the ``**kwargs`` the reference forwards to the diffusers pipeline.
 One denoise step = {time embeddings → UNet (CFG batch 2 or 3) → fused CFG + Euler update + next scaled input}, all
 device-resident (step counter, sigma table and timestep table live in HBM) and captured once into a HIP graph that is
 replayed ``num_inference_steps`` times.
+
+``generate_inflight`` serves a QUEUE of single generations, each with its own step count, guidance and seed, on the G slots
+of one captured step (``_SlotDenoiseLoop``): per-slot counters, tables and guidance scales in HBM, finished slots harvested and
+refilled between replays, nothing re-captured.
 """
 import math
 import os
@@ -240,6 +244,54 @@ class _DenoiseLoop:
         self.stagger = int(os.environ.get("SX_CHAIN_STAGGER", "0"))   # chain c starts when chain c-1 has passed this many progress marks
         self._side = None
 
+    def _chains_for(self, nloc):
+        """Concurrent kernel chains for a UNet batch of ``nloc`` rows (and the side streams they need)."""
+        chains = self.chains if (nloc % self.chains == 0 and nloc >= 2 * self.chains and self.unet.comm.world == 1) else 1
+        if chains > 1 and (self._side is None or len(self._side) < chains - 1):
+            self._side = [torch.cuda.Stream() for _ in range(chains - 1)]
+        return chains
+
+    def _unet_eps(self, scaled, temb, ctx, lo, hi, chains, H, W):
+        """eps [hi - lo, H*W, out_channels] fp32 of rows [lo, hi) of ``scaled``, the UNet run as ``chains`` kernel chains; ``temb`` and
+        ``ctx`` hold those rows only. The part of a denoise step that the lock-step and the slot loop share."""
+        unet = self.unet
+        nloc = hi - lo
+        if chains == 1:
+            return unet.forward_nhwc(scaled[lo:hi], temb, ctx, nloc, H, W)
+        # the samples of a UNet batch are independent: run them as `chains` concurrent kernel chains (forked HIP
+        # streams, captured as parallel branches of the step's graph). A chain's memory-bound kernels and kernel
+        # tails then fill under the other chain's MFMA-bound GEMMs instead of serialising behind them.
+        per = nloc // chains
+        eps = torch.empty((nloc, H * W, unet.cfg["out_channels"]), dtype=torch.float32, device=unet.device)
+        main = torch.cuda.current_stream()
+        fork = torch.cuda.Event()
+        fork.record(main)
+        parts = []
+        # stagger: identical chains started together run the SAME kernel at the same time (two HBM-bound launches compete,
+        # two MFMA-bound ones share the power budget); started `stagger` progress marks apart, a chain's HBM-bound launches
+        # meet the other chain's MFMA-bound ones on the CU pool
+        started = [torch.cuda.Event() for _ in range(chains - 1)] if self.stagger > 0 else None
+        for c in range(chains):
+            sl = slice(lo + c * per, lo + (c + 1) * per)
+            cctx = [[kv[c * per:(c + 1) * per] for kv in per_t] for per_t in ctx]
+            st = main if c == 0 else self._side[c - 1]
+            if c:
+                st.wait_event(fork)
+                if started is not None:
+                    st.wait_event(started[c - 1])
+            hook = None
+            if started is not None and c < chains - 1:
+                def hook(i, ev=started[c], s_=st):
+                    if i == self.stagger:
+                        ev.record(s_)
+            with torch.cuda.stream(st):
+                e = unet.forward_nhwc(scaled[sl], temb[c * per:(c + 1) * per], cctx, per, H, W, on_mark=hook)
+                ops.copy2d(e.view(-1, e.shape[-1]), eps[c * per:(c + 1) * per].view(-1, e.shape[-1]), 0)
+                parts.append(e)
+        for st in self._side[:chains - 1]:
+            main.wait_stream(st)
+        return eps
+
     def run(self, mode, latents_nchw, prompt_embeds, pooled, time_ids, scheduler, num_steps, guidance_scale,
             image_guidance_scale=1.5, image_latents_nchw=None, trace=None):
         """mode 0 (t2i): prompt_embeds ordered [uncond, text]; mode 1 (edit): [text, image, uncond].
@@ -298,47 +350,11 @@ class _DenoiseLoop:
             self._ctx_static = ctx
 
         nloc = hi - lo
-        chains = self.chains if (nloc % self.chains == 0 and nloc >= 2 * self.chains and unet.comm.world == 1) else 1
-        if chains > 1 and (self._side is None or len(self._side) < chains - 1):
-            self._side = [torch.cuda.Stream() for _ in range(chains - 1)]
+        chains = self._chains_for(nloc)
 
         def step_body():
             temb = unet.time_embeddings(S["ts"], S["step"], S["pooled"][lo:hi], S["tid"][lo:hi], nloc)
-            if chains == 1:
-                eps = unet.forward_nhwc(S["scaled"][lo:hi], temb, ctx, nloc, H, W)
-            else:
-                # the samples of a UNet batch are independent: run them as `chains` concurrent kernel chains (forked HIP
-                # streams, captured as parallel branches of the step's graph). A chain's memory-bound kernels and kernel
-                # tails then fill under the other chain's MFMA-bound GEMMs instead of serialising behind them.
-                per = nloc // chains
-                eps = torch.empty((nloc, H * W, unet.cfg["out_channels"]), dtype=torch.float32, device=dev)
-                main = torch.cuda.current_stream()
-                fork = torch.cuda.Event()
-                fork.record(main)
-                parts = []
-                # stagger: identical chains started together run the SAME kernel at the same time (two HBM-bound launches compete,
-                # two MFMA-bound ones share the power budget); started `stagger` progress marks apart, a chain's HBM-bound launches
-                # meet the other chain's MFMA-bound ones on the CU pool
-                started = [torch.cuda.Event() for _ in range(chains - 1)] if self.stagger > 0 else None
-                for c in range(chains):
-                    sl = slice(lo + c * per, lo + (c + 1) * per)
-                    cctx = [[kv[c * per:(c + 1) * per] for kv in per_t] for per_t in ctx]
-                    st = main if c == 0 else self._side[c - 1]
-                    if c:
-                        st.wait_event(fork)
-                        if started is not None:
-                            st.wait_event(started[c - 1])
-                    hook = None
-                    if started is not None and c < chains - 1:
-                        def hook(i, ev=started[c], s_=st):
-                            if i == self.stagger:
-                                ev.record(s_)
-                    with torch.cuda.stream(st):
-                        e = unet.forward_nhwc(S["scaled"][sl], temb[c * per:(c + 1) * per], cctx, per, H, W, on_mark=hook)
-                        ops.copy2d(e.view(-1, e.shape[-1]), eps[c * per:(c + 1) * per].view(-1, e.shape[-1]), 0)
-                        parts.append(e)
-                for st in self._side[:chains - 1]:
-                    main.wait_stream(st)
+            eps = self._unet_eps(S["scaled"], temb, ctx, lo, hi, chains, H, W)
             if cfgp:
                 eps = comm.all_gather(eps).reshape(NB, HW, -1)                    # [nb, G, HW, C] → [branch][generation]
             ops.cfg_euler_step(eps, S["lat"], S["scaled"], S["sig"], S["step"], nb, Cl, cin, guidance_scale,
@@ -372,6 +388,164 @@ class _DenoiseLoop:
                 self._graph.replay()
                 snap_trace(i + 1)
         return ops.nhwc_to_nchw(S["lat"], Cl, H, W)
+
+
+def slot_schedule(scheduler, num_steps, max_steps):
+    """One request's rows of the slot loop's tables, from ``scheduler.set_timesteps(num_steps)``: (sigmas [max_steps + 1] fp32 — the
+    schedule's num_steps + 1 sigmas, zero padded —, timesteps [max_steps] fp32, zero padded, init_noise_sigma, sigma_0)."""
+    if not 1 <= num_steps <= max_steps:
+        raise ValueError(f"num_inference_steps must be in 1..{max_steps} (max_steps), got {num_steps}")
+    scheduler.set_timesteps(num_steps)
+    sig = torch.zeros(max_steps + 1, dtype=torch.float32)
+    ts = torch.zeros(max_steps, dtype=torch.float32)
+    sig[:num_steps + 1] = scheduler.sigmas
+    ts[:num_steps] = scheduler.timesteps
+    return sig, ts, scheduler.init_noise_sigma, float(scheduler.sigmas[0])
+
+
+class _SlotDenoiseLoop(_DenoiseLoop):
+    """In-flight batching of the denoise loop: G generations ("slots") share ONE captured UNet step, rows ordered [branch][slot] as in
+    ``_DenoiseLoop.run``. Every slot has its own step counter, sigma / timestep table and guidance scales in device memory
+    (ops.timestep_embedding_slots, ops.cfg_euler_step_slots, ops.denoise_advance), so requests with any step count and guidance are
+    admitted into free slots and harvested between replays, and nothing is ever re-captured: the graph key holds no step count and no
+    guidance value. A slot is live when 0 <= step < n_steps and parked (-1) otherwise; a parked slot's rows still go through the UNet
+    (stale, finite data: wasted work) and the Euler kernel writes none of them. The UNet part of the step is the lock-step loop's
+    (``_unet_eps``: same launches, chain split and stagger at the same G). Single rank only."""
+
+    def __init__(self, unet, use_graph=True, comm=None):
+        super().__init__(unet, use_graph, comm)
+        self.check_single_rank()
+        self.graph_captures = 0
+        self._host_step, self._host_n = [], []
+
+    def check_single_rank(self):
+        for what, c in (("the denoise loop", self.comm), ("the UNet", getattr(self.unet, "comm", None))):
+            if c is not None and c.world > 1:
+                raise ValueError(f"in-flight batching of the de-tokenizer runs on one rank: {what} has comm.world = {c.world}")
+
+    def configure(self, mode, G, H, W, ehs_shape, pooled_dim, max_steps):
+        """(Re)allocates the state for G slots of [4, H, W] latents; ehs_shape = (tokens, dim) of one row of the conditioning. All slots
+        start parked on zeros. Returns True when the state is new."""
+        unet = self.unet
+        unet._pack()
+        dev = unet.device
+        nb = 2 if mode == 0 else 3
+        Cl, cin = 4, unet.cfg["in_channels"]
+        assert cin == (Cl if mode == 0 else 2 * Cl), f"UNet in_channels {cin} does not match mode {mode}"
+        key = (mode, G, H, W, tuple(ehs_shape), int(pooled_dim), int(max_steps), unet.dtype, str(dev), self.chains, self.stagger)
+        if self._state is not None and self._graph_key == key:
+            return False
+        NB, HW, f32, i32 = nb * G, H * W, torch.float32, torch.int32
+        z = lambda *shape, dtype=f32: torch.zeros(shape, dtype=dtype, device=dev)
+        self._state = dict(lat=z(G, HW, Cl), scaled=z(NB, HW, cin), ehs=z(NB, *ehs_shape), pooled=z(NB, pooled_dim), tid=z(NB, 6),
+                           sig_tab=z(G, max_steps + 1), t_tab=z(G, max_steps), step=torch.full((G,), -1, dtype=i32, device=dev),
+                           n_steps=z(G, dtype=i32), gs=z(G), igs=z(G))
+        self._dims = dict(mode=mode, nb=nb, G=G, H=H, W=W, Cl=Cl, cin=cin, max_steps=max_steps)
+        self._graph, self._graph_key, self.graph_captures = None, key, 0
+        self._host_step, self._host_n = [-1] * G, [0] * G
+        unet._ctx_key = None
+        self._ctx_static = unet.prepare_context(self._state["ehs"])       # the addresses the graph reads; rows rewritten at admission
+        return True
+
+    def admit(self, entries, scheduler):
+        """One admission round. ``entries``: [(slot, dict(latents [1,4,H,W] unit noise, num_steps, guidance_scale, image_guidance_scale,
+        ehs [nb, tokens, dim], pooled [nb, P], tid [nb, 6], image_latents [nb, 4, H, W] or None))] for parked slots. Writes the slots'
+        tables, latents (noise * init_noise_sigma), scaled model input of step 0 and conditioning rows, recomputes the cross-attention
+        K / V at the full [nb*G] batch shape (a GEMM over the admitted rows alone could pick other tiles than the lock-step loop's and
+        differ in bits) and copies the admitted rows into the context the graph reads; then the slots go live (step 0)."""
+        S, D, unet = self._state, self._dims, self.unet
+        dev = unet.device
+        nb, G, H, W, Cl, cin = D["nb"], D["G"], D["H"], D["W"], D["Cl"], D["cin"]
+        HW = H * W
+        scaled = S["scaled"].view(nb, G, HW, cin)
+        rows = []
+        for g, e in entries:
+            assert self._host_step[g] < 0, f"slot {g} is live"
+            n = int(e["num_steps"])
+            sig, ts, init_sigma, s0 = slot_schedule(scheduler, n, D["max_steps"])
+            S["sig_tab"][g].copy_(sig); S["t_tab"][g].copy_(ts)
+            S["n_steps"][g:g + 1].fill_(n)
+            S["gs"][g:g + 1].fill_(float(e["guidance_scale"])); S["igs"][g:g + 1].fill_(float(e["image_guidance_scale"]))
+            lat = e["latents"].to(dev, torch.float32) * init_sigma
+            ops.nchw_to_nhwc(lat, dst=S["lat"][g:g + 1])
+            scaled[:, g, :, :Cl] = S["lat"][g] / math.sqrt(s0 * s0 + 1.0)             # scale_model_input, step 0
+            if D["mode"] == 1:
+                il = e["image_latents"].to(dev, torch.float32)                        # [3,4,H,W] = [enc, enc, 0]
+                scaled[:, g, :, Cl:] = il.permute(0, 2, 3, 1).reshape(nb, HW, Cl)
+            for k in range(nb):
+                S["ehs"][k * G + g].copy_(e["ehs"][k].to(dev).float()); S["pooled"][k * G + g].copy_(e["pooled"][k].to(dev).float())
+                S["tid"][k * G + g].copy_(e["tid"][k].to(dev).float())
+                rows.append(k * G + g)
+        unet._ctx_key = None
+        ctx = unet.prepare_context(S["ehs"])
+        idx = torch.tensor(rows, dtype=torch.int64, device=dev)
+        for per_s, per_n in zip(self._ctx_static, ctx):
+            for kv_s, kv_n in zip(per_s, per_n):
+                if kv_s.data_ptr() != kv_n.data_ptr():
+                    kv_s.index_copy_(0, idx, kv_n.index_select(0, idx))
+        for g, e in entries:
+            S["step"][g:g + 1].zero_()
+            self._host_step[g], self._host_n[g] = 0, int(e["num_steps"])
+
+    def park_all(self):
+        """Parks every slot (a queue that ended early leaves none live for the next one)."""
+        self._state["step"].fill_(-1)
+        self._host_step = [-1] * self._dims["G"]
+
+    def _step_body(self, chains):
+        S, D, unet = self._state, self._dims, self.unet
+        nb, G = D["nb"], D["G"]
+        NB = nb * G
+        ts = ops.timestep_embedding_slots(S["t_tab"], S["step"], nb, unet.cfg["block_out_channels"][0], unet.dtype)
+        temb = unet.time_embeddings(None, None, S["pooled"], S["tid"], NB, ts=ts)
+        eps = self._unet_eps(S["scaled"], temb, self._ctx_static, 0, NB, chains, D["H"], D["W"])
+        ops.cfg_euler_step_slots(eps, S["lat"], S["scaled"], S["sig_tab"], S["step"], S["n_steps"], S["gs"], S["igs"], nb, D["Cl"],
+                                 D["cin"], D["mode"])
+        ops.denoise_advance(S["step"], S["n_steps"])
+
+    def _graphed(self):
+        return self.use_graph and self.comm.graph_safe and getattr(self.unet, "comm", self.comm).graph_safe
+
+    def ensure_graph(self):
+        """Captures the slot step, once per configuration, with every slot parked: the warm-up and the capture run then write no
+        latents and move no counter, so there is nothing to restore."""
+        if not self._graphed() or self._graph is not None:
+            return
+        assert all(s < 0 for s in self._host_step), "the slot step is captured with every slot parked"
+        chains = self._chains_for(self._dims["nb"] * self._dims["G"])
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self._step_body(chains)                                               # warm-up (allocator, lazy loads)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with ops.graph_capture(g):
+            self._step_body(chains)
+        self._graph = g
+        self.graph_captures += 1
+
+    def step(self):
+        """One UNet step of every slot (one graph replay). Returns the slots whose schedule ended with it — known from the host mirror
+        of the counters, so nothing is read back."""
+        if self._graphed():
+            self.ensure_graph()
+            self._graph.replay()
+        else:
+            self._step_body(self._chains_for(self._dims["nb"] * self._dims["G"]))
+        done = []
+        for g in range(self._dims["G"]):
+            if self._host_step[g] >= 0:
+                self._host_step[g] += 1
+                if self._host_step[g] >= self._host_n[g]:
+                    self._host_step[g] = -1
+                    done.append(g)
+        return done
+
+    def harvest(self, g):
+        """fp32 [1,4,H,W] latents of slot g (a copy: the slot may be refilled at once)."""
+        D = self._dims
+        return ops.nhwc_to_nchw(self._state["lat"][g:g + 1], D["Cl"], D["H"], D["W"])
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -414,6 +588,8 @@ class SDXLAdapter:
         self.visual_encoder = self.image_transform = self.discrete_model = self.vae = self.scheduler = None
         self._neg_cache = {}
         self._loop = None
+        self._slot_loop = None
+        self.last_inflight_stats = None
         self.use_graph = True
 
     @classmethod
@@ -443,6 +619,7 @@ class SDXLAdapter:
         self._neg_cache = {}
         if self._loop is not None:
             self._loop._graph = self._loop._state = self._loop._ctx_static = None
+        self._slot_loop = None
         return self
 
     def eval(self):
@@ -476,6 +653,7 @@ class SDXLAdapter:
         self.to(self.device, self.dtype)
         self._neg_cache = {}                                                        # new encoder / dtype → new negatives
         self._loop = _DenoiseLoop(self.unet, self.use_graph, comm=getattr(self, "comm", None))
+        self._slot_loop = None
 
     def _negative_embeds(self, image_size, pooled):
         """ViT features of an all-zero image: constant per model → cached (the reference recomputes a full ViT forward
@@ -569,8 +747,174 @@ class SDXLAdapter:
         return self._finish(out, output_type)
 
 
+    # ---- in-flight batching: a queue of single generations on the G slots of ONE captured UNet step ---------------------------------
+    _INFLIGHT_MODE = 0
+    _INFLIGHT_KEYS = ("image_pil", "image_tensor", "image_embeds", "seed", "latents", "num_inference_steps", "guidance_scale",
+                      "input_image_size")
+
+    def _check_request(self, i, req, height, width, max_steps):
+        """ValueError for a request that generate_inflight cannot run; touches nothing."""
+        err = lambda msg: ValueError(f"generate_inflight: request {i}: {msg}")
+        if not isinstance(req, dict):
+            raise err(f"a request is a dict of generate() arguments, got {type(req).__name__}")
+        unknown = sorted(set(req) - set(self._INFLIGHT_KEYS))
+        if unknown:
+            raise err(f"unknown keys {unknown}; allowed: {list(self._INFLIGHT_KEYS)}")
+        src = [k for k in ("image_pil", "image_tensor", "image_embeds") if req.get(k) is not None]
+        if len(src) != 1:
+            raise err(f"exactly one of image_pil / image_tensor / image_embeds is needed, got {src}")
+        if (req.get("seed") is None) == (req.get("latents") is None):
+            raise err("exactly one of seed / latents is needed")
+        n = req.get("num_inference_steps", 30)
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= max_steps:
+            raise err(f"num_inference_steps must be an int in 1..{max_steps} (max_steps), got {n!r}")
+        for k in ("guidance_scale", "image_guidance_scale"):
+            if k in req and not (isinstance(req[k], (int, float, np.integer, np.floating)) and not isinstance(req[k], bool)
+                                 and math.isfinite(req[k])):
+                raise err(f"{k} must be a finite number, got {req[k]!r}")
+        one = "a request is ONE generation"
+        if req.get("image_pil") is not None:
+            from PIL import Image
+            if not isinstance(req["image_pil"], Image.Image):
+                raise err(f"image_pil must be a PIL image ({one}), got {type(req['image_pil']).__name__}")
+        if req.get("image_tensor") is not None:
+            t = req["image_tensor"]
+            if not torch.is_tensor(t) or t.ndim not in (3, 4) or (t.ndim == 4 and t.shape[0] != 1):
+                raise err(f"image_tensor must be [3, S, S] or [1, 3, S, S] ({one}), got {tuple(getattr(t, 'shape', ()))}")
+        if req.get("image_embeds") is not None:
+            t = req["image_embeds"]
+            if not torch.is_tensor(t) or t.ndim not in (2, 3) or (t.ndim == 3 and t.shape[0] != 1):
+                raise err(f"image_embeds must be [tokens, dim] or [1, tokens, dim] ({one}), got {tuple(getattr(t, 'shape', ()))}")
+        if req.get("seed") is not None and (isinstance(req["seed"], bool) or not isinstance(req["seed"], (int, np.integer))):
+            raise err(f"seed must be one int ({one}), got {req['seed']!r}")
+        want = (4, height // 8, width // 8)
+        for k in ("latents",) + (("image_latents",) if "image_latents" in self._INFLIGHT_KEYS else ()):
+            t = req.get(k)
+            if t is not None and (not torch.is_tensor(t) or tuple(t.shape) not in (want, (1,) + want)):
+                raise err(f"{k} must be {list(want)} or {[1] + list(want)} for {height}x{width} ({one}), got {tuple(getattr(t, 'shape', ()))}")
+
+    def _request_condition(self, req, height, width):
+        """One request's conditioning rows ordered by guidance branch, as ``generate`` builds them for a batch of one:
+        (ehs [nb, tokens, dim], pooled [nb, P], image latents [nb, 4, h, w] or None, image_guidance_scale)."""
+        pe, pe_neg, pool, pool_neg = self._request_embeds(req)
+        return torch.cat([pe_neg, pe], dim=0), torch.cat([pool_neg, pool], dim=0), None, 1.5     # order [uncond, text]
+
+    def _request_embeds(self, req):
+        img = {k: req.get(k) for k in ("image_pil", "image_tensor", "image_embeds")}
+        if img["image_tensor"] is not None and img["image_tensor"].ndim == 3:
+            img["image_tensor"] = img["image_tensor"].unsqueeze(0)
+        if img["image_embeds"] is not None and img["image_embeds"].ndim == 2:
+            img["image_embeds"] = img["image_embeds"].unsqueeze(0)
+        return self.get_image_embeds(return_negative=True, image_size=req.get("input_image_size", 448), **img)
+
+    @torch.no_grad()
+    def generate_inflight(self, requests, slots=4, height=1024, width=1024, max_steps=128, output_type=None, max_admit=None):
+        """Serves a queue of single generations on ``slots`` slots of ONE captured UNet step (``_SlotDenoiseLoop``). Every request is
+        a dict of this adapter's ``generate`` arguments for ONE generation — exactly one of image_pil / image_tensor / image_embeds,
+        ``seed`` or ``latents``, ``num_inference_steps`` (1..max_steps, default 30), ``guidance_scale`` (default 7.5),
+        ``input_image_size`` and, for the edit adapter, ``latent_image`` / ``image_latents`` / ``image_guidance_scale`` — with its own
+        step count, guidance and seed. Scheduling is ``inflight.SlotScheduler``: first in, first out, lowest free slot first, finished
+        slots harvested after every step and refilled before the next (at most ``max_admit`` per pass); nothing is re-captured for a
+        new step count or guidance value. Conditioning is computed per request, as ``generate`` computes it for a batch of one.
+        Returns a list in request order of what ``generate`` returns for each request. ``last_inflight_stats``: unet_steps,
+        live_slot_steps, parked_slot_steps (a parked slot still costs its share of every UNet step), admissions, admission_passes and
+        graph_captures (captures of the slot step since its state was allocated: 1 under graph replay, 0 eager).
+        ValueError, before anything is touched, for a malformed request or a multi-rank loop / UNet."""
+        from .inflight import SlotScheduler
+        requests = list(requests)
+        if isinstance(slots, bool) or not isinstance(slots, int) or slots < 1:
+            raise ValueError(f"generate_inflight: slots must be an int >= 1, got {slots!r}")
+        if isinstance(max_steps, bool) or not isinstance(max_steps, int) or max_steps < 1:
+            raise ValueError(f"generate_inflight: max_steps must be an int >= 1, got {max_steps!r}")
+        if max_admit is not None and (isinstance(max_admit, bool) or not isinstance(max_admit, int) or max_admit < 1):
+            raise ValueError(f"generate_inflight: max_admit must be None or an int >= 1, got {max_admit!r}")
+        if height % 8 or width % 8 or height < 8 or width < 8:
+            raise ValueError(f"generate_inflight: height and width must be multiples of 8, got {height}x{width}")
+        for what, c in (("the denoise loop", getattr(self._loop, "comm", None)), ("the UNet", getattr(self.unet, "comm", None))):
+            if c is not None and c.world > 1:
+                raise ValueError(f"generate_inflight runs on one rank: {what} has comm.world = {c.world}")
+        for i, req in enumerate(requests):
+            self._check_request(i, req, height, width, max_steps)
+        stats = dict(unet_steps=0, live_slot_steps=0, parked_slot_steps=0, admissions=0, admission_passes=0, graph_captures=0)
+        if not requests:
+            self.last_inflight_stats = stats
+            return []
+        if self._loop is None:
+            raise RuntimeError("generate_inflight needs init_pipe() first")
+        self.last_inflight_stats = stats
+        mode, G, H, W = self._INFLIGHT_MODE, slots, height // 8, width // 8
+        nb = 2 if mode == 0 else 3
+        if self._slot_loop is None:
+            self._slot_loop = _SlotDenoiseLoop(self.unet, self._loop.use_graph)
+        loop = self._slot_loop
+        loop.use_graph, loop.chains, loop.stagger = self._loop.use_graph, self._loop.chains, self._loop.stagger
+        tid = self._time_ids(height, width, nb)
+        sch = SlotScheduler(G, len(requests), max_admit)
+        results = [None] * len(requests)
+        configured = False
+        while not sch.done:
+            sch.new_pass()
+            while True:
+                adm = sch.admit()
+                if not adm:
+                    break
+                entries = []
+                for g, r in adm:
+                    req = requests[r]
+                    ehs, pooled, il3, igs = self._request_condition(req, height, width)
+                    lat = req["latents"] if req.get("latents") is not None else self._noise(int(req["seed"]), height, width, 1)
+                    entries.append((g, dict(latents=lat.reshape(1, 4, H, W), num_steps=int(req.get("num_inference_steps", 30)),
+                                            guidance_scale=req.get("guidance_scale", 7.5), image_guidance_scale=igs, ehs=ehs,
+                                            pooled=pooled, tid=tid, image_latents=il3)))
+                if not configured:                        # the conditioning's shape is known from the first request on
+                    e0 = entries[0][1]
+                    if not loop.configure(mode, G, H, W, tuple(e0["ehs"].shape[1:]), e0["pooled"].shape[1], max_steps):
+                        loop.park_all()
+                    loop.ensure_graph()
+                    configured = True
+                loop.admit(entries, self.scheduler)
+                stats["admissions"] += len(adm)
+                stats["admission_passes"] += 1
+            live = sch.live_slots()
+            if not live:
+                continue
+            done = loop.step()
+            stats["unet_steps"] += 1
+            stats["live_slot_steps"] += len(live)
+            stats["parked_slot_steps"] += G - len(live)
+            for g in done:
+                results[sch.finish(g)] = self._finish(loop.harvest(g), output_type)
+        stats["graph_captures"] = loop.graph_captures
+        return results
+
+
 class SDXLAdapterWithLatentImage(SDXLAdapter):
     """Edit variant (adapter_modules.py:172-287): 8-channel UNet input, 3-way guidance."""
+    _INFLIGHT_MODE = 1
+    _INFLIGHT_KEYS = SDXLAdapter._INFLIGHT_KEYS + ("latent_image", "image_latents", "image_guidance_scale")
+
+    def _request_condition(self, req, height, width):
+        pe, pe_neg, pool, pool_neg = self._request_embeds(req)
+        image_latents = req.get("image_latents")
+        if image_latents is None:
+            if req.get("latent_image") is None:
+                image_latents = torch.zeros(1, 4, height // 8, width // 8)          # pipeline…:909-910 (no source image)
+            else:
+                src = vae_image_preprocess(req["latent_image"])                      # pipeline…:823
+                if src.shape[1] == 4:                                                # already latents (:500-505)
+                    image_latents = src
+                else:
+                    if self.vae is None:
+                        raise RuntimeError("an RGB `latent_image` needs a VAE with encoder weights (init_pipe(vae=...)); "
+                                           "or pass 4-channel latents = vae.encode(img).latent_dist.mode() (NOT scaled, :523)")
+                    image_latents = self.vae.encode(src).latent_dist.mode()
+                if tuple(image_latents.shape) != (1, 4, height // 8, width // 8):
+                    raise ValueError(f"generate_inflight: `latent_image` gives image latents {tuple(image_latents.shape)}, the request "
+                                     f"needs {(1, 4, height // 8, width // 8)}")
+        il = image_latents.to(self.device, torch.float32).reshape(1, 4, height // 8, width // 8)
+        il3 = torch.cat([il, il, torch.zeros_like(il)], dim=0)                       # [img, img, 0]  (:544-546)
+        return (torch.cat([pe, pe_neg, pe_neg], dim=0), torch.cat([pool, pool_neg, pool_neg], dim=0), il3,   # [text, image, uncond] (:884)
+                req.get("image_guidance_scale", 1.5))
 
     def __init__(self, unet, resampler, full_ft=False, set_trainable_late=False, vit_down=False):
         super().__init__(unet, resampler, full_ft=full_ft, vit_down=vit_down)

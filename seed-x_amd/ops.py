@@ -1562,6 +1562,50 @@ def cfg_euler_step(eps, latents, scaled_next, sigmas_dev, step_dev, nb, C_lat, l
                                 ld_scaled, float(gs), float(igs), mode, _stream()), "sx_cfg_euler_step")
 
 
+# ---- per-slot denoise step (in-flight batching of the de-tokenizer) ----------------------------------------------------
+def _slot_vec(t, G, dtype, what):
+    assert t.dtype == dtype and t.is_contiguous() and t.numel() == G and t.is_cuda, f"{what}: {dtype} [{G}] on the device"
+
+
+def cfg_euler_step_slots(eps, latents, scaled_next, sig_tab, step_dev, n_steps_dev, gs_dev, igs_dev, nb, C_lat, ld_scaled, mode):
+    """latents [G, HW, C] fp32, eps [nb*G, HW, C], scaled_next [nb*G, HW, ld_scaled] (or None), rows ordered [branch][slot];
+    sig_tab [G, ld_sig] fp32; step / n_steps int32 [G]; gs / igs fp32 [G]. Live slots (0 <= step < n_steps) take one CFG + Euler
+    step, bit for bit cfg_euler_step's; parked slots are left untouched."""
+    lib = _lib.load()
+    G = latents.shape[0]
+    n_slot = latents.numel() // G
+    f32 = torch.float32
+    assert latents.dtype == f32 and latents.is_contiguous() and eps.dtype == f32 and eps.is_contiguous()
+    assert eps.numel() == nb * G * n_slot, "eps must hold nb * G slots"
+    assert sig_tab.dtype == f32 and sig_tab.is_contiguous() and sig_tab.dim() == 2 and sig_tab.shape[0] == G
+    if scaled_next is not None:
+        assert scaled_next.dtype == f32 and scaled_next.is_contiguous() and scaled_next.numel() == nb * G * (n_slot // C_lat) * ld_scaled
+    _slot_vec(step_dev, G, torch.int32, "step"); _slot_vec(n_steps_dev, G, torch.int32, "n_steps")
+    _slot_vec(gs_dev, G, f32, "gs"); _slot_vec(igs_dev, G, f32, "igs")
+    check(lib.sx_cfg_euler_step_slots(_p(eps), _p(latents), _p(scaled_next), _p(sig_tab), sig_tab.shape[1], _p(step_dev), _p(n_steps_dev),
+                                      _p(gs_dev), _p(igs_dev), nb, G, n_slot, C_lat, ld_scaled, mode, _stream()),
+          "sx_cfg_euler_step_slots")
+
+
+def timestep_embedding_slots(t_tab, step_dev, nb, dim, dtype):
+    """t_tab [G, ld_t] fp32, step int32 [G] → [nb*G, dim]: row k*G + g embeds t_tab[g, step[g]] (t = 0 for a parked slot)."""
+    lib = _lib.load()
+    assert t_tab.dtype == torch.float32 and t_tab.is_contiguous() and t_tab.dim() == 2
+    G = t_tab.shape[0]
+    _slot_vec(step_dev, G, torch.int32, "step")
+    out = torch.empty((nb * G, dim), dtype=dtype, device=t_tab.device)
+    check(lib.sx_timestep_embedding_slots(_p(t_tab), t_tab.shape[1], _p(step_dev), _p(out), G, nb, dim, _DT[dtype], _stream()),
+          "sx_timestep_embedding_slots")
+    return out
+
+
+def denoise_advance(step_dev, n_steps_dev):
+    """step[g] += 1 for a live slot, -1 once it reaches n_steps[g]; parked slots stay -1."""
+    G = step_dev.numel()
+    _slot_vec(step_dev, G, torch.int32, "step"); _slot_vec(n_steps_dev, G, torch.int32, "n_steps")
+    check(_lib.load().sx_denoise_advance(_p(step_dev), _p(n_steps_dev), G, _stream()), "sx_denoise_advance")
+
+
 # ---- KV-cache prefix fork (prefix reuse of in-flight batching) --------------------------------------------------------
 KV_CACHE_KEYS = ("kc", "vc", "ks", "vs")
 

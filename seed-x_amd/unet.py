@@ -446,13 +446,16 @@ class UNet2DConditionModel:
         self._ctx_key, self._ctx = key, ctx
         return ctx
 
-    def time_embeddings(self, t_vals, idx_dev, text_embeds, time_ids, B):
+    def time_embeddings(self, t_vals, idx_dev, text_embeds, time_ids, B, ts=None):
         """emb = time_embedding(sinusoid(t)) + add_embedding([text_embeds | sinusoid(time_ids)]); returns the fused
         per-resnet time adds [B, sum(Co)] fp32. t_vals: fp32 device tensor of timesteps; idx_dev: optional device int
-        index into it (graph-replayable denoise step)."""
+        index into it (graph-replayable denoise step). ``ts``: the sinusoid [B, block_out_channels[0]] itself, already computed
+        (the slot loop: one timestep per slot, ops.timestep_embedding_slots) — t_vals / idx_dev are then not read."""
         P, dt, c = self._P, self.dtype, self.cfg
         boc0 = c["block_out_channels"][0]
-        ts = ops.timestep_embedding(t_vals, boc0, dt, idx_dev=idx_dev, n=B)
+        if ts is None:
+            ts = ops.timestep_embedding(t_vals, boc0, dt, idx_dev=idx_dev, n=B)
+        assert ts.shape == (B, boc0) and ts.dtype == dt
         e = ops.gemm(ts, P["te1"][0], bias=P["te1"][1], act="silu")
         e = ops.gemm(e, P["te2"][0], bias=P["te2"][1], out_dtype=torch.float32)
         tid = ops.timestep_embedding(time_ids.reshape(-1).float().contiguous(), c["addition_time_embed_dim"], torch.float32)
