@@ -650,6 +650,45 @@ typedef struct sx_kv_fork_args {
 } sx_kv_fork_args;
 int sx_kv_fork(const sx_kv_fork_args* args, void* stream);
 
+/* KV-cache rows <-> a linear staging buffer (the host-memory tier of the prefix cache, kvstore.py): sx_kv_fork generalised. ONE launch
+ * moves the first rows of any number of slots, every layer and head of ALL cache tensors of the model (kc, vc and, under the FP8
+ * format, ks, vs), between the caches and a device staging buffer: direction 0 packs (cache -> staging), 1 unpacks (staging -> cache).
+ * Every tensor is addressed as bytes, [outer][G][inner][Tmax][row_bytes] as in sx_kv_fork_args; outer, G, inner and Tmax are shared,
+ * the base pointer, the three strides and row_bytes are per tensor (passed by value: the kernel reads them from its arguments).
+ * Staging layout of job j, from byte offset[j] (a multiple of 16): spans in the order [tensor][outer][inner], the span of tensor t
+ * holding n * row_bytes[t] bytes (the rows [0, n) of one head) and taking that size rounded UP to a multiple of 16; the padding bytes
+ * are never read or written. sx_kv_rows_job_bytes states the size of a job; host and kernel compute it by this one rule.
+ * A job is SKIPPED (nothing is read or written) when slot[j] lies outside [0, G) or n_rows[j] <= 0 — and, as a guard, when its offset
+ * is not a multiple of 16 or its bytes would end beyond staging_bytes; n_rows[j] above Tmax is CLAMPED to Tmax. The jobs of a launch
+ * are not ordered: no two unpack jobs may name one slot, no two jobs may overlap in staging (ops.kv_rows_copy refuses both).
+ * 16-byte accesses wherever the cache span is 16-byte aligned (the staging side always is), 4-byte accesses for the tail of such spans
+ * and for whole spans that are not (scale rows under an odd Tmax); vector stores only, no LDS, no atomics.
+ * host_slot / host_n_rows / host_offset are the host's copies of the three device arrays: the entry point checks the jobs as the host
+ * states them. SX_ERR_INVALID, never a fall-back: a null pointer, n_tensors outside 1..4, an offset that is no multiple of 16, a job
+ * that ends beyond staging_bytes, staging not 16-byte aligned, a base / stride / row_bytes that is no multiple of 4, strides that do
+ * not describe the view, n_tensors * outer * inner or n_jobs above 65535, direction other than 0 / 1. */
+typedef struct sx_kv_tensor {
+  void* base;                                        /* bytes, viewed as [outer][G][inner][Tmax][row_bytes]  */
+  int64_t outer_stride, slot_stride, inner_stride;   /* bytes                                                */
+  int32_t row_bytes, reserved;
+} sx_kv_tensor;
+typedef struct sx_kv_rows_args {
+  sx_kv_tensor tensor[4];
+  const int32_t* slot;          /* device [n_jobs]                                                           */
+  const int32_t* n_rows;        /* device [n_jobs] rows [0, n) of the slot                                   */
+  const int64_t* offset;        /* device [n_jobs] byte offset of the job in staging                         */
+  const int32_t* host_slot;     /* host copies of the three arrays                                           */
+  const int32_t* host_n_rows;
+  const int64_t* host_offset;
+  void* staging;                /* device, 16-byte aligned                                                   */
+  int64_t staging_bytes;
+  int32_t n_tensors, n_jobs, outer, G, inner, Tmax, direction, reserved;
+} sx_kv_rows_args;
+int sx_kv_rows_copy(const sx_kv_rows_args* args, void* stream);
+/* bytes of one job of n_rows rows (clamped to Tmax; 0 for n_rows <= 0): outer * inner * sum over tensors of
+ * round_up(n * row_bytes[t], 16); -1 for n_tensors outside 1..4 */
+int64_t sx_kv_rows_job_bytes(const int32_t* row_bytes, int n_tensors, int outer, int inner, int Tmax, int n_rows);
+
 /* Decode tiles → the row-major matrix (LlamaForCausalLM(weight_residency="tiles"): the quantised tiles are the only copy of a
  * projection, prefill rebuilds it into a shared scratch buffer in front of its sx_gemm). The exact inverse of the packers of ops.py:
  * out[n][k] (16-bit, `dtype`, row-major [N][K]) = the value the skinny GEMM feeds its MFMAs for weight (n, k) —

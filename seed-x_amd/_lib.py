@@ -118,6 +118,17 @@ class KvForkArgs(C.Structure):
                 ("n_pairs", c_i32), ("outer", c_i32), ("G", c_i32), ("inner", c_i32), ("Tmax", c_i32), ("row_bytes", c_i32)]
 
 
+class KvTensor(C.Structure):
+    _fields_ = [("base", c_vp), ("outer_stride", c_i64), ("slot_stride", c_i64), ("inner_stride", c_i64), ("row_bytes", c_i32), ("reserved", c_i32)]
+
+
+class KvRowsArgs(C.Structure):
+    _fields_ = [("tensor", KvTensor * 4), ("slot", c_vp), ("n_rows", c_vp), ("offset", c_vp),
+                ("host_slot", c_vp), ("host_n_rows", c_vp), ("host_offset", c_vp), ("staging", c_vp), ("staging_bytes", c_i64),
+                ("n_tensors", c_i32), ("n_jobs", c_i32), ("outer", c_i32), ("G", c_i32), ("inner", c_i32), ("Tmax", c_i32),
+                ("direction", c_i32), ("reserved", c_i32)]
+
+
 class DequantTilesArgs(C.Structure):
     _fields_ = [("tiles", c_vp), ("w_scale", c_vp), ("w_block_scale", c_vp), ("out", c_vp), ("out_bytes", C.c_uint64),
                 ("w_dtype", c_i32), ("w_layout", c_i32), ("N", c_i32), ("K", c_i32), ("dtype", c_i32), ("reserved", c_i32)]
@@ -201,6 +212,8 @@ SIGNATURES = {
     "sx_spec_draft_ngram": [C.POINTER(SpecDraftArgs), c_vp],
     "sx_scatter_rows_spec": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp],
     "sx_kv_fork": [C.POINTER(KvForkArgs), c_vp],
+    "sx_kv_rows_copy": [C.POINTER(KvRowsArgs), c_vp],
+    "sx_kv_rows_job_bytes": [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32],      # returns int64_t
     "sx_dequant_tiles": [C.POINTER(DequantTilesArgs), c_vp],
     "sx_scatter_rows_step": [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp],
     "sx_add_i32_n": [c_vp, c_i32, c_i32, c_vp],
@@ -262,6 +275,7 @@ def load():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.argtypes = argtypes
         fn.restype = C.c_int
+    lib.sx_kv_rows_job_bytes.restype = C.c_int64
     lib.sx_last_error.argtypes = []
     lib.sx_last_error.restype = C.c_char_p
     _lib = lib

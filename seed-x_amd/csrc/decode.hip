@@ -2510,6 +2510,116 @@ extern "C" int sx_kv_fork(const sx_kv_fork_args* a, void* stream) {
   return SX_OK;
 }
 
+// ---- KV-cache rows <-> linear staging (include/seedx_hip.h: sx_kv_rows_copy) ------------------------------------------------------------
+// kv_fork_kernel with one side in a staging buffer. Block (x, y, z) = (byte chunk, tensor * outer * inner + outer index * inner + head,
+// job). The span of one (job, tensor, outer, inner) is n * row_bytes contiguous bytes on both sides; the staging side starts on a
+// multiple of 16 (offsets and span sizes are), so a 16-byte aligned cache span moves as 16-byte vectors (lane i at base + 16 i, four
+// independent loads per lane ahead of their stores) with a dword tail, any other span as dwords. The blocks of one span stride over
+// it. The small spans of a launch (scale rows: 4 bytes a row beside 128) share gridDim.x with the large ones: their extra blocks find
+// no work and leave.
+__host__ __device__ __forceinline__ int64_t kv_span_bytes(int64_t n, int32_t row_bytes) { return (n * row_bytes + 15) & ~(int64_t)15; }
+
+__global__ void __launch_bounds__(256) kv_rows_copy_kernel(sx_kv_rows_args a) {
+  const int job = blockIdx.z;
+  const int g = a.slot[job];
+  int n = a.n_rows[job];
+  const int64_t off = a.offset[job];
+  if (g < 0 || g >= a.G || n <= 0 || off < 0 || (off & 15)) return;                 // block-uniform: the skip rules
+  n = n > a.Tmax ? a.Tmax : n;
+  const int oi = a.outer * a.inner;
+  const int ti = blockIdx.y / oi, s = blockIdx.y - ti * oi;
+  const int o = s / a.inner, h = s - o * a.inner;
+  int64_t before = 0, total = 0;                                                    // the job's bytes in front of tensor ti, and in all
+  sx_kv_tensor t = a.tensor[0];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (k < a.n_tensors) {
+      const int64_t b = (int64_t)oi * kv_span_bytes(n, a.tensor[k].row_bytes);
+      before += k < ti ? b : 0;
+      total += b;
+      if (k == ti) t = a.tensor[k];
+    }
+  }
+  if (off + total > a.staging_bytes) return;                                        // the guard: never beyond the staging buffer
+  char* cp = (char*)t.base + (int64_t)o * t.outer_stride + (int64_t)g * t.slot_stride + (int64_t)h * t.inner_stride;
+  char* gp = (char*)a.staging + off + before + (int64_t)s * kv_span_bytes(n, t.row_bytes);
+  const char* sp = a.direction ? gp : cp;
+  char* dp = a.direction ? cp : gp;
+  const int64_t nbytes = (int64_t)n * t.row_bytes;
+  const int64_t body = ((uintptr_t)cp & 15) == 0 ? nbytes & ~(int64_t)15 : 0;
+  const int64_t stride = (int64_t)gridDim.x * 256, t0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint4* sv = (const uint4*)sp;
+  uint4* dv = (uint4*)dp;
+  const int64_t nvec = body >> 4;
+  int64_t v = t0;
+  for (; v + 3 * stride < nvec; v += 4 * stride) {                                  // full quads: four loads issued, then four stores
+    const uint4 r0 = sv[v], r1 = sv[v + stride], r2 = sv[v + 2 * stride], r3 = sv[v + 3 * stride];
+    dv[v] = r0;
+    dv[v + stride] = r1;
+    dv[v + 2 * stride] = r2;
+    dv[v + 3 * stride] = r3;
+  }
+  for (; v < nvec; v += stride) dv[v] = sv[v];                                      // the last, partial quad
+  const int64_t nw = (nbytes - body) >> 2;                                          // the tail words, or the whole unaligned span
+  for (int64_t w = t0; w < nw; w += stride) *(uint32_t*)(dp + body + w * 4) = *(const uint32_t*)(sp + body + w * 4);
+}
+
+extern "C" int64_t sx_kv_rows_job_bytes(const int32_t* row_bytes, int n_tensors, int outer, int inner, int Tmax, int n_rows) {
+  if (!row_bytes || n_tensors < 1 || n_tensors > 4) return -1;
+  const int64_t n = n_rows <= 0 ? 0 : (n_rows > Tmax ? Tmax : n_rows);
+  int64_t sum = 0;
+  for (int k = 0; k < n_tensors; ++k) sum += (int64_t)outer * inner * kv_span_bytes(n, row_bytes[k]);
+  return sum;
+}
+
+extern "C" int sx_kv_rows_copy(const sx_kv_rows_args* a, void* stream) {
+  SX_CHECK(a && a->slot && a->n_rows && a->offset && a->host_slot && a->host_n_rows && a->host_offset && a->staging,
+           "sx_kv_rows_copy: null pointer");
+  SX_CHECK(a->n_tensors >= 1 && a->n_tensors <= 4, "sx_kv_rows_copy: n_tensors=%d must be 1..4 (kc, vc, ks, vs)", a->n_tensors);
+  SX_CHECK(a->direction == 0 || a->direction == 1, "sx_kv_rows_copy: direction=%d must be 0 (pack) or 1 (unpack)", a->direction);
+  SX_CHECK(a->n_jobs >= 0 && a->n_jobs <= 65535, "sx_kv_rows_copy: n_jobs=%d must be 0..65535", a->n_jobs);
+  SX_CHECK(a->outer >= 1 && a->G >= 1 && a->inner >= 1 && a->Tmax >= 1, "sx_kv_rows_copy: bad dims");
+  SX_CHECK((int64_t)a->n_tensors * a->outer * a->inner <= 65535, "sx_kv_rows_copy: n_tensors * outer * inner = %lld exceeds 65535",
+           (long long)a->n_tensors * a->outer * a->inner);
+  SX_CHECK(((uintptr_t)a->staging & 15) == 0 && a->staging_bytes >= 0, "sx_kv_rows_copy: staging must be 16-byte aligned");
+  int32_t row_bytes[4];
+  int64_t max_span = 0;
+  for (int k = 0; k < a->n_tensors; ++k) {
+    const sx_kv_tensor& t = a->tensor[k];
+    SX_CHECK(t.base, "sx_kv_rows_copy: null pointer (tensor %d)", k);
+    SX_CHECK(t.row_bytes >= 4 && t.row_bytes % 4 == 0 && ((uintptr_t)t.base & 3) == 0 && t.outer_stride % 4 == 0 && t.slot_stride % 4 == 0 &&
+                 t.inner_stride % 4 == 0, "sx_kv_rows_copy: base, strides and row_bytes of tensor %d must be multiples of 4 bytes", k);
+    const int64_t span = (int64_t)a->Tmax * t.row_bytes;
+    SX_CHECK(t.inner_stride >= span && t.slot_stride >= (a->inner - 1) * t.inner_stride + span &&
+                 t.outer_stride >= (a->G - 1) * t.slot_stride + (a->inner - 1) * t.inner_stride + span,
+             "sx_kv_rows_copy: the strides of tensor %d do not describe [outer][G][inner][Tmax][row_bytes]", k);
+    row_bytes[k] = t.row_bytes;
+    max_span = span > max_span ? span : max_span;
+  }
+  int64_t longest = 0;
+  for (int j = 0; j < a->n_jobs; ++j) {                                             // the jobs as the host states them
+    const int64_t off = a->host_offset[j];
+    SX_CHECK(off >= 0 && off % 16 == 0, "sx_kv_rows_copy: offset[%d]=%lld must be a multiple of 16 (and >= 0)", j, (long long)off);
+    if (a->host_slot[j] < 0 || a->host_slot[j] >= a->G || a->host_n_rows[j] <= 0) continue;       // skipped by the kernel
+    const int64_t need = sx_kv_rows_job_bytes(row_bytes, a->n_tensors, a->outer, a->inner, a->Tmax, a->host_n_rows[j]);
+    SX_CHECK(off + need <= a->staging_bytes, "sx_kv_rows_copy: job %d (slot %d, %d rows) ends at byte %lld of a staging buffer of %lld",
+             j, a->host_slot[j], a->host_n_rows[j], (long long)(off + need), (long long)a->staging_bytes);
+    const int64_t n = a->host_n_rows[j] > a->Tmax ? a->Tmax : a->host_n_rows[j];
+    longest = n > longest ? n : longest;
+  }
+  if (a->n_jobs == 0 || longest == 0) return SX_OK;
+  // kv_fork's sizing: chunks of 16 KB (256 lanes x 4 vectors), as many blocks per span as fill the machine (~4096 in all) and no more
+  // than the longest span of the launch has chunks
+  const int64_t spans = (int64_t)a->n_jobs * a->n_tensors * a->outer * a->inner;
+  int64_t chunks = (max_span / a->Tmax * longest + 16383) / 16384;
+  int64_t gx = (4096 + spans - 1) / spans;
+  gx = gx < 1 ? 1 : (gx > chunks ? chunks : gx);
+  hipLaunchKernelGGL(kv_rows_copy_kernel, dim3((unsigned)gx, (unsigned)(a->n_tensors * a->outer * a->inner), (unsigned)a->n_jobs), dim3(256),
+                     0, ST, *a);
+  SX_HIP_LAUNCH_CHECK();
+  return SX_OK;
+}
+
 // ---- decode tiles → row-major 16-bit matrix (include/seedx_hip.h: sx_dequant_tiles) ---------------------------------------------------
 // The skinny GEMM's weight fragment load, run backwards: a wave takes one 64-k slab of a row group per step. The two half-waves own rows
 // 0..7 and 8..15 of the 16-row tile: lane (s = lane >> 5, r8 = (lane >> 2) & 7, g = lane & 3) loads what lane (row r8 + 8 s, group g) of

@@ -13,7 +13,8 @@
 With ``prefix_cache=True`` the engine also remembers what every slot's KV cache holds (``PrefixIndex``) and lets ``plan_admission``
 choose the slots of a round: a request whose prompt starts like a slot's record keeps those rows (in place, when the slot is free) or
 gets them copied from the donor slot by one sx_kv_fork launch, and prefills only the rest. The requests admitted per pass, hence the
-decode-step counts, are those of the plain schedule; ``simulate_prefix`` is ``simulate``'s counterpart with the token counts.
+decode-step counts, are those of the plain schedule; ``simulate_prefix`` is ``simulate``'s counterpart with the token counts. Records a
+slot is about to lose may be parked in host memory and restored later (kvstore.py: ``simulate_prefix(host_bytes=...)`` counts that too).
 
 On a paged KV cache (``LlamaForCausalLM(kv_pages=N)``) a request is admitted only when the pages for its prompt and budget are free:
 ``SlotScheduler.admit(fits)`` stops a round at a queue head that does not fit, and ``simulate_paged`` is ``simulate`` with that gate.
@@ -334,7 +335,8 @@ def plan_admission(index, free_slots, live_slots, requests, min_tokens, epoch=0)
     return [(c[1], c[0], c[2], c[3]) for c in placed], deferred
 
 
-def simulate_prefix(prompts, lengths, n_slots, max_admit=None, min_tokens=16, sigs=None, generated=None, index=None, adapters=None):
+def simulate_prefix(prompts, lengths, n_slots, max_admit=None, min_tokens=16, sigs=None, generated=None, index=None, adapters=None,
+                    host_bytes=0, host_min_tokens=16, row_bytes=1, host_store=None):
     """``simulate`` with prefix reuse: request i has the prompt ids ``prompts[i]`` (row signatures ``sigs[i]``; None: the ids themselves)
     and produces ``lengths[i]`` tokens by decode steps (a forced image chunk's tokens left out, as for ``simulate``). ``generated[i]``
     (optional) are ALL the ids it produced: a finished slot then holds its prompt and every produced id but the last, which later
@@ -343,7 +345,13 @@ def simulate_prefix(prompts, lengths, n_slots, max_admit=None, min_tokens=16, si
     prefill_passes counting the rounds actually run, plus prefill_tokens (rows forwarded at admission), prefix_hit_tokens (rows not
     forwarded), forked_tokens (those of them that were copied) and fork_launches (rounds with at least one copy).
     ``adapters[i]`` (optional): the LoRA adapter request i runs under, or None — its rows' signatures, prompt rows and fed-back rows
-    alike, are tagged with it (``tag_signatures``) exactly as the engine tags them."""
+    alike, are tagged with it (``tag_signatures``) exactly as the engine tags them.
+    ``host_bytes`` > 0 (default 0: nothing changes, no key is added) adds the host-memory tier of kvstore.py with that budget: every
+    round runs ``kvstore.plan_host_tier`` behind ``plan_admission`` exactly as the engine does, on a ``HostPrefixStore(host_bytes,
+    host_min_tokens, row_bytes)`` without buffers (``row_bytes``: the cache bytes of one token, ``llm.kv_row_bytes``), or on
+    ``host_store``, a store to start from and leave behind, as a second call of the engine finds it. The dict then also predicts
+    host_spills, host_spill_tokens, host_restores, host_restore_tokens (rows copied back: prefix hits, none of them forked),
+    host_evictions and host_bytes_peak (most bytes the store held during the call)."""
     lengths = [int(n) for n in lengths]
     prompts = [list(p) for p in prompts]
     sigs = prompts if sigs is None else [list(s) for s in sigs]
@@ -356,6 +364,12 @@ def simulate_prefix(prompts, lengths, n_slots, max_admit=None, min_tokens=16, si
     made = {}
     stats = dict(decode_steps=0, live_slot_steps=0, parked_slot_steps=0, admissions=0, prefill_passes=0, finish_order=[],
                  prefill_tokens=0, prefix_hit_tokens=0, forked_tokens=0, fork_launches=0)
+    store = host_store
+    if host_bytes or store is not None:
+        from .kvstore import HostPrefixStore, plan_host_tier
+        store = HostPrefixStore(host_bytes, host_min_tokens, row_bytes) if store is None else store
+        stats.update(host_spills=0, host_spill_tokens=0, host_restores=0, host_restore_tokens=0, host_evictions=0, host_bytes_peak=0)
+        evicted0, store.peak = store.evictions, store.bytes
 
     def finish(g):
         r = sch.finish(g)
@@ -370,6 +384,12 @@ def simulate_prefix(prompts, lengths, n_slots, max_admit=None, min_tokens=16, si
             if not cand:
                 break
             plan, _ = plan_admission(index, sch.free_slots(), sch.live_slots(), [(r, prompts[r], sigs[r]) for r in cand], min_tokens)
+            if store is not None:
+                plan, spills, restores = plan_host_tier(store, index, plan, {r: (prompts[r], sigs[r]) for r in cand}, 0, store.min_tokens)
+                stats["host_spills"] += len(spills)
+                stats["host_spill_tokens"] += sum(e.n_rows for _, e in spills)
+                stats["host_restores"] += len(restores)
+                stats["host_restore_tokens"] += sum(p for _, _, p in restores)
             stats["admissions"] += len(plan)
             stats["prefill_passes"] += 1
             stats["fork_launches"] += any(d is not None for _, _, _, d in plan)
@@ -396,4 +416,6 @@ def simulate_prefix(prompts, lengths, n_slots, max_admit=None, min_tokens=16, si
             made[g] += 1
             if made[g] >= lengths[sch.slot_req[g]]:
                 finish(g)
+    if store is not None:
+        stats["host_evictions"], stats["host_bytes_peak"] = store.evictions - evicted0, store.peak
     return stats

@@ -755,6 +755,15 @@ class LlamaForCausalLM:
                     "total": w + tiles + kv + sum(ad.values())}
         return {"weights": w, "decode_tiles": tiles, "kv_cache": kv, **ad, "total": w + tiles + kv + sum(ad.values())}
 
+    @property
+    def kv_row_bytes(self):
+        """Bytes the contiguous KV cache holds per token of one sequence, over every layer and head of this rank: memory_footprint()'s
+        "kv_cache" = G * Tmax * kv_row_bytes (1.2 MB at 13B dims with the mixed cache). What a spilled prefix costs per row in the
+        host tier of the prefix cache (kvstore.py). ``kv_v16`` is settled when the weights are packed: read it after ``_pack()``."""
+        if self.kv_format == "fp8_e4m3":
+            return self.L * self.nh_l * (2 * self.hd + 8)
+        return self.L * self.nh_l * self.hd * ((4 + (2 if self.kv_v16 else 4)) if self.precise else 4)
+
     def _adapter_slot_bytes(self):
         """Bytes of one adapter slot: R (K + N) 16-bit elements per projection (q, k, v, o: H x H; gate, up: I x H; down: H x I), the
         2 L + 1 fp32 gammas and the fp32 scale. 0.25 GB at 13B dims with R = 32."""

@@ -1646,3 +1646,70 @@ def kv_fork(caches, pairs):
                             len(pairs), t.shape[0], G, t.shape[2], Tmax, row * es)
         check(lib.sx_kv_fork(C.byref(a), _stream()), "sx_kv_fork")
     return len(caches)
+
+
+# ---- KV-cache rows <-> a linear staging buffer (the host-memory tier of the prefix cache) --------------------------------------
+def _kv_cache_list(caches):
+    if isinstance(caches, dict):
+        return [caches[k] for k in KV_CACHE_KEYS if caches.get(k) is not None]
+    return [caches] if isinstance(caches, torch.Tensor) else list(caches)
+
+
+def _kv_row_bytes(t):
+    return (t.shape[4] if t.dim() == 5 else 1) * t.element_size()
+
+
+def kv_rows_bytes(caches, n_rows):
+    """Bytes one job of ``n_rows`` rows (clamped to Tmax; 0 for n_rows <= 0) takes in the staging buffer of ``kv_rows_copy``: for every
+    cache tensor outer * inner spans of n_rows * row_bytes bytes, each rounded up to a multiple of 16 — the rule of
+    sx_kv_rows_job_bytes (include/seedx_hip.h), computed here without the library."""
+    caches = _kv_cache_list(caches)
+    outer, Tmax, inner = caches[0].shape[0], caches[0].shape[3], caches[0].shape[2]
+    n = min(max(int(n_rows), 0), Tmax)
+    return sum(outer * inner * ((n * _kv_row_bytes(t) + 15) // 16 * 16) for t in caches)
+
+
+def kv_rows_copy(caches, jobs, staging, direction):
+    """Moves cache rows [0, n) of slot ``slot`` between the caches and the bytes from ``offset`` of ``staging`` (a contiguous uint8 device
+    tensor) for every (slot, n, offset) of ``jobs``: every layer and head of ALL cache tensors in ONE sx_kv_rows_copy launch.
+    ``direction`` 0 packs (cache -> staging), 1 unpacks (staging -> cache). ``caches`` as for ``kv_fork``: the LLM's pack, one cache
+    tensor or a list of at most four. The layout of a job in staging: spans in the order [tensor][outer][inner], each n * row_bytes bytes
+    padded up to a multiple of 16 (``kv_rows_bytes`` gives a job's size; padding bytes are never touched). The kernel skips a job whose
+    slot is outside [0, G) or whose n <= 0; such jobs are passed on and take no part in the checks below. The jobs of a launch are not
+    ordered, so among the others two unpack jobs into one slot, n > Tmax and overlapping staging ranges raise ValueError; the entry
+    point refuses (RuntimeError) offsets that are no multiple of 16, a staging buffer too small for the jobs and more than four tensors."""
+    caches = _kv_cache_list(caches)
+    jobs = [(int(g), int(n), int(off)) for g, n, off in jobs]
+    assert caches, "kv_rows_copy: no cache tensor"
+    assert direction in (0, 1), "kv_rows_copy: direction is 0 (pack) or 1 (unpack)"
+    outer, G, inner, Tmax = caches[0].shape[:4]
+    live = [(g, n, off) for g, n, off in jobs if 0 <= g < G and n > 0]
+    if any(n > Tmax for _, n, _ in live):
+        raise ValueError(f"kv_rows_copy: a job is longer than the cache ({Tmax} rows): {jobs}")
+    if direction == 1 and len({g for g, _, _ in live}) != len(live):
+        raise ValueError(f"kv_rows_copy: a slot is unpacked into twice in one call: {jobs}")
+    end = 0
+    for off, n in sorted((off, n) for _, n, off in live):
+        if off < end:
+            raise ValueError(f"kv_rows_copy: the staging ranges of two jobs overlap: {jobs}")
+        end = off + kv_rows_bytes(caches[:4], n)
+    if not jobs:
+        return 0
+    assert staging.is_cuda and staging.dtype == torch.uint8 and staging.dim() == 1 and staging.is_contiguous(), \
+        "kv_rows_copy: staging is a contiguous uint8 device tensor"
+    lib = _lib.load()
+    a = _lib.KvRowsArgs()
+    for i, t in enumerate(caches[:4]):
+        assert t.is_cuda and t.dim() in (4, 5) and tuple(t.shape[:4]) == (outer, G, inner, Tmax), "kv_rows_copy: caches of one model"
+        es, row = t.element_size(), (t.shape[4] if t.dim() == 5 else 1)
+        assert t.stride(3) == row and (t.dim() == 4 or t.stride(4) == 1), "kv_rows_copy: a head's [Tmax, hd] block must be contiguous"
+        a.tensor[i] = _lib.KvTensor(t.data_ptr(), t.stride(0) * es, t.stride(1) * es, t.stride(2) * es, row * es, 0)
+    host32 = torch.tensor([[g for g, _, _ in jobs], [n for _, n, _ in jobs]], dtype=torch.int32)
+    host64 = torch.tensor([off for _, _, off in jobs], dtype=torch.int64)
+    dev32, dev64 = host32.to(staging.device), host64.to(staging.device)
+    a.slot, a.n_rows, a.offset = _p(dev32[0]), _p(dev32[1]), _p(dev64)
+    a.host_slot, a.host_n_rows, a.host_offset = host32[0].data_ptr(), host32[1].data_ptr(), host64.data_ptr()
+    a.staging, a.staging_bytes = _p(staging), staging.numel()
+    a.n_tensors, a.n_jobs, a.outer, a.G, a.inner, a.Tmax, a.direction = len(caches), len(jobs), outer, G, inner, Tmax, direction
+    check(lib.sx_kv_rows_copy(C.byref(a), _stream()), "sx_kv_rows_copy")
+    return 1

@@ -10,7 +10,8 @@ When ``<img>`` is emitted the 64 forced ``<img_i>`` tokens are run as ONE 65-tok
 ``generate_inflight`` serves a queue of any length on those G slots: the stop rule runs on the device, a finished slot idles
 inside the captured step and is refilled from the queue before the next one (inflight.py holds the schedule). With
 ``agent.prefix_cache = True`` an admitted request keeps, or gets copied from another slot by one sx_kv_fork launch, the cache rows of the
-longest prompt prefix some slot already holds, and prefills only the rest.
+longest prompt prefix some slot already holds, and prefills only the rest; ``agent.prefix_host_bytes > 0`` parks the rows a slot is about
+to lose in pinned host memory and copies them back for a later prompt that starts like them (kvstore.py).
 """
 import functools
 
@@ -45,6 +46,7 @@ class ContinuousLVLM:
     # default of ``prefix_min_tokens``: the fork / prefill crossover measured on the 40-layer model. Repeated runs put it at 4 or at 8
     # rows (at 4 the gain is below the run-to-run spread): the larger one (profiles/prefix_cache.md, prefix_cache_crossover_runs.md)
     PREFIX_MIN_TOKENS = 8
+    PREFIX_HOST_MIN_TOKENS = 8       # default of ``prefix_host_min_tokens`` (profiles/prefix_host.md)
 
     def __init__(self, llm, input_resampler, output_resampler, lm_loss_scale=1.0, rec_loss_scale=1.0,
                  add_patch_pos=False, vit_down=False, mse=False):
@@ -59,6 +61,11 @@ class ContinuousLVLM:
         self.chunk_forced_image_tokens = True
         self.prefix_cache = False        # generate_inflight: reuse the cache rows of a prompt prefix some slot already holds (opt-in)
         self.prefix_min_tokens = self.PREFIX_MIN_TOKENS   # shortest prefix worth a slot-to-slot copy, or worth waiting one round for
+        self.prefix_host_bytes = 0       # generate_inflight: budget of the host-memory tier behind prefix_cache (kvstore.py); 0 = off
+        # shortest record worth a spill and shortest host match worth a restore: the restore / prefill crossover measured on the 40-layer
+        # model, rounded up to a multiple of 8. The restore wins from the smallest length measured, 8 rows (0.27 against 14.5 ms), on
+        # (profiles/prefix_host.md, tools/bench_prefix_host.py)
+        self.prefix_host_min_tokens = self.PREFIX_HOST_MIN_TOKENS
         self.speculative = False         # generate_inflight: lossless speculative decoding on an LLM built with spec_tokens > 0 (opt-in)
         self.spec_ngram = (3, 1)         # (longest, shortest) n-gram of its prompt-lookup drafter
         self._conv = {}                  # sequence → (token ids, row fingerprints, LLM cache epoch, adapter name) held by its KV cache
@@ -589,6 +596,20 @@ class ContinuousLVLM:
         ``last_inflight_stats`` also counts prefix_hit_tokens, forked_tokens and fork_launches (inflight.simulate_prefix predicts them).
         Reused rows are the rows an earlier pass wrote: results agree with the uncached call like generate_batch's ``reuse_cache``
         (identical ids, states within the prefill-shape rounding).
+        The records are only as large as the slots: a free slot is the victim of the next unrelated request. ``agent.prefix_host_bytes
+        = N`` > 0 (0, the default: nothing is allocated, launched or counted differently; needs ``prefix_cache``, ValueError otherwise
+        and for a negative value, before anything is touched) adds a host-memory tier of N bytes behind them (kvstore.py). Behind
+        ``plan_admission`` every round runs spill → restore → fork → suffix prefill: a planned slot whose record holds more rows than
+        the request keeps there is SPILLED if the store wants it (>= ``agent.prefix_host_min_tokens`` rows, not covered by a stored
+        entry, within the budget) — one sx_kv_rows_copy launch packs the rows of every layer, head and cache tensor into a staging
+        buffer on this stream, a side stream copies them to pinned host memory — and a planned request whose longest host match has
+        >= ``prefix_host_min_tokens`` rows and more than the device gave it is RESTORED: host → staging → one unpack launch into its
+        slot, synchronously, and only the rest is prefilled. Least recently used entries are evicted under the budget; a hit never
+        depends on timing (it waits for the entry's copy). The store belongs to this pack (it goes when the pack or the special ids
+        change) and survives ``llm.reset()``, ``kv_epoch`` changes and outside writes: host copies are immutable. Works with every
+        contiguous cache form (fp32, mixed, 16-bit, FP8 codes + scales), adapters (tagged signatures) and ``agent.speculative``;
+        ``last_inflight_stats`` gains host_spills, host_spill_tokens, host_restores, host_restore_tokens, host_evictions and
+        host_bytes_peak (inflight.simulate_prefix(host_bytes=...) predicts them). Only free slots are spilled (no preemption).
         Speculative decoding is switched on the engine too: ``agent.speculative = True`` (off by default) with an LLM built with
         ``spec_tokens=K`` runs the verify step (``llm.decode_step(..., spec=True)``) instead of the plain slot step: every live slot
         feeds its current token and up to K ids drafted from its own history by prompt lookup (``agent.spec_ngram``) and keeps the
@@ -627,6 +648,14 @@ class ContinuousLVLM:
         ``agent.speculative`` and with ``force_image_at`` on the same request (follow-ups)."""
         llm = self.llm
         requests = list(requests)
+        host_bytes, host_min_tokens = self.prefix_host_bytes, self.prefix_host_min_tokens
+        if isinstance(host_bytes, bool) or not isinstance(host_bytes, int) or host_bytes < 0:
+            raise ValueError(f"generate_inflight: agent.prefix_host_bytes must be an int >= 0 (0: the host tier is off), got {host_bytes!r}")
+        if host_bytes and not self.prefix_cache:
+            raise ValueError("generate_inflight: agent.prefix_host_bytes needs agent.prefix_cache = True (the host tier spills and restores "
+                             "the records of the prefix cache)")
+        if host_bytes and (isinstance(host_min_tokens, bool) or not isinstance(host_min_tokens, int) or host_min_tokens < 1):
+            raise ValueError(f"generate_inflight: agent.prefix_host_min_tokens must be an int >= 1, got {host_min_tokens!r}")
         gnames = self._grammar_names("generate_inflight", requests, [req.get("force_image_at") is not None for req in requests])
         constrained = any(n is not None for n in gnames)
         if constrained:
@@ -692,7 +721,9 @@ class ContinuousLVLM:
         rows = max(budget) + 8 + K
         keep = self._inflight
         if keep is None or keep["key"] != (tuple(img_ids), eos, G, id(P)) or keep["out_ids"].shape[1] < rows:
+            same = keep is not None and keep["key"] == (tuple(img_ids), eos, G, id(P))
             keep = self._inflight = dict(
+                host=keep.get("host") if same else None,        # the host tier's store belongs to the pack: another pack, another store
                 key=(tuple(img_ids), eos, G, id(P)),
                 img_ids_dev=torch.tensor(img_ids, dtype=torch.int32, device=dev),
                 out_ids=torch.full((G, rows), -1, dtype=torch.int32, device=dev),
@@ -702,6 +733,14 @@ class ContinuousLVLM:
         index = None
         if prefix_cache:                                 # what each slot's cache holds; lives next to the buffers, across calls
             index = keep["prefix"] = keep["prefix"] or PrefixIndex(G)
+        store = mover = None
+        if host_bytes:                                   # the host tier: the store and its staging buffers live next to the records
+            from .kvstore import HostPrefixStore, KVMover, plan_host_tier
+            if keep.get("host") is None:
+                keep["host"] = (HostPrefixStore(host_bytes, host_min_tokens, llm.kv_row_bytes), KVMover(P))
+            store, mover = keep["host"]
+            store.budget, store.min_tokens = host_bytes, host_min_tokens       # (a smaller budget takes effect at the next spill)
+            evicted0, store.peak = store.evictions, store.bytes
 
         def owned(fn, *a):
             # a step of this call that moves kv_epoch without touching a recorded row: the records move with it. A write from outside
@@ -756,6 +795,8 @@ class ContinuousLVLM:
             self.last_spec_emitted = [[] for _ in range(N)]      # per request: tokens emitted by each verify step it was live in
         if prefix_cache:
             stats.update(prefix_hit_tokens=0, forked_tokens=0, fork_launches=0)
+        if store is not None:
+            stats.update(host_spills=0, host_spill_tokens=0, host_restores=0, host_restore_tokens=0, host_evictions=0, host_bytes_peak=0)
         if paged:
             stats.update(page_waits=0, peak_pages=0)
             llm._pool.peak = llm._pool.used             # (0: the reset above released every sequence)
@@ -912,14 +953,24 @@ class ContinuousLVLM:
                     harvest(g, n_new[g])
 
         def admit_round_prefix(cand):
-            # plan → fork → suffix prefill. The forks of a round are issued before its prefill: a donor's rows are read as they were
+            # plan → (host tier: spill → restore) → fork → suffix prefill. The forks of a round are issued before its prefill: a donor's
+            # rows are read as they were; so are the packs of the records the round is about to overwrite
             for r in cand:
                 if r not in prompts:                     # (a deferred request keeps its embeddings for the next round)
                     ids, x = self._prompt_embeds(tokenizer, requests[r])
                     prompts[r] = (ids, x, sigs_of(x, names[r]))
             plan, _ = plan_admission(index, sched.free_slots(), sched.live_slots(), [(r, prompts[r][0], prompts[r][2]) for r in cand],
                                      prefix_min_tokens, llm.kv_epoch)
-            forks = [(d, g, start) for g, _, start, d in plan if d is not None]
+            if store is not None:
+                plan, spills, restores = plan_host_tier(store, index, plan, {r: (prompts[r][0], prompts[r][2]) for r in cand},
+                                                        llm.kv_epoch, host_min_tokens)
+                mover.spill(spills)                      # packed on this stream, ahead of everything that rewrites the rows
+                mover.restore(restores)
+                stats["host_spills"] += len(spills)
+                stats["host_spill_tokens"] += sum(e.n_rows for _, e in spills)
+                stats["host_restores"] += len(restores)
+                stats["host_restore_tokens"] += sum(p for _, _, p in restores)
+            forks =[(d, g, start) for g, _, start, d in plan if d is not None]
             if forks:
                 ops.kv_fork(P, forks)
                 stats["fork_launches"] += 1
@@ -1004,6 +1055,8 @@ class ContinuousLVLM:
         if paged:
             stats["peak_pages"] = llm._pool.peak
         owned(llm.reset)                                 # pos / ctx / step leave their idle values
+        if store is not None:
+            stats["host_evictions"], stats["host_bytes_peak"] = store.evictions - evicted0, store.peak
         self.last_inflight_stats = stats
         return results
 
