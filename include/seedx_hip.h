@@ -892,6 +892,21 @@ int sx_silu_cast(const float* x, void* y, int dtype, int64_t n, void* stream);
 int sx_cfg_euler_step(const float* eps, float* latents, float* scaled_next, const float* sigmas_dev,
                       const int32_t* step_dev, int nb, int64_t n, int C, int ld_scaled, float gs, float igs, int mode,
                       void* stream);
+/* Fused classifier-free guidance + DPM-Solver++(2M) step (Lu et al. 2022, Algorithm 2: second order, multistep, one UNet evaluation per
+ * step) on the same buffers and layout as sx_cfg_euler_step, plus x0_prev [HW][C] fp32, the previous step's denoised sample.
+ * coef_dev [steps][3] fp32 holds (a, b, c) of every step, computed on the host (seedx_amd/solvers.py: a = sigma'/sigma,
+ * b = 1 - e^-h, c = h / (2 h_last); c = 0 on step 0 and on the step onto sigma' = 0, whose row is (0, 1, 0)): the kernel takes no
+ * logarithm or exponential.
+ *     mode 0: e = e0 + gs*(e1 - e0);  x0 = lat - sigma*e
+ *     mode 1: x0_k = lat - sigma*e_k;  x0 = x0_u + gs*(x0_t - x0_i) + igs*(x0_i - x0_u)
+ *     d = x0 + c*(x0 - x0_prev);  lat = a*lat + b*d;  x0_prev = x0;  scaled[k][hw][c] = lat / sqrt(sigma_next^2 + 1), k < nb
+ * x0_prev is NOT read when c = 0, so it needs no initial value. scaled_next may be NULL; channels C..ld_scaled-1 are never written.
+ * step is read from *step_dev; a negative step reads row 0, and the caller keeps step + 1 inside sigmas_dev (the kernel knows no table
+ * length, like sx_cfg_euler_step). n = 0 is SX_OK. SX_ERR_INVALID: a null pointer, nb / mode other than (2, 0) or (3, 1), C <= 0,
+ * n % C != 0, ld_scaled < C. */
+int sx_cfg_dpmpp2m_step(const float* eps, float* latents, float* x0_prev, float* scaled_next, const float* sigmas_dev,
+                        const float* coef_dev, const int32_t* step_dev, int nb, int64_t n, int C, int ld_scaled, float gs, float igs,
+                        int mode, void* stream);
 
 /* In-flight batching of the denoise loop: G generations ("slots") share ONE captured UNet step, rows ordered [branch][slot], and every
  * slot carries its own step counter, schedule and guidance scales in device memory. Slot g is LIVE when 0 <= step_dev[g] < n_steps_dev[g],
@@ -906,6 +921,16 @@ int sx_cfg_euler_step(const float* eps, float* latents, float* scaled_next, cons
 int sx_cfg_euler_step_slots(const float* eps, float* latents, float* scaled_next, const float* sig_tab, int ld_sig,
                             const int32_t* step_dev, const int32_t* n_steps_dev, const float* gs_dev, const float* igs_dev, int nb,
                             int G, int64_t n_slot, int C, int ld_scaled, int mode, void* stream);
+/* sx_cfg_dpmpp2m_step on every live slot (x0_prev [G][HW][C]; the other buffers as for sx_cfg_euler_step_slots) with the slot's own
+ * sigmas sig_tab[g][step], sig_tab[g][step + 1] and coefficients coef_tab[g][step] (coef_tab [G][ld_sig][3] fp32; the indices are
+ * clamped into [0, ld_sig)). The arithmetic is sx_cfg_dpmpp2m_step's instruction for instruction: a live slot's latents, x0_prev and
+ * scaled_next rows equal that kernel's bit for bit. For a parked slot nothing is written: not its latents, not its x0_prev, not its rows
+ * of scaled_next. One launch may hold slots on step 0 (c = 0), mid-way and on their last step (sigma' = 0). The step counters move with
+ * sx_denoise_advance, as for the Euler step. */
+int sx_cfg_dpmpp2m_step_slots(const float* eps, float* latents, float* x0_prev, float* scaled_next, const float* sig_tab,
+                              const float* coef_tab, int ld_sig, const int32_t* step_dev, const int32_t* n_steps_dev,
+                              const float* gs_dev, const float* igs_dev, int nb, int G, int64_t n_slot, int C, int ld_scaled, int mode,
+                              void* stream);
 /* out [nb*G][dim]: row k*G + g = sx_timestep_embedding's row for t = t_tab[g][step_dev[g]] (t_tab [G][ld_t] fp32), bit for bit; a slot
  * whose step is outside [0, ld_t) (a parked slot: -1) embeds t = 0, which is finite */
 int sx_timestep_embedding_slots(const float* t_tab, int ld_t, const int32_t* step_dev, void* out, int G, int nb, int dim, int dtype,

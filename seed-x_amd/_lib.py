@@ -254,6 +254,9 @@ SIGNATURES = {
     "sx_l2norm_dim1": [c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp],
     "sx_cfg_euler_step": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_f32, c_f32, c_i32, c_vp],
     "sx_cfg_euler_step_slots": [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i64, c_i32, c_i32, c_i32, c_vp],
+    "sx_cfg_dpmpp2m_step": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_f32, c_f32, c_i32, c_vp],
+    "sx_cfg_dpmpp2m_step_slots": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i64, c_i32, c_i32,
+                                  c_i32, c_vp],
     "sx_timestep_embedding_slots": [c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp],
     "sx_denoise_advance": [c_vp, c_vp, c_i32, c_vp],
 }

@@ -1,5 +1,6 @@
 // Inline device functions shared by elementwise.hip and denoise_slots.hip: the lock-step kernels (timestep_embedding_kernel,
-// cfg_euler_kernel) and their per-slot forms are compiled from ONE body each, so a slot's result is the lock-step kernel's bit for bit.
+// cfg_euler_kernel, cfg_dpmpp2m_kernel) and their per-slot forms are compiled from ONE body each, so a slot's result is the lock-step
+// kernel's bit for bit.
 #pragma once
 #include "sx_common.h"
 
@@ -47,6 +48,37 @@ __device__ __forceinline__ void cfg_euler_elem(const float* eps, float* lat, flo
     const int c = (int)(i - hw * C);
     const int64_t HW = eps_bs / C;
     for (int k = 0; k < nb; ++k) scaled_next[((int64_t)k * HW + hw) * ld + c] = sv;
+  }
+}
+
+// CFG + DPM-Solver++(2M) update of element i of ONE generation, laid out as cfg_euler_elem's: x0 the guided denoised sample,
+// d = x0 + c (x0 - x0_prev), x' = a x + b d, x0_prev <- x0. (a, b, c) is the step's row of the host table (seedx_amd/solvers.py): no
+// logarithm or exponential here. c == 0 (step 0, and the step onto sigma_next = 0) is the same in every lane and skips the read of
+// x0_prev, so whatever the buffer holds before step 0 is harmless. Shared by the lock-step and the per-slot kernel.
+__device__ __forceinline__ void cfg_dpmpp2m_elem(const float* eps, float* lat, float* x0_prev, float* scaled_next, int64_t i,
+                                                 int64_t eps_bs, int nb, int C, int ld, float gs, float igs, int mode, float sigma, float a,
+                                                 float b, float c, float inv_next) {
+  const float x = lat[i];
+  float x0;
+  if (mode == 0) {
+    const float eu = eps[i], et = eps[eps_bs + i];
+    const float e = eu + gs * (et - eu);
+    x0 = x - sigma * e;
+  } else {
+    const float x0t = x - sigma * eps[i], x0i = x - sigma * eps[eps_bs + i], x0u = x - sigma * eps[2 * eps_bs + i];
+    x0 = x0u + gs * (x0t - x0i) + igs * (x0i - x0u);
+  }
+  float d = x0;
+  if (c != 0.0f) d = x0 + c * (x0 - x0_prev[i]);
+  const float xn = a * x + b * d;
+  lat[i] = xn;
+  x0_prev[i] = x0;
+  if (scaled_next) {
+    const float sv = xn * inv_next;
+    const int64_t hw = i / C;
+    const int ch = (int)(i - hw * C);
+    const int64_t HW = eps_bs / C;
+    for (int k = 0; k < nb; ++k) scaled_next[((int64_t)k * HW + hw) * ld + ch] = sv;
   }
 }
 

@@ -8,6 +8,8 @@ Reference interfaces mirrored (same names, argument meaning, defaults):
   * t2i loop ``StableDiffusionXLPipeline.__call__`` [ext diffusers 0.25.0] as driven by adapter_modules.py:156-167
   * edit loop ``StableDiffusionXLText2ImageAndEditPipeline.__call__``  pipeline_stable_diffusion_xl_t2i_edit.py:900-963
   * ``EulerDiscreteScheduler`` [ext] with the SDXL scheduler config (eval_seed_x_detokenizer.py:30)
+  * ``DPMSolverMultistepScheduler`` [ext], opt-in through ``init_pipe(scheduler=...)``: DPM-Solver++(2M), optionally over Karras sigmas
+    (solvers.py states the rule; the loops pick the step kernel by the scheduler's ``order``)
 ``generate`` returns what the reference returns — a list of PIL images (``sdxl_pipe(...).images``,
 adapter_modules.py:156-169 / :273-287) — whenever a VAE was given to ``init_pipe``; without a VAE (the reference would
 fail there) it returns the final latents. ``output_type`` ("pil" | "np" | "pt" | "latent" | "raw" | "u8" = device uint8 [B,H,W,3]) overrides, exactly like
@@ -226,9 +228,56 @@ class EulerDiscreteScheduler:
         return float((self.sigmas.max() ** 2 + 1) ** 0.5)
 
 
+class DPMSolverMultistepScheduler(EulerDiscreteScheduler):
+    """diffusers' DPMSolverMultistepScheduler [ext] in the one form the device step implements: DPM-Solver++(2M) (Lu et al. 2022,
+    Algorithm 2; ``algorithm_type="dpmsolver++"``, ``solver_order=2``, epsilon prediction) over the SDXL training sigmas, `leading`
+    spacing, optionally re-spaced by Karras et al. (rho = 7) between the same sigma_min and sigma_max. One UNet evaluation per step,
+    as Euler. The rule and the tables are ``solvers.py``'s; ``set_timesteps`` fills ``timesteps`` (fp32, fractional under Karras),
+    ``sigmas`` (n + 1, the last 0) and ``coefficients`` ([n, 3] rows (a, b, c)). Without Karras, sigmas and timesteps are exactly
+    EulerDiscreteScheduler's. The denoise loops pick the step kernel by ``order``."""
+    order = 2
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, steps_offset=1, use_karras_sigmas=False,
+                 algorithm_type="dpmsolver++", solver_order=2, **kw):
+        if algorithm_type != "dpmsolver++":
+            raise ValueError(f"DPMSolverMultistepScheduler: algorithm_type {algorithm_type!r} is not implemented (only 'dpmsolver++')")
+        if solver_order != 2:
+            raise ValueError(f"DPMSolverMultistepScheduler: solver_order {solver_order!r} is not implemented (only 2)")
+        self._check_config(kw)
+        super().__init__(num_train_timesteps, beta_start, beta_end, steps_offset)
+        self.config.update(use_karras_sigmas=bool(use_karras_sigmas), algorithm_type=algorithm_type, solver_order=solver_order)
+        self.coefficients = None
+
+    @staticmethod
+    def _check_config(j):
+        for key, want in (("timestep_spacing", "leading"), ("beta_schedule", "scaled_linear"), ("prediction_type", "epsilon")):
+            if j.get(key, want) != want:
+                raise ValueError(f"DPMSolverMultistepScheduler: {key} {j[key]!r} is not implemented (only {want!r})")
+
+    @classmethod
+    def from_pretrained(cls, path, subfolder=None):
+        import json
+        j = json.load(open(os.path.join(path, subfolder or "", "scheduler_config.json")))
+        return cls(j["num_train_timesteps"], j["beta_start"], j["beta_end"], j.get("steps_offset", 0),
+                   **{k: j[k] for k in ("use_karras_sigmas", "algorithm_type", "solver_order", "timestep_spacing", "beta_schedule",
+                                        "prediction_type") if k in j})
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        from . import solvers
+        super().set_timesteps(num_inference_steps)
+        sig = self.sigmas.numpy().astype(np.float64)
+        if self.config["use_karras_sigmas"] and num_inference_steps > 1:
+            ac = self.alphas_cumprod.numpy().astype(np.float64)
+            sig = np.concatenate([solvers.karras_sigmas(sig[num_inference_steps - 1], sig[0], num_inference_steps), [0.0]])
+            ts = solvers.sigma_to_t(sig[:-1], ((1 - ac) / ac) ** 0.5)
+            self.timesteps, self.sigmas = torch.from_numpy(ts.astype(np.float32)), torch.from_numpy(sig.astype(np.float32))
+        self.coefficients = torch.from_numpy(solvers.dpmpp2m_coefficients(self.sigmas.numpy()))   # of the fp32 sigmas the kernel reads
+
+
 # ---------------------------------------------------------------------------------------------------------------
 class _DenoiseLoop:
-    """Device-resident CFG + Euler loop around UNet.forward_nhwc, one HIP graph replay per step.
+    """Device-resident CFG + Euler (or, for a scheduler of order 2, DPM-Solver++(2M)) loop around UNet.forward_nhwc, one HIP graph
+    replay per step.
 
     ``comm`` with world == nb (2 for t2i, 3 for edit): CFG-parallel — rank r runs guidance branch r of every generation
     (UNet batch G instead of nb·G), the eps of all branches are all-gathered once per step (G·H·W·4 fp32 per rank) and
@@ -312,8 +361,12 @@ class _DenoiseLoop:
         scheduler.set_timesteps(num_steps)
         ts_dev = scheduler.timesteps.to(dev)
         sig_dev = scheduler.sigmas.to(dev)
+        order = getattr(scheduler, "order", 1)
+        if order not in (1, 2):
+            raise ValueError(f"the denoise loop has a step kernel for schedulers of order 1 (Euler) and 2 (DPM-Solver++(2M)), got order {order}")
+        # the solver is part of the key: a pipe that swaps schedulers re-captures instead of replaying the other solver's step
         key = (mode, G, H, W, num_steps, float(guidance_scale), float(image_guidance_scale), tuple(prompt_embeds.shape),
-               tuple(pooled.shape), tuple(time_ids.shape), unet.dtype, str(dev), self.chains, self.stagger)
+               tuple(pooled.shape), tuple(time_ids.shape), unet.dtype, str(dev), self.chains, self.stagger, order)
         if self._state is None or self._graph_key != key:
             self._state = dict(lat=torch.empty((G, HW, Cl), dtype=torch.float32, device=dev),
                                scaled=torch.zeros((NB, HW, cin), dtype=torch.float32, device=dev),
@@ -322,6 +375,9 @@ class _DenoiseLoop:
                                pooled=torch.empty(pooled.shape, dtype=torch.float32, device=dev),
                                tid=torch.empty(time_ids.shape, dtype=torch.float32, device=dev),
                                ts=torch.empty_like(ts_dev), sig=torch.empty_like(sig_dev))
+            if order == 2:                               # the previous denoised sample (not read on step 0) and the (a, b, c) rows
+                self._state.update(x0_prev=torch.empty((G, HW, Cl), dtype=torch.float32, device=dev),
+                                   coef=torch.empty((num_steps, 3), dtype=torch.float32, device=dev))
             self._graph, self._graph_key = None, key
             self._ctx_static = None
         S = self._state
@@ -330,6 +386,8 @@ class _DenoiseLoop:
         assert not cfgp or comm.world == nb, f"CFG-parallel needs one rank per guidance branch ({nb}), got {comm.world}"
         lo, hi = (comm.rank * G, (comm.rank + 1) * G) if cfgp else (0, NB)      # this rank's rows of the [branch][gen] batch
         S["ts"].copy_(ts_dev); S["sig"].copy_(sig_dev)
+        if order == 2:
+            S["coef"].copy_(scheduler.coefficients.to(dev))
         S["ehs"].copy_(prompt_embeds.to(dev).float()); S["pooled"].copy_(pooled.to(dev).float())
         S["tid"].copy_(time_ids.to(dev).float())
         S["step"].zero_()
@@ -357,8 +415,12 @@ class _DenoiseLoop:
             eps = self._unet_eps(S["scaled"], temb, ctx, lo, hi, chains, H, W)
             if cfgp:
                 eps = comm.all_gather(eps).reshape(NB, HW, -1)                    # [nb, G, HW, C] → [branch][generation]
-            ops.cfg_euler_step(eps, S["lat"], S["scaled"], S["sig"], S["step"], nb, Cl, cin, guidance_scale,
-                               image_guidance_scale, mode)
+            if order == 2:
+                ops.cfg_dpmpp2m_step(eps, S["lat"], S["x0_prev"], S["scaled"], S["sig"], S["coef"], S["step"], nb, Cl, cin,
+                                     guidance_scale, image_guidance_scale, mode)
+            else:
+                ops.cfg_euler_step(eps, S["lat"], S["scaled"], S["sig"], S["step"], nb, Cl, cin, guidance_scale,
+                                   image_guidance_scale, mode)
             ops.add_i32(S["step"], 1)
 
         def snap_trace(done):
@@ -392,7 +454,8 @@ class _DenoiseLoop:
 
 def slot_schedule(scheduler, num_steps, max_steps):
     """One request's rows of the slot loop's tables, from ``scheduler.set_timesteps(num_steps)``: (sigmas [max_steps + 1] fp32 — the
-    schedule's num_steps + 1 sigmas, zero padded —, timesteps [max_steps] fp32, zero padded, init_noise_sigma, sigma_0)."""
+    schedule's num_steps + 1 sigmas, zero padded —, timesteps [max_steps] fp32, zero padded, init_noise_sigma, sigma_0) and, for a
+    scheduler of order 2, a fifth entry: its coefficient rows [max_steps + 1, 3] fp32, zero padded."""
     if not 1 <= num_steps <= max_steps:
         raise ValueError(f"num_inference_steps must be in 1..{max_steps} (max_steps), got {num_steps}")
     scheduler.set_timesteps(num_steps)
@@ -400,7 +463,12 @@ def slot_schedule(scheduler, num_steps, max_steps):
     ts = torch.zeros(max_steps, dtype=torch.float32)
     sig[:num_steps + 1] = scheduler.sigmas
     ts[:num_steps] = scheduler.timesteps
-    return sig, ts, scheduler.init_noise_sigma, float(scheduler.sigmas[0])
+    out = (sig, ts, scheduler.init_noise_sigma, float(scheduler.sigmas[0]))
+    if getattr(scheduler, "order", 1) == 2:
+        coef = torch.zeros(max_steps + 1, 3, dtype=torch.float32)
+        coef[:num_steps] = scheduler.coefficients
+        out += (coef,)
+    return out
 
 
 class _SlotDenoiseLoop(_DenoiseLoop):
@@ -410,7 +478,9 @@ class _SlotDenoiseLoop(_DenoiseLoop):
     admitted into free slots and harvested between replays, and nothing is ever re-captured: the graph key holds no step count and no
     guidance value. A slot is live when 0 <= step < n_steps and parked (-1) otherwise; a parked slot's rows still go through the UNet
     (stale, finite data: wasted work) and the Euler kernel writes none of them. The UNet part of the step is the lock-step loop's
-    (``_unet_eps``: same launches, chain split and stagger at the same G). Single rank only."""
+    (``_unet_eps``: same launches, chain split and stagger at the same G). Single rank only. A loop configured for a scheduler of
+    order 2 steps with ops.cfg_dpmpp2m_step_slots: its state also holds x0_prev and every slot's coefficient rows, and the solver is
+    part of the graph key; the solver is the loop's, not a request's."""
 
     def __init__(self, unet, use_graph=True, comm=None):
         super().__init__(unet, use_graph, comm)
@@ -423,16 +493,18 @@ class _SlotDenoiseLoop(_DenoiseLoop):
             if c is not None and c.world > 1:
                 raise ValueError(f"in-flight batching of the de-tokenizer runs on one rank: {what} has comm.world = {c.world}")
 
-    def configure(self, mode, G, H, W, ehs_shape, pooled_dim, max_steps):
-        """(Re)allocates the state for G slots of [4, H, W] latents; ehs_shape = (tokens, dim) of one row of the conditioning. All slots
-        start parked on zeros. Returns True when the state is new."""
+    def configure(self, mode, G, H, W, ehs_shape, pooled_dim, max_steps, order=1):
+        """(Re)allocates the state for G slots of [4, H, W] latents; ehs_shape = (tokens, dim) of one row of the conditioning; ``order``
+        is the scheduler's (1: Euler, 2: DPM-Solver++(2M)). All slots start parked on zeros. Returns True when the state is new."""
+        if order not in (1, 2):
+            raise ValueError(f"the denoise loop has a step kernel for schedulers of order 1 (Euler) and 2 (DPM-Solver++(2M)), got order {order}")
         unet = self.unet
         unet._pack()
         dev = unet.device
         nb = 2 if mode == 0 else 3
         Cl, cin = 4, unet.cfg["in_channels"]
         assert cin == (Cl if mode == 0 else 2 * Cl), f"UNet in_channels {cin} does not match mode {mode}"
-        key = (mode, G, H, W, tuple(ehs_shape), int(pooled_dim), int(max_steps), unet.dtype, str(dev), self.chains, self.stagger)
+        key = (mode, G, H, W, tuple(ehs_shape), int(pooled_dim), int(max_steps), unet.dtype, str(dev), self.chains, self.stagger, order)
         if self._state is not None and self._graph_key == key:
             return False
         NB, HW, f32, i32 = nb * G, H * W, torch.float32, torch.int32
@@ -440,7 +512,9 @@ class _SlotDenoiseLoop(_DenoiseLoop):
         self._state = dict(lat=z(G, HW, Cl), scaled=z(NB, HW, cin), ehs=z(NB, *ehs_shape), pooled=z(NB, pooled_dim), tid=z(NB, 6),
                            sig_tab=z(G, max_steps + 1), t_tab=z(G, max_steps), step=torch.full((G,), -1, dtype=i32, device=dev),
                            n_steps=z(G, dtype=i32), gs=z(G), igs=z(G))
-        self._dims = dict(mode=mode, nb=nb, G=G, H=H, W=W, Cl=Cl, cin=cin, max_steps=max_steps)
+        if order == 2:
+            self._state.update(x0_prev=z(G, HW, Cl), coef_tab=z(G, max_steps + 1, 3))
+        self._dims = dict(mode=mode, nb=nb, G=G, H=H, W=W, Cl=Cl, cin=cin, max_steps=max_steps, order=order)
         self._graph, self._graph_key, self.graph_captures = None, key, 0
         self._host_step, self._host_n = [-1] * G, [0] * G
         unet._ctx_key = None
@@ -450,7 +524,8 @@ class _SlotDenoiseLoop(_DenoiseLoop):
     def admit(self, entries, scheduler):
         """One admission round. ``entries``: [(slot, dict(latents [1,4,H,W] unit noise, num_steps, guidance_scale, image_guidance_scale,
         ehs [nb, tokens, dim], pooled [nb, P], tid [nb, 6], image_latents [nb, 4, H, W] or None))] for parked slots. Writes the slots'
-        tables, latents (noise * init_noise_sigma), scaled model input of step 0 and conditioning rows, recomputes the cross-attention
+        tables (for order 2 also the coefficient rows; x0_prev needs none: step 0 does not read it), latents (noise *
+        init_noise_sigma), scaled model input of step 0 and conditioning rows, recomputes the cross-attention
         K / V at the full [nb*G] batch shape (a GEMM over the admitted rows alone could pick other tiles than the lock-step loop's and
         differ in bits) and copies the admitted rows into the context the graph reads; then the slots go live (step 0)."""
         S, D, unet = self._state, self._dims, self.unet
@@ -458,12 +533,16 @@ class _SlotDenoiseLoop(_DenoiseLoop):
         nb, G, H, W, Cl, cin = D["nb"], D["G"], D["H"], D["W"], D["Cl"], D["cin"]
         HW = H * W
         scaled = S["scaled"].view(nb, G, HW, cin)
+        if getattr(scheduler, "order", 1) != D["order"]:
+            raise ValueError(f"the slot loop was configured for a scheduler of order {D['order']}, got order {getattr(scheduler, 'order', 1)}")
         rows = []
         for g, e in entries:
             assert self._host_step[g] < 0, f"slot {g} is live"
             n = int(e["num_steps"])
-            sig, ts, init_sigma, s0 = slot_schedule(scheduler, n, D["max_steps"])
+            sig, ts, init_sigma, s0, *coef = slot_schedule(scheduler, n, D["max_steps"])
             S["sig_tab"][g].copy_(sig); S["t_tab"][g].copy_(ts)
+            if D["order"] == 2:
+                S["coef_tab"][g].copy_(coef[0])
             S["n_steps"][g:g + 1].fill_(n)
             S["gs"][g:g + 1].fill_(float(e["guidance_scale"])); S["igs"][g:g + 1].fill_(float(e["image_guidance_scale"]))
             lat = e["latents"].to(dev, torch.float32) * init_sigma
@@ -499,8 +578,12 @@ class _SlotDenoiseLoop(_DenoiseLoop):
         ts = ops.timestep_embedding_slots(S["t_tab"], S["step"], nb, unet.cfg["block_out_channels"][0], unet.dtype)
         temb = unet.time_embeddings(None, None, S["pooled"], S["tid"], NB, ts=ts)
         eps = self._unet_eps(S["scaled"], temb, self._ctx_static, 0, NB, chains, D["H"], D["W"])
-        ops.cfg_euler_step_slots(eps, S["lat"], S["scaled"], S["sig_tab"], S["step"], S["n_steps"], S["gs"], S["igs"], nb, D["Cl"],
-                                 D["cin"], D["mode"])
+        if D["order"] == 2:
+            ops.cfg_dpmpp2m_step_slots(eps, S["lat"], S["x0_prev"], S["scaled"], S["sig_tab"], S["coef_tab"], S["step"], S["n_steps"],
+                                       S["gs"], S["igs"], nb, D["Cl"], D["cin"], D["mode"])
+        else:
+            ops.cfg_euler_step_slots(eps, S["lat"], S["scaled"], S["sig_tab"], S["step"], S["n_steps"], S["gs"], S["igs"], nb, D["Cl"],
+                                     D["cin"], D["mode"])
         ops.denoise_advance(S["step"], S["n_steps"])
 
     def _graphed(self):
@@ -868,7 +951,8 @@ class SDXLAdapter:
                                             pooled=pooled, tid=tid, image_latents=il3)))
                 if not configured:                        # the conditioning's shape is known from the first request on
                     e0 = entries[0][1]
-                    if not loop.configure(mode, G, H, W, tuple(e0["ehs"].shape[1:]), e0["pooled"].shape[1], max_steps):
+                    if not loop.configure(mode, G, H, W, tuple(e0["ehs"].shape[1:]), e0["pooled"].shape[1], max_steps,
+                                          order=getattr(self.scheduler, "order", 1)):
                         loop.park_all()
                     loop.ensure_graph()
                     configured = True

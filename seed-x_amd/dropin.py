@@ -100,13 +100,14 @@ def install(reference_root=None):
         if len(parts) > 1:
             setattr(sys.modules[".".join(parts[:-1])], parts[-1], mod)
     if "diffusers" not in sys.modules or getattr(sys.modules["diffusers"], "_seedx_dropin", False):
-        from seedx_amd.detokenizer import EulerDiscreteScheduler
+        from seedx_amd.detokenizer import DPMSolverMultistepScheduler, EulerDiscreteScheduler
         from seedx_amd.unet import UNet2DConditionModel
         from seedx_amd.vae import AutoencoderKL
         d = types.ModuleType("diffusers")
         d.__spec__ = importlib.machinery.ModuleSpec("diffusers", None)
         d._seedx_dropin = True
         d.AutoencoderKL, d.UNet2DConditionModel, d.EulerDiscreteScheduler = AutoencoderKL, UNet2DConditionModel, EulerDiscreteScheduler
+        d.DPMSolverMultistepScheduler = DPMSolverMultistepScheduler
 
         class Transformer2DModel:   # eval_img2edit_seed_x_edit.py:8 imports the name and never uses it
             def __init__(self, *a, **kw):

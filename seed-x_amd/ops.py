@@ -1562,6 +1562,19 @@ def cfg_euler_step(eps, latents, scaled_next, sigmas_dev, step_dev, nb, C_lat, l
                                 ld_scaled, float(gs), float(igs), mode, _stream()), "sx_cfg_euler_step")
 
 
+def cfg_dpmpp2m_step(eps, latents, x0_prev, scaled_next, sigmas_dev, coef_dev, step_dev, nb, C_lat, ld_scaled, gs, igs, mode):
+    """cfg_euler_step's buffers plus x0_prev (fp32, the shape of latents: the previous denoised sample, not read on a step whose c is 0)
+    and coef_dev [steps, 3] fp32, the (a, b, c) rows of solvers.dpmpp2m_coefficients: one CFG + DPM-Solver++(2M) step."""
+    lib = _lib.load()
+    n = latents.numel()
+    f32 = torch.float32
+    assert x0_prev.dtype == f32 and x0_prev.is_contiguous() and x0_prev.numel() == n and latents.dtype == f32 and latents.is_contiguous()
+    assert coef_dev.dtype == f32 and coef_dev.is_contiguous() and coef_dev.dim() == 2 and coef_dev.shape[1] == 3
+    assert sigmas_dev.dtype == f32 and sigmas_dev.numel() >= coef_dev.shape[0] + 1, "sigmas must hold one more entry than coef has rows"
+    check(lib.sx_cfg_dpmpp2m_step(_p(eps), _p(latents), _p(x0_prev), _p(scaled_next), _p(sigmas_dev), _p(coef_dev), _p(step_dev), nb, n,
+                                  C_lat, ld_scaled, float(gs), float(igs), mode, _stream()), "sx_cfg_dpmpp2m_step")
+
+
 # ---- per-slot denoise step (in-flight batching of the de-tokenizer) ----------------------------------------------------
 def _slot_vec(t, G, dtype, what):
     assert t.dtype == dtype and t.is_contiguous() and t.numel() == G and t.is_cuda, f"{what}: {dtype} [{G}] on the device"
@@ -1585,6 +1598,28 @@ def cfg_euler_step_slots(eps, latents, scaled_next, sig_tab, step_dev, n_steps_d
     check(lib.sx_cfg_euler_step_slots(_p(eps), _p(latents), _p(scaled_next), _p(sig_tab), sig_tab.shape[1], _p(step_dev), _p(n_steps_dev),
                                       _p(gs_dev), _p(igs_dev), nb, G, n_slot, C_lat, ld_scaled, mode, _stream()),
           "sx_cfg_euler_step_slots")
+
+
+def cfg_dpmpp2m_step_slots(eps, latents, x0_prev, scaled_next, sig_tab, coef_tab, step_dev, n_steps_dev, gs_dev, igs_dev, nb, C_lat,
+                           ld_scaled, mode):
+    """cfg_euler_step_slots's buffers plus x0_prev [G, HW, C] fp32 and coef_tab [G, ld_sig, 3] fp32 (every slot's (a, b, c) rows, zero
+    padded). Live slots take one CFG + DPM-Solver++(2M) step, bit for bit cfg_dpmpp2m_step's; parked slots are left untouched."""
+    lib = _lib.load()
+    G = latents.shape[0]
+    n_slot = latents.numel() // G
+    f32 = torch.float32
+    assert latents.dtype == f32 and latents.is_contiguous() and eps.dtype == f32 and eps.is_contiguous()
+    assert x0_prev.dtype == f32 and x0_prev.is_contiguous() and x0_prev.shape == latents.shape
+    assert eps.numel() == nb * G * n_slot, "eps must hold nb * G slots"
+    assert sig_tab.dtype == f32 and sig_tab.is_contiguous() and sig_tab.dim() == 2 and sig_tab.shape[0] == G
+    assert coef_tab.dtype == f32 and coef_tab.is_contiguous() and tuple(coef_tab.shape) == (G, sig_tab.shape[1], 3)
+    if scaled_next is not None:
+        assert scaled_next.dtype == f32 and scaled_next.is_contiguous() and scaled_next.numel() == nb * G * (n_slot // C_lat) * ld_scaled
+    _slot_vec(step_dev, G, torch.int32, "step"); _slot_vec(n_steps_dev, G, torch.int32, "n_steps")
+    _slot_vec(gs_dev, G, f32, "gs"); _slot_vec(igs_dev, G, f32, "igs")
+    check(lib.sx_cfg_dpmpp2m_step_slots(_p(eps), _p(latents), _p(x0_prev), _p(scaled_next), _p(sig_tab), _p(coef_tab), sig_tab.shape[1],
+                                        _p(step_dev), _p(n_steps_dev), _p(gs_dev), _p(igs_dev), nb, G, n_slot, C_lat, ld_scaled, mode,
+                                        _stream()), "sx_cfg_dpmpp2m_step_slots")
 
 
 def timestep_embedding_slots(t_tab, step_dev, nb, dim, dtype):
